@@ -23,6 +23,8 @@ the NumPy-vectorised restatement rides along as a labelled secondary.  At N = 1 
 (benchmarks/other_configs.py): configs[2] (turbo), one GPU's share of configs[3] (64-QAM soft demodulator -> LDPC min-sum and
 sum-product) and the soft demodulator alone, each device-resident, HIP-event timed for the same K steps and checked against
 the oracle after its timed region -- the headline fields are untouched by it (``--no-other-configs`` leaves it out).
+``--dump-outputs DIR`` writes what the last timed step decoded as float32 .npy files (see dump_outputs), so that two builds
+can be compared output for output on identical inputs.
 """
 import argparse
 import ctypes
@@ -40,6 +42,9 @@ MSG_BITS = 1024
 EBN0_DB = 3.0
 ALG_BYTES_PER_CW = 2060 * 8 + 1030 * 1      # float64 LLRs in + uint8 bits out
 HBM_PEAK_GBS = 8000.0                       # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20                 # --dump-outputs: everything written, at most
+DUMP_SAMPLE_CODEWORDS = 8192                # --dump-outputs: rows of the decoded batch written in full (a fixed, seeded sample)
+DUMP_SAMPLE_SEED = 20261015
 PMC_FILES = ("r06_viterbi_c2_pmc.json", "r05_viterbi_c2_pmc.json", "r04_viterbi_c2_pmc.json")   # written by scripts/collect_pmc.py from rocprofv3 passes over this script; newest first
 
 
@@ -228,6 +233,41 @@ def cpu_baseline(tr, llr_sample, gpu_bits=None, budget_s=8.0):
     return res
 
 
+def dump_sample_rows(B):
+    """Indices (sorted) of the codewords --dump-outputs writes in full: the same for every run with the same --batch."""
+    n = min(B, DUMP_SAMPLE_CODEWORDS)
+    return np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(B, n, replace=False))
+
+
+def dump_bytes(B, L):
+    n = min(B, DUMP_SAMPLE_CODEWORDS)
+    return n * L * 4 + n * 8 + B * 4
+
+
+def dump_outputs(out_dir, bits, suffix=""):
+    """What the timed path returned in its last step, [B, L] decoded bits (uint8 on the device), as float32 / float64 .npy:
+
+    * decoded_bits: the full rows of a fixed, seeded sample of DUMP_SAMPLE_CODEWORDS codewords (all of them when B is smaller);
+    * decoded_bits_rows: which codewords those are (float64 indices into the batch);
+    * decoded_bits_weighted_sum: for EVERY codeword, sum_j (j + 1) * bit_j (exact in float32), so that a difference outside the
+      sample still shows.
+    Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    B, L = bits.shape
+    rows = dump_sample_rows(B)
+    w = np.arange(1, L + 1, dtype=np.int64)
+    arrays = {"decoded_bits": bits[rows].astype(np.float32),
+              "decoded_bits_rows": rows.astype(np.float64),
+              "decoded_bits_weighted_sum": np.concatenate([bits[i:i + 4096].astype(np.int64) @ w
+                                                           for i in range(0, B, 4096)]).astype(np.float32)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    names = []
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+        names.append(name + suffix + ".npy")
+    return names
+
+
 def free_port():
     import socket
     with socket.socket() as sock:
@@ -330,7 +370,17 @@ def main():
     ap.add_argument("--precision", choices=("fp64-parity", "fp32-fast"), default="fp64-parity",
                     help="fp32-fast: the float32 variant of the fused kernel (cpx_set_precision) -- NOT the parity mode and not the "
                          "headline: the line then carries dtype f32 and the measured mismatch count against the float64 oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the bits the last timed step decoded to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB; a fixed, seeded sample of the batch plus a checksum per codeword); N > 1: every rank "
+                         "writes its own files, suffixed _rank<r>")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and dump_bytes(args.batch, MSG_BITS + 6) > DUMP_LIMIT_BYTES:
+        ap.error("--dump-outputs: --batch %d needs more than %d bytes of output" % (args.batch, DUMP_LIMIT_BYTES))
 
     mode, rank, world = resolve_world(args)
     if mode == "launch":
@@ -512,6 +562,10 @@ def main():
 
     elapsed, kernel_ms = timed_region(False)                       # `value`: the decode path alone (no data-path collective)
     kernel_name = _lib.last_kernel()                               # what the library really launched for this workload
+    dumped = None
+    if args.dump_outputs:                                          # what the LAST timed step decoded, before anything else runs
+        dumped = np.empty((B, L), dtype=np.uint8)
+        _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(dumped), d_bits, dumped.nbytes))
     elapsed_g = gather_ms = None
     if args.gather:
         elapsed_g, gather_ms = timed_region(True)                  # `value_with_gather`: the same K steps + the all-gather
@@ -712,6 +766,10 @@ def main():
             out["cpu_baseline"] = cpu_baseline(tr, llr_s, bits[:ns, :].astype(np.int64))
         else:
             out["cpu_baseline"] = None
+    if dumped is not None:
+        names = dump_outputs(args.dump_outputs, dumped, "_rank%d" % rank if world > 1 else "")
+        if out is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": names}
     if comm is not None:
         comm.barrier()
         comm.close()

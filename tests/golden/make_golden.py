@@ -1070,6 +1070,28 @@ def gen_channels():
 
 GENS["channels"] = gen_channels
 
+def gen_fingerprints():
+    """tests/golden/reference_fingerprints.json for tests/test_no_verbatim_copies.py: per reference file of its PAIRS, the
+    fingerprints (truncated SHA-256) of the normalised statements, in order, and of every function's body -- no source text."""
+    import json
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_no_verbatim_copies as nv
+    files = {}
+    for _, theirs in nv.PAIRS:
+        path = os.path.join(REF, "commpy", theirs)
+        files[theirs] = {"statements": [nv.fingerprint(s) for s in nv._statements(path)],
+                         "functions": {k: [nv.fingerprint(s) for s in v] for k, v in sorted(nv._functions(path).items())}}
+    out = os.path.join(HERE, "reference_fingerprints.json")
+    with open(out, "w") as f:
+        json.dump({"what": "sha256(normalised statement)[:16] of the reference files, tests/test_no_verbatim_copies.py",
+                   "python": "%d.%d" % sys.version_info[:2], "files": files}, f, separators=(",", ":"), sort_keys=True)
+        f.write("\n")
+    print("wrote %s (%.1f kB)" % (out, os.path.getsize(out) / 1e3))
+
+
+GENS["fingerprints"] = gen_fingerprints
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)

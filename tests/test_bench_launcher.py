@@ -160,3 +160,51 @@ def test_bench_gpus_2_end_to_end_against_the_host_stand_in(tmp_path):
             assert name in calls, (rank, name)
         assert calls.index("cpx_comm_init_rank") < calls.index("cpx_comm_allgather_u8") < calls.index("cpx_comm_info")
         assert ("cpx_comm_unique_id" in calls) == (rank == 0)          # rank 0 makes the id, rank 1 reads it from the nonce-keyed file
+
+
+def _bench_single_on_the_host_stand_in(tmp_path, *extra):
+    """`bench.py --gpus 1` against tests/fake_engine.py (host stand-in for the C-ABI, tests/ only); returns (exit code, JSON line or
+    None, stderr)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "CPX_COMM_NONCE")}
+    env["CPX_FAKE_DIR"] = str(tmp_path)
+    env["CPX_FAKE_DEVICES"] = "1"
+    argv = [sys.executable, os.path.join(ROOT, "tests", "fake_engine.py"), "--gpus", "1", "--batch", "40", "--no-cpu-baseline",
+            "--no-other-configs", "--no-path-check", "--sustain-seconds", "0"] + list(extra)
+    r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) <= 1, lines
+    return r.returncode, (json.loads(lines[0]) if lines else None), r.stderr
+
+
+def test_bench_dump_outputs_writes_the_timed_decode_and_is_reproducible(tmp_path):
+    """--dump-outputs DIR: after the timed steps, the bits the last timed step decoded land in DIR as float32 / float64 .npy
+    (a fixed, seeded sample of rows plus a checksum of every codeword), identical from run to run with the same arguments;
+    --steps is the number of timed steps and the line carries ms_per_step."""
+    import numpy as np
+    runs = []
+    for k, steps in enumerate((3, 4)):
+        out_dir = tmp_path / ("dump%d" % k)
+        code, j, err = _bench_single_on_the_host_stand_in(tmp_path, "--steps", str(steps), "--warmup", "1",
+                                                          "--dump-outputs", str(out_dir))
+        assert code == 0, err[-2000:]
+        assert j["steps"] == steps and j["ms_per_step"] > 0 and j["oracle_mismatched_bits"] == 0
+        assert sorted(j["dump_outputs"]["files"]) == ["decoded_bits.npy", "decoded_bits_rows.npy", "decoded_bits_weighted_sum.npy"]
+        arrays = {f: np.load(out_dir / f) for f in j["dump_outputs"]["files"]}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        runs.append(arrays)
+    bits, rows, wsum = (runs[0][f] for f in ("decoded_bits.npy", "decoded_bits_rows.npy", "decoded_bits_weighted_sum.npy"))
+    assert bits.shape == (40, 1030) and np.array_equal(rows, np.arange(40)) and wsum.shape == (40,)
+    assert set(np.unique(bits)) <= {0.0, 1.0} and bits.sum() > 0
+    assert np.array_equal(wsum, bits @ np.arange(1, 1031, dtype=np.float32))
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f             # same inputs, same outputs, whatever the number of steps
+    # a larger batch than the sample: a seeded subset of rows, the same every time
+    assert np.array_equal(bench.dump_sample_rows(65536), bench.dump_sample_rows(65536))
+    assert len(bench.dump_sample_rows(65536)) == bench.DUMP_SAMPLE_CODEWORDS
+    assert bench.dump_bytes(65536, 1030) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_bench_refuses_zero_steps(tmp_path):
+    code, j, err = _bench_single_on_the_host_stand_in(tmp_path, "--steps", "0")
+    assert code != 0 and j is None and "--steps" in err

@@ -99,6 +99,17 @@ SYMBOLS = {
     "cpx_demod_soft_scaled_dev": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p]),
     "cpx_demod_hard": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "cpx_demod_hard_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cpx_kbest_set_path": (c_int, [c_char_p]),
+    "cpx_mimo_ml": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
+    "cpx_mimo_ml_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "cpx_kbest_hard": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p]),
+    "cpx_kbest_hard_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cpx_kbest_soft": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_double, c_void_p]),
+    "cpx_kbest_soft_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_double, c_void_p,
+                                   c_void_p]),
+    "cpx_kbest_list": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cpx_kbest_list_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p,
+                                   c_void_p]),
     "cpx_random_bits_dev": (c_int, [c_void_p, c_int64, c_uint64, c_uint64, c_void_p]),
     "cpx_conv_encode_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "cpx_gather_u8_dev": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
@@ -259,6 +270,11 @@ def ldpc_set_path(mode):
     """Force an LDPC decoder path: None/'auto', 'tiled' (HBM-resident tiles), 'resident' (LDS-resident, strict), 'resident-log' (the same with
     the log-domain sum-product row instead of the ratio-domain kernel)."""
     check(load().cpx_ldpc_set_path(None if mode is None else mode.encode()))
+
+
+def kbest_set_path(mode):
+    """K-best kernel storage: None/'auto' (LDS-resident where the state of a vector fits 64 KB) or 'general' (global workspace)."""
+    check(load().cpx_kbest_set_path(None if mode is None else mode.encode()))
 
 
 class DeviceHandles:

@@ -3,17 +3,21 @@
 Mirrors the part of /root/reference/commpy/channels.py the decoding path uses:
 ``SISOFlatChannel`` (channels.py:99-240, with ``_FlatChannel.set_SNR_dB`` :57-74 and
 ``generate_noises`` :37-55) and the ``bec`` / ``bsc`` / ``awgn`` helpers (:630-708).
-MIMO channels are out of scope.  ``propagate`` also accepts a 2-D
-``[batch, nsym]`` message so that a whole Monte-Carlo batch is generated at once.
+``SISOFlatChannel.propagate`` also accepts a 2-D ``[batch, nsym]`` message so that a whole Monte-Carlo batch is
+generated at once.  ``MIMOFlatChannel`` (channels.py:242-627, the Kronecker model) produces the per-vector channel
+matrices the MIMO detectors of commpy_amd.modulation consume; it draws from NumPy's global generator in the reference's
+order (noises, then gains) so that a seeded run reproduces the reference's outputs.
 
 Kept quirk B7: for a complex channel the generated noise is
 ``(randn + 1j*randn) * noise_std * 0.5`` (channels.py:53) while receivers are told
 ``noise_std**2`` (links.py:242-243).
 """
+import numpy as np
 from numpy import abs, absolute, asarray, isrealobj, sqrt, where, zeros
+from scipy.linalg import sqrtm
 from numpy.random import randn, random, standard_normal
 
-__all__ = ['SISOFlatChannel', 'bec', 'bsc', 'awgn']
+__all__ = ['SISOFlatChannel', 'MIMOFlatChannel', 'bec', 'bsc', 'awgn']
 
 
 class SISOFlatChannel:
@@ -85,6 +89,127 @@ class SISOFlatChannel:
         clean = self.unnoisy_output = gains * msg
         return clean + self.noises
 
+
+
+def _exponent_matrix(n):
+    """[[j - i]] for i, j < n: the exponents of the exponential correlation model."""
+    k = np.arange(n)
+    return k[None, :] - k[:, None]
+
+
+class MIMOFlatChannel:
+    """nb_tx x nb_rx flat-fading channel of the Kronecker model -- same constructor, attributes and setters as
+    channels.py:242.  ``fading_param = (mean [nb_rx, nb_tx], Rt [nb_tx, nb_tx], Rr [nb_rx, nb_rx])``; the default is
+    uncorrelated Rayleigh fading.  ``channel_gains[i]`` is the [nb_rx, nb_tx] matrix of the i-th vector."""
+
+    def __init__(self, nb_tx, nb_rx, noise_std=None, fading_param=None):
+        self.noises = None
+        self.channel_gains = None
+        self.unnoisy_output = None
+        self.nb_tx, self.nb_rx = nb_tx, nb_rx
+        self.noise_std = noise_std
+        if fading_param is None:
+            fading_param = (zeros((nb_rx, nb_tx)), np.identity(nb_tx), np.identity(nb_rx))
+        self.fading_param = fading_param
+
+    # the SISO channel's noise and SNR rules are the reference's shared base-class ones (channels.py:37-90)
+    generate_noises = SISOFlatChannel.generate_noises
+    set_SNR_dB = SISOFlatChannel.set_SNR_dB
+    set_SNR_lin = SISOFlatChannel.set_SNR_lin
+    isComplex = SISOFlatChannel.isComplex
+
+    @staticmethod
+    def _gains(param):
+        """(NLOS power tr(Rt^T kron Rr), LOS power sum |mean|^2)."""
+        mean, rt, rr = param
+        return np.trace(rt) * np.trace(rr), np.sum(absolute(mean) ** 2)
+
+    @property
+    def fading_param(self):
+        return self._fading_param
+
+    @fading_param.setter
+    def fading_param(self, value):
+        nlos, los = self._gains(value)
+        if absolute(nlos + los - self.nb_tx * self.nb_rx) > 1e-3:
+            raise ValueError('With this parameters, the channel would add or remove energy.')
+        self._fading_param = value
+        self._isComplex = isinstance(value[0][0, 0], complex)
+
+    @property
+    def k_factor(self):
+        """LOS / NLOS power ratio."""
+        nlos, los = self._gains(self.fading_param)
+        return los / nlos
+
+    def propagate(self, msg):
+        """Send ``msg`` (padded with zeros to a multiple of nb_tx) as vectors of nb_tx symbols; returns [nb_vect, nb_rx]."""
+        cplx = self.isComplex
+        if not cplx and isinstance(msg[0], complex):
+            raise TypeError('a complex message cannot be propagated in a real channel.')
+        nb_vect = -(-len(msg) // self.nb_tx)
+        short = nb_vect * self.nb_tx - len(msg)
+        x = np.hstack((msg, zeros(short))) if short else np.asarray(msg)
+        x = x.reshape(nb_vect, self.nb_tx)
+        shape = (nb_vect, self.nb_rx, self.nb_tx)
+        self.generate_noises(shape[:2])                             # noises first, then the gains (channels.py:359-366)
+        g = standard_normal(shape)
+        g = (g + 1j * standard_normal(shape)) * sqrt(0.5) if cplx else g
+        mean, rt, rr = self.fading_param
+        g = np.matmul(np.matmul(sqrtm(rr), g), sqrtm(rt).T) + mean
+        self.channel_gains = g
+        self.unnoisy_output = np.matmul(g, x[:, :, None])[:, :, 0]
+        return self.unnoisy_output + self.noises
+
+    def specular_compo(self, thetat, dt, thetar, dr):
+        """Line-of-sight component exp(2j pi (n dr cos thetar + m dt cos thetat)) [nb_rx, nb_tx] (channels.py:437)."""
+        if dr < 0 or dt < 0:
+            raise ValueError("the distance must be positive ")
+        rx = np.arange(self.nb_rx)[:, None] * dr * np.cos(thetar)
+        tx = np.arange(self.nb_tx)[None, :] * dt * np.cos(thetat)
+        return np.exp(1j * 2 * np.pi * (rx + tx))
+
+    def _kbsm(self, betat, betar):
+        """KBSM-BD-AA weighting of the correlation matrices (channels.py:404-430)."""
+        if betar < 0 or betat < 0:
+            raise ValueError("beta must be positif")
+        et = np.exp(-betat * abs(_exponent_matrix(self.nb_tx)))
+        er = np.exp(-betar * abs(_exponent_matrix(self.nb_rx)))
+        mean, rt, rr = self.fading_param
+        self.fading_param = mean, rt * et, rr * er
+
+    @staticmethod
+    def _check_unit(t, r):
+        for name, v in (('t', t), ('r', r)):
+            if abs(v) - 1 > 1e-4:
+                raise ValueError('abs(%s) must be one.' % name)
+
+    def _scaled_mean(self, mean, k_factor):
+        nlos = mean.size / (k_factor + 1)
+        return mean * sqrt(k_factor * nlos / np.sum(absolute(mean) ** 2)), nlos
+
+    def uncorr_rayleigh_fading(self, dtype):
+        """Uncorrelated Rayleigh fading of type ``dtype`` (complex or float)."""
+        self.fading_param = zeros((self.nb_rx, self.nb_tx), dtype), np.identity(self.nb_tx), np.identity(self.nb_rx)
+
+    def expo_corr_rayleigh_fading(self, t, r, betat=0, betar=0):
+        """Rayleigh fading with exponential correlation t^(j-i) / r^(j-i), |t| = |r| = 1, optional KBSM betas."""
+        self._check_unit(t, r)
+        self.fading_param = (zeros((self.nb_rx, self.nb_tx), complex), t ** _exponent_matrix(self.nb_tx),
+                             r ** _exponent_matrix(self.nb_rx))
+        self._kbsm(betat, betar)
+
+    def uncorr_rician_fading(self, mean, k_factor):
+        """Uncorrelated Rician fading: ``mean`` rescaled to the requested k-factor."""
+        mean, nlos = self._scaled_mean(mean, k_factor)
+        self.fading_param = mean, np.identity(self.nb_tx) * nlos / mean.size, np.identity(self.nb_rx)
+
+    def expo_corr_rician_fading(self, mean, k_factor, t, r, betat=0, betar=0):
+        """Rician fading with exponential correlation; ``mean`` rescaled to the requested k-factor."""
+        self._check_unit(t, r)
+        mean, nlos = self._scaled_mean(mean, k_factor)
+        self.fading_param = mean, t ** _exponent_matrix(self.nb_tx) * nlos / mean.size, r ** _exponent_matrix(self.nb_rx)
+        self._kbsm(betat, betar)
 
 def bec(input_bits, p_e):
     """Binary erasure channel: erased bits become -1 (channels.py:630-649)."""

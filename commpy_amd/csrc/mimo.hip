@@ -1,0 +1,443 @@
+// MIMO detection (commpy/modulation.py:299-406, 568-646): exhaustive ML search and K-best Schnorr-Euchner search with hard,
+// soft (max-log over the final candidate list) and candidate-list outputs.  float64 throughout, -ffp-contract=off.
+//
+// One wave (64 lanes, one workgroup) per received vector, grid-striding over the batch.
+//   ML      the nt x m table of column-times-point products sits in LDS (when it fits); lanes stride over hypothesis PREFIXES
+//           (antennas 0..nt-2) and each prefix's residual is reused for the m points of the last antenna, so a hypothesis
+//           costs nr complex subtractions and squares.  A lexicographic (metric, index) argmin across the wave gives the first
+//           minimum -- NumPy's argmin, NaN first.
+//   K-best complex Householder QR of [H | y] in the workgroup's storage, then the breadth-first search of the reference: children
+//           at position point * nb_can + parent, the min(nb_hyp, K) smallest accumulated distances kept IN ASCENDING ORDER, ties
+//           (and NaN, which sorts last) broken by the lowest child position.  Selection is K rounds of a wave argmin: every lane
+//           caches the minimum of the children it owns, one cross-lane reduction per round picks the winner, only the winner's
+//           lane rescans.  That yields exactly the sorted prefix the reference's argsort takes, for K * (6 shuffles + N / 64)
+//           steps instead of the N^2 / 64 of rank counting or N log^2 N / 64 of a bitonic sort.
+// The state of a vector (QR workspace, two candidate buffers, the children) lives in LDS on the fast path and in a global
+// workspace on the general path (same code, templated on the storage): arguments whose state exceeds LDS_MAX take the latter,
+// cpx_kbest_set_path("general") forces it.
+#include "cpx_internal.h"
+
+#include <atomic>
+#include <cmath>
+#include <cstdlib>
+
+using namespace cpx;
+
+namespace {
+
+constexpr int WAVE = 64;
+constexpr size_t LDS_MAX = 64 * 1024;   // dynamic LDS budget of one workgroup on the fast paths
+constexpr int64_t MAX_HYP = int64_t(1) << 31;
+
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ double abs2(double2 a) { return a.x * a.x + a.y * a.y; }
+
+// (metric, index) order: NaN before numbers (ML: argmin returns the first NaN) or after them (K-best: argsort puts NaN last),
+// equal metrics by index
+template <bool NAN_FIRST>
+__device__ __forceinline__ bool key_less(double a, long long ia, double b, long long ib) {
+    const bool an = a != a, bn = b != b;
+    if (an || bn) return (an && bn) ? ia < ib : (NAN_FIRST ? an : bn);
+    if (a != b) return a < b;
+    return ia < ib;
+}
+
+template <bool NAN_FIRST>
+__device__ __forceinline__ void wave_argmin(double &m, long long &i) {
+#pragma unroll
+    for (int off = WAVE / 2; off >= 1; off >>= 1) {
+        const double om = __shfl_xor(m, off);
+        const long long oi = __shfl_xor(i, off);
+        if (key_less<NAN_FIRST>(om, oi, m, i)) { m = om; i = oi; }
+    }
+}
+
+// ---- ML --------------------------------------------------------------------------------------------------------------------
+// LDS: H [nr][nt], y [nr], per-lane residual [64][nr], TAB: products [nt][m][nr]
+template <bool TAB>
+__global__ __launch_bounds__(WAVE) void mimo_ml_kernel(const double2 *__restrict__ y, const double2 *__restrict__ H, int64_t hstride,
+                                                       int64_t B, int nr, int nt, const double2 *__restrict__ c, int m, int lgm,
+                                                       int32_t *__restrict__ out) {
+    extern __shared__ double2 lds[];
+    double2 *sH = lds, *sy = sH + nr * nt, *res = sy + nr, *T = res + WAVE * nr;
+    const int lane = threadIdx.x;
+    double2 *my = res + lane * nr;
+    const long long P = 1ll << (lgm * (nt - 1));   // prefixes over antennas 0..nt-2
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        const double2 *Hb = H + b * hstride, *yb = y + b * nr;
+        for (int i = lane; i < nr * nt; i += WAVE) sH[i] = Hb[i];
+        for (int i = lane; i < nr; i += WAVE) sy[i] = yb[i];
+        __syncthreads();
+        if (TAB) {
+            for (int i = lane; i < nt * m * nr; i += WAVE) {
+                const int r = i % nr, p = (i / nr) % m, t = i / (nr * m);
+                T[i] = cmul(sH[r * nt + t], c[p]);
+            }
+            __syncthreads();
+        }
+        double best = INFINITY;
+        long long bi = 0x7fffffffffffffffll;
+        const int last = nt - 1;
+        for (long long p = lane; p < P; p += WAVE) {
+            for (int r = 0; r < nr; r++) my[r] = sy[r];
+            for (int t = 0; t < last; t++) {
+                const int d = int(p >> (lgm * (last - 1 - t))) & (m - 1);
+                for (int r = 0; r < nr; r++) my[r] = csub(my[r], TAB ? T[(t * m + d) * nr + r] : cmul(sH[r * nt + t], c[d]));
+            }
+            for (int q = 0; q < m; q++) {
+                double met = 0.0;
+                for (int r = 0; r < nr; r++)
+                    met += abs2(csub(my[r], TAB ? T[(last * m + q) * nr + r] : cmul(sH[r * nt + last], c[q])));
+                const long long idx = (p << lgm) | q;
+                if (key_less<true>(met, idx, best, bi)) { best = met; bi = idx; }
+            }
+        }
+        wave_argmin<true>(best, bi);
+        for (int t = lane; t < nt; t += WAVE) out[b * nt + t] = int32_t(bi >> (lgm * (nt - 1 - t))) & (m - 1);
+        __syncthreads();
+    }
+}
+
+// ---- K-best -----------------------------------------------------------------------------------------------------------------
+struct KbLayout {   // byte offsets into one vector's state
+    size_t A, Pd0, Pd1, Pt0, Pt1, Pi0, Pi1, Ct, sel, Ck, bytes;
+};
+
+KbLayout kb_layout(int nr, int nt, int K, int m) {
+    KbLayout L;
+    size_t o = 0;
+    auto take = [&](size_t n, size_t al) { o = (o + al - 1) / al * al; size_t r = o; o += n; return r; };
+    const size_t N = size_t(K) * m;
+    L.A = take(16 * size_t(nr) * (nt + 1), 16);
+    L.Pd0 = take(16 * size_t(K) * nt, 16);
+    L.Pd1 = take(16 * size_t(K) * nt, 16);
+    L.Pt0 = take(8 * size_t(K), 8);
+    L.Pt1 = take(8 * size_t(K), 8);
+    L.Ct = take(8 * N, 8);
+    L.Pi0 = take(4 * size_t(K) * nt, 4);
+    L.Pi1 = take(4 * size_t(K) * nt, 4);
+    L.sel = take(4 * size_t(K), 4);
+    L.Ck = take(N, 1);
+    L.bytes = (o + 15) / 16 * 16;
+    return L;
+}
+
+enum { KB_HARD = 0, KB_SOFT = 1, KB_LIST = 2 };
+
+template <bool GLOBAL>
+__global__ __launch_bounds__(WAVE) void kbest_kernel(const double2 *__restrict__ y, const double2 *__restrict__ H, int64_t hstride,
+                                                     int64_t B, int nr, int nt, const double2 *__restrict__ c, int m, int nbits, int K,
+                                                     KbLayout L, char *ws, int mode, double noise_var, int32_t *__restrict__ out_idx,
+                                                     double *__restrict__ out_llr, int32_t *__restrict__ out_count) {
+    extern __shared__ double2 lds_d2[];
+    char *base = GLOBAL ? ws + size_t(blockIdx.x) * L.bytes : reinterpret_cast<char *>(lds_d2);
+    double2 *A = reinterpret_cast<double2 *>(base + L.A);
+    double2 *Pd[2] = {reinterpret_cast<double2 *>(base + L.Pd0), reinterpret_cast<double2 *>(base + L.Pd1)};
+    double *Pt[2] = {reinterpret_cast<double *>(base + L.Pt0), reinterpret_cast<double *>(base + L.Pt1)};
+    int32_t *Pi[2] = {reinterpret_cast<int32_t *>(base + L.Pi0), reinterpret_cast<int32_t *>(base + L.Pi1)};
+    double *Ct = reinterpret_cast<double *>(base + L.Ct);
+    int32_t *sel = reinterpret_cast<int32_t *>(base + L.sel);
+    uint8_t *Ck = reinterpret_cast<uint8_t *>(base + L.Ck);
+    const int lane = threadIdx.x;
+    const int w = nt + 1;   // row stride of [H | y]
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        const double2 *Hb = H + b * hstride, *yb = y + b * nr;
+        for (int i = lane; i < nr * w; i += WAVE) {
+            const int r = i / w, j = i - r * w;
+            A[i] = j < nt ? Hb[r * nt + j] : yb[r];
+        }
+        __syncthreads();
+        // Householder QR: after column k, A[0..nt-1][0..nt-1] holds R (upper part) and A[0..nt-1][nt] = Q^H y
+        for (int k = 0; k < nt; k++) {
+            double tail = 0.0;
+            for (int i = k + 1; i < nr; i++) tail += abs2(A[i * w + k]);
+            const double2 x0 = A[k * w + k];
+            const double nx = sqrt(abs2(x0) + tail);
+            const double ax0 = hypot(x0.x, x0.y);
+            const double2 ph = ax0 > 0.0 ? make_double2(x0.x / ax0, x0.y / ax0) : make_double2(1.0, 0.0);
+            const double2 alpha = make_double2(-ph.x * nx, -ph.y * nx);
+            const double2 v0 = csub(x0, alpha);
+            const double vn2 = abs2(v0) + tail;
+            const bool reflect = nx > 0.0 && vn2 > 0.0;
+            if (reflect) {
+                for (int j = k + 1 + lane; j < w; j += WAVE) {
+                    double2 s = make_double2(v0.x * A[k * w + j].x + v0.y * A[k * w + j].y, v0.x * A[k * w + j].y - v0.y * A[k * w + j].x);
+                    for (int i = k + 1; i < nr; i++) {
+                        const double2 vi = A[i * w + k], a = A[i * w + j];
+                        s.x += vi.x * a.x + vi.y * a.y;      // conj(v_i) a
+                        s.y += vi.x * a.y - vi.y * a.x;
+                    }
+                    const double2 f = make_double2(2.0 * s.x / vn2, 2.0 * s.y / vn2);
+                    A[k * w + j] = csub(A[k * w + j], cmul(f, v0));
+                    for (int i = k + 1; i < nr; i++) A[i * w + j] = csub(A[i * w + j], cmul(f, A[i * w + k]));
+                }
+            }
+            __syncthreads();
+            if (lane == 0 && reflect) A[k * w + k] = alpha;
+            __syncthreads();
+        }
+        // the search, antenna nt-1 down to 0
+        int cur = 0, nb = 1;
+        for (int t = lane; t < nt; t += WAVE) { Pd[0][t] = A[t * w + nt]; Pi[0][t] = 0; }
+        if (lane == 0) Pt[0][0] = 0.0;
+        __syncthreads();
+        for (int coor = nt - 1; coor >= 0; coor--) {
+            const int N = nb * m;
+            const double2 rcc = A[coor * w + coor];
+            double lm = NAN;
+            long long li = 0x7fffffffffffffffll;
+            for (int j = lane; j < N; j += WAVE) {
+                const int p = j / nb, q = j - p * nb;
+                const double2 e = csub(Pd[cur][q * nt + coor], cmul(rcc, c[p]));
+                const double tot = Pt[cur][q] + abs2(e);
+                Ct[j] = tot;
+                Ck[j] = 0;
+                if (li == 0x7fffffffffffffffll || key_less<false>(tot, j, lm, li)) { lm = tot; li = j; }
+            }
+            const int nk = N < K ? N : K;
+            for (int k = 0; k < nk; k++) {
+                double bm = lm;
+                long long bj = li;
+                wave_argmin<false>(bm, bj);   // lanes without a child left carry index INT64_MAX: never chosen while one remains
+                if (lane == 0) sel[k] = int32_t(bj);
+                if (bj == li) {               // the owner lane: retire the child, rescan its own
+                    Ck[bj] = 1;
+                    lm = NAN;
+                    li = 0x7fffffffffffffffll;
+                    for (int j = lane; j < N; j += WAVE)
+                        if (!Ck[j] && (li == 0x7fffffffffffffffll || key_less<false>(Ct[j], j, lm, li))) { lm = Ct[j]; li = j; }
+                }
+            }
+            __syncthreads();
+            const int nxt = cur ^ 1;
+            for (int i = lane; i < nk * nt; i += WAVE) {
+                const int k = i / nt, t = i - k * nt;
+                const int j = sel[k], p = j / nb, q = j - p * nb;
+                const double2 d = Pd[cur][q * nt + t];
+                double2 nd = d;
+                if (t < coor) nd = csub(d, cmul(A[t * w + coor], c[p]));
+                else if (t == coor) nd = csub(d, cmul(rcc, c[p]));
+                Pd[nxt][i] = nd;
+                Pi[nxt][i] = t == coor ? p : Pi[cur][q * nt + t];
+                if (t == 0) Pt[nxt][k] = Ct[j];
+            }
+            __syncthreads();
+            cur = nxt;
+            nb = nk;
+        }
+        if (mode == KB_HARD) {
+            for (int t = lane; t < nt; t += WAVE) out_idx[b * nt + t] = Pi[cur][t];
+        } else if (mode == KB_LIST) {
+            for (int i = lane; i < K * nt; i += WAVE) out_idx[b * K * nt + i] = i < nb * nt ? Pi[cur][i] : -1;
+            if (lane == 0) out_count[b] = nb;
+        } else {
+            // max-log LLRs on the ORIGINAL y and H: metric = norm(y - H x)**2 (sqrt, then squared, as the reference)
+            for (int k = lane; k < nb; k += WAVE) {
+                double s = 0.0;
+                for (int r = 0; r < nr; r++) {
+                    double2 hx = make_double2(0.0, 0.0);
+                    for (int t = 0; t < nt; t++) {
+                        const double2 pr = cmul(Hb[r * nt + t], c[Pi[cur][k * nt + t]]);
+                        hx.x += pr.x;
+                        hx.y += pr.y;
+                    }
+                    s += abs2(csub(yb[r], hx));
+                }
+                const double n = sqrt(s);
+                Ct[k] = n * n;
+            }
+            __syncthreads();
+            const int nbt = nt * nbits;
+            for (int i = lane; i < nbt; i += WAVE) {
+                const int t = i / nbits, sh = nbits - 1 - (i - t * nbits);
+                double mn[2] = {INFINITY, INFINITY};
+                for (int k = 0; k < nb; k++) {
+                    const int bit = (Pi[cur][k * nt + t] >> sh) & 1;
+                    const double v = Ct[k];
+                    if (mn[bit] == mn[bit] && (v != v || v < mn[bit])) mn[bit] = v;   // NumPy's min: NaN propagates
+                }
+                out_llr[b * nbt + i] = -(mn[0] - mn[1]) / (2.0 * noise_var);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+std::atomic<int> g_kbest_general{-1};   // -1: not read yet; initial value from CPX_KBEST_PATH
+
+bool kbest_forced_general() {
+    int v = g_kbest_general.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("CPX_KBEST_PATH");
+        v = e && strcmp(e, "general") == 0 ? 1 : 0;
+        g_kbest_general.store(v, std::memory_order_relaxed);
+    }
+    return v == 1;
+}
+
+int grid_for(int64_t B) { return int(B < 1048576 ? B : 1048576); }
+
+int mimo_check(const cpx_modem *md, int64_t B, int nr, int nt, const char *what) {
+    CPX_REQUIRE(md, CPX_EINVAL, "%s: null modem", what);
+    if (int rc = check_handle_device(md->device, what)) return rc;
+    CPX_REQUIRE(B >= 0 && nr >= 1 && nt >= 1, CPX_EINVAL, "%s: need B >= 0, nr >= 1, nt >= 1", what);
+    return CPX_OK;
+}
+
+// K clipped to what the search can ever hold (m^nt survivors), saturating
+int kbest_effective_K(int K, int m, int nt) {
+    int64_t cap = 1;
+    for (int t = 0; t < nt && cap < K; t++) cap *= m;
+    return int(cap < K ? cap : K);
+}
+
+int kbest_run(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt, int K, int mode,
+              double noise_var, int32_t *d_idx, double *d_llr, int32_t *d_count, void *stream) {
+    const char *what = "kbest";
+    if (int rc = mimo_check(md, B, nr, nt, what)) return rc;
+    CPX_REQUIRE(nt <= nr, CPX_EINVAL, "h has more columns than rows");
+    CPX_REQUIRE(K >= 1, CPX_EINVAL, "kbest: K must be a positive integer");
+    if (B == 0) return CPX_OK;
+    const int m = md->M, Ke = kbest_effective_K(K, m, nt);
+    CPX_REQUIRE(int64_t(Ke) * m < MAX_HYP, CPX_ELIMIT, "kbest: K * m above 2^31 children");
+    hipStream_t st = pick_stream(stream);
+    const KbLayout L = kb_layout(nr, nt, Ke, m);
+    const double2 *y = reinterpret_cast<const double2 *>(d_y), *H = reinterpret_cast<const double2 *>(d_h);
+    const double2 *c = reinterpret_cast<const double2 *>(md->d_const);
+    const int64_t hs = h_batched ? int64_t(nr) * nt : 0;
+    if (L.bytes <= LDS_MAX && !kbest_forced_general()) {
+        hipLaunchKernelGGL(kbest_kernel<false>, dim3(grid_for(B)), dim3(WAVE), L.bytes, st, y, H, hs, B, nr, nt, c, m, md->nbits, Ke, L,
+                           (char *)nullptr, mode, noise_var, d_idx, d_llr, d_count);
+        CPX_HIP(hipGetLastError());
+        note_kernel("kbest_kernel<lds> (K %d, m %d, %dx%d)", Ke, m, nr, nt);
+        return CPX_OK;
+    }
+    IssueGuard guard;
+    int64_t grid = B < 2048 ? B : 2048;
+    const int64_t budget = (int64_t(1) << 31) / int64_t(L.bytes);   // at most 2 GB of workspace
+    if (grid > budget) grid = budget > 0 ? budget : 1;
+    void *ws = nullptr;
+    if (int rc = workspace(st, 13, size_t(grid) * L.bytes, &ws)) return rc;
+    hipLaunchKernelGGL(kbest_kernel<true>, dim3(int(grid)), dim3(WAVE), 0, st, y, H, hs, B, nr, nt, c, m, md->nbits, Ke, L,
+                       static_cast<char *>(ws), mode, noise_var, d_idx, d_llr, d_count);
+    CPX_HIP(hipGetLastError());
+    note_kernel("kbest_kernel<global> (K %d, m %d, %dx%d)", Ke, m, nr, nt);
+    return CPX_OK;
+}
+
+// host-buffer wrapper: upload y and H, run `dev`, download `out_bytes` (and `out2_bytes`)
+template <class F>
+int mimo_host(const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, void *out, size_t out_bytes, void *out2,
+              size_t out2_bytes, F dev) {
+    int rc = ensure_device();
+    if (rc) return rc;
+    CPX_REQUIRE(B >= 0 && nr >= 1 && nt >= 1, CPX_EINVAL, "mimo: need B >= 0, nr >= 1, nt >= 1");
+    CPX_REQUIRE((y && h && out) || B == 0, CPX_EINVAL, "mimo: null pointer");
+    if (B == 0) return dev(nullptr, nullptr, nullptr, nullptr, lib_stream());
+    const size_t ybytes = 16 * size_t(B) * nr, hbytes = 16 * size_t(nr) * nt * (h_batched ? size_t(B) : 1);
+    DevBuf dy, dh, dout, dout2;
+    if ((rc = dy.alloc(ybytes)) || (rc = dh.alloc(hbytes)) || (rc = dout.alloc(out_bytes)) || (rc = dout2.alloc(out2_bytes))) return rc;
+    hipStream_t st = lib_stream();
+    CPX_HIP(hipMemcpyAsync(dy.p, y, ybytes, hipMemcpyHostToDevice, st));
+    CPX_HIP(hipMemcpyAsync(dh.p, h, hbytes, hipMemcpyHostToDevice, st));
+    if ((rc = dev(dy.as<double>(), dh.as<double>(), dout.p, dout2.p, st))) return rc;
+    if ((rc = d2h_pageable(out, dout.p, out_bytes, st))) return rc;
+    if (out2 && out2_bytes) CPX_HIP(hipMemcpyAsync(out2, dout2.p, out2_bytes, hipMemcpyDeviceToHost, st));
+    CPX_HIP(hipStreamSynchronize(st));
+    return CPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cpx_kbest_set_path(const char *mode) {
+    if (mode && mode[0] && strcmp(mode, "auto") != 0 && strcmp(mode, "general") != 0) {
+        set_error("cpx_kbest_set_path: unknown mode '%s' (auto | general)", mode);
+        return CPX_EINVAL;
+    }
+    g_kbest_general.store(mode && strcmp(mode, "general") == 0 ? 1 : 0, std::memory_order_relaxed);
+    return CPX_OK;
+}
+
+int cpx_mimo_ml_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt,
+                    int32_t *d_idx, void *stream) {
+    CPX_TRACE("cpx_mimo_ml_dev");
+    if (int rc = mimo_check(md, B, nr, nt, "mimo_ml")) return rc;
+    const int m = md->M, lgm = md->nbits;
+    CPX_REQUIRE(int64_t(lgm) * nt <= 31, CPX_EINVAL, "mimo_ml: m^nt above 2^31 hypotheses per vector");
+    if (B == 0) return CPX_OK;
+    const size_t base = 16 * (size_t(nr) * nt + nr + size_t(WAVE) * nr), tab = 16 * size_t(nt) * m * nr;
+    CPX_REQUIRE(base <= LDS_MAX, CPX_ELIMIT, "mimo_ml: %d receive antennas exceed the kernel's LDS", nr);
+    hipStream_t st = pick_stream(stream);
+    const double2 *y = reinterpret_cast<const double2 *>(d_y), *H = reinterpret_cast<const double2 *>(d_h);
+    const double2 *c = reinterpret_cast<const double2 *>(md->d_const);
+    const int64_t hs = h_batched ? int64_t(nr) * nt : 0;
+    const bool use_tab = base + tab <= LDS_MAX;
+    if (use_tab)
+        hipLaunchKernelGGL(mimo_ml_kernel<true>, dim3(grid_for(B)), dim3(WAVE), base + tab, st, y, H, hs, B, nr, nt, c, m, lgm, d_idx);
+    else
+        hipLaunchKernelGGL(mimo_ml_kernel<false>, dim3(grid_for(B)), dim3(WAVE), base, st, y, H, hs, B, nr, nt, c, m, lgm, d_idx);
+    CPX_HIP(hipGetLastError());
+    note_kernel("mimo_ml_kernel<%s> (m %d, %dx%d)", use_tab ? "table" : "direct", m, nr, nt);
+    return CPX_OK;
+}
+
+int cpx_mimo_ml(const cpx_modem *md, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, int32_t *idx) {
+    CPX_TRACE("cpx_mimo_ml");
+    return mimo_host(y, h, h_batched, B, nr, nt, idx, 4 * size_t(B) * nt, nullptr, 0,
+                     [&](const double *dy, const double *dh, void *o, void *, hipStream_t st) {
+                         return cpx_mimo_ml_dev(md, dy, dh, h_batched, B, nr, nt, static_cast<int32_t *>(o), st);
+                     });
+}
+
+int cpx_kbest_hard_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt, int K,
+                       int32_t *d_idx, void *stream) {
+    CPX_TRACE("cpx_kbest_hard_dev");
+    return kbest_run(md, d_y, d_h, h_batched, B, nr, nt, K, KB_HARD, 0.0, d_idx, nullptr, nullptr, stream);
+}
+
+int cpx_kbest_hard(const cpx_modem *md, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, int K, int32_t *idx) {
+    CPX_TRACE("cpx_kbest_hard");
+    return mimo_host(y, h, h_batched, B, nr, nt, idx, 4 * size_t(B) * nt, nullptr, 0,
+                     [&](const double *dy, const double *dh, void *o, void *, hipStream_t st) {
+                         return cpx_kbest_hard_dev(md, dy, dh, h_batched, B, nr, nt, K, static_cast<int32_t *>(o), st);
+                     });
+}
+
+int cpx_kbest_soft_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt, int K,
+                       double noise_var, double *d_llr, void *stream) {
+    CPX_TRACE("cpx_kbest_soft_dev");
+    return kbest_run(md, d_y, d_h, h_batched, B, nr, nt, K, KB_SOFT, noise_var, nullptr, d_llr, nullptr, stream);
+}
+
+int cpx_kbest_soft(const cpx_modem *md, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, int K,
+                   double noise_var, double *llr) {
+    CPX_TRACE("cpx_kbest_soft");
+    const size_t nbits = md ? size_t(md->nbits) : 0;
+    return mimo_host(y, h, h_batched, B, nr, nt, llr, 8 * size_t(B) * nt * nbits, nullptr, 0,
+                     [&](const double *dy, const double *dh, void *o, void *, hipStream_t st) {
+                         return cpx_kbest_soft_dev(md, dy, dh, h_batched, B, nr, nt, K, noise_var, static_cast<double *>(o), st);
+                     });
+}
+
+int cpx_kbest_list_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt, int K,
+                       int32_t *d_cand, int32_t *d_count, void *stream) {
+    CPX_TRACE("cpx_kbest_list_dev");
+    return kbest_run(md, d_y, d_h, h_batched, B, nr, nt, K, KB_LIST, 0.0, d_cand, nullptr, d_count, stream);
+}
+
+int cpx_kbest_list(const cpx_modem *md, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, int K,
+                   int32_t *cand, int32_t *count) {
+    CPX_TRACE("cpx_kbest_list");
+    CPX_REQUIRE(md && K >= 1 && nt >= 1, CPX_EINVAL, "kbest: null modem, K < 1 or nt < 1");
+    const size_t ke = size_t(kbest_effective_K(K, md->M, nt));
+    return mimo_host(y, h, h_batched, B, nr, nt, cand, 4 * size_t(B) * ke * nt, count, 4 * size_t(B),
+                     [&](const double *dy, const double *dh, void *o, void *o2, hipStream_t st) {
+                         return cpx_kbest_list_dev(md, dy, dh, h_batched, B, nr, nt, K, static_cast<int32_t *>(o),
+                                                   static_cast<int32_t *>(o2), st);
+                     });
+}
+
+}  // extern "C"

@@ -12,14 +12,21 @@ of ``tx_batch`` transmissions is generated, modulated, propagated, demodulated a
 arrays -- one GPU launch per stage instead of one Python call per transmission -- and the reference's
 sequential stop rule is applied to the per-transmission error counts afterwards.  As soon as one callback is
 not marked, transmissions run one at a time exactly like the reference (same random stream, same stop rule,
-six-argument decoders recognised by arity).  MIMO channels are out of scope.
+six-argument decoders recognised by arity).
+
+MIMO channels (``commpy_amd.channels.MIMOFlatChannel``) always run one transmission at a time, as the reference's loop
+does (links.py:229-249).  ``receive`` is then called once per received vector with its channel matrix -- or, when it is
+marked ``batched``, once per transmission with ``y [nb_vect, nr]`` and ``H [nb_vect, nr, nt]`` (one GPU launch);
+``mimo_receiver`` builds such a receiver around the K-best or ML kernels.
 """
 from fractions import Fraction
 from inspect import getfullargspec
 
 import numpy as np
 
-__all__ = ['link_performance', 'LinkModel']
+from commpy_amd.channels import MIMOFlatChannel
+
+__all__ = ['link_performance', 'LinkModel', 'mimo_receiver']
 
 
 def link_performance(link_model, SNRs, send_max, err_min, send_chunk=None, code_rate=1):
@@ -29,6 +36,33 @@ def link_performance(link_model, SNRs, send_max, err_min, send_chunk=None, code_
 
 def _is_batched(fn):
     return bool(getattr(fn, 'batched', False))
+
+
+def mimo_receiver(modem, detector='kbest', K=16, output_type='hard'):
+    """A batched ``receive(y, H, constellation, noise_var)`` for LinkModel over a MIMOFlatChannel: every vector of one
+    transmission detected in one launch.  ``detector`` 'kbest' (``K``, 'hard' -> bits of the detected symbols, 'soft' ->
+    max-log LLRs) or 'ml' (hard bits).  Bits are the modem's labels, MSB first, antenna after antenna: what
+    ``modem.demodulate(kbest(y_i, H_i, constellation, K), 'hard')`` gives vector by vector."""
+    from commpy_amd.modulation import kbest_batch, mimo_ml_batch
+    if detector not in ('kbest', 'ml') or output_type not in ('hard', 'soft') or (detector == 'ml' and output_type == 'soft'):
+        raise ValueError("detector must be 'kbest' (hard or soft) or 'ml' (hard)")
+    nb = modem.num_bits_symbol
+    shifts = np.arange(nb - 1, -1, -1)
+
+    def receive(y, h, constellation, noise_var):
+        y = np.atleast_2d(y)
+        if output_type == 'soft':
+            return kbest_batch(y, h, modem, K, noise_var, 'soft').reshape(-1)
+        if detector == 'ml':
+            symbols = mimo_ml_batch(y, h, modem)
+        else:
+            symbols = kbest_batch(y, h, modem, K)
+        # a detected symbol is a constellation point: its index is its label
+        labels = np.argmax(symbols.reshape(-1)[:, None] == modem.constellation[None, :], axis=1)
+        return ((labels[:, None] >> shifts) & 1).reshape(-1)
+
+    receive.batched = True
+    return receive
 
 
 class LinkModel:
@@ -46,7 +80,20 @@ class LinkModel:
 
     # -- one block of transmissions ------------------------------------------------------------
     def _all_batched(self):
-        return _is_batched(self.modulate) and _is_batched(self.receive) and _is_batched(self.decoder)
+        return (_is_batched(self.modulate) and _is_batched(self.receive) and _is_batched(self.decoder)
+                and not isinstance(self.channel, MIMOFlatChannel))
+
+    def _receive_mimo(self, out, n_bits, noise_var):
+        """The received words of one MIMO transmission (links.py:232-239): per vector, or all vectors at once for a batched
+        ``receive``."""
+        gains = self.channel.channel_gains
+        if _is_batched(self.receive):
+            return np.asarray(self.receive(out, gains, self.constellation, noise_var)).reshape(-1)
+        size = self.channel.nb_tx * self.num_bits_symbol
+        words = np.empty(int(np.ceil(n_bits / float(self.rate))))
+        for i in range(len(out)):
+            words[size * i:size * (i + 1)] = self.receive(out[i], gains[i], self.constellation, noise_var)
+        return words
 
     def _block_size(self, remaining):
         """Transmissions per block: ``tx_batch`` on the batched (GPU) path; ONE when any callback is the reference's
@@ -71,7 +118,10 @@ class LinkModel:
             msg = np.random.choice((0, 1), n_bits)
             out = self.channel.propagate(self.modulate(msg))
             noise_var = self.channel.noise_std ** 2
-            received = self.receive(out, self.channel.channel_gains, self.constellation, noise_var)
+            if isinstance(self.channel, MIMOFlatChannel):
+                received = self._receive_mimo(out, n_bits, noise_var)
+            else:
+                received = self.receive(out, self.channel.channel_gains, self.constellation, noise_var)
             if full_args_decoder:
                 dec = self.decoder(out, self.channel.channel_gains, self.constellation, noise_var, received,
                                    self.channel.nb_tx * self.num_bits_symbol)

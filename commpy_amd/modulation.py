@@ -3,8 +3,10 @@
 Same public names, arguments and return conventions as /root/reference/commpy/modulation.py:39-262
 (``Modem``, ``PSKModem``, ``QAMModem``).  Construction, Gray re-indexing, ``modulate`` and ``Es`` stay on
 the host; ``demodulate`` ('hard' and 'soft') runs on the GPU through ``cpx_demod_hard`` /
-``cpx_demod_soft`` (csrc/demod.hip).  MIMO detectors and OFDM helpers of the reference module are
-out of scope.
+``cpx_demod_soft`` (csrc/demod.hip).  The MIMO detectors ``mimo_ml`` and ``kbest`` (modulation.py:299-406) run on the
+GPU too (csrc/mimo.hip), with batched forms ``mimo_ml_batch`` / ``kbest_batch`` for throughput; ``max_log_approx`` and
+``bit_lvl_repr`` are small host functions.  ``best_first_detector`` and the OFDM helpers of the reference module are out
+of scope.
 """
 import ctypes
 
@@ -13,7 +15,8 @@ import numpy as np
 from commpy_amd import _lib
 from commpy_amd.utilities import signal_power
 
-__all__ = ['PSKModem', 'QAMModem', 'Modem']
+__all__ = ['PSKModem', 'QAMModem', 'Modem', 'mimo_ml', 'kbest', 'max_log_approx', 'bit_lvl_repr', 'mimo_ml_batch',
+           'kbest_batch']
 
 
 def _gray_rank(m):
@@ -145,3 +148,133 @@ class QAMModem(Modem):
         imag = np.tile(np.hstack((pam, pam[::-1])), side // 2)
         real = pam.repeat(side)
         super().__init__(imag * 1j + real)
+
+
+# ---- MIMO detection (csrc/mimo.hip) ------------------------------------------------------------------------------------------
+_const_modems = {}
+
+
+def _modem_for(constellation):
+    """A Modem over ``constellation`` as given (no Gray re-indexing): the device copy the MIMO kernels search over.  Kept per
+    constellation so that a link simulation does not re-upload it for every vector.  The engine's modems need a power-of-two
+    number of points (ValueError otherwise)."""
+    pts = np.ascontiguousarray(constellation, dtype=np.complex128).reshape(-1)
+    key = pts.tobytes()
+    md = _const_modems.get(key)
+    if md is None:
+        if len(_const_modems) > 64:
+            _const_modems.clear()
+        md = _const_modems[key] = Modem(pts, reorder_as_gray=False)
+    return md
+
+
+def _mimo_inputs(y, h):
+    """(y [B, nr], h, h_batched, B, nr, nt) as complex128 C arrays; h is [nr, nt] (shared) or [B, nr, nt]."""
+    y2 = np.ascontiguousarray(np.atleast_2d(y), dtype=np.complex128)
+    hh = np.ascontiguousarray(h, dtype=np.complex128)
+    if hh.ndim not in (2, 3):
+        raise ValueError('h must be [nr, nt] or [B, nr, nt]')
+    B, nr = y2.shape
+    if hh.shape[-2] != nr or (hh.ndim == 3 and hh.shape[0] != B):
+        raise ValueError('shape mismatch: y %s, h %s' % (y2.shape, hh.shape))
+    return y2, hh, int(hh.ndim == 3), B, nr, hh.shape[-1]
+
+
+def _kbest_checks(nr, nt, output_type):
+    if nt > nr:
+        raise ValueError('h has more columns than rows')
+    if output_type not in ('hard', 'soft'):
+        raise ValueError('output_type must be "hard" or "soft"')
+
+
+def _ml_indices(y, h, modem):
+    y2, hh, hb, B, nr, nt = _mimo_inputs(y, h)
+    idx = np.zeros((B, nt), dtype=np.int32)
+    if B:
+        _lib.check(_lib.load().cpx_mimo_ml(modem._device_handle(), _lib.ptr(y2), _lib.ptr(hh), hb, B, nr, nt, _lib.ptr(idx)))
+    return idx
+
+
+def _kbest_list(y, h, modem, K):
+    """Final K-best candidates: (indices [B, Ke, nt] with -1 past the count, count [B]); Ke = min(K, m^nt)."""
+    y2, hh, hb, B, nr, nt = _mimo_inputs(y, h)
+    ke = min(int(K), modem.m ** nt)
+    cand = np.zeros((B, ke, nt), dtype=np.int32)
+    count = np.zeros(B, dtype=np.int32)
+    if B:
+        _lib.check(_lib.load().cpx_kbest_list(modem._device_handle(), _lib.ptr(y2), _lib.ptr(hh), hb, B, nr, nt, int(K),
+                                              _lib.ptr(cand), _lib.ptr(count)))
+    return cand, count
+
+
+def mimo_ml(y, h, constellation):
+    """Exhaustive ML detection of one received vector (modulation.py:299): the hypothesis of ``constellation`` points
+    minimising ``|y - h x|``, first minimum in the reference's hypothesis order.  Returns complex [nt]."""
+    md = _modem_for(constellation)
+    return md.constellation.astype(complex)[_ml_indices(y, h, md)[0]]
+
+
+def mimo_ml_batch(y, h, constellation):
+    """``mimo_ml`` for every row of ``y [B, nr]`` in one launch; ``h`` is [nr, nt] or [B, nr, nt].  Returns complex [B, nt]."""
+    md = constellation if isinstance(constellation, Modem) else _modem_for(constellation)
+    return md.constellation.astype(complex)[_ml_indices(y, h, md)]
+
+
+def kbest(y, h, constellation, K, noise_var=0, output_type='hard', demode=None):
+    """K-best Schnorr-Euchner detection of one vector (modulation.py:325).  'hard': the best candidate, as the
+    constellation's dtype; 'soft': ``max_log_approx`` over the final list with ``demode`` (search on the GPU, the LLRs on the
+    host so that any ``demode`` behaves as in the reference).  Ties between equal distances go to the lowest child position."""
+    h = np.asarray(h)
+    nr, nt = h.shape
+    _kbest_checks(nr, nt, output_type)
+    pts = np.asarray(constellation)
+    kind = complex if isinstance(pts[0], complex) else float
+    md = _modem_for(pts)
+    if output_type == 'hard':
+        y2, hh, hb, B, nr, nt = _mimo_inputs(y, h)
+        idx = np.zeros((1, nt), dtype=np.int32)
+        _lib.check(_lib.load().cpx_kbest_hard(md._device_handle(), _lib.ptr(y2), _lib.ptr(hh), hb, 1, nr, nt, int(K),
+                                              _lib.ptr(idx)))
+        return pts[idx[0]].astype(kind)
+    cand, count = _kbest_list(y, h, md, K)
+    survivors = pts[cand[0, :count[0]]].astype(kind).T            # [nt, n] points column-wise
+    return max_log_approx(np.asarray(y), h, noise_var, survivors, demode)
+
+
+def kbest_batch(y, h, modem, K, noise_var=0, output_type='hard'):
+    """``kbest`` for every row of ``y [B, nr]`` in one launch; ``h`` is [nr, nt] or [B, nr, nt].  'hard': symbols
+    [B, nt] of ``modem.constellation``; 'soft': LLRs [B, nt * num_bits_symbol] computed on the device with the modem's labels
+    (what ``demode = modem.demodulate(., 'hard')`` gives the single-vector form)."""
+    y2, hh, hb, B, nr, nt = _mimo_inputs(y, h)
+    _kbest_checks(nr, nt, output_type)
+    lib, dev = _lib.load(), modem._device_handle()
+    if output_type == 'hard':
+        idx = np.zeros((B, nt), dtype=np.int32)
+        if B:
+            _lib.check(lib.cpx_kbest_hard(dev, _lib.ptr(y2), _lib.ptr(hh), hb, B, nr, nt, int(K), _lib.ptr(idx)))
+        return modem.constellation[idx]
+    llr = np.zeros((B, nt * modem.num_bits_symbol))
+    if B:
+        _lib.check(lib.cpx_kbest_soft(dev, _lib.ptr(y2), _lib.ptr(hh), hb, B, nr, nt, int(K), float(noise_var), _lib.ptr(llr)))
+    return llr
+
+
+def max_log_approx(y, h, noise_var, pts_list, demode):
+    """Max-log LLRs of the bits of a candidate list (modulation.py:599): ``pts_list`` [nt, n] holds the candidates
+    column-wise, ``demode`` maps their points (candidate after candidate) to bits.  LLR of bit k =
+    (min distance with bit 1 - min distance with bit 0) / (2 noise_var), an empty side counting as +inf."""
+    n = pts_list.shape[1]
+    words = np.asarray(demode(pts_list.reshape(-1, order='F'))).reshape(n, -1)
+    dist = np.linalg.norm(y[:, None] - h.dot(pts_list), axis=0) ** 2
+    gap = np.empty(words.shape[1])
+    for k, column in enumerate(words.T):
+        best = [np.min(np.append(dist[column == v], np.inf)) for v in (0, 1)]
+        gap[k] = best[0] - best[1]
+    return -gap / (2 * noise_var)
+
+
+def bit_lvl_repr(H, w):
+    """Bit-level channel matrix ``H (I_nt kron w)`` (modulation.py:568); ``w`` must have an even length."""
+    if len(w) % 2:
+        raise ValueError('Beta (length of w) must be even.')
+    return np.asarray(H).dot(np.kron(np.identity(np.shape(H)[1]), w))

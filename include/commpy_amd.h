@@ -306,6 +306,43 @@ int cpx_demod_hard(const cpx_modem *m, const double *y_re_im, int64_t Ns, int8_t
 int cpx_demod_hard_dev(const cpx_modem *m, const double *d_y_re_im, int64_t Ns, int8_t *d_bits,
                        void *stream);
 
+/* ---- MIMO detection ------------------------------------------------------------------------------
+ * Replace mimo_ml / kbest of commpy/modulation.py:299-406 (with max_log_approx :599-646 for the soft output) for a batch of B
+ * received vectors.  The constellation is the modem's (cpx_modem_create), float64 throughout.
+ *   y [B][nr] complex (re, im); h [nr][nt] complex shared by the batch (h_batched = 0) or [B][nr][nt] (h_batched = 1);
+ *   outputs are constellation INDICES.
+ * cpx_mimo_ml:    idx [B][nt] of the first minimum of |y - H x|^2 over all m^nt hypotheses, antenna 0 the most significant
+ *                 base-m digit (modulation.py:314-317).  CPX_EINVAL above 2^31 hypotheses per vector; CPX_ELIMIT when nr is
+ *                 so large that one vector's H and residuals exceed 64 KB of LDS.
+ * cpx_kbest_*:    K-best breadth-first search after a Householder QR of each H; the K smallest accumulated distances survive
+ *                 each antenna, ties broken by the lowest child position (point index * nb_can + parent).  nt > nr: CPX_EINVAL.
+ *   _hard         idx [B][nt] of the best surviving candidate;
+ *   _soft         llr [B][nt * log2 m]: max-log LLRs over the final list on the original y and H, bit k of a candidate = the
+ *                 MSB-first bits of its indices (the modem's labels), value (min_1 - min_0) / (2 noise_var), +-inf where no
+ *                 candidate carries a bit value, IEEE results for noise_var = 0;
+ *   _list         cand [B][Ke][nt] the final candidates in ascending distance (rows past count[b] hold -1), count [B];
+ *                 Ke = min(K, m^nt).
+ * States up to 64 KB per vector run LDS-resident; larger ones, or all after cpx_kbest_set_path("general") (initial value:
+ * environment variable CPX_KBEST_PATH), take the same search with its state in a global workspace.  cpx_last_kernel names
+ * what ran. */
+int cpx_kbest_set_path(const char *mode);
+int cpx_mimo_ml(const cpx_modem *m, const double *y_re_im, const double *h_re_im, int h_batched, int64_t B, int nr, int nt,
+                int32_t *idx);
+int cpx_mimo_ml_dev(const cpx_modem *m, const double *d_y_re_im, const double *d_h_re_im, int h_batched, int64_t B, int nr, int nt,
+                    int32_t *d_idx, void *stream);
+int cpx_kbest_hard(const cpx_modem *m, const double *y_re_im, const double *h_re_im, int h_batched, int64_t B, int nr, int nt,
+                   int K, int32_t *idx);
+int cpx_kbest_hard_dev(const cpx_modem *m, const double *d_y_re_im, const double *d_h_re_im, int h_batched, int64_t B, int nr,
+                       int nt, int K, int32_t *d_idx, void *stream);
+int cpx_kbest_soft(const cpx_modem *m, const double *y_re_im, const double *h_re_im, int h_batched, int64_t B, int nr, int nt,
+                   int K, double noise_var, double *llr);
+int cpx_kbest_soft_dev(const cpx_modem *m, const double *d_y_re_im, const double *d_h_re_im, int h_batched, int64_t B, int nr,
+                       int nt, int K, double noise_var, double *d_llr, void *stream);
+int cpx_kbest_list(const cpx_modem *m, const double *y_re_im, const double *h_re_im, int h_batched, int64_t B, int nr, int nt,
+                   int K, int32_t *cand, int32_t *count);
+int cpx_kbest_list_dev(const cpx_modem *m, const double *d_y_re_im, const double *d_h_re_im, int h_batched, int64_t B, int nr,
+                       int nt, int K, int32_t *d_cand, int32_t *d_count, void *stream);
+
 /* ---- link-simulation stages around the decoders ("next" rows) ---------------------------
  * Device-resident (all pointers are device pointers, asynchronous on `stream`), so that a Monte-Carlo
  * BER sweep (commpy/links.py:155-267, commpy/wifi80211.py:132-216) never leaves HBM.

@@ -4,9 +4,13 @@ that covers the clock ramp; results are checked against the single-vector API af
     python benchmarks/bench_mimo.py [--scale 1.0]
   kbest_hard / kbest_soft  4x4 16-QAM, K = 16, B = 2^20 vectors, one H per vector
   ml_qpsk / ml_qam16       4x4 QPSK (B = 2^20) and 4x4 16-QAM (B = 16384: 1.07e9 hypotheses)
-The bound is the float64 VALU rate: `flop` counts the float64 operations of the search (per ML hypothesis nr complex
+  best_first               4x4 16-QAM, stack sizes (1, 3, 5), llr_max 500, B = 2^20 vectors, one H per vector; also the mean and
+                           maximum number of search iterations per vector (a second, untimed launch with the iteration counter)
+For ML and K-best the bound is the float64 VALU rate: `flop` counts the float64 operations of the search (per ML hypothesis nr complex
 subtractions, squares and sums: 6 nr; per K-best child one complex multiply-subtract, a square and a sum: 12; the QR and the
-selection are not counted) against the spec vector FP64 peak.  The counters of a rocprofv3 --pmc run of their own are
+selection are not counted) against the spec vector FP64 peak.  Best-first is a serial search of one wave per vector: its
+`flop` is an upper bound (every pop evaluating m children twice at 8 depth + 6 float64 operations each), quoted only to show
+how far it is from that bound.  The counters of a rocprofv3 --pmc run of their own are
 quoted from profiles/ (profiles/README.md)."""
 import argparse
 import ctypes
@@ -104,18 +108,50 @@ def bench_ml(lib, scale, rs):
         dev.free()
 
 
+def bench_best_first(lib, scale, rs):
+    from commpy_amd.modulation import QAMModem, best_first_detector
+    md = QAMModem(16)
+    dem = lambda s: md.demodulate(s, 'hard')  # noqa: E731
+    B, nr, nt, stacks = int((1 << 20) * scale), 4, 4, (1, 3, 5)
+    y, h = _problem(rs, B, nr, nt, md, 0.5)
+    dev = Dev(lib)
+    dy, dh = dev.put(y), dev.put(h)
+    dllr, diters = dev.empty(8 * B * nr * 4), dev.empty(4 * B)
+    sizes = np.array(stacks, dtype=np.int32)
+    mh = md._device_handle()
+
+    def run(iters=None):
+        _lib.check(lib.cpx_best_first_dev(mh, dy, dh, 1, B, nr, nt, _lib.ptr(sizes), 500.0, None, dllr, iters, None))
+    ms, _ = timeit(lib, run, steps=5, warmup=2)
+    kernel = _lib.last_kernel()
+    got = dev.get(dllr, (B, nr * 4), np.float64)
+    run(diters)
+    it = dev.get(diters, (B,), np.int32)
+    pick = rs.choice(B, 24, replace=False)
+    ok = bool(all(np.array_equal(best_first_detector(y[b], h[b], md.constellation, stacks, 0.25, dem, 500), got[b]) for b in pick))
+    ok = ok and bool(np.all(it > 0)) and bool(np.array_equal(dev.get(dllr, (B, nr * 4), np.float64), got))
+    children = float(it.sum()) * (nr - 1) * 2 * 16            # upper bound: every stack popped in every iteration
+    flop = children * (8 * nr + 6)
+    emit("best_first", "4x4 16-QAM stacks (1,3,5) llr_max 500, B=%d, H per vector" % B, B, children, ms, flop,
+         {"checked_vectors": len(pick), "check_ok": ok, "kernel_path": kernel, "iterations_mean": float(it.mean()),
+          "iterations_max": int(it.max()), "us_per_vector_per_wave": ms * 1e3 / B})
+    dev.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0)
-    ap.add_argument("--which", default="kbest,ml")
+    ap.add_argument("--which", default="kbest,ml,best_first")
     a = ap.parse_args()
     lib = _lib.load()
     _lib.require_device()
     rs = np.random.RandomState(11)
     if "kbest" in a.which:
         bench_kbest(lib, a.scale, rs)
-    if "ml" in a.which:
+    if "ml" in a.which.split(","):
         bench_ml(lib, a.scale, rs)
+    if "best_first" in a.which:
+        bench_best_first(lib, a.scale, rs)
 
 
 if __name__ == "__main__":

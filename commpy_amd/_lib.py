@@ -110,6 +110,10 @@ SYMBOLS = {
     "cpx_kbest_list": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cpx_kbest_list_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p]),
+    "cpx_best_first_set_path": (c_int, [c_char_p]),
+    "cpx_best_first": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_double, c_void_p, c_void_p]),
+    "cpx_best_first_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_double, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]),
     "cpx_random_bits_dev": (c_int, [c_void_p, c_int64, c_uint64, c_uint64, c_void_p]),
     "cpx_conv_encode_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "cpx_gather_u8_dev": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
@@ -275,6 +279,11 @@ def ldpc_set_path(mode):
 def kbest_set_path(mode):
     """K-best kernel storage: None/'auto' (LDS-resident where the state of a vector fits 64 KB) or 'general' (global workspace)."""
     check(load().cpx_kbest_set_path(None if mode is None else mode.encode()))
+
+
+def best_first_set_path(mode):
+    """Best-first kernel storage: None/'auto' (LDS-resident where the state of a vector fits 64 KB) or 'general' (global workspace)."""
+    check(load().cpx_best_first_set_path(None if mode is None else mode.encode()))
 
 
 class DeviceHandles:

@@ -1,5 +1,6 @@
-// MIMO detection (commpy/modulation.py:299-406, 568-646): exhaustive ML search and K-best Schnorr-Euchner search with hard,
-// soft (max-log over the final candidate list) and candidate-list outputs.  float64 throughout, -ffp-contract=off.
+// MIMO detection (commpy/modulation.py:299-565, 568-646): exhaustive ML search, K-best Schnorr-Euchner search with hard,
+// soft (max-log over the final candidate list) and candidate-list outputs, and the soft-output best-first stack search (see
+// the section below and DESIGN.md 4.7).  float64 throughout, -ffp-contract=off.
 //
 // One wave (64 lanes, one workgroup) per received vector, grid-striding over the batch.
 //   ML      the nt x m table of column-times-point products sits in LDS (when it fits); lanes stride over hypothesis PREFIXES
@@ -99,6 +100,40 @@ __global__ __launch_bounds__(WAVE) void mimo_ml_kernel(const double2 *__restrict
     }
 }
 
+// complex Householder QR of the row-major [nr][w] matrix A = [H | y] (w = nt + 1) by one wave, in place: after the first
+// kend columns, the upper part of A[0..kend-1][0..w-2] holds R and A[0..kend-1][w-1] = Q^H y.  Below the diagonal: the
+// reflectors (not read by the searches).
+__device__ __forceinline__ void householder_qr(double2 *A, int nr, int w, int kend, int lane) {
+    for (int k = 0; k < kend; k++) {
+        double tail = 0.0;
+        for (int i = k + 1; i < nr; i++) tail += abs2(A[i * w + k]);
+        const double2 x0 = A[k * w + k];
+        const double nx = sqrt(abs2(x0) + tail);
+        const double ax0 = hypot(x0.x, x0.y);
+        const double2 ph = ax0 > 0.0 ? make_double2(x0.x / ax0, x0.y / ax0) : make_double2(1.0, 0.0);
+        const double2 alpha = make_double2(-ph.x * nx, -ph.y * nx);
+        const double2 v0 = csub(x0, alpha);
+        const double vn2 = abs2(v0) + tail;
+        const bool reflect = nx > 0.0 && vn2 > 0.0;
+        if (reflect) {
+            for (int j = k + 1 + lane; j < w; j += WAVE) {
+                double2 s = make_double2(v0.x * A[k * w + j].x + v0.y * A[k * w + j].y, v0.x * A[k * w + j].y - v0.y * A[k * w + j].x);
+                for (int i = k + 1; i < nr; i++) {
+                    const double2 vi = A[i * w + k], a = A[i * w + j];
+                    s.x += vi.x * a.x + vi.y * a.y;      // conj(v_i) a
+                    s.y += vi.x * a.y - vi.y * a.x;
+                }
+                const double2 f = make_double2(2.0 * s.x / vn2, 2.0 * s.y / vn2);
+                A[k * w + j] = csub(A[k * w + j], cmul(f, v0));
+                for (int i = k + 1; i < nr; i++) A[i * w + j] = csub(A[i * w + j], cmul(f, A[i * w + k]));
+            }
+        }
+        __syncthreads();
+        if (lane == 0 && reflect) A[k * w + k] = alpha;
+        __syncthreads();
+    }
+}
+
 // ---- K-best -----------------------------------------------------------------------------------------------------------------
 struct KbLayout {   // byte offsets into one vector's state
     size_t A, Pd0, Pd1, Pt0, Pt1, Pi0, Pi1, Ct, sel, Ck, bytes;
@@ -148,35 +183,7 @@ __global__ __launch_bounds__(WAVE) void kbest_kernel(const double2 *__restrict__
             A[i] = j < nt ? Hb[r * nt + j] : yb[r];
         }
         __syncthreads();
-        // Householder QR: after column k, A[0..nt-1][0..nt-1] holds R (upper part) and A[0..nt-1][nt] = Q^H y
-        for (int k = 0; k < nt; k++) {
-            double tail = 0.0;
-            for (int i = k + 1; i < nr; i++) tail += abs2(A[i * w + k]);
-            const double2 x0 = A[k * w + k];
-            const double nx = sqrt(abs2(x0) + tail);
-            const double ax0 = hypot(x0.x, x0.y);
-            const double2 ph = ax0 > 0.0 ? make_double2(x0.x / ax0, x0.y / ax0) : make_double2(1.0, 0.0);
-            const double2 alpha = make_double2(-ph.x * nx, -ph.y * nx);
-            const double2 v0 = csub(x0, alpha);
-            const double vn2 = abs2(v0) + tail;
-            const bool reflect = nx > 0.0 && vn2 > 0.0;
-            if (reflect) {
-                for (int j = k + 1 + lane; j < w; j += WAVE) {
-                    double2 s = make_double2(v0.x * A[k * w + j].x + v0.y * A[k * w + j].y, v0.x * A[k * w + j].y - v0.y * A[k * w + j].x);
-                    for (int i = k + 1; i < nr; i++) {
-                        const double2 vi = A[i * w + k], a = A[i * w + j];
-                        s.x += vi.x * a.x + vi.y * a.y;      // conj(v_i) a
-                        s.y += vi.x * a.y - vi.y * a.x;
-                    }
-                    const double2 f = make_double2(2.0 * s.x / vn2, 2.0 * s.y / vn2);
-                    A[k * w + j] = csub(A[k * w + j], cmul(f, v0));
-                    for (int i = k + 1; i < nr; i++) A[i * w + j] = csub(A[i * w + j], cmul(f, A[i * w + k]));
-                }
-            }
-            __syncthreads();
-            if (lane == 0 && reflect) A[k * w + k] = alpha;
-            __syncthreads();
-        }
+        householder_qr(A, nr, w, nt, lane);   // A[0..nt-1][0..nt-1] holds R (upper part), A[0..nt-1][nt] = Q^H y
         // the search, antenna nt-1 down to 0
         int cur = 0, nb = 1;
         for (int t = lane; t < nt; t += WAVE) { Pd[0][t] = A[t * w + nt]; Pi[0][t] = 0; }
@@ -326,6 +333,335 @@ int kbest_run(const cpx_modem *md, const double *d_y, const double *d_h, int h_b
     return CPX_OK;
 }
 
+// ---- best-first (soft output) -----------------------------------------------------------------------------------------------
+// The stack search of commpy/modulation.py:422-565.  Stack i (0 <= i < nr) holds nodes of depth d = nr - i: the symbols of
+// positions i..nr-1.  A stack is an array of records sorted by metric (insertion after equal metrics, bisect.insort); a
+// record is 8-byte words {metric, parent metric, int32 rank among its siblings, int32 symbols[d]}, so that a node's next
+// sibling is found again by re-evaluating its parent's m children (one per lane) and selecting rank + 1.  Stack i never
+// holds more than cap[i] = min(stack_size[i-1] + 1, m^d) records (one pop and at most two pushes per iteration, each tree
+// node pushed at most once); stack 0 holds at most the one leaf of an iteration.
+constexpr int BF_MAXNR = 64;
+
+struct BfLayout {
+    int64_t off[BF_MAXNR];    // byte offset of stack i's records
+    int32_t cap[BF_MAXNR];    // capacity of stack i (records)
+    int32_t keep[BF_MAXNR];   // stack i is truncated to keep[i] records after each iteration (stack_size[i-1]; keep[0] = 0)
+    size_t A, counter, cm, mapsym, cnt, cur, sel, bytes;
+    int64_t max_iter;         // sum_{c=1..nr} m^c, saturated: the number of tree nodes, a hard cap on the iterations
+};
+
+__host__ __device__ inline int bf_words(int d) { return 2 + (d + 2) / 2; }   // record of a depth-d node, 8-byte words
+
+// m^e saturated at `limit`
+int64_t pow_sat(int64_t m, int e, int64_t limit) {
+    int64_t r = 1;
+    for (int i = 0; i < e; i++) {
+        if (r > limit / m) return limit;
+        r *= m;
+    }
+    return r < limit ? r : limit;
+}
+
+// false: the state of one vector exceeds what the engine can address (a stack of over 2^31 records or 2^40 bytes)
+bool bf_layout(int nr, int nt, int m, int nbits, const int32_t *stack_size, BfLayout *L) {
+    memset(L, 0, sizeof(*L));
+    size_t o = 0;
+    auto take = [&](size_t n, size_t al) { o = (o + al - 1) / al * al; size_t r = o; o += n; return r; };
+    L->A = take(16 * size_t(nr) * (nt + 1), 16);
+    L->counter = take(8 * size_t(nr) * nbits, 8);
+    L->cm = take(8 * size_t(m), 8);
+    L->cur = take(8 * size_t(bf_words(nr)), 8);
+    L->sel = take(16, 8);
+    L->mapsym = take(4 * size_t(nr), 4);
+    L->cnt = take(4 * size_t(nr), 4);
+    for (int i = 0; i < nr; i++) {
+        const int64_t s = i == 0 ? 0 : stack_size[i - 1];
+        const int64_t cap = i == 0 ? 1 : pow_sat(m, nr - i, s + 1);
+        if (cap > INT32_MAX) return false;
+        L->cap[i] = int32_t(cap);
+        L->keep[i] = int32_t(s < cap ? s : cap);
+        L->off[i] = int64_t(take(8 * size_t(cap) * bf_words(nr - i), 8));
+        if (o > (size_t(1) << 40)) return false;
+    }
+    L->bytes = (o + 15) / 16 * 16;
+    int64_t total = 0;
+    for (int c = 1; c <= nr; c++) {
+        const int64_t t = pow_sat(m, c, INT64_MAX);
+        total = t > INT64_MAX - total ? INT64_MAX : total + t;
+    }
+    L->max_iter = total;
+    return true;
+}
+
+// NumPy's maximum / minimum: a NaN operand propagates
+__device__ __forceinline__ double np_max(double a, double b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
+__device__ __forceinline__ double np_min(double a, double b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = WAVE / 2; off >= 1; off >>= 1) v = np_max(v, __shfl_xor(v, off));
+    return v;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int off = WAVE / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+template <bool GLOBAL>
+__global__ __launch_bounds__(WAVE) void best_first_kernel(const double2 *__restrict__ y, const double2 *__restrict__ H, int64_t hstride,
+                                                          int64_t B, int nr, int nt, const double2 *__restrict__ c, int m, int nbits,
+                                                          const uint8_t *__restrict__ labels, double llr_max, BfLayout L, char *ws,
+                                                          double *__restrict__ out_llr, int32_t *__restrict__ out_iters) {
+    extern __shared__ double2 lds_bf[];
+    char *base = GLOBAL ? ws + size_t(blockIdx.x) * L.bytes : reinterpret_cast<char *>(lds_bf);
+    double2 *A = reinterpret_cast<double2 *>(base + L.A);
+    double *counter = reinterpret_cast<double *>(base + L.counter);
+    double *cm = reinterpret_cast<double *>(base + L.cm);
+    uint64_t *cur = reinterpret_cast<uint64_t *>(base + L.cur);
+    double *sel_m = reinterpret_cast<double *>(base + L.sel);
+    int32_t *sel_q = reinterpret_cast<int32_t *>(base + L.sel + 8);
+    int32_t *mapsym = reinterpret_cast<int32_t *>(base + L.mapsym);
+    int32_t *cnt = reinterpret_cast<int32_t *>(base + L.cnt);
+    const int lane = threadIdx.x;
+    const int w = nt + 1;
+    const int nbt = nr * nbits;
+    auto stack = [&](int i) { return reinterpret_cast<uint64_t *>(base + L.off[i]); };
+    auto rec_metric = [](const uint64_t *r) { return __longlong_as_double((long long)r[0]); };
+    auto rec_ints = [](uint64_t *r) { return reinterpret_cast<int32_t *>(r + 2); };   // [0] rank, [1..d] symbols
+    auto label = [&](int sym, int b) -> int { return labels ? labels[sym * nbits + b] != 0 : (sym >> (nbits - 1 - b)) & 1; };
+
+    // metrics of the m children of the depth-(cd-1) node {parent symbols `ps`, metric pm} into cm[], then the child of rank r
+    // in (metric, index) order -- NaN last, equal metrics to the lowest index: -> (*q, *met), uniform
+    auto select_child = [&](int cd, const int32_t *ps, double pm, int r, int *q_out, double *met_out) {
+        const int row = nr - cd, col0 = nt - cd;
+        const double2 *Ar = A + row * w;
+        double lm = NAN;
+        int li = INT32_MAX;
+        for (int q = lane; q < m; q += WAVE) {
+            double2 s = cmul(Ar[col0], c[q]);
+            for (int k = 1; k < cd; k++) {
+                const double2 p = cmul(Ar[col0 + k], c[ps[k - 1]]);
+                s.x += p.x;
+                s.y += p.y;
+            }
+            const double2 e = csub(Ar[nt], s);
+            const double a = hypot(e.x, e.y);
+            const double met = a * a + pm;
+            cm[q] = met;
+            if (li == INT32_MAX || key_less<false>(met, q, lm, li)) { lm = met; li = q; }
+        }
+        __syncthreads();
+        if (r == 0) {
+            long long li64 = li == INT32_MAX ? 0x7fffffffffffffffll : li;
+            wave_argmin<false>(lm, li64);
+            *q_out = int(li64);
+            *met_out = lm;
+            return;
+        }
+        for (int q = lane; q < m; q += WAVE) {
+            const double mq = cm[q];
+            int rank = 0;
+            for (int o = 0; o < m; o++) rank += key_less<false>(cm[o], o, mq, q);
+            if (rank == r) { *sel_q = q; *sel_m = mq; }
+        }
+        __syncthreads();
+        *q_out = *sel_q;
+        *met_out = *sel_m;
+        __syncthreads();
+    };
+
+    // insert a depth-(nr-i) record {met, pm, rank, [q, ps[0..d-2]]} into stack i after the records of metric <= met.
+    // false: the stack is full, which the capacity bound excludes (the vector is then reported, not written)
+    auto insert = [&](int i, double met, double pm, int rank, int q, const int32_t *ps) -> bool {
+        const int d = nr - i, W = bf_words(d), n = cnt[i];
+        if (n >= L.cap[i]) return false;
+        uint64_t *st = stack(i);
+        int le = 0;
+        for (int k = lane; k < n; k += WAVE) le += rec_metric(st + size_t(k) * W) <= met;
+        const int pos = wave_sum(le);
+        const int64_t lo = int64_t(pos) * W;
+        for (int64_t hi = int64_t(n) * W; hi > lo; hi -= WAVE) {   // shift [pos, n) one record up, top chunk first
+            const int64_t j = hi - WAVE + lane;
+            const bool mv = j >= lo;
+            const uint64_t v = mv ? st[j] : 0;
+            __syncthreads();
+            if (mv) st[j + W] = v;
+            __syncthreads();
+        }
+        if (lane == 0) {
+            uint64_t *r = st + size_t(pos) * W;
+            r[0] = (uint64_t)__double_as_longlong(met);
+            r[1] = (uint64_t)__double_as_longlong(pm);
+            int32_t *ri = rec_ints(r);
+            ri[0] = rank;
+            ri[1] = q;
+            for (int k = 0; k + 1 < d; k++) ri[2 + k] = ps[k];
+            cnt[i] = n + 1;
+        }
+        __syncthreads();
+        return true;
+    };
+
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        const double2 *Hb = H + b * hstride, *yb = y + b * nr;
+        for (int i = lane; i < nr * w; i += WAVE) {
+            const int r = i / w, j = i - r * w;
+            A[i] = j < nt ? Hb[r * nt + j] : yb[r];
+        }
+        for (int e = lane; e < nbt; e += WAVE) counter[e] = INFINITY;
+        for (int i = lane; i < nr; i += WAVE) cnt[i] = 0;
+        __syncthreads();
+        householder_qr(A, nr, w, nr, lane);   // nr <= nt: R is [nr][nt], upper trapezoidal
+        bool have_map = false, bad = false;
+        double map = INFINITY;
+        // the best child of the root goes to the last stack unconditionally
+        {
+            int q;
+            double met;
+            select_child(1, nullptr, 0.0, 0, &q, &met);
+            bad |= !insert(nr - 1, met, 0.0, 0, q, nullptr);
+        }
+        int64_t iter = 0;
+        for (;;) {
+            bool any = false;
+            for (int i = 1; i < nr; i++) any |= cnt[i] > 0;
+            if (!any || bad) break;
+            if (++iter > L.max_iter) { bad = true; break; }
+            for (int i = 1; i < nr; i++) {   // pop stack i, push its next sibling back and its best child into stack i - 1
+                const int n = cnt[i];
+                if (n == 0) continue;
+                const int d = nr - i, W = bf_words(d);
+                uint64_t *st = stack(i);
+                for (int k = lane; k < W; k += WAVE) cur[k] = st[k];
+                __syncthreads();
+                for (int64_t lo = 0; lo < int64_t(n - 1) * W; lo += WAVE) {   // pop the front: shift [1, n) one record down
+                    const int64_t j = lo + lane;
+                    const bool mv = j < int64_t(n - 1) * W;
+                    const uint64_t v = mv ? st[j + W] : 0;
+                    __syncthreads();
+                    if (mv) st[j] = v;
+                    __syncthreads();
+                }
+                if (lane == 0) cnt[i] = n - 1;
+                __syncthreads();
+                const double node_met = rec_metric(cur), node_pm = __longlong_as_double((long long)cur[1]);
+                const int32_t *ci = rec_ints(cur);
+                const int rank = ci[0];
+                const int32_t *syms = ci + 1;   // positions i..nr-1
+                // search radius: inf before the first leaf, else max(max(counter[:i]), max(counter[i:] where the bits differ
+                // from the MAP's)), an empty selection counting as +inf
+                double radius = INFINITY;
+                if (have_map) {
+                    double lo_max = -INFINITY, a2 = -INFINITY;
+                    bool differ = false;
+                    for (int e = lane; e < nbt; e += WAVE) {
+                        const int t = e / nbits, bb = e - t * nbits;
+                        if (t < i) lo_max = np_max(lo_max, counter[e]);
+                        else if (label(syms[t - i], bb) != label(mapsym[t], bb)) { a2 = np_max(a2, counter[e]); differ = true; }
+                    }
+                    lo_max = wave_max(lo_max);
+                    a2 = __any(differ) ? wave_max(a2) : INFINITY;
+                    radius = a2 > lo_max ? a2 : lo_max;   // Python's max(a, b)
+                }
+                if (rank + 1 < m) {
+                    int q;
+                    double met;
+                    select_child(d, syms + 1, node_pm, rank + 1, &q, &met);
+                    if (met <= radius) bad |= !insert(i, met, node_pm, rank + 1, q, syms + 1);
+                }
+                {
+                    int q;
+                    double met;
+                    select_child(d + 1, syms, node_met, 0, &q, &met);
+                    if (met <= radius) bad |= !insert(i - 1, met, node_met, 0, q, syms);
+                }
+            }
+            if (cnt[0] > 0) {   // the leaf of this iteration
+                const uint64_t *leaf = stack(0);
+                const double lm = rec_metric(leaf);
+                const int32_t *ls = reinterpret_cast<const int32_t *>(leaf + 2) + 1;
+                const bool better = lm < map;
+                const double with = better ? map : lm;
+                if (better) {
+                    map = lm;
+                    have_map = true;
+                    for (int t = lane; t < nr; t += WAVE) mapsym[t] = ls[t];
+                }
+                const double lo = map - llr_max, hi = map + llr_max;
+                for (int e = lane; e < nbt; e += WAVE) counter[e] = np_min(np_max(np_min(counter[e], with), lo), hi);
+                __syncthreads();
+            }
+            if (lane == 0)
+                for (int i = 0; i < nr; i++) cnt[i] = cnt[i] < L.keep[i] ? cnt[i] : L.keep[i];
+            __syncthreads();
+        }
+        for (int e = lane; e < nbt; e += WAVE) {
+            double v = NAN;
+            if (have_map && !bad) {
+                const int t = e / nbits;
+                v = (map - counter[e]) * (label(mapsym[t], e - t * nbits) ? 1.0 : -1.0);
+            }
+            out_llr[b * nbt + e] = v;
+        }
+        if (out_iters && lane == 0) out_iters[b] = bad ? -1 : int32_t(iter < INT32_MAX ? iter : INT32_MAX);
+        __syncthreads();
+    }
+}
+
+std::atomic<int> g_bf_general{-1};   // -1: not read yet; initial value from CPX_BEST_FIRST_PATH
+
+bool bf_forced_general() {
+    int v = g_bf_general.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("CPX_BEST_FIRST_PATH");
+        v = e && strcmp(e, "general") == 0 ? 1 : 0;
+        g_bf_general.store(v, std::memory_order_relaxed);
+    }
+    return v == 1;
+}
+
+int bf_run(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt,
+           const int32_t *stack_size, double llr_max, const uint8_t *d_labels, double *d_llr, int32_t *d_iters, void *stream) {
+    const char *what = "best_first";
+    if (int rc = mimo_check(md, B, nr, nt, what)) return rc;
+    CPX_REQUIRE(nr >= 2, CPX_EINVAL, "best_first: need at least 2 receive antennas (h has %d rows)", nr);
+    CPX_REQUIRE(nr <= nt, CPX_EINVAL, "best_first: h has more rows than columns (%d > %d): no leaf can be reached", nr, nt);
+    CPX_REQUIRE(nr <= BF_MAXNR, CPX_ELIMIT, "best_first: %d receive antennas above the engine's %d", nr, BF_MAXNR);
+    CPX_REQUIRE(stack_size, CPX_EINVAL, "best_first: null stack_size");
+    for (int i = 0; i + 1 < nr; i++)
+        CPX_REQUIRE(stack_size[i] >= 1, CPX_EINVAL, "best_first: stack_size[%d] = %d; every stack must hold a node", i, stack_size[i]);
+    const int m = md->M;
+    CPX_REQUIRE(m >= 2 && (m & (m - 1)) == 0, CPX_EINVAL, "best_first: the constellation length %d is not a power of two", m);
+    BfLayout L;
+    CPX_REQUIRE(bf_layout(nr, nt, m, md->nbits, stack_size, &L), CPX_ELIMIT, "best_first: the stacks of one vector exceed the engine's state limit");
+    if (B == 0) return CPX_OK;
+    hipStream_t st = pick_stream(stream);
+    const double2 *y = reinterpret_cast<const double2 *>(d_y), *H = reinterpret_cast<const double2 *>(d_h);
+    const double2 *c = reinterpret_cast<const double2 *>(md->d_const);
+    const int64_t hs = h_batched ? int64_t(nr) * nt : 0;
+    if (L.bytes <= LDS_MAX && !bf_forced_general()) {
+        hipLaunchKernelGGL(best_first_kernel<false>, dim3(grid_for(B)), dim3(WAVE), L.bytes, st, y, H, hs, B, nr, nt, c, m, md->nbits,
+                           d_labels, llr_max, L, (char *)nullptr, d_llr, d_iters);
+        CPX_HIP(hipGetLastError());
+        note_kernel("best_first_kernel<lds> (m %d, %dx%d, %zu B per vector)", m, nr, nt, L.bytes);
+        return CPX_OK;
+    }
+    CPX_REQUIRE(L.bytes <= (size_t(1) << 31), CPX_ELIMIT, "best_first: %zu bytes of state per vector above the 2 GB workspace", L.bytes);
+    IssueGuard guard;
+    int64_t grid = B < 2048 ? B : 2048;
+    const int64_t budget = (int64_t(1) << 31) / int64_t(L.bytes);   // at most 2 GB of workspace
+    if (grid > budget) grid = budget > 0 ? budget : 1;
+    void *ws = nullptr;
+    if (int rc = workspace(st, 14, size_t(grid) * L.bytes, &ws)) return rc;
+    hipLaunchKernelGGL(best_first_kernel<true>, dim3(int(grid)), dim3(WAVE), 0, st, y, H, hs, B, nr, nt, c, m, md->nbits, d_labels,
+                       llr_max, L, static_cast<char *>(ws), d_llr, d_iters);
+    CPX_HIP(hipGetLastError());
+    note_kernel("best_first_kernel<global> (m %d, %dx%d, %zu B per vector)", m, nr, nt, L.bytes);
+    return CPX_OK;
+}
+
 // host-buffer wrapper: upload y and H, run `dev`, download `out_bytes` (and `out2_bytes`)
 template <class F>
 int mimo_host(const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, void *out, size_t out_bytes, void *out2,
@@ -438,6 +774,53 @@ int cpx_kbest_list(const cpx_modem *md, const double *y, const double *h, int h_
                          return cpx_kbest_list_dev(md, dy, dh, h_batched, B, nr, nt, K, static_cast<int32_t *>(o),
                                                    static_cast<int32_t *>(o2), st);
                      });
+}
+
+}  // extern "C"
+
+extern "C" {
+
+int cpx_best_first_set_path(const char *mode) {
+    if (mode && mode[0] && strcmp(mode, "auto") != 0 && strcmp(mode, "general") != 0) {
+        set_error("cpx_best_first_set_path: unknown mode '%s' (auto | general)", mode);
+        return CPX_EINVAL;
+    }
+    g_bf_general.store(mode && strcmp(mode, "general") == 0 ? 1 : 0, std::memory_order_relaxed);
+    return CPX_OK;
+}
+
+int cpx_best_first_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt,
+                       const int32_t *stack_size, double llr_max, const uint8_t *d_labels, double *d_llr, int32_t *d_iters,
+                       void *stream) {
+    CPX_TRACE("cpx_best_first_dev");
+    return bf_run(md, d_y, d_h, h_batched, B, nr, nt, stack_size, llr_max, d_labels, d_llr, d_iters, stream);
+}
+
+int cpx_best_first(const cpx_modem *md, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt,
+                   const int32_t *stack_size, double llr_max, const uint8_t *labels, double *llr) {
+    CPX_TRACE("cpx_best_first");
+    CPX_REQUIRE(md, CPX_EINVAL, "best_first: null modem");
+    const int nbits = md->nbits;
+    if (labels)
+        for (int i = 0; i < md->M * nbits; i++)
+            CPX_REQUIRE(labels[i] <= 1, CPX_EINVAL, "best_first: label table entry %d is %d, not 0 or 1", i, int(labels[i]));
+    int rc = ensure_device();
+    if (rc) return rc;
+    DevBuf dl;
+    if (labels && B > 0) {
+        if ((rc = dl.alloc(size_t(md->M) * nbits))) return rc;
+        CPX_HIP(hipMemcpy(dl.p, labels, size_t(md->M) * nbits, hipMemcpyHostToDevice));
+    }
+    std::vector<int32_t> iters(size_t(B > 0 ? B : 0));
+    rc = mimo_host(y, h, h_batched, B, nr, nt, llr, 8 * size_t(B) * nr * nbits, iters.data(), 4 * iters.size(),
+                   [&](const double *dy, const double *dh, void *o, void *o2, hipStream_t st) {
+                       return cpx_best_first_dev(md, dy, dh, h_batched, B, nr, nt, stack_size, llr_max, dl.as<uint8_t>(),
+                                                 static_cast<double *>(o), static_cast<int32_t *>(o2), st);
+                   });
+    if (rc) return rc;
+    for (int64_t b = 0; b < B; b++)
+        CPX_REQUIRE(iters[b] >= 0, CPX_EHIP, "best_first: vector %lld hit the search's iteration cap (an engine fault)", (long long)b);
+    return CPX_OK;
 }
 
 }  // extern "C"

@@ -17,8 +17,10 @@ six-argument decoders recognised by arity).
 MIMO channels (``commpy_amd.channels.MIMOFlatChannel``) always run one transmission at a time, as the reference's loop
 does (links.py:229-249).  ``receive`` is then called once per received vector with its channel matrix -- or, when it is
 marked ``batched``, once per transmission with ``y [nb_vect, nr]`` and ``H [nb_vect, nr, nt]`` (one GPU launch);
-``mimo_receiver`` builds such a receiver around the K-best or ML kernels.
+``mimo_receiver`` builds such a receiver around the K-best, ML or best-first kernels; ``idd_decoder`` builds the
+reference's iterative detection-and-decoding decoder from host callbacks.
 """
+import operator
 from fractions import Fraction
 from inspect import getfullargspec
 
@@ -26,7 +28,7 @@ import numpy as np
 
 from commpy_amd.channels import MIMOFlatChannel
 
-__all__ = ['link_performance', 'LinkModel', 'mimo_receiver']
+__all__ = ['link_performance', 'LinkModel', 'mimo_receiver', 'idd_decoder']
 
 
 def link_performance(link_model, SNRs, send_max, err_min, send_chunk=None, code_rate=1):
@@ -38,14 +40,29 @@ def _is_batched(fn):
     return bool(getattr(fn, 'batched', False))
 
 
-def mimo_receiver(modem, detector='kbest', K=16, output_type='hard'):
+def mimo_receiver(modem, detector='kbest', K=16, output_type='hard', stack_size=(1, 3, 5), llr_max=500):
     """A batched ``receive(y, H, constellation, noise_var)`` for LinkModel over a MIMOFlatChannel: every vector of one
     transmission detected in one launch.  ``detector`` 'kbest' (``K``, 'hard' -> bits of the detected symbols, 'soft' ->
-    max-log LLRs) or 'ml' (hard bits).  Bits are the modem's labels, MSB first, antenna after antenna: what
-    ``modem.demodulate(kbest(y_i, H_i, constellation, K), 'hard')`` gives vector by vector."""
-    from commpy_amd.modulation import kbest_batch, mimo_ml_batch
+    max-log LLRs), 'ml' (hard bits) or 'best_first' (soft: the LLRs of ``best_first_detector`` with ``stack_size`` and
+    ``llr_max``; ``output_type`` is not used).  Bits are the modem's labels, MSB first, antenna after antenna: what
+    ``modem.demodulate(kbest(y_i, H_i, constellation, K), 'hard')`` gives vector by vector, and what
+    ``best_first_detector(y_i, H_i, constellation, stack_size, noise_var, demode, llr_max)`` gives with
+    ``demode = modem.demodulate(., 'hard')``."""
+    from commpy_amd.modulation import _bf_stacks, best_first_batch, kbest_batch, mimo_ml_batch
+    if detector == 'best_first':
+        sizes = tuple(stack_size)
+        if len(sizes) < 1 or min(operator.index(s) for s in sizes) < 1:
+            raise ValueError('stack_size must hold positive integers')
+        llr_max = float(llr_max)
+
+        def receive_bf(y, h, constellation, noise_var):
+            y = np.atleast_2d(y)
+            _bf_stacks(y.shape[1], np.shape(h)[-1], sizes)
+            return best_first_batch(y, h, modem, sizes, llr_max).reshape(-1)
+        receive_bf.batched = True
+        return receive_bf
     if detector not in ('kbest', 'ml') or output_type not in ('hard', 'soft') or (detector == 'ml' and output_type == 'soft'):
-        raise ValueError("detector must be 'kbest' (hard or soft) or 'ml' (hard)")
+        raise ValueError("detector must be 'kbest' (hard or soft), 'ml' (hard) or 'best_first'")
     nb = modem.num_bits_symbol
     shifts = np.arange(nb - 1, -1, -1)
 
@@ -63,6 +80,25 @@ def mimo_receiver(modem, detector='kbest', K=16, output_type='hard'):
 
     receive.batched = True
     return receive
+
+
+def idd_decoder(detector, decoder, decision, n_it):
+    """Iterative detection and decoding (links.py:345-407): returns the six-argument
+    ``decode(y, h, constellation, noise_var, a_priori, bits_per_send)`` that LinkModel recognises by its arity.  Each of the
+    ``n_it`` rounds feeds the decoder's extrinsic LLRs (its output minus its input) to ``detector(y_i, h_i, constellation,
+    noise_var, a_priori_i)`` vector by vector (``bits_per_send`` LLRs each) and removes them again from what the detector
+    returns; ``decision`` gets the last detector output plus the last extrinsic LLRs.  Host-only: the callbacks do the work."""
+    def decode(y, h, constellation, noise_var, a_priori, bits_per_send):
+        llr_dec = np.array(a_priori, copy=True)
+        for _ in range(n_it):
+            extrinsic = decoder(llr_dec) - llr_dec
+            for v in range(np.shape(h)[0]):
+                part = slice(v * bits_per_send, (v + 1) * bits_per_send)
+                llr_dec[part] = detector(y[v], h[v], constellation, noise_var, extrinsic[part])
+            llr_dec -= extrinsic
+        return decision(llr_dec + extrinsic)
+
+    return decode
 
 
 class LinkModel:

@@ -4,11 +4,13 @@ Same public names, arguments and return conventions as /root/reference/commpy/mo
 (``Modem``, ``PSKModem``, ``QAMModem``).  Construction, Gray re-indexing, ``modulate`` and ``Es`` stay on
 the host; ``demodulate`` ('hard' and 'soft') runs on the GPU through ``cpx_demod_hard`` /
 ``cpx_demod_soft`` (csrc/demod.hip).  The MIMO detectors ``mimo_ml`` and ``kbest`` (modulation.py:299-406) run on the
-GPU too (csrc/mimo.hip), with batched forms ``mimo_ml_batch`` / ``kbest_batch`` for throughput; ``max_log_approx`` and
-``bit_lvl_repr`` are small host functions.  ``best_first_detector`` and the OFDM helpers of the reference module are out
-of scope.
+GPU too (csrc/mimo.hip), with batched forms ``mimo_ml_batch`` / ``kbest_batch`` for throughput; The soft-output
+``best_first_detector`` (modulation.py:422-565) runs on the GPU as well, with ``best_first_batch`` as its batched form.
+``max_log_approx`` and ``bit_lvl_repr`` are small host functions.  The OFDM helpers of the reference module are out of scope
+(SURVEY section 2, row 7).
 """
 import ctypes
+import operator
 
 import numpy as np
 
@@ -16,7 +18,7 @@ from commpy_amd import _lib
 from commpy_amd.utilities import signal_power
 
 __all__ = ['PSKModem', 'QAMModem', 'Modem', 'mimo_ml', 'kbest', 'max_log_approx', 'bit_lvl_repr', 'mimo_ml_batch',
-           'kbest_batch']
+           'kbest_batch', 'best_first_detector', 'best_first_batch']
 
 
 def _gray_rank(m):
@@ -257,6 +259,92 @@ def kbest_batch(y, h, modem, K, noise_var=0, output_type='hard'):
     if B:
         _lib.check(lib.cpx_kbest_soft(dev, _lib.ptr(y2), _lib.ptr(hh), hb, B, nr, nt, int(K), float(noise_var), _lib.ptr(llr)))
     return llr
+
+
+def _bf_stacks(nr, nt, stack_size):
+    """The reference's failures as ValueError, then the nr - 1 stack sizes as int32 (entries past them are ignored, sizes
+    above 2^31 - 1 clipped: no stack of a tree this engine can search is that deep)."""
+    if nr < 2:
+        raise ValueError('best_first_detector needs at least 2 receive antennas (h has %d rows)' % nr)
+    if nr > nt:
+        raise ValueError('h has more rows than columns (%d > %d): the best-first search reaches no leaf' % (nr, nt))
+    sizes = [operator.index(s) for s in tuple(stack_size)[:nr - 1]]
+    if len(sizes) < nr - 1:
+        raise ValueError('stack_size needs %d entries (one per stack but the first), got %d' % (nr - 1, len(sizes)))
+    if min(sizes) < 1:
+        raise ValueError('every stack size must be at least 1 (got %s): the search would reach no leaf' % (sizes,))
+    return np.array([min(s, 2 ** 31 - 1) for s in sizes], dtype=np.int32)
+
+
+_label_tables = {}
+
+
+def _demode_labels(demode, constellation, nbits):
+    """``demode``'s bits of every constellation point as a [m, nbits] uint8 table, built once per (demode, constellation).
+    ValueError unless ``demode`` maps each point on its own (checked on a fixed permutation of the points) to 0 / 1 bits."""
+    pts = np.asarray(constellation)
+    key = (id(demode), pts.tobytes())
+    hit = _label_tables.get(key)
+    if hit is not None and hit[0] is demode:
+        return hit[1]
+    m = pts.size
+    table = np.asarray(demode(pts)).reshape(-1)
+    if table.size != m * nbits:
+        raise ValueError('demode returned %d bits for %d points; %d expected' % (table.size, m, m * nbits))
+    if not np.all((table == 0) | (table == 1)):
+        raise ValueError('demode must return 0 / 1 bits')
+    table = table.reshape(m, nbits)
+    perm = np.random.RandomState(m).permutation(m)[::-1]
+    again = np.asarray(demode(pts[perm])).reshape(-1)
+    if again.size != m * nbits or not np.array_equal(again.reshape(m, nbits), table[perm]):
+        raise ValueError('demode is not symbol-wise: the bits of a point depend on the other points given with it')
+    labels = np.ascontiguousarray(table, dtype=np.uint8)
+    if len(_label_tables) > 64:
+        _label_tables.clear()
+    _label_tables[key] = (demode, labels)
+    return labels
+
+
+def _best_first(y, h, modem, stack_size, llr_max, labels):
+    y2, hh, hb, B, nr, nt = _mimo_inputs(y, h)
+    sizes = _bf_stacks(nr, nt, stack_size)
+    llr = np.zeros((B, nr * modem.num_bits_symbol))
+    if labels is not None:
+        labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        if labels.shape != (modem.m, modem.num_bits_symbol):
+            raise ValueError('labels must be [%d, %d]' % (modem.m, modem.num_bits_symbol))
+    if B:
+        _lib.check(_lib.load().cpx_best_first(modem._device_handle(), _lib.ptr(y2), _lib.ptr(hh), hb, B, nr, nt, _lib.ptr(sizes),
+                                              float(llr_max), None if labels is None else _lib.ptr(labels), _lib.ptr(llr)))
+    return llr
+
+
+def best_first_detector(y, h, constellation, stack_size, noise_var, demode, llr_max):
+    """Soft-output best-first detection of one vector (modulation.py:422): LLRs float64 [nr * log2 m], position after
+    position, each ``(map metric - counter metric) * (+1 / -1)`` for the MAP's bit as ``demode`` labels it, clipped to
+    ``llr_max``.  As in the reference there are nr stacks (``nb_tx, nb_rx = h.shape``), ``stack_size`` needs nr - 1 entries
+    (more are ignored) and ``noise_var`` is not used.  ValueError where the reference fails (nr < 2, nr > nt, a short
+    stack_size or a size below 1) and for a vector that reaches no leaf (NaN / inf input: the reference raises TypeError);
+    also for a ``demode`` that is not symbol-wise or returns other than 0 / 1.  Children of equal metric are taken in
+    ascending constellation index."""
+    h = np.asarray(h)
+    if h.ndim != 2:
+        raise ValueError('h must be [nr, nt]')
+    nr, nt = h.shape
+    _bf_stacks(nr, nt, stack_size)
+    md = _modem_for(constellation)
+    labels = _demode_labels(demode, np.asarray(constellation), md.num_bits_symbol)
+    llr = _best_first(np.asarray(y).reshape(1, -1), h, md, stack_size, llr_max, labels)[0]
+    if np.all(np.isnan(llr)):
+        raise ValueError('best_first_detector: the search reached no leaf (NaN or inf in y or h?)')
+    return llr
+
+
+def best_first_batch(y, h, modem, stack_size, llr_max, labels=None):
+    """``best_first_detector`` for every row of ``y [B, nr]`` in one launch; ``h`` is [nr, nt] or [B, nr, nt].  LLRs
+    [B, nr * num_bits_symbol] with the bits of ``labels`` ([m, num_bits_symbol] 0/1, default: the modem's labels, what
+    ``demode = modem.demodulate(., 'hard')`` gives); a row of NaN marks a vector that reached no leaf."""
+    return _best_first(y, h, modem, stack_size, llr_max, labels)
 
 
 def max_log_approx(y, h, noise_var, pts_list, demode):

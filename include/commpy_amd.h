@@ -343,6 +343,27 @@ int cpx_kbest_list(const cpx_modem *m, const double *y_re_im, const double *h_re
 int cpx_kbest_list_dev(const cpx_modem *m, const double *d_y_re_im, const double *d_h_re_im, int h_batched, int64_t B, int nr,
                        int nt, int K, int32_t *d_cand, int32_t *d_count, void *stream);
 
+/* cpx_best_first: the soft-output best-first stack search of commpy/modulation.py:422-565 after a Householder QR of [H | y]:
+ *   nr stacks (one per receive antenna, as the reference's nb_tx, nb_rx = h.shape), stack i truncated to stack_size[i-1]
+ *   records after every iteration (stack_size has nr - 1 entries, further entries are ignored), LLR clipping at llr_max.
+ *   llr [B][nr * log2 m] = (map metric - counter metric) * (+1 / -1 for the MAP's bit), position after position, bits in the
+ *   label order of `labels` [m][log2 m] (0/1 bytes; null: the index bits, MSB first -- what Modem.demodulate(., 'hard')
+ *   gives).  A vector that reaches no leaf (NaN / inf input) gets NaN LLRs.  Children of equal metric are taken in
+ *   ascending constellation index.  CPX_EINVAL: nr < 2, nr > nt (the reference then reaches no leaf), a stack size < 1, a
+ *   label entry other than 0 / 1; CPX_ELIMIT: nr > 64.  The iterations are capped at the number of tree nodes
+ *   (sum_{c=1..nr} m^c), which the search cannot exceed: a vector that hits the cap is an engine fault (cpx_best_first:
+ *   CPX_EHIP; _dev: iters[b] = -1 and NaN LLRs).  noise_var of the reference is not an argument: it does not use it.
+ * cpx_best_first_dev: device pointers (labels too, nullable) on `stream`, except stack_size (host);
+ *   d_iters [B] (nullable) receives the number of search iterations of each vector.
+ * States up to 64 KB per vector run LDS-resident; larger ones, or all after cpx_best_first_set_path("general") (initial
+ * value: environment variable CPX_BEST_FIRST_PATH), take the same search with its state in a global workspace. */
+int cpx_best_first_set_path(const char *mode);
+int cpx_best_first(const cpx_modem *m, const double *y_re_im, const double *h_re_im, int h_batched, int64_t B, int nr, int nt,
+                   const int32_t *stack_size, double llr_max, const uint8_t *labels, double *llr);
+int cpx_best_first_dev(const cpx_modem *m, const double *d_y_re_im, const double *d_h_re_im, int h_batched, int64_t B, int nr,
+                       int nt, const int32_t *stack_size, double llr_max, const uint8_t *d_labels, double *d_llr,
+                       int32_t *d_iters, void *stream);
+
 /* ---- link-simulation stages around the decoders ("next" rows) ---------------------------
  * Device-resident (all pointers are device pointers, asynchronous on `stream`), so that a Monte-Carlo
  * BER sweep (commpy/links.py:155-267, commpy/wifi80211.py:132-216) never leaves HBM.

@@ -92,8 +92,7 @@ def bench_demod(lib, scale):
         d_ls = [dev.empty(ns * nb * 8) for _ in range(2)]
         h = md._device_handle()
         for mode in (None, "libm"):
-            _lib.demod_set_path(mode)
-            try:
+            with _lib.forced_path("demod", mode):
                 cnt = [0]
 
                 def step():
@@ -102,8 +101,6 @@ def bench_demod(lib, scale):
                 ms, _ = timeit(lib, step, steps=6, warmup=2)
                 emit(_lib.last_kernel(), "%d-PSK soft LLR, %d symbols, HBM-resident (2 inputs in turn)" % (m, ns), ns, "symbols", ms,
                      ns * (16 + 8 * nb), "hbm + valu")
-            finally:
-                _lib.demod_set_path(None)
         dev.free()
 
 
@@ -253,12 +250,9 @@ def bench_viterbi_variants(lib, scale):
         dev = Dev(lib)
         d_in, d_out = dev.put(llr), dev.empty(B * 1030)
         h = tr._device_handle()
-        _lib.viterbi_set_path(path)
-        try:
+        with _lib.forced_path("viterbi", path):
             ms, _ = timeit(lib, lambda: _lib.check(lib.cpx_viterbi_decode_batch_dev(h, d_in, B, 2060, 1030, 1030, tb, 1, d_out, None)), steps=10)
             name = _lib.last_kernel()
-        finally:
-            _lib.viterbi_set_path(None)
         emit(name, "config-2 geometry, %s, B=%d" % (what, B), B * 1024, "info-bits", ms, B * 17510, "valu")
         dev.free()
 
@@ -275,12 +269,9 @@ def bench_viterbi_k9(lib, scale):
         dev = Dev(lib)
         d_in, d_out = dev.put(llr), dev.empty(B * L)
         h = tr._device_handle()
-        _lib.viterbi_set_path(path)
-        try:
+        with _lib.forced_path("viterbi", path):
             ms, _ = timeit(lib, lambda: _lib.check(lib.cpx_viterbi_decode_batch_dev(h, d_in, B, coded.shape[1], L, T, 40, 1, d_out, None)), steps=3)
             name = _lib.last_kernel()
-        finally:
-            _lib.viterbi_set_path(None)
         emit(name, "K=9 (561,753) r=1/2, 1024-bit blocks, soft, tb_depth 40, B=%d" % B, B * 1024, "info-bits", ms, B * (coded.shape[1] * 8 + L), "valu")
         dev.free()
 

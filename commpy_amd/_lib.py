@@ -2,6 +2,7 @@
 include/commpy_amd.h.  There is NO CPU fallback: if the library is missing or no HIP device is
 usable, the decoders raise -- loudly -- instead of computing on the host.
 """
+import contextlib
 import ctypes
 import os
 from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_int8, c_int32, c_int64, c_size_t,
@@ -233,9 +234,14 @@ def build_id():
     return dict(part.split(":", 1) for part in txt.split(";") if ":" in part)
 
 
+def _set_mode(setter, mode):
+    """Set one of the engine's process-wide kernel-path switches through its C setter; None resets it to the default."""
+    check(getattr(load(), setter)(None if mode is None else mode.encode()))
+
+
 def set_precision(mode):
     """'fp64-parity' (default; None resets to it) or 'fp32-fast' (float32 variants where they exist; not bit-exact)."""
-    check(load().cpx_set_precision(None if mode is None else mode.encode()))
+    _set_mode("cpx_set_precision", mode)
 
 
 def get_precision():
@@ -261,29 +267,46 @@ def viterbi_last_path():
 
 def viterbi_set_path(mode):
     """Force a Viterbi kernel path: None/'auto', 'wave', 'cw', 'cw!', 'cw2', 'cw2!', 'general' (tests and benchmarks)."""
-    check(load().cpx_viterbi_set_path(None if mode is None else mode.encode()))
+    _set_mode("cpx_viterbi_set_path", mode)
 
 
 def demod_set_path(mode):
     """Soft-demodulator form: None/'auto' (two exponentials per axis for square QAM of 64 points and more, table-driven exp / log),
     'libm' (the same with the library's exp / log) or 'plain' (one exponential per level)."""
-    check(load().cpx_demod_set_path(None if mode is None else mode.encode()))
+    _set_mode("cpx_demod_set_path", mode)
 
 
 def ldpc_set_path(mode):
     """Force an LDPC decoder path: None/'auto', 'tiled' (HBM-resident tiles), 'resident' (LDS-resident, strict), 'resident-log' (the same with
     the log-domain sum-product row instead of the ratio-domain kernel)."""
-    check(load().cpx_ldpc_set_path(None if mode is None else mode.encode()))
+    _set_mode("cpx_ldpc_set_path", mode)
 
 
 def kbest_set_path(mode):
     """K-best kernel storage: None/'auto' (LDS-resident where the state of a vector fits 64 KB) or 'general' (global workspace)."""
-    check(load().cpx_kbest_set_path(None if mode is None else mode.encode()))
+    _set_mode("cpx_kbest_set_path", mode)
 
 
 def best_first_set_path(mode):
     """Best-first kernel storage: None/'auto' (LDS-resident where the state of a vector fits 64 KB) or 'general' (global workspace)."""
-    check(load().cpx_best_first_set_path(None if mode is None else mode.encode()))
+    _set_mode("cpx_best_first_set_path", mode)
+
+
+PATH_KINDS = ("viterbi", "ldpc", "demod", "kbest", "best_first")
+
+
+@contextlib.contextmanager
+def forced_path(kind, mode):
+    """Force a kernel path for the duration of a ``with`` block: ``kind`` is one of PATH_KINDS, ``mode`` a name its
+    ``<kind>_set_path`` accepts.  The path is reset to automatic on exit, also when the block raises."""
+    if kind not in PATH_KINDS:
+        raise ValueError("forced_path: unknown kind %r (%s)" % (kind, " | ".join(PATH_KINDS)))
+    setter = "cpx_%s_set_path" % kind
+    _set_mode(setter, mode)
+    try:
+        yield
+    finally:
+        _set_mode(setter, None)
 
 
 class DeviceHandles:

@@ -1158,8 +1158,6 @@ int pick_gw(int S, int64_t B) {
 // pairs per workgroup: four (eight waves, one workgroup per CU at full size) when there are enough pairs to give every
 // CU such a workgroup, else one pair per workgroup
 int pick_npair(int64_t npairs) {
-    static const int forced = [] { const char *e = getenv("CPX_BCJR_NPAIR"); return e ? atoi(e) : 0; }();   // experiments
-    if (forced == 1 || forced == 2 || forced == NPAIR) return forced;
     return npairs >= (int64_t)NPAIR * device_cus() ? NPAIR : 1;
 }
 
@@ -1328,12 +1326,11 @@ int cpx_turbo_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const 
         }
         return CPX_OK;
     };
-    static const bool no_pout = [] { const char *e = getenv("CPX_TURBO_POUT"); return e && e[0] == '0'; }();   // A/B runs
     int prev_pout = 1;                                            // (turbo_init_kernel wrote a prior)
     for (int h = 0; h < 2 * n_iter; h++) {
         // every pass but the last two hands prior0(E) to the next one directly (epilogue): the last MAP 2 needs L_int_2 and E_2 as
         // LLRs for the decision L_2 = L_int_2 + E_2 > 0 (:148-152, :326-331), so the last MAP 1 writes E_1 itself
-        const int pout = (h <= 2 * n_iter - 3 && !no_pout) ? 1 : 0;
+        const int pout = h <= 2 * n_iter - 3 ? 1 : 0;
         const int last = h == 2 * n_iter - 1;
         // the prior of MAP 2 is interlv(E_1) (:319): row perm[t]; of MAP 1 deinterlv(E_2) (:329): row inverse_perm[t]; of the very
         // first pass L_int_1 as turbo_init_kernel laid it out: row t

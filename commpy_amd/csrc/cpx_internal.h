@@ -83,7 +83,6 @@ int ldpc_resident_tables(::cpx_ldpc *c, const int32_t *row_ptr, const int32_t *r
 void ldpc_resident_free(::cpx_ldpc *c);
 // nanflags (min-sum only, else null): [B] bytes, written for every block: 1 = a NaN among its LLRs (ldpc.hip decodes it again)
 // block_major: d_dec / d_out are [B][n_v] (one block per row) instead of [n_v][B]
-int ldpc_forced_path();   // cpx_ldpc_set_path / CPX_LDPC_PATH: 0 auto, 1 'tiled', 2 'resident', 3 'resident-log' (forced modes never substitute another kernel)
 bool ldpc_resident_path(const ::cpx_ldpc *c, double *d_llr, int64_t B, int alg, int n_iters, int8_t *d_dec, double *d_out,
                         int block_major, int32_t *d_iters, int *d_clipped, uint8_t *nanflags, hipStream_t st, int *rc);
 
@@ -94,9 +93,6 @@ int bcjr_exact_map(const ::cpx_trellis *t, const double *sys, const double *par,
 int bcjr_exact_turbo(const ::cpx_trellis *t, const double *sys, const double *p1, const double *p2, const double *Lint_or_null,
                      const int32_t *perm, int64_t B, int64_t N, double nv2, int n_iter, uint8_t *bits, const uint8_t *flags,
                      hipStream_t st);
-
-// CPX_LDPC_SPA=exact: sum-product check rows always by the exact-order sequence (ldpc_dev.h)
-bool ldpc_spa_exact();
 
 // per-device issue lock for entry points that take scratch-arena memory (runtime.hip)
 struct IssueGuard {
@@ -124,12 +120,24 @@ bool trace_enabled();
 #define CPX_TRACE_CAT(a, b) CPX_TRACE_CAT2(a, b)
 #define CPX_TRACE(name) cpx::TraceRange CPX_TRACE_CAT(cpx_trace_, __LINE__)(name)
 
-// precision mode (cpx_set_precision / CPX_PRECISION): false = fp64-parity (default), true = fp32-fast
-bool precision_fast();
+// Kernel-path switches: one process-wide table in runtime.hip holds, per switch, its environment variable, its public setter
+// and the mode names it accepts.
+enum class Switch { precision, viterbi_path, ldpc_path, demod, kbest_path, best_first_path, ldpc_spa, viterbi_overlap, count };
+int mode_of(Switch s);                      // the current mode: one relaxed atomic load once the environment has been read
+int set_mode(Switch s, const char *name);   // null, "" and the default's names reset; CPX_EINVAL for a name not in the switch's row
+
+// cpx_set_precision / CPX_PRECISION: false = fp64-parity (default), true = fp32-fast
+inline bool precision_fast() { return mode_of(Switch::precision) == 1; }
+// cpx_ldpc_set_path / CPX_LDPC_PATH: 0 auto, 1 'tiled', 2 'resident', 3 'resident-log' (forced modes never substitute another kernel)
+inline int ldpc_forced_path() { return mode_of(Switch::ldpc_path); }
+// CPX_LDPC_SPA=exact: sum-product check rows always by the exact-order sequence (ldpc_dev.h)
+inline bool ldpc_spa_exact() { return mode_of(Switch::ldpc_spa) == 1; }
 
 void viterbi_lean_ring(bool on);   // thread-local: the next 64-state rounds of this thread take the unmirrored ring where that flavour exists
 void viterbi_prefer_cw(bool on);   // thread-local: the next dispatches of this thread take the codeword path whatever the batch size
-int viterbi_path_flags();   // bit 0 wave only, bit 1 codeword path forced, bit 2 strict, bit 3 two-kernel form, bit 4 general kernel
+// cpx_viterbi_set_path / CPX_VITERBI_PATH: bit 0 wave only, bit 1 codeword path forced, bit 2 strict ("!": fail instead of
+// falling back), bit 3 two-kernel form even where the fused kernel applies, bit 4 general kernel (viterbi_generic.hip)
+inline int viterbi_path_flags() { return mode_of(Switch::viterbi_path); }
 // the general Viterbi kernel (viterbi_generic.hip): any trellis cpx_trellis_create accepts, any traceback depth
 int viterbi_generic(const ::cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L, int64_t T, int tb, int type,
                     uint8_t *d_bits, hipStream_t st);

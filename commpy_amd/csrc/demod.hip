@@ -854,21 +854,10 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_hard_any_kernel(const doubl
     }
 }
 
-// "plain": the R-exponentials-per-axis form of the separable kernel also where the progression applies (A/B runs, tests);
-// initial value from the environment variable CPX_DEMOD, changed through cpx_demod_set_path()
-// 0 auto; 1 "plain": R exponentials per axis, no progression; 2 "libm": the progression with the library's exp / log instead of the
-// table-driven ones (the round-4 / early round-5 kernel: kept as the row the table-driven kernel is tested against)
-std::atomic<int> g_demod_plain{-1};
-int parse_demod_mode(const char *e) { return (e && strcmp(e, "plain") == 0) ? 1 : (e && strcmp(e, "libm") == 0) ? 2 : 0; }
-int demod_mode() {
-    int v = g_demod_plain.load(std::memory_order_relaxed);
-    if (v < 0) {
-        v = parse_demod_mode(getenv("CPX_DEMOD"));
-        g_demod_plain.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-bool demod_plain() { return demod_mode() == 1; }
+// cpx_demod_set_path / CPX_DEMOD (A/B runs, tests): 0 auto; 1 "plain": R exponentials per axis, no progression (the separable
+// kernel also where the progression applies); 2 "libm": the progression with the library's exp / log instead of the table-driven
+// ones (the round-4 / early round-5 kernel: kept as the row the table-driven kernel is tested against)
+int demod_mode() { return mode_of(Switch::demod); }
 
 unsigned grid_for(int64_t Ns) {
     int64_t blocks = (Ns + DEMOD_BLOCK - 1) / DEMOD_BLOCK;
@@ -933,14 +922,7 @@ int cpx_modem_create(const double *constellation_re_im, int M, cpx_modem **out) 
     return CPX_OK;
 }
 
-int cpx_demod_set_path(const char *mode) {
-    if (mode && mode[0] && strcmp(mode, "auto") != 0 && strcmp(mode, "plain") != 0 && strcmp(mode, "libm") != 0) {
-        set_error("cpx_demod_set_path: unknown mode '%s' (auto | plain | libm)", mode);
-        return CPX_EINVAL;
-    }
-    g_demod_plain.store(parse_demod_mode(mode), std::memory_order_relaxed);
-    return CPX_OK;
-}
+int cpx_demod_set_path(const char *mode) { return set_mode(Switch::demod, mode); }
 
 int cpx_modem_destroy(cpx_modem *m) {
     if (!m) return CPX_OK;
@@ -1003,7 +985,7 @@ int cpx_demod_soft_scaled_dev(const cpx_modem *m, const double *d_y, int64_t Ns,
     }
     const bool al16 = ((uintptr_t)d_llr & 15) == 0;                // the fast kernels store 16 bytes per lane
     const bool gen = demod_mode() != 2 && al16;                   // generic constellations: the table-driven kernel unless "libm"
-    const bool gp = m->gp && (m->nbits >= 6 || m->nbits == 2) && !demod_plain();
+    const bool gp = m->gp && (m->nbits >= 6 || m->nbits == 2) && demod_mode() != 1;
     const bool tab = gp && m->nbits >= 6 && demod_mode() != 2;       // table-driven exp / log (round 5); "libm" keeps the library's
     if (m->separable && al16) {
         switch (m->nbits / 2) {

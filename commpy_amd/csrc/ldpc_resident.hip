@@ -758,27 +758,6 @@ __global__ __launch_bounds__(256) void ldpc_unstage_kernel(const double *__restr
     }
 }
 
-std::atomic<int> g_ldpc_path{-1};                                 // 0 auto, 1 tiled, 2 resident (strict), 3 resident (strict), sum-product by the log-domain row
-int parse_ldpc_path(const char *m) {
-    if (!m || !m[0] || strcmp(m, "auto") == 0) return 0;
-    if (strcmp(m, "tiled") == 0) return 1;
-    if (strcmp(m, "resident") == 0) return 2;
-    if (strcmp(m, "resident-log") == 0) return 3;
-    return -2;
-}
-int ldpc_path() {
-    int v = g_ldpc_path.load(std::memory_order_relaxed);
-    if (v < 0) {
-        static std::once_flag once;
-        std::call_once(once, [] {
-            const int e = parse_ldpc_path(getenv("CPX_LDPC_PATH"));
-            g_ldpc_path.store(e < 0 ? 0 : e, std::memory_order_relaxed);
-        });
-        v = g_ldpc_path.load(std::memory_order_relaxed);
-    }
-    return v;
-}
-
 template <int ALG, int CQ>
 int launch_resident(const ResParams &p, int grid, int threads, size_t lds, hipStream_t st) {
     static bool raised[64] = {};                                  // > 64 KiB of dynamic LDS is opt-in, once per kernel and device
@@ -827,15 +806,8 @@ size_t res_lds_bytes(const cpx_ldpc *c) { return (size_t)res_roff(c->n_v) + 8 * 
 
 namespace cpx {
 
-bool ldpc_spa_exact() {
-    static const bool v = [] { const char *e = getenv("CPX_LDPC_SPA"); return e && strcmp(e, "exact") == 0; }();
-    return v;
-}
 // CPX_LDPC_SPA=log: the resident path keeps the log-domain one-division row (the round-3 kernel) instead of the ratio-domain kernel (A/B runs)
-static bool ldpc_spa_log() {
-    static const bool v = [] { const char *e = getenv("CPX_LDPC_SPA"); return e && strcmp(e, "log") == 0; }();
-    return v;
-}
+static bool ldpc_spa_log() { return mode_of(Switch::ldpc_spa) == 2; }
 
 // Offset tables of the resident path, built once per handle from the blob's tables (host pointers).
 int ldpc_resident_tables(cpx_ldpc *c, const int32_t *row_ptr, const int32_t *row_pad, const int32_t *col_ptr,
@@ -877,12 +849,10 @@ void ldpc_resident_free(cpx_ldpc *c) {
     (void)hipFree(c->d_res_row_deg); (void)hipFree(c->d_res_row_q); (void)hipFree(c->d_res_col_r); (void)hipFree(c->d_res_vgrp); (void)hipFree(c->d_res_row_q32); (void)hipFree(c->d_res_col_r32);
 }
 
-int ldpc_forced_path() { return ldpc_path(); }
-
 bool ldpc_resident_path(const cpx_ldpc *c, double *d_llr, int64_t B, int alg, int n_iters, int8_t *d_dec, double *d_out,
                         int block_major, int32_t *d_iters, int *d_clipped, uint8_t *nanflags, hipStream_t st, int *rc) {
     *rc = CPX_OK;
-    const int mode = ldpc_path();
+    const int mode = ldpc_forced_path();
     auto reject = [&](const char *why) {
         if (mode >= 2) { set_error("ldpc: resident path forced but not applicable: %s", why); *rc = CPX_EINVAL; return true; }
         return false;
@@ -894,14 +864,10 @@ bool ldpc_resident_path(const cpx_ldpc *c, double *d_llr, int64_t B, int alg, in
     const bool f32 = precision_fast() && res_lds_bytes_f32(c) <= 64 * 1024;   // "fp32-fast": float32 state (ldpc_resident_f32_kernel)
     const size_t lds = f32 ? res_lds_bytes_f32(c) : res_lds_bytes(c);
     // workgroup size.  float64: the check pass in one round (two for > 1024 checks) -- (1944,1296): 704 threads, the variable
-    // pass takes three rounds; measured 2.51 ms at 704, 2.75 at 512, 3.38 at 1024 (scripts/micro/ldpc_knobs.py).  float32: 512.
+    // pass takes three rounds; measured 2.51 ms at 704, 2.75 at 512, 3.38 at 1024.  float32: 512.
     const int rounds = (c->n_c + 1023) / 1024;
-    int threads = f32 ? std::min(512, std::max(64, (c->n_c + 63) / 64 * 64))
-                      : std::min(1024, std::max(64, ((c->n_c + rounds - 1) / rounds + 63) / 64 * 64));
-    if (const char *e = getenv("CPX_LDPC_THREADS")) {             // experiment knob
-        const int t = atoi(e);
-        if (!f32 && t >= 64 && t <= 1024 && t % 64 == 0) threads = t;
-    }
+    const int threads = f32 ? std::min(512, std::max(64, (c->n_c + 63) / 64 * 64))
+                            : std::min(1024, std::max(64, ((c->n_c + rounds - 1) / rounds + 63) / 64 * 64));
     // Outputs.  Block-major (one block per row, the memory layout of the reference's own results): retired blocks go straight
     // to the caller's arrays.  [n_v][B]: they go to a staging buffer and ldpc_unstage_kernel transposes it.
     // persistent grid: as many workgroups as fit a compute unit (LDS, 2048 threads, 16 workgroups), no more than blocks
@@ -952,12 +918,4 @@ bool ldpc_resident_path(const cpx_ldpc *c, double *d_llr, int64_t B, int alg, in
 
 }  // namespace cpx
 
-extern "C" int cpx_ldpc_set_path(const char *mode) {
-    const int v = parse_ldpc_path(mode);
-    if (v < 0) {
-        cpx::set_error("cpx_ldpc_set_path: unknown mode '%s' (auto | tiled | resident | resident-log)", mode);
-        return CPX_EINVAL;
-    }
-    g_ldpc_path.store(v, std::memory_order_relaxed);
-    return CPX_OK;
-}
+extern "C" int cpx_ldpc_set_path(const char *mode) { return cpx::set_mode(cpx::Switch::ldpc_path, mode); }

@@ -271,17 +271,7 @@ __global__ __launch_bounds__(WAVE) void kbest_kernel(const double2 *__restrict__
     }
 }
 
-std::atomic<int> g_kbest_general{-1};   // -1: not read yet; initial value from CPX_KBEST_PATH
-
-bool kbest_forced_general() {
-    int v = g_kbest_general.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("CPX_KBEST_PATH");
-        v = e && strcmp(e, "general") == 0 ? 1 : 0;
-        g_kbest_general.store(v, std::memory_order_relaxed);
-    }
-    return v == 1;
-}
+bool kbest_forced_general() { return mode_of(Switch::kbest_path) == 1; }   // cpx_kbest_set_path / CPX_KBEST_PATH
 
 int grid_for(int64_t B) { return int(B < 1048576 ? B : 1048576); }
 
@@ -610,17 +600,7 @@ __global__ __launch_bounds__(WAVE) void best_first_kernel(const double2 *__restr
     }
 }
 
-std::atomic<int> g_bf_general{-1};   // -1: not read yet; initial value from CPX_BEST_FIRST_PATH
-
-bool bf_forced_general() {
-    int v = g_bf_general.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("CPX_BEST_FIRST_PATH");
-        v = e && strcmp(e, "general") == 0 ? 1 : 0;
-        g_bf_general.store(v, std::memory_order_relaxed);
-    }
-    return v == 1;
-}
+bool bf_forced_general() { return mode_of(Switch::best_first_path) == 1; }   // cpx_best_first_set_path / CPX_BEST_FIRST_PATH
 
 int bf_run(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt,
            const int32_t *stack_size, double llr_max, const uint8_t *d_labels, double *d_llr, int32_t *d_iters, void *stream) {
@@ -688,14 +668,7 @@ int mimo_host(const double *y, const double *h, int h_batched, int64_t B, int nr
 
 extern "C" {
 
-int cpx_kbest_set_path(const char *mode) {
-    if (mode && mode[0] && strcmp(mode, "auto") != 0 && strcmp(mode, "general") != 0) {
-        set_error("cpx_kbest_set_path: unknown mode '%s' (auto | general)", mode);
-        return CPX_EINVAL;
-    }
-    g_kbest_general.store(mode && strcmp(mode, "general") == 0 ? 1 : 0, std::memory_order_relaxed);
-    return CPX_OK;
-}
+int cpx_kbest_set_path(const char *mode) { return set_mode(Switch::kbest_path, mode); }
 
 int cpx_mimo_ml_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt,
                     int32_t *d_idx, void *stream) {
@@ -780,14 +753,7 @@ int cpx_kbest_list(const cpx_modem *md, const double *y, const double *h, int h_
 
 extern "C" {
 
-int cpx_best_first_set_path(const char *mode) {
-    if (mode && mode[0] && strcmp(mode, "auto") != 0 && strcmp(mode, "general") != 0) {
-        set_error("cpx_best_first_set_path: unknown mode '%s' (auto | general)", mode);
-        return CPX_EINVAL;
-    }
-    g_bf_general.store(mode && strcmp(mode, "general") == 0 ? 1 : 0, std::memory_order_relaxed);
-    return CPX_OK;
-}
+int cpx_best_first_set_path(const char *mode) { return set_mode(Switch::best_first_path, mode); }
 
 int cpx_best_first_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt,
                        const int32_t *stack_size, double llr_max, const uint8_t *d_labels, double *d_llr, int32_t *d_iters,

@@ -141,8 +141,6 @@ int ensure_device() {
 
 using namespace cpx;
 
-static std::atomic<int> g_precision{-1};   // -1: not read from CPX_PRECISION yet, 0 fp64-parity, 1 fp32-fast
-
 extern "C" {
 
 const char *cpx_last_error(void) { return g_err; }
@@ -188,16 +186,9 @@ int cpx_last_kernel(char *name, int cap) {
     return CPX_OK;
 }
 
-int cpx_set_precision(const char *mode) {
-    int v = -1;
-    if (!mode || !mode[0] || strcmp(mode, "fp64-parity") == 0 || strcmp(mode, "fp64") == 0) v = 0;
-    else if (strcmp(mode, "fp32-fast") == 0 || strcmp(mode, "fp32") == 0) v = 1;
-    CPX_REQUIRE(v >= 0, CPX_EINVAL, "cpx_set_precision: unknown mode '%s' (fp64-parity | fp32-fast)", mode);
-    g_precision.store(v, std::memory_order_relaxed);
-    return CPX_OK;
-}
+int cpx_set_precision(const char *mode) { return set_mode(Switch::precision, mode); }
 
-int cpx_get_precision(void) { return cpx::precision_fast() ? 1 : 0; }
+int cpx_get_precision(void) { return mode_of(Switch::precision); }
 
 }  // extern "C"
 
@@ -289,18 +280,69 @@ TraceRange::TraceRange(const char *name) : on(roctx().push != nullptr) { if (on)
 TraceRange::~TraceRange() { if (on) roctx().pop(); }
 bool trace_enabled() { return roctx().push != nullptr; }
 
-bool precision_fast() {
-    int v = g_precision.load(std::memory_order_relaxed);
-    if (v < 0) {
-        static std::once_flag once;
-        std::call_once(once, [] {
-            const char *e = getenv("CPX_PRECISION");
-            g_precision.store(e && (strcmp(e, "fp32-fast") == 0 || strcmp(e, "fp32") == 0) ? 1 : 0, std::memory_order_relaxed);
-        });
-        v = g_precision.load(std::memory_order_relaxed);
-    }
-    return v == 1;
+// ---- kernel-path switches (cpx_internal.h) ----------------------------------------------------------------------------------------
+// Every switch is process-wide: a setter call (or, before any, the environment variable, read on first use) decides the kernel
+// path of every thread's next call.  There are no per-call or per-thread options.
+namespace {
+struct ModeName { const char *name; int value; };
+struct SwitchRow {
+    const char *env;       // read once, on the first mode_of(); an unknown value leaves the default
+    const char *setter;    // the public setter, for error messages; null: environment only
+    int dflt;
+    ModeName names[8];     // accepted names (aliases included), ended by a null name
+};
+// one row per Switch, in its order
+const SwitchRow kSwitches[] = {
+    {"CPX_PRECISION", "cpx_set_precision", 0, {{"fp64-parity", 0}, {"fp32-fast", 1}, {"fp64", 0}, {"fp32", 1}}},
+    // the flag bits of viterbi_path_flags()
+    {"CPX_VITERBI_PATH", "cpx_viterbi_set_path", 0,
+     {{"auto", 0}, {"wave", 1}, {"cw", 2}, {"cw!", 6}, {"cw2", 10}, {"cw2!", 14}, {"general", 16}}},
+    {"CPX_LDPC_PATH", "cpx_ldpc_set_path", 0, {{"auto", 0}, {"tiled", 1}, {"resident", 2}, {"resident-log", 3}}},
+    {"CPX_DEMOD", "cpx_demod_set_path", 0, {{"auto", 0}, {"plain", 1}, {"libm", 2}}},
+    {"CPX_KBEST_PATH", "cpx_kbest_set_path", 0, {{"auto", 0}, {"general", 1}}},
+    {"CPX_BEST_FIRST_PATH", "cpx_best_first_set_path", 0, {{"auto", 0}, {"general", 1}}},
+    {"CPX_LDPC_SPA", nullptr, 0, {{"exact", 1}, {"log", 2}}},
+    {"CPX_VITERBI_OVERLAP", nullptr, 1, {{"0", 0}, {"1", 1}}},
+};
+static_assert(sizeof(kSwitches) / sizeof(kSwitches[0]) == (size_t)Switch::count, "one row per switch");
+
+constexpr int kUnread = -1;                 // the environment variable has not been read yet
+struct ModeCell { std::atomic<int> v{kUnread}; };
+ModeCell g_mode[(int)Switch::count];
+
+int mode_named(const SwitchRow &r, const char *name) {
+    for (const ModeName *m = r.names; m->name; m++)
+        if (strcmp(m->name, name) == 0) return m->value;
+    return -1;
 }
+}  // namespace
+
+int mode_of(Switch s) {
+    std::atomic<int> &cell = g_mode[(int)s].v;
+    const int v = cell.load(std::memory_order_relaxed);
+    if (v != kUnread) return v;
+    const SwitchRow &r = kSwitches[(int)s];
+    const char *e = getenv(r.env);
+    const int named = e ? mode_named(r, e) : -1;
+    const int from_env = named < 0 ? r.dflt : named;
+    int seen = kUnread;                     // a setter that ran first, or meanwhile, wins
+    return cell.compare_exchange_strong(seen, from_env, std::memory_order_relaxed) ? from_env : seen;
+}
+
+int set_mode(Switch s, const char *name) {
+    const SwitchRow &r = kSwitches[(int)s];
+    const int v = name && name[0] ? mode_named(r, name) : r.dflt;
+    if (v < 0) {
+        char allowed[160] = "";
+        for (const ModeName *m = r.names; m->name; m++)
+            snprintf(allowed + strlen(allowed), sizeof(allowed) - strlen(allowed), "%s%s", m == r.names ? "" : " | ", m->name);
+        set_error("%s: unknown mode '%s' (%s)", r.setter, name, allowed);
+        return CPX_EINVAL;
+    }
+    g_mode[(int)s].v.store(v, std::memory_order_relaxed);
+    return CPX_OK;
+}
+
 int device_cus() {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 256;

@@ -767,10 +767,7 @@ struct DemodSrc {                  // fused hard demodulation: symbols instead o
 };
 
 // ---- side stream of the remainder (viterbi_dispatch, round 6) -------------------------------------------------------------------
-static bool overlap_enabled() {
-    static const bool on = [] { const char *e = getenv("CPX_VITERBI_OVERLAP"); return !(e && e[0] == '0'); }();
-    return on;
-}
+static bool overlap_enabled() { return mode_of(Switch::viterbi_overlap) == 1; }   // CPX_VITERBI_OVERLAP
 
 // One lowest-priority stream per device, shared by the host threads (its queue orders their remainders); the fork / join events are
 // per THREAD and device: a shared pair would let thread B's record slip between thread A's record and A's hipStreamWaitEvent, and A's

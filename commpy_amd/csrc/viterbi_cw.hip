@@ -1013,30 +1013,6 @@ CPX_SPEC(CPX_VIT_UNQUANTIZED, false) CPX_SPEC(CPX_VIT_UNQUANTIZED, true)
 
 namespace cpx {
 
-// Kernel-path override (tests, benchmarks): bit 0 = "wave" (state-per-lane kernels only), bit 1 = forced codeword path,
-// bit 2 = strict ("!": fail instead of falling back), bit 3 = two-kernel form even where the fused kernel applies,
-// bit 4 = "general" (the slow-but-complete kernel of viterbi_generic.hip whatever the trellis).
-// Initialised once from the environment variable CPX_VITERBI_PATH, changed at run time through cpx_viterbi_set_path().
-static std::atomic<int> g_vit_path{-1};
-
-static int parse_path(const char *e) {
-    if (!e || !e[0]) return 0;
-    if (e[0] == 'w') return 1;
-    if (e[0] == 'g') return 16;                      // "general": viterbi_generic.hip for every trellis
-    if (e[0] != 'c') return 0;
-    return 2 | (strchr(e, '!') ? 4 : 0) | (strchr(e, '2') ? 8 : 0);
-}
-
-int viterbi_path_flags() {
-    int v = g_vit_path.load(std::memory_order_relaxed);
-    if (v < 0) {
-        static std::once_flag once;
-        std::call_once(once, [] { g_vit_path.store(parse_path(getenv("CPX_VITERBI_PATH")), std::memory_order_relaxed); });
-        v = g_vit_path.load(std::memory_order_relaxed);
-    }
-    return v;
-}
-
 // Set by the host-buffer pipeline (viterbi.hip) around its per-chunk calls: a chunk of a large batch takes the codeword path
 // whatever its own size (a round costs the same however full it is and hides behind the next chunk's upload; the fused
 // kernel -- and with it the precision mode -- then serves the host API exactly as it serves the device API).
@@ -1054,8 +1030,8 @@ bool viterbi_codeword_path(const cpx_trellis *t, const double *d_coded, int64_t 
                            int tb, int type, uint8_t *d_bits, uint8_t *nanflags, hipStream_t st, int *rc) {
     *rc = CPX_OK;
     // path override (cpx_viterbi_set_path / CPX_VITERBI_PATH): "wave" = state-per-lane kernels; "cw" = this path whatever
-    // the batch size; "cw!" = fail instead of falling back; a '2' anywhere ("cw2", "cw2!") = the two-kernel form even
-    // where the fused kernel applies
+    // the batch size; "cw!" = fail instead of falling back; "cw2", "cw2!" = the two-kernel form even where the fused
+    // kernel applies
     const int pf = viterbi_path_flags();
     if (pf & 1) return false;
     const bool forced = (pf & 2) || tl_prefer_cw, strict = pf & 4, two_kernels = pf & 8;
@@ -1164,14 +1140,7 @@ bool viterbi_codeword_path(const cpx_trellis *t, const double *d_coded, int64_t 
 
 }  // namespace cpx
 
-extern "C" int cpx_viterbi_set_path(const char *mode) {
-    if (mode && mode[0] && mode[0] != 'w' && mode[0] != 'c' && mode[0] != 'g' && strcmp(mode, "auto") != 0) {
-        cpx::set_error("cpx_viterbi_set_path: unknown mode '%s' (auto | wave | cw | cw! | cw2 | cw2! | general)", mode);
-        return CPX_EINVAL;
-    }
-    cpx::g_vit_path.store((mode && strcmp(mode, "auto") != 0) ? cpx::parse_path(mode) : 0, std::memory_order_relaxed);
-    return CPX_OK;
-}
+extern "C" int cpx_viterbi_set_path(const char *mode) { return cpx::set_mode(cpx::Switch::viterbi_path, mode); }
 
 // ---- per-pair code objects (round 6): query and attach -------------------------------------------------------------------------
 namespace {

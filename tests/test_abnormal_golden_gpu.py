@@ -22,11 +22,8 @@ def test_viterbi_nan_inputs(gpu):
         tname = key[4:key.rindex("_")]
         tr = make_trellis(tname)
         for path in ((None, "cw!", "cw2!", "wave") if tname == "k7_133_171" else (None,)):
-            _lib.viterbi_set_path(path)
-            try:
+            with _lib.forced_path("viterbi", path):
                 got = viterbi_decode(g[key + "__rx"], tr, None, "soft")
-            finally:
-                _lib.viterbi_set_path(None)
             assert np.array_equal(got, g[key + "__dec"]), (key, path)
 
 
@@ -37,11 +34,8 @@ def test_min_sum_nan_llrs(gpu):
     for key in names:
         p = ldpc_params(key[4:])
         for path in ("resident", "tiled"):
-            _lib.ldpc_set_path(path)
-            try:
+            with _lib.forced_path("ldpc", path):
                 dec, out = ldpc_bp_decode(g[key + "__llr"].copy(), p, "MSA", int(g[key + "__iters"]))
-            finally:
-                _lib.ldpc_set_path(None)
             assert out.shape == g[key + "__out"].shape
             assert np.array_equal(out, g[key + "__out"], equal_nan=True), (key, path)
             assert np.array_equal(dec, g[key + "__dec"]), (key, path)
@@ -83,11 +77,8 @@ def test_sum_product_zero_llrs(gpu):
         ref = g[key + "__out"]
         fin = np.isfinite(ref)
         for path in ("resident", "tiled"):
-            _lib.ldpc_set_path(path)
-            try:
+            with _lib.forced_path("ldpc", path):
                 dec, out = ldpc_bp_decode(g[key + "__llr"].copy(), p, "SPA", int(g[key + "__iters"]))
-            finally:
-                _lib.ldpc_set_path(None)
             assert np.array_equal(np.isnan(out), np.isnan(ref)), (key, path)
             assert np.array_equal(np.signbit(out), np.signbit(ref)), (key, path)
             assert np.all(np.abs(out[fin] - ref[fin]) <= TOL + 1e-6 * np.abs(ref[fin])), (key, path)

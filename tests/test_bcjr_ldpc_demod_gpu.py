@@ -407,13 +407,10 @@ def test_soft_demod_ragged_sizes_path_modes_and_bounds(gpu, m, snr_db):
         d_y = DeviceBuf.from_array(y)
         for mode in (None, "libm", "plain"):
             d_l = DeviceBuf.from_array(np.full(ns * nb + guard, -777.25))
-            _lib.demod_set_path(mode)
-            try:
+            with _lib.forced_path("demod", mode):
                 _lib.check(lib.cpx_demod_soft_dev(h, d_y.ptr, ns, float(N0), d_l.ptr, None))
                 _lib.check(lib.cpx_stream_sync(None))
                 kern = _lib.last_kernel()
-            finally:
-                _lib.demod_set_path(None)
             got = d_l.to_array((ns * nb + guard,), np.float64)
             d_l.free()
             assert np.all(got[ns * nb:] == -777.25), (ns, mode, kern)
@@ -452,13 +449,10 @@ def test_generic_soft_demod_fast_kernel(gpu, kind, m, snr_db):
         d_y = DeviceBuf.from_array(y)
         for mode, off in ((None, 0), ("libm", 0), (None, 8)):  # off = 8: an output pointer that is only 8-byte aligned
             d_l = DeviceBuf.from_array(np.full(ns * nb + guard + 1, -777.25))
-            _lib.demod_set_path(mode)
-            try:
+            with _lib.forced_path("demod", mode):
                 _lib.check(lib.cpx_demod_soft_dev(h, d_y.ptr, ns, float(N0), ctypes.c_void_p(d_l.ptr.value + off), None))
                 _lib.check(lib.cpx_stream_sync(None))
                 kern = _lib.last_kernel()
-            finally:
-                _lib.demod_set_path(None)
             got = d_l.to_array((ns * nb + guard + 1,), np.float64)[off // 8:]
             d_l.free()
             fast = "demod_soft_sep_kernel" if kind == "qam" else "demod_soft_gen_kernel"

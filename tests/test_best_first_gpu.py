@@ -109,12 +109,9 @@ def test_general_equals_lds(gpu, nr, nt, m, stacks):
     y = np.einsum('bij,bj->bi', h, md.constellation[rs.randint(0, m, (B, nt))]) + 0.6 * _rnd(rs, B, nr)
     fast = best_first_batch(y, h, md, stacks, 500)
     assert "best_first_kernel<lds>" in _lib.last_kernel(), _lib.last_kernel()
-    _lib.best_first_set_path("general")
-    try:
+    with _lib.forced_path("best_first", "general"):
         general = best_first_batch(y, h, md, stacks, 500)
         assert "best_first_kernel<global>" in _lib.last_kernel(), _lib.last_kernel()
-    finally:
-        _lib.best_first_set_path(None)
     assert np.array_equal(fast, general, equal_nan=True)
 
 

@@ -17,7 +17,6 @@ import pytest
 import oracle
 from helpers import Perm, golden, ldpc_params, make_trellis
 from test_oracle_golden import c2u_case, c2x_case
-from test_viterbi_cw_gpu import _path
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -26,11 +25,12 @@ TOL = 1e-5
 # ------------------------------------------------------------------------------------------------ config 2
 @pytest.mark.parametrize("path", ["cw!", "cw2!", "wave"])
 def test_config2_reference_codewords(gpu, path):
+    from commpy_amd import _lib
     from commpy_amd.channelcoding import viterbi_decode
     tr = make_trellis("k7_133_171")
     for tag in ("e1", "e3", "e5"):
         llr, dec, _ = c2x_case(tag)
-        with _path(path):
+        with _lib.forced_path("viterbi", path):
             got = viterbi_decode(llr, tr, None, "soft")
         assert got.shape == dec.shape and np.array_equal(got, dec), (tag, path, int(np.sum(got != dec)))
 
@@ -38,10 +38,11 @@ def test_config2_reference_codewords(gpu, path):
 @pytest.mark.parametrize("path", ["cw!", "cw2!", "wave"])
 def test_config2_unquantised_reference_codewords(gpu, path):
     """viterbi_c2u.npz: 256 codewords whose LLRs are the reference modem's float64 outputs as they are (no 1/256 grid)."""
+    from commpy_amd import _lib
     from commpy_amd.channelcoding import viterbi_decode
     tr = make_trellis("k7_133_171")
     llr, dec, _ = c2u_case()
-    with _path(path):
+    with _lib.forced_path("viterbi", path):
         got = viterbi_decode(llr, tr, None, "soft")
     assert got.shape == dec.shape and np.array_equal(got, dec), (path, int(np.sum(got != dec)))
 
@@ -268,14 +269,11 @@ def test_config4_chain_128_blocks_vs_oracle(gpu):
             # round 5: the STRICT bound -- every value below |LLR| = 26 within 1e-5 of the oracle -- for the default
             # (ratio-domain) kernel and, forced, for both log-domain rows
             spa_strict(out, oo, "128 blocks, default kernel vs oracle")
-            try:
-                for path in ("resident-log", "tiled"):
-                    _lib.ldpc_set_path(path)
+            for path in ("resident-log", "tiled"):
+                with _lib.forced_path("ldpc", path):
                     d2, o2, i2 = ldpc_bp_decode(llr.copy(), p, alg, 50, return_iterations=True)
-                    assert np.array_equal(i2, io) and np.array_equal(d2, do), path
-                    spa_strict(o2, oo, "128 blocks, %s vs oracle" % path)
-            finally:
-                _lib.ldpc_set_path(None)
+                assert np.array_equal(i2, io) and np.array_equal(d2, do), path
+                spa_strict(o2, oo, "128 blocks, %s vs oracle" % path)
 
 
 def test_ldpc_saturation_case_l026(gpu):

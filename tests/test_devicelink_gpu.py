@@ -106,12 +106,9 @@ def test_device_wifi_link_batched_sweep_noiseless_and_equal_paths(gpu):
     res = {}
     from commpy_amd import _lib
     for path in ("wave", "auto"):
-        _lib.viterbi_set_path(path)
-        try:
+        with _lib.forced_path("viterbi", path):
             res[path] = DeviceWifiLink(5, 1200, generator_matrix=[[0o133, 0o171]], seed=9).ber_sweep_batched(snrs, 1200 * 20000)
             assert _lib.viterbi_last_path() == ("wave" if path == "wave" else "fused")    # 60000 frames: one round
-        finally:
-            _lib.viterbi_set_path(None)
     assert np.array_equal(res["wave"], res["auto"]) and res["auto"][0] > 0
 
 
@@ -186,12 +183,9 @@ def test_fused_front_end_sweep_and_fallbacks(gpu):
     with pytest.raises(ValueError):
         DeviceWifiLink(1, 600, generator_matrix=[[0o133, 0o171]], seed=3, fused=True)
     link = DeviceWifiLink(5, 1200, generator_matrix=[[0o133, 0o171]], seed=9, fused=True)
-    _lib.demod_set_path("libm")
-    try:
+    with _lib.forced_path("demod", "libm"):
         e_libm = link.run_batch(15.0, 40)
         assert "link_front" not in link.front_last_kernel
-    finally:
-        _lib.demod_set_path(None)
     link2 = DeviceWifiLink(5, 1200, generator_matrix=[[0o133, 0o171]], seed=9, fused=True)
     e_def = link2.run_batch(15.0, 40)
     assert "link_front" in link2.front_last_kernel

@@ -86,11 +86,8 @@ def test_fast_mode_leaves_every_other_kernel_alone(gpu, lib):
     s_, p_ = rs.randn(50), rs.randn(50)
 
     def run():
-        lib.ldpc_set_path("tiled")
-        try:
+        with lib.forced_path("ldpc", "tiled"):
             d, o = ldpc_bp_decode(l.copy(), p, "SPA", 5)
-        finally:
-            lib.ldpc_set_path(None)
         return (viterbi_decode(x, tr, None, "soft"), d, o, md.demodulate(y, "hard"),
                 map_decode(s_, p_, tr4, 0.7, np.zeros(50), "compute")[0])
 

@@ -42,12 +42,9 @@ def test_viterbi_general_vs_live_reference(gpu, key):
     assert dec.dtype == np.int64 and np.array_equal(dec[:, :nv], g[key + "__dec"][:, :nv])
     one = viterbi_decode(rx[0], tr, tbd, dtype)                    # 1-D call, the reference's own shape
     assert np.array_equal(one[:nv], g[key + "__dec"][0, :nv])
-    try:
-        _lib.viterbi_set_path("general")
+    with _lib.forced_path("viterbi", "general"):
         forced = viterbi_decode(rx, tr, tbd, dtype)
         assert _lib.viterbi_last_path() == "general"
-    finally:
-        _lib.viterbi_set_path(None)
     assert np.array_equal(forced[:, :nv], g[key + "__dec"][:, :nv])
 
 
@@ -73,12 +70,9 @@ def test_general_kernel_equals_specialised_kernels(gpu, name, dtype):
         else:
             rx = (2.0 * coded - 1) + rs.randn(*coded.shape)
         ref = viterbi_decode(rx, tr, tb, dtype)
-        try:
-            _lib.viterbi_set_path("general")
+        with _lib.forced_path("viterbi", "general"):
             dec = viterbi_decode(rx, tr, tb, dtype)
             assert _lib.viterbi_last_path() == "general"
-        finally:
-            _lib.viterbi_set_path(None)
         assert np.array_equal(dec, ref), (name, dtype, B, nbits, tb)
         want = oracle.viterbi_decode(rx, tr, tb, dtype)
         if tb is None or tb - 1 <= int((want.shape[1] + tr.total_memory) / tr.k) - 1:   # else the reference returns np.empty memory
@@ -108,11 +102,8 @@ def test_k9_batch_on_the_wide_kernel_vs_oracle_and_general_kernel(gpu):
             assert _lib.viterbi_last_path() == "wide", _lib.last_kernel()
             want = oracle.viterbi_decode(rx[:40], tr, tb, dtype)
             assert np.array_equal(dec[:40], want), (dtype, tb)
-            try:
-                _lib.viterbi_set_path("general")
+            with _lib.forced_path("viterbi", "general"):
                 gen = viterbi_decode(rx, tr, tb, dtype)
-            finally:
-                _lib.viterbi_set_path(None)
             assert np.array_equal(dec, gen), (dtype, tb)
 
 
@@ -273,12 +264,9 @@ def test_soft_demod_progression_form_equals_plain_form_and_oracle(gpu, m):
             y[6] = complex(np.nan, 1.0)
             soft = md.demodulate(y, "soft", N0)
             assert ",gp" in _lib.last_kernel(), _lib.last_kernel()
-            try:
-                _lib.demod_set_path("plain")
+            with _lib.forced_path("demod", "plain"):
                 plain = md.demodulate(y, "soft", N0)
                 assert ",gp" not in _lib.last_kernel()
-            finally:
-                _lib.demod_set_path(None)
             want = oracle.demodulate(md.constellation, y, "soft", N0)
             for got in (soft, plain):
                 assert np.array_equal(np.isfinite(got), np.isfinite(want)), (scale, snr_db)

@@ -121,12 +121,9 @@ def test_kbest_general_equals_fast(gpu, nr, nt, m, K):
     with np.errstate(divide="ignore", invalid="ignore"):
         fast = (kbest_batch(y, h, md, K), kbest_batch(y, h, md, K, 0.3, 'soft'))
         assert "kbest_kernel<lds>" in _lib.last_kernel(), _lib.last_kernel()
-        _lib.kbest_set_path("general")
-        try:
+        with _lib.forced_path("kbest", "general"):
             general = (kbest_batch(y, h, md, K), kbest_batch(y, h, md, K, 0.3, 'soft'))
             assert "kbest_kernel<global>" in _lib.last_kernel(), _lib.last_kernel()
-        finally:
-            _lib.kbest_set_path(None)
     assert np.array_equal(fast[0], general[0])
     assert np.array_equal(fast[1], general[1], equal_nan=True)
 

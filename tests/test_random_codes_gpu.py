@@ -175,12 +175,9 @@ def test_ldpc_rolled_rows_on_the_tiled_path(gpu, seed, n_v, n_c, lo, hi):
     for alg, iters in (("MSA", 7), ("SPA", 4)):
         got = {}
         for path in ("tiled", "resident-log"):
-            _lib.ldpc_set_path(path)
-            try:
+            with _lib.forced_path("ldpc", path):
                 got[path] = ldpc_bp_decode(llr.copy(), dict(p), alg, iters, return_iterations=True)
                 assert ("tiled" in _lib.last_kernel()) == (path == "tiled"), _lib.last_kernel()
-            finally:
-                _lib.ldpc_set_path(None)
         for a, b in zip(got["tiled"], got["resident-log"]):
             assert np.array_equal(a, b, equal_nan=True), alg
         dec, out, its = got["tiled"]

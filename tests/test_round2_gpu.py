@@ -247,8 +247,7 @@ def test_concurrent_host_threads_share_the_arena_safely(gpu):
     ldpc_in = [rs.randn(b * 1440) * 2 + 1.5 for b in sizes]
     vit_in = [rs.randn(b * 2, 2 * 70) * 2 for b in sizes]
     tur_in = [[rs.randn(b, 64) for _ in range(3)] for b in sizes]
-    _lib.viterbi_set_path("cw2")                                    # two-kernel form: takes arena slots 0 and 1 as well
-    try:
+    with _lib.forced_path("viterbi", "cw2"):                        # two-kernel form: takes arena slots 0 and 1 as well
         want_l = [ldpc_bp_decode(x.copy(), p, "MSA", 8) for x in ldpc_in]
         want_v = [viterbi_decode(x, tr, 20, "soft") for x in vit_in]
         want_t = [turbo_decode(s, a, b, tr4, 0.8, 3, il) for s, a, b in tur_in]
@@ -277,8 +276,6 @@ def test_concurrent_host_threads_share_the_arena_safely(gpu):
         for t in th:
             t.join()
         assert not errs, errs[:5]
-    finally:
-        _lib.viterbi_set_path(None)
 
 
 @pytest.mark.parametrize("m,N0", [(64, 0.1), (64, 0.02), (256, 0.05), (256, 0.02), (16, 0.01)])  # the last: saturates below 600 too

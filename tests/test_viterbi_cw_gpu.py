@@ -13,24 +13,10 @@ from helpers import golden, make_trellis
 pytestmark = pytest.mark.gpu
 
 
-class _path:
-    """Force a Viterbi kernel path for the duration of a ``with`` block (cpx_viterbi_set_path)."""
-
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        from commpy_amd import _lib
-        _lib.viterbi_set_path(self.name)
-
-    def __exit__(self, *a):
-        from commpy_amd import _lib
-        _lib.viterbi_set_path(None)
-
-
 def _decode(x, tr, tb, dtype, path):
+    from commpy_amd import _lib
     from commpy_amd.channelcoding import viterbi_decode
-    with _path(path):
+    with _lib.forced_path("viterbi", path):
         return viterbi_decode(x, tr, tb, dtype)
 
 

@@ -119,11 +119,8 @@ def test_soft_nan_inputs_follow_the_reference(gpu, name):
             rx[100:] = rs.randn(B - 100, steps * tr.n) * 3          # whole wavefronts / redo groups without a NaN
         want = oracle.viterbi_decode(rx, tr, None, "soft")
         for path in ((None, "cw!", "cw2!", "wave") if name == "k7_133_171" else (None,)):
-            _lib.viterbi_set_path(path)
-            try:
+            with _lib.forced_path("viterbi", path):
                 got = viterbi_decode(rx, tr, None, "soft")
-            finally:
-                _lib.viterbi_set_path(None)
             assert np.array_equal(got, want), (name, B, steps, path)
 
 
@@ -153,11 +150,8 @@ def test_abnormal_inputs_all_types_vs_oracle(gpu):
                         rx[rs.rand(B, length) < 0.004] = v
                 want = oracle.viterbi_decode(rx, tr, None, dtype)
                 for path in ((None, "cw!", "cw2!", "wave") if name == "k7_133_171" else (None,)):
-                    _lib.viterbi_set_path(path)
-                    try:
+                    with _lib.forced_path("viterbi", path):
                         got = viterbi_decode(rx, tr, None, dtype)
-                    finally:
-                        _lib.viterbi_set_path(None)
                     n_cases += 1
                     assert np.array_equal(got, want), (name, dtype, B, steps, path, int(np.sum(got != want)))
     assert n_cases >= 250

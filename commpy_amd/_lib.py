@@ -115,6 +115,11 @@ SYMBOLS = {
     "cpx_best_first": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_double, c_void_p, c_void_p]),
     "cpx_best_first_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_double, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
+    "cpx_mimo_channel_create": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "cpx_mimo_channel_destroy": (c_int, [c_void_p]),
+    "cpx_mimo_channel_run_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_uint64, c_double, c_uint64, c_uint64, c_uint64,
+                                         c_void_p, c_void_p, c_void_p]),
+    "cpx_mimo_hard_errors_dev": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "cpx_random_bits_dev": (c_int, [c_void_p, c_int64, c_uint64, c_uint64, c_void_p]),
     "cpx_conv_encode_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "cpx_gather_u8_dev": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),

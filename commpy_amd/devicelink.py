@@ -12,19 +12,24 @@ quirk B1 (decimal generators) unless ``generator_matrix`` is given.  Only the er
 to the host.  The random streams are Philox-based, so results are statistically -- not bit-wise --
 comparable with the reference; the deterministic stages are bit-exact (tests/test_devicelink_gpu.py).
 
+``DeviceMimoLink`` does the same for a MIMO link over a ``MIMOFlatChannel`` (bits -> [LDPC encode] -> Kronecker fading channel ->
+ML / K-best / best-first detector -> [LDPC decode] -> error count), the device counterpart of ``LinkModel`` with ``mimo_receiver``.
+
 ``DeviceBuf`` / the ``*_dev`` helpers are thin wrappers over the C-ABI for callers that keep data in HBM.
 """
 import ctypes
 import math
+import operator
+from fractions import Fraction
 
 import numpy as np
 
 from commpy_amd import _lib
 from commpy_amd.wifi80211 import Wifi80211
 
-__all__ = ['DeviceBuf', 'DeviceWifiLink', 'DeviceBscLink', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu', 'puncturing_gpu',
-           'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder',
-           'gf2_generator', 'triang_ldpc_systematic_encode_gpu']
+__all__ = ['DeviceBuf', 'DeviceWifiLink', 'DeviceBscLink', 'DeviceMimoLink', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu',
+           'mimo_channel_gpu', 'puncturing_gpu', 'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu',
+           'LdpcEncoder', 'gf2_generator', 'triang_ldpc_systematic_encode_gpu']
 
 
 class DeviceBuf:
@@ -614,3 +619,310 @@ class DeviceWifiLink:
         ck(lib.cpx_stream_sync(None))
         errs = bufs['errs'].to_array((P, T * self.agg), np.int32)
         return errs.sum(axis=1) / float(T * self.nbits)
+
+
+# ---- MIMO links ---------------------------------------------------------------------------------------------------------------
+
+def _fading_matrices(channel):
+    """(sqrtm(Rr) [nr, nr], sqrtm(Rt).T [nt, nt], mean [nr, nt]) as complex128 C arrays: the three matrices
+    ``MIMOFlatChannel.propagate`` multiplies G with, computed once on the host."""
+    from scipy.linalg import sqrtm
+    mean, rt, rr = channel.fading_param
+    return (np.ascontiguousarray(sqrtm(rr), dtype=np.complex128), np.ascontiguousarray(sqrtm(rt).T, dtype=np.complex128),
+            np.ascontiguousarray(np.broadcast_to(mean, (channel.nb_rx, channel.nb_tx)), dtype=np.complex128))
+
+
+def _channel_handles(channel):
+    """cpx_mimo_channel handles (one per device) of the channel's current fading_param."""
+    lib = _lib.load()
+    a, bt, mean = _fading_matrices(channel)
+
+    def create():
+        h = ctypes.c_void_p()
+        _lib.check(lib.cpx_mimo_channel_create(channel.nb_rx, channel.nb_tx, _lib.ptr(a), _lib.ptr(bt), _lib.ptr(mean),
+                                               ctypes.byref(h)))
+        return h
+    return _lib.DeviceHandles(create, 'cpx_mimo_channel_destroy')
+
+
+def _require_complex(channel):
+    if not channel.isComplex:
+        raise ValueError('the device MIMO channel is complex valued: call uncorr_rayleigh_fading(complex) or give a complex fading_param')
+
+
+def mimo_channel_gpu(channel, modem, bits, seed=0, stream_id=0):
+    """``MIMOFlatChannel.propagate(modem.modulate(bits))`` on the GPU: returns ``(y [V, nr], H [V, nr, nt])`` for the
+    ``V = len(bits) / (nt * num_bits_symbol)`` vectors the bits fill (a partial vector is a ValueError).  The fading G and the noise
+    come from the Philox streams ``(seed, 2 stream_id)`` and ``(seed, 2 stream_id + 1)`` instead of NumPy's generator (statistically,
+    not bit-wise, the reference's); ``H = sqrtm(Rr) G sqrtm(Rt).T + mean`` and the noise of per-component std ``noise_std / 2``
+    follow channels.py (quirk B7)."""
+    _require_complex(channel)
+    if channel.noise_std is None:
+        raise AssertionError('Noise standard deviation must be set before propagation.')
+    nr, nt, nb = channel.nb_rx, channel.nb_tx, modem.num_bits_symbol
+    flat = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+    if flat.size % (nt * nb):
+        raise ValueError('%d bits do not fill whole vectors of %d symbols of %d bits' % (flat.size, nt, nb))
+    V = flat.size // (nt * nb)
+    lib = _lib.load()
+    handles = _channel_handles(channel)
+    try:
+        d_bits, d_y, d_h = DeviceBuf.from_array(flat), DeviceBuf(V * nr * 16), DeviceBuf(V * nr * nt * 16)
+        _lib.check(lib.cpx_mimo_channel_run_dev(handles.get(), modem._device_handle(), d_bits.ptr, V, 0,
+                                                float(channel.noise_std) * 0.5, int(seed), 2 * int(stream_id),
+                                                2 * int(stream_id) + 1, d_y.ptr, d_h.ptr, None))
+        _lib.check(lib.cpx_stream_sync(None))
+        return d_y.to_array((V, nr), np.complex128), d_h.to_array((V, nr, nt), np.complex128)
+    finally:
+        handles.drop()
+
+
+_ML_LDS = 64 * 1024            # mimo_ml_kernel's LDS budget for H, y and the per-lane residuals (mimo.hip)
+_VECTORS_PER_LAUNCH = 1 << 20  # detector batch the default tx_batch aims at
+
+
+class DeviceMimoLink:
+    """BER of a MIMO link over a ``MIMOFlatChannel``, simulated entirely on the GPU.
+
+    The detector arguments mean what they mean in ``mimo_receiver``: 'ml' or 'kbest' with 'hard' output make an uncoded link
+    (bits -> channel -> detector -> hard-decision error count); with ``ldpc_params``, 'kbest' with 'soft' output or 'best_first'
+    make an LDPC-coded one (bits -> systematic encode -> channel -> soft detector -> block-major decode -> errors in the first k
+    bits of each block).  A transmission carries ``send_chunk`` message bits, rounded like ``LinkModel._prepare``; coded, that is
+    ``send_chunk / k`` codewords sent one after another, as ``triang_ldpc_systematic_encode(...).reshape(-1, order='F')`` lays them
+    out.  The SNR convention is channels.py's: ``noise_std = sqrt(2 nt Es / (rate 10^(SNR/10)))``, noise of per-component std
+    ``noise_std / 2`` while the detector is told ``noise_std**2`` (quirk B7).  Random streams are Philox (seed, call, stage), so
+    BERs are statistically, not bit-wise, the host link's.
+
+    Refusals (``ValueError``, before anything is launched): other detector / code combinations, a real channel, a shape the
+    detector refuses, a ``send_chunk`` that does not fill whole vectors (or whole codewords).
+    """
+
+    def __init__(self, modem, channel, detector='kbest', K=16, output_type='hard', stack_size=(1, 3, 5), llr_max=500,
+                 ldpc_params=None, ldpc_alg='MSA', ldpc_iters=15, send_chunk=720, seed=1):
+        self.modem, self.channel = modem, channel
+        self.detector, self.output_type = detector, output_type
+        self.K, self.llr_max = int(K), float(llr_max)
+        self.seed = int(seed)
+        self.ldpc_params, self.ldpc_iters = ldpc_params, int(ldpc_iters)
+        self._plan(detector, output_type, stack_size, ldpc_params, ldpc_alg, send_chunk)
+        self.tx_batch = max(1, _VECTORS_PER_LAUNCH // self.vectors_per_tx)
+        self.keep_rx = False               # tests: keep the last batch's y, H, detector output and messages (self.last_rx)
+        self.last_rx = None
+        self._calls = 0
+        self._bufs = {}
+        # device state, only once every argument has been accepted
+        self.lib = _lib.load()
+        _lib.require_device()
+        self._chan = _channel_handles(channel)
+        self.encoder = None
+        if self.coded:
+            from commpy_amd.channelcoding.ldpc import _device_code
+            self.encoder = LdpcEncoder(ldpc_params)
+            self._code = _device_code(ldpc_params)
+
+    # -- the plan: every check that needs no device ------------------------------------------------------------------------------
+    def _plan(self, detector, output_type, stack_size, ldpc_params, ldpc_alg, send_chunk):
+        from commpy_amd.channels import MIMOFlatChannel
+        from commpy_amd.modulation import _bf_stacks
+        if not isinstance(self.channel, MIMOFlatChannel):
+            raise ValueError('DeviceMimoLink needs a MIMOFlatChannel')
+        _require_complex(self.channel)
+        nr, nt, nb = self.channel.nb_rx, self.channel.nb_tx, self.modem.num_bits_symbol
+        m = int(np.size(self.modem.constellation))
+        if m != 1 << nb:
+            raise ValueError('the modem must have 2^num_bits_symbol points')
+        self.coded = ldpc_params is not None
+        uncoded_ok = detector == 'ml' and output_type == 'hard' or detector == 'kbest' and output_type == 'hard'
+        coded_ok = detector == 'kbest' and output_type == 'soft' or detector == 'best_first'
+        if not (coded_ok if self.coded else uncoded_ok):
+            raise ValueError("detector %r with output %r %s an LDPC code is not a device MIMO link: uncoded links take 'ml' or "
+                             "'kbest' with 'hard' output, coded ones 'kbest' with 'soft' output or 'best_first'"
+                             % (detector, output_type, 'and' if self.coded else 'without'))
+        self.stacks = None
+        if detector == 'ml':
+            if nb * nt > 31:
+                raise ValueError('mimo_ml: m^nt above 2^31 hypotheses per vector')
+            if 16 * (nr * nt + nr + 64 * nr) > _ML_LDS:
+                raise ValueError('mimo_ml: %d receive antennas exceed the kernel\'s LDS' % nr)
+        elif detector == 'kbest':
+            if nt > nr:
+                raise ValueError('h has more columns than rows')
+            if self.K < 1:
+                raise ValueError('kbest: K must be a positive integer')
+            if min(self.K, m ** nt) * m >= 2 ** 31:
+                raise ValueError('kbest: K * m above 2^31 children')
+        else:
+            self.stacks = _bf_stacks(nr, nt, stack_size)
+            if nr > 64:
+                raise ValueError('best_first: %d receive antennas above the engine\'s 64' % nr)
+            if nr != nt:
+                raise ValueError('best_first gives nr * num_bits_symbol LLRs per vector: the link needs nr == nt (got %dx%d)' % (nr, nt))
+        if self.coded:
+            if ldpc_alg not in ('SPA', 'MSA'):
+                raise ValueError("ldpc_alg must be 'SPA' or 'MSA'")
+            self.alg = 0 if ldpc_alg == 'SPA' else 1
+            self.n = int(ldpc_params['n_vnodes'])
+            self.k = self.n - int(ldpc_params['n_cnodes'])
+            self.rate = Fraction(self.k, self.n)
+        else:
+            self.k = self.n = None
+            self.rate = Fraction(1)
+        divider = (Fraction(1, nb * nt) / self.rate).denominator          # LinkModel._prepare (links.py:203-214)
+        chunk = _whole(send_chunk)
+        self.send_chunk = max(divider, chunk // divider * divider)
+        if self.coded:
+            if self.send_chunk % self.k:
+                raise ValueError('send_chunk %d is not a whole number of %d-bit LDPC messages' % (self.send_chunk, self.k))
+            self.codewords_per_tx = self.send_chunk // self.k
+            self.tx_bits = self.codewords_per_tx * self.n
+        else:
+            self.codewords_per_tx = 0
+            self.tx_bits = self.send_chunk
+        if self.tx_bits % (nt * nb):
+            raise ValueError('%d transmitted bits per transmission do not fill whole vectors of %d x %d bits' % (self.tx_bits, nt, nb))
+        self.vectors_per_tx = self.tx_bits // (nt * nb)
+        self.nr, self.nt, self.nb = nr, nt, nb
+
+    def noise_std(self, snr_db):
+        """channels.py:74 for a complex channel: sqrt(2 nt Es / (rate 10^(SNR/10)))."""
+        return math.sqrt(2.0 * self.nt * self.modem.Es / (float(self.rate) * 10 ** (float(snr_db) / 10.0)))
+
+    # -- buffers ---------------------------------------------------------------------------------------------------------------
+    def _alloc(self, T):
+        if self._bufs.get('T') == T:
+            return self._bufs
+        for b in self._bufs.values():
+            if isinstance(b, DeviceBuf):
+                b.free()
+        V = T * self.vectors_per_tx
+        bufs = {'T': T, 'msg': DeviceBuf(T * self.send_chunk), 'y': DeviceBuf(V * self.nr * 16),
+                'h': DeviceBuf(V * self.nr * self.nt * 16), 'errs': DeviceBuf(T * 4)}
+        if self.coded:
+            B = T * self.codewords_per_tx
+            bufs.update(code=DeviceBuf(B * self.n), llr=DeviceBuf(B * self.n * 8), dec=DeviceBuf(B * self.n),
+                        out=DeviceBuf(B * self.n * 8), blk_errs=DeviceBuf(B * 4))
+        else:
+            bufs['idx'] = DeviceBuf(V * self.nt * 4)
+        self._bufs = bufs
+        return bufs
+
+    # -- one batch -------------------------------------------------------------------------------------------------------------
+    def run_batch(self, snr_db, T, mark=None):
+        """Bit errors per transmission (int32 ``[T]``) of ``T`` transmissions at ``snr_db``; every call draws from fresh
+        streams.  ``mark(stage, start)`` (benchmarks) is called around the stages 'source' (bits, encoder), 'channel', 'detector',
+        'decoder' (coded links) and 'count'."""
+        T = _whole(T)
+        if T < 1:
+            raise ValueError('T must be at least 1')
+        lib, ck, bufs = self.lib, _lib.check, self._alloc(T)
+        mark = mark or (lambda stage, start: None)
+        md = self.modem._device_handle()
+        noise_std = self.noise_std(snr_db)
+        self._calls += 1
+        s_bits, s_fade, s_noise = 3 * self._calls, 3 * self._calls + 1, 3 * self._calls + 2
+        V, nr, nt = T * self.vectors_per_tx, self.nr, self.nt
+        B = T * self.codewords_per_tx
+        mark('source', True)
+        ck(lib.cpx_random_bits_dev(bufs['msg'].ptr, T * self.send_chunk, self.seed, s_bits, None))
+        tx = bufs['msg']
+        if self.coded:
+            self.encoder.encode_dev(bufs['msg'].ptr, B, bufs['code'].ptr)
+            tx = bufs['code']
+        mark('source', False)
+        mark('channel', True)
+        ck(lib.cpx_mimo_channel_run_dev(self._chan.get(), md, tx.ptr, V, 0, noise_std * 0.5, self.seed, s_fade, s_noise,
+                                        bufs['y'].ptr, bufs['h'].ptr, None))
+        mark('channel', False)
+        mark('detector', True)
+        if self.detector == 'ml':
+            ck(lib.cpx_mimo_ml_dev(md, bufs['y'].ptr, bufs['h'].ptr, 1, V, nr, nt, bufs['idx'].ptr, None))
+        elif self.detector == 'kbest' and not self.coded:
+            ck(lib.cpx_kbest_hard_dev(md, bufs['y'].ptr, bufs['h'].ptr, 1, V, nr, nt, self.K, bufs['idx'].ptr, None))
+        elif self.detector == 'kbest':
+            ck(lib.cpx_kbest_soft_dev(md, bufs['y'].ptr, bufs['h'].ptr, 1, V, nr, nt, self.K, noise_std ** 2, bufs['llr'].ptr, None))
+        else:
+            ck(lib.cpx_best_first_dev(md, bufs['y'].ptr, bufs['h'].ptr, 1, V, nr, nt, _lib.ptr(self.stacks), self.llr_max, None,
+                                      bufs['llr'].ptr, None, None))
+        mark('detector', False)
+        llr_copy = None
+        if self.coded:
+            if self.keep_rx:                       # the decoder clips its input in place: keep what the detector gave
+                llr_copy = DeviceBuf(B * self.n * 8)
+                ck(lib.cpx_memcpy_d2d_async(llr_copy.ptr, bufs['llr'].ptr, B * self.n * 8, None))
+            mark('decoder', True)
+            ck(lib.cpx_ldpc_bp_decode_batch_bm_dev(self._code, bufs['llr'].ptr, B, self.alg, self.ldpc_iters, bufs['dec'].ptr,
+                                                   bufs['out'].ptr, None, None))
+            mark('decoder', False)
+            mark('count', True)
+            ck(lib.cpx_count_errors_dev(bufs['msg'].ptr, self.k, bufs['dec'].ptr, self.n, B, 1, self.k, bufs['blk_errs'].ptr, None))
+            mark('count', False)
+            ck(lib.cpx_stream_sync(None))
+            errs = bufs['blk_errs'].to_array((T, self.codewords_per_tx), np.int32).sum(axis=1, dtype=np.int32)
+        else:
+            mark('count', True)
+            ck(lib.cpx_mimo_hard_errors_dev(bufs['idx'].ptr, self.nb, bufs['msg'].ptr, T, self.send_chunk, bufs['errs'].ptr, None))
+            mark('count', False)
+            ck(lib.cpx_stream_sync(None))
+            errs = bufs['errs'].to_array((T,), np.int32)
+        if self.keep_rx:
+            rx = {'snr_db': float(snr_db), 'noise_std': noise_std, 'msg': bufs['msg'].to_array((T, self.send_chunk), np.uint8),
+                  'y': bufs['y'].to_array((V, nr), np.complex128), 'h': bufs['h'].to_array((V, nr, nt), np.complex128),
+                  'errs': errs.copy()}
+            if self.coded:
+                rx['tx'] = bufs['code'].to_array((T, self.tx_bits), np.uint8)
+                rx['llr'] = llr_copy.to_array((V, self.tx_bits // self.vectors_per_tx), np.float64)
+                rx['dec'] = bufs['dec'].to_array((B, self.n), np.int8)
+                llr_copy.free()
+            else:
+                rx['tx'] = rx['msg']
+                rx['idx'] = bufs['idx'].to_array((V, nt), np.int32)
+            self.last_rx = rx
+        return errs
+
+    # -- sweeps ----------------------------------------------------------------------------------------------------------------
+    def ber_sweep(self, snrs_db, n_bits, tx_batch=None):
+        """BER per SNR over at least ``n_bits`` message bits each (a fixed budget: no early stop)."""
+        tx_batch = self.tx_batch if tx_batch is None else max(1, _whole(tx_batch))
+        out = []
+        for snr in snrs_db:
+            done = errs = 0
+            while done < n_bits:
+                T = int(min(tx_batch, math.ceil((n_bits - done) / self.send_chunk)))
+                errs += int(self.run_batch(float(snr), T).sum())
+                done += T * self.send_chunk
+            out.append(errs / done)
+        return np.array(out)
+
+    def link_performance(self, SNRs, send_max, err_min):
+        """``LinkModel.link_performance`` on the device: per SNR, transmissions count in order while ``sent < send_max`` and
+        ``errors < err_min`` (the surplus of a batch is dropped); the sweep ends after a point that stayed below ``err_min``."""
+        return _sequential_ber(SNRs, send_max, err_min, self.send_chunk, self.tx_batch, self.run_batch)
+
+
+def _whole(v):
+    """``int(v)`` for integers and integral floats (what the reference's float arguments such as 5e5 are); ValueError otherwise."""
+    if isinstance(v, (float, np.floating)):
+        if not float(v).is_integer():
+            raise ValueError('%r is not a whole number' % (v,))
+        return int(v)
+    return operator.index(v)
+
+
+def _sequential_ber(SNRs, send_max, err_min, send_chunk, tx_batch, run):
+    """The stop rule of links.py:269-343 over batches: ``run(snr, T)`` returns the bit errors of T transmissions of ``send_chunk``
+    bits, which are taken one by one while ``sent < send_max and wrong < err_min``; BER = wrong / sent; the points after the first
+    one that ends with fewer than ``err_min`` errors stay 0.  ``send_max`` may be a float."""
+    curve = np.zeros(len(SNRs), dtype=float)
+    for i, snr in enumerate(SNRs):
+        sent = wrong = 0
+        while sent < send_max and wrong < err_min:
+            T = max(1, min(int(tx_batch), math.ceil((send_max - sent) / send_chunk)))
+            for e in run(snr, T):
+                if not (sent < send_max and wrong < err_min):
+                    break
+                sent += send_chunk
+                wrong += int(e)
+        curve[i] = wrong / sent
+        if wrong < err_min:
+            break
+    return curve

@@ -364,6 +364,34 @@ int cpx_best_first_dev(const cpx_modem *m, const double *d_y_re_im, const double
                        int nt, const int32_t *stack_size, double llr_max, const uint8_t *d_labels, double *d_llr,
                        int32_t *d_iters, void *stream);
 
+/* ---- MIMO link stages on the device ---------------------------------------------------
+ * The MIMO flat-fading channel of commpy/channels.py:242-330 (MIMOFlatChannel.propagate, Kronecker model) and the hard-decision
+ * error count of a MIMO link, so that a Monte-Carlo MIMO point never leaves HBM.  Device pointers, asynchronous on `stream`.
+ *   cpx_mimo_channel_create   HOST matrices, complex (re, im), row-major: sqrt_rr = sqrtm(Rr) [nr][nr], sqrt_rt_T = sqrtm(Rt).T [nt][nt],
+ *                             mean [nr][nt] -- the three matrices propagate uses (fading_param); an exact identity sqrt_rr / sqrt_rt_T
+ *                             (the uncorrelated case) skips its product.  Non-finite entries: CPX_EINVAL.
+ *   cpx_mimo_channel_run_dev  V vectors of nt symbols: d_bits [V][nt][nb] uint8 (the modem's labels, MSB first: modulate_kernel and
+ *                             the reference's row-major reshape(nb_vect, nb_tx)) -> d_h_re_im [V][nr][nt] = A G Bt + mean with G of
+ *                             i.i.d. CN(0, 1) entries (N(0, 1/2) per component) and d_y_re_im [V][nr] = H x + noise_scale (n_re + j n_im),
+ *                             n ~ N(0, 1).  Philox streams keyed by (seed, stream_fading, (first_vector + v) nr nt + r nt + a) for G and
+ *                             (seed, stream_noise, (first_vector + v) nr + r) for the noise (cpx_awgn_dev's draws), so a batch split
+ *                             into launches at any vector gives the same bytes.  Sums run in ascending index order from 0: T = A G
+ *                             (over q), H = T Bt (over p) + mean, y = H x (over a) + noise.  Any nr, nt >= 1.
+ *   cpx_mimo_hard_errors_dev  errs [T] int32: bits of msg [T][bits_per_tx] uint8 that differ from the MSB-first nb-bit labels of the
+ *                             detected indices d_idx (symbol s of transmission t = d_idx[t bits_per_tx / nb + s], i.e. [V][nt] with
+ *                             whole vectors per transmission): what mimo_receiver's hard path and LinkModel count on the host.
+ *                             bits_per_tx must be a multiple of nb (CPX_EINVAL).
+ * The handle belongs to the device that was current at cpx_mimo_channel_create.
+ */
+typedef struct cpx_mimo_channel cpx_mimo_channel;
+int cpx_mimo_channel_create(int nr, int nt, const double *sqrt_rr, const double *sqrt_rt_T, const double *mean, cpx_mimo_channel **out);
+int cpx_mimo_channel_destroy(cpx_mimo_channel *ch);
+int cpx_mimo_channel_run_dev(const cpx_mimo_channel *ch, const cpx_modem *m, const uint8_t *d_bits, int64_t V, uint64_t first_vector,
+                             double noise_scale, uint64_t seed, uint64_t stream_fading, uint64_t stream_noise, double *d_y_re_im,
+                             double *d_h_re_im, void *stream);
+int cpx_mimo_hard_errors_dev(const int32_t *d_idx, int nb, const uint8_t *d_msg, int64_t T, int64_t bits_per_tx, int32_t *d_errs,
+                             void *stream);
+
 /* ---- link-simulation stages around the decoders ("next" rows) ---------------------------
  * Device-resident (all pointers are device pointers, asynchronous on `stream`), so that a Monte-Carlo
  * BER sweep (commpy/links.py:155-267, commpy/wifi80211.py:132-216) never leaves HBM.

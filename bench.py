@@ -2,29 +2,38 @@
 """Headline benchmark: soft-decision Viterbi, K=7 rate-1/2 (0o133, 0o171), 1024-bit blocks,
 QPSK + AWGN at Eb/N0 = 3 dB, batch 65536 codewords per GPU (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the HIP Viterbi decoder over the whole per-GPU batch with the float64 LLRs
 already resident in HBM.  N > 1 is weak scaling, one process per GPU, every rank decodes its own 65536-codeword batch.
 The ranks come from either launcher: ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`` (RANK /
 WORLD_SIZE in the environment; WORLD_SIZE != N is an error), or plain ``python bench.py --gpus N``, which starts the N
 ranks ITSELF (subprocesses, no torch) after checking that N devices are visible -- it never silently runs one GPU.
-The path shards by codeword and has no exchange step, so `value` times the decode alone; the SAME K steps are then timed
-again with the one collective north_star names -- an RCCL all-gather of the decoded bits (uint8, 67.5 MB per rank and
-step) on the decode stream -- in every step and reported as `value_with_gather`; `comm_world` is what RCCL itself
+The path shards by codeword and has no exchange step, so `value` times the decode alone; `comm_world` is what RCCL itself
 reports for the communicator (ncclCommCount).
 Collectives (closing barrier, max over ranks, error-count all-reduce, the optional all-gather) go through the
 engine's own RCCL binding (``cpx_comm_*``, commpy_amd.parallel.RankComm); torch is NOT imported anywhere in this file (round 5:
-the ``--comm torch`` alternative is gone -- if the RCCL communicator cannot be formed the run fails).  Rank 0 prints ONE JSON line with the contract fields plus `roofline`
-(dominant kernel as reported by the library, HIP-event timed on its own stream) and `cpu_baseline`: the UNMODIFIED reference
-timed on the host cores when it is present on the box ($CPX_REFERENCE_PATH, /root/reference, importable `commpy`; kind
-"reference"), else the C oracle -- a line-by-line port of the same function -- on >= 4096 distinct codewords (kind "port");
-the NumPy-vectorised restatement rides along as a labelled secondary.  At N = 1 the line also carries `other_configs`
-(benchmarks/other_configs.py): configs[2] (turbo), one GPU's share of configs[3] (64-QAM soft demodulator -> LDPC min-sum and
-sum-product) and the soft demodulator alone, each device-resident, HIP-event timed for the same K steps and checked against
-the oracle after its timed region -- the headline fields are untouched by it (``--no-other-configs`` leaves it out).
+the ``--comm torch`` alternative is gone -- if the RCCL communicator cannot be formed the run fails).
+
+A plain run does what the headline needs and no more: it generates the input, runs the untimed kernel-path check (see main;
+it is also what brings the GPU to its clock before the warm-up), the W warm-up and the K timed steps, writes --dump-outputs,
+and rank 0 prints ONE JSON line with the contract fields plus `roofline` (dominant kernel as reported by the library, its
+launches HIP-event timed on their own stream during the K steps).  Every field that only ``--full`` fills is there as null.
+``--full`` adds, after the timed steps and without touching their figures:
+  * the checks of what was timed: BER against the messages, 16 386 codewords against the CPU oracle, the demodulator's LLRs;
+  * N > 1: the SAME K steps timed again with the one collective north_star names -- an RCCL all-gather of the decoded bits
+    (uint8, 67.5 MB per rank and step) on the decode stream in every step -- reported as `value_with_gather`;
+  * `roofline.clock` (the shader clock during a repetition of the K steps) and, N = 1, `roofline.sustained` (the step back to
+    back for --sustain-seconds);
+  * N = 1: `other_configs` (benchmarks/other_configs.py): configs[2] (turbo), one GPU's share of configs[3] (64-QAM soft
+    demodulator -> LDPC min-sum and sum-product) and the soft demodulator alone, each device-resident, HIP-event timed for the
+    same K steps and checked against the oracle after its timed region (``--no-other-configs`` leaves it out);
+  * N = 1: `cpu_baseline`: the UNMODIFIED reference timed on the host cores when it is present ($CPX_REFERENCE_PATH, a
+    reference checkout, importable `commpy`; kind "reference"), else the C oracle -- a line-by-line port of the same
+    function -- on >= 4096 distinct codewords (kind "port"); the NumPy-vectorised restatement rides along as a labelled
+    secondary (``--no-cpu-baseline`` leaves it out).
 ``--dump-outputs DIR`` writes what the last timed step decoded as float32 .npy files (see dump_outputs), so that two builds
-can be compared output for output on identical inputs.
+can be compared output for output on identical inputs; it is the same with or without ``--full``.
 """
 import argparse
 import ctypes
@@ -353,17 +362,22 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=65536, help="codewords per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything the headline does not need: the checks of what was timed "
+                         "(BER, oracle sample, demodulator), the clock probe, N > 1: the decode + all-gather region, N = 1: the "
+                         "sustained phase, `other_configs` and `cpu_baseline` (~30 s); without it their fields are null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave `cpu_baseline` out")
     ap.add_argument("--no-path-check", action="store_true",
                     help="skip the untimed full-batch comparison of the three Viterbi kernel families before the warm-up")
     ap.add_argument("--gather", action="store_true",
-                    help="accepted for older command lines; N > 1 always times both regions (decode alone -> value, decode + "
-                         "RCCL all-gather of the decoded bits on the decode stream -> value_with_gather)")
-    ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the second (decode + all-gather) timed region")
+                    help="accepted for older command lines; N > 1 with --full always times both regions (decode alone -> value, "
+                         "decode + RCCL all-gather of the decoded bits on the decode stream -> value_with_gather)")
+    ap.add_argument("--no-gather", action="store_true", help="--full, N > 1: skip the second (decode + all-gather) timed region")
     ap.add_argument("--sustain-seconds", type=float, default=2.0,
-                    help="N = 1: after the timed region run the same step back to back for this long (GPU-busy evidence; 0 = skip)")
+                    help="--full, N = 1: after the timed region run the same step back to back for this long (GPU-busy "
+                         "evidence; 0 = skip)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N = 1: skip the `other_configs` lines (turbo, LDPC chain, soft demodulator; ~15 s)")
+                    help="--full, N = 1: skip the `other_configs` lines (turbo, LDPC chain, soft demodulator; ~15 s)")
     ap.add_argument("--synth", choices=("device", "host"), default="device",
                     help="where the synthetic input is generated: on the GPU (Philox bits/noise, device encoder and "
                          "modulator; fast, no large host arrays) or on the host (NumPy MT19937, SURVEY 8d seeds)")
@@ -388,7 +402,7 @@ def main():
         sys.exit(launch_ranks(world, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
     local_rank = int(os.environ.get("LOCAL_RANK", str(rank)))
     distributed = mode == "rank"
-    args.gather = distributed and world > 1 and not args.no_gather
+    args.gather = args.full and distributed and world > 1 and not args.no_gather
     comm = None
     from commpy_amd import _lib
     lib = _lib.load()
@@ -445,10 +459,11 @@ def main():
         sc = float(np.sqrt(N0 / 2))
         _lib.check(lib.cpx_awgn_dev(d_sym, B * nsym, sc, sc, 11 + 1000 * rank, 2, d_y, stream))
         sync()
-        msgs = np.empty((B, MSG_BITS), dtype=np.uint8)
-        _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(msgs), d_msg, msgs.nbytes))
-        y = np.empty((1, nsym), dtype=np.complex128)              # first codeword's symbols for the demod spot check
-        _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(y), d_y, y.nbytes))
+        if args.full:                                              # what the checks after the timed region compare against
+            msgs = np.empty((B, MSG_BITS), dtype=np.uint8)
+            _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(msgs), d_msg, msgs.nbytes))
+            y = np.empty((1, nsym), dtype=np.complex128)          # first codeword's symbols for the demod spot check
+            _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(y), d_y, y.nbytes))
         for d in (d_msg, d_coded, d_sym):
             _lib.check(lib.cpx_free(d))
 
@@ -477,7 +492,8 @@ def main():
     # (the fused kernel), the two-kernel codeword path and the state-per-lane kernels must return the same bits for all B codewords
     # (the oracle comparison after the timed region covers 16 386 of them).  Said plainly: these ~7 ms of decoding also mean that the
     # GPU is no longer at its idle clock when the W warm-up steps start (BENCH_DEBUG=1 prints the per-step times; --no-path-check
-    # leaves the check out).
+    # leaves the check out).  That is why a plain run keeps it: without it more of the clock ramp falls into the timed steps, and
+    # the same kernel has measured 41.5 - 42.5 G instead of 43.2 G (profiles/README.md, r03).
     path_check = None
     if not args.no_path_check and args.precision == "fp64-parity":
         d_alt, d_errs = ctypes.c_void_p(), ctypes.c_void_p()
@@ -569,114 +585,116 @@ def main():
     elapsed_g = gather_ms = None
     if args.gather:
         elapsed_g, gather_ms = timed_region(True)                  # `value_with_gather`: the same K steps + the all-gather
-    # Clock evidence (round 5), untimed: the same K steps once more with the engine's shader-clock probe (one sleeping wavefront on its own
-    # stream, cpx_sclk_probe_*) running alongside: average sclk over the interval and the per-launch times measured DURING it.  sclk x
-    # time = cycles per launch, which is what rocprofv3's GRBM_GUI_ACTIVE / 8 reports for the same kernel at the lower clock it runs
-    # at under the profiler (profiles/README.md) -- recorded instead of argued.
-    clock = None
-    probe = ctypes.c_void_p()
-    try:
-        probe = ctypes.c_void_p()                                   # a throw-away probe first: its one-time costs (stream, buffer, code
-        _lib.check(lib.cpx_sclk_probe_start(ctypes.byref(probe), 0.2))   # object) must not leave the GPU idle in front of the real interval
-        _lib.check(lib.cpx_sclk_probe_read(probe, None, None))
+    clock = sustained = None
+    if args.full:
+        # Clock evidence (round 5), untimed: the same K steps once more with the engine's shader-clock probe (one sleeping wavefront on its own
+        # stream, cpx_sclk_probe_*) running alongside: average sclk over the interval and the per-launch times measured DURING it.  sclk x
+        # time = cycles per launch, which is what the profiler's GRBM_GUI_ACTIVE / 8 reports for the same kernel at the lower clock it
+        # runs at under the profiler (profiles/README.md) -- recorded instead of argued.
         probe = ctypes.c_void_p()
-        for _ in range(max(args.warmup, 8)):                       # the host read the timers meanwhile: no idle clock in the interval
-            step(None, False)
-        sync()
-        probe = ctypes.c_void_p()
-        _lib.check(lib.cpx_sclk_probe_start(ctypes.byref(probe), max(0.5, 0.9 * args.steps * float(np.median(kernel_ms)))))
-        tm2 = make_timers(args.steps)
-        for k in range(args.steps):
-            step(tm2[k], False)
-        sync()
-        ms2 = read_timers(tm2)
-        for tmr in tm2:
-            lib.cpx_timer_destroy(tmr)
-        mhz, ival = ctypes.c_double(), ctypes.c_double()
-        started, probe = probe, ctypes.c_void_p()                   # (read frees the probe whatever it returns)
-        _lib.check(lib.cpx_sclk_probe_read(started, ctypes.byref(mhz), ctypes.byref(ival)))
-        clock = {"sclk_mhz": mhz.value, "probe_interval_ms": ival.value, "kernel_ms_avg_during_probe": float(np.mean(ms2)),
-                 "kernel_ms_median_during_probe": float(np.median(ms2)),
-                 "shader_cycles_per_launch": mhz.value * 1e3 * float(np.median(ms2)),
-                 "how": "cpx_sclk_probe: s_memtime (shader-clock counter) over s_memrealtime (constant-rate counter) of one sleeping "
-                        "wavefront on its own stream while the same K steps ran again, outside the timed region"}
-    except Exception as exc:                                       # evidence, never a reason to lose the line
-        clock = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:200])}
-        if probe:                                                  # a probe that was started and never read goes back to the library
-            lib.cpx_sclk_probe_destroy(probe)
-    # Sustained phase (round 6), untimed for `value`: the K timed steps are ~30 ms of a run that lasts many seconds, so an outside sampler
-    # (rocm-smi style GPU-busy polling, the driver's own clock) cannot see them.  The same step then runs back to back for
-    # --sustain-seconds of wall time; its average per step is reported next to the timed one and has to agree with it.
-    sustained = None
-    if world == 1 and args.sustain_seconds > 0:
         try:
-            t0s, n_s = time.perf_counter(), 0
-            while time.perf_counter() - t0s < args.sustain_seconds:
-                for _ in range(100):
-                    step(None, False)
-                sync()
-                n_s += 100
-            dts = time.perf_counter() - t0s
-            sustained = {"steps": n_s, "seconds": dts, "ms_per_step": dts / n_s * 1e3, "info_bits_per_s": B * MSG_BITS * n_s / dts,
-                         "note": "the headline step back to back (host clock around batches of 100 launches + a stream sync), after the timed "
-                                 "region; not part of `value`"}
-        except Exception as exc:                                   # evidence, never a reason to lose the line
-            sustained = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:200])}
+            probe = ctypes.c_void_p()                                   # a throw-away probe first: its one-time costs (stream, buffer, code
+            _lib.check(lib.cpx_sclk_probe_start(ctypes.byref(probe), 0.2))   # object) must not leave the GPU idle in front of the real interval
+            _lib.check(lib.cpx_sclk_probe_read(probe, None, None))
+            probe = ctypes.c_void_p()
+            for _ in range(max(args.warmup, 8)):                       # the host read the timers meanwhile: no idle clock in the interval
+                step(None, False)
+            sync()
+            probe = ctypes.c_void_p()
+            _lib.check(lib.cpx_sclk_probe_start(ctypes.byref(probe), max(0.5, 0.9 * args.steps * float(np.median(kernel_ms)))))
+            tm2 = make_timers(args.steps)
+            for k in range(args.steps):
+                step(tm2[k], False)
+            sync()
+            ms2 = read_timers(tm2)
+            for tmr in tm2:
+                lib.cpx_timer_destroy(tmr)
+            mhz, ival = ctypes.c_double(), ctypes.c_double()
+            started, probe = probe, ctypes.c_void_p()                   # (read frees the probe whatever it returns)
+            _lib.check(lib.cpx_sclk_probe_read(started, ctypes.byref(mhz), ctypes.byref(ival)))
+            clock = {"sclk_mhz": mhz.value, "probe_interval_ms": ival.value, "kernel_ms_avg_during_probe": float(np.mean(ms2)),
+                     "kernel_ms_median_during_probe": float(np.median(ms2)),
+                     "shader_cycles_per_launch": mhz.value * 1e3 * float(np.median(ms2)),
+                     "how": "cpx_sclk_probe: s_memtime (shader-clock counter) over s_memrealtime (constant-rate counter) of one sleeping "
+                            "wavefront on its own stream while the same K steps ran again, outside the timed region"}
+        except Exception as exc:                                       # evidence, never a reason to lose the line
+            clock = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:200])}
+            if probe:                                                  # a probe that was started and never read goes back to the library
+                lib.cpx_sclk_probe_destroy(probe)
+        # Sustained phase (round 6), untimed for `value`: the K timed steps are ~30 ms of a run that lasts many seconds, so an outside sampler
+        # (GPU-busy polling, the driver's own clock) cannot see them.  The same step then runs back to back for
+        # --sustain-seconds of wall time; its average per step is reported next to the timed one and has to agree with it.
+        if world == 1 and args.sustain_seconds > 0:
+            try:
+                t0s, n_s = time.perf_counter(), 0
+                while time.perf_counter() - t0s < args.sustain_seconds:
+                    for _ in range(100):
+                        step(None, False)
+                    sync()
+                    n_s += 100
+                dts = time.perf_counter() - t0s
+                sustained = {"steps": n_s, "seconds": dts, "ms_per_step": dts / n_s * 1e3, "info_bits_per_s": B * MSG_BITS * n_s / dts,
+                             "note": "the headline step back to back (host clock around batches of 100 launches + a stream sync), after the timed "
+                                     "region; not part of `value`"}
+            except Exception as exc:                                   # evidence, never a reason to lose the line
+                sustained = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:200])}
     comm_world = None
     if comm is not None:
         nr, nl, fr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         _lib.check(lib.cpx_comm_info(comm.h, ctypes.byref(nr), ctypes.byref(nl), ctypes.byref(fr)))
         comm_world = {"nranks": nr.value, "this_rank": fr.value, "source": "ncclCommCount / ncclCommUserRank"}
 
-    # ---- correctness of what was timed: BER vs the messages, parity vs the oracle on a sample ----
-    bits = np.empty((B, L), dtype=np.uint8)
-    _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(bits), d_bits, bits.nbytes))
-    nerr = int(np.sum(bits[:, :MSG_BITS] != msgs))
-    gather_ok = None
+    # ---- --full: correctness of what was timed: BER vs the messages, parity vs the oracle on a sample ----
+    bits = ber = gather_ok = None
+    if args.full:
+        bits = np.empty((B, L), dtype=np.uint8)
+        _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(bits), d_bits, bits.nbytes))
+        nerr = int(np.sum(bits[:, :MSG_BITS] != msgs))
 
-    def allreduce_i64(v):
-        v = np.ascontiguousarray(v, dtype=np.int64)
-        return comm.allreduce(v)
+        def allreduce_i64(v):
+            v = np.ascontiguousarray(v, dtype=np.int64)
+            return comm.allreduce(v)
 
-    if world > 1:
-        # error counts of all shards: an RCCL all-reduce of int64 counters (links.py:252-260), outside the timed region
-        nerr = int(allreduce_i64([nerr])[0])
-    if args.gather:
-        # every rank holds every rank's bits: this rank's own slot must equal what it decoded, and every OTHER slot must carry
-        # the checksums (ones count, position-weighted sum) its owner computed from its own decode and published by all-reduce
-        full = np.empty((world, B, L), dtype=np.uint8)
-        _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(full), d_full, full.nbytes))
-        w = (np.arange(L, dtype=np.int64) % 251) + 1
+        if world > 1:
+            # error counts of all shards: an RCCL all-reduce of int64 counters (links.py:252-260), outside the timed region
+            nerr = int(allreduce_i64([nerr])[0])
+        if args.gather:
+            # every rank holds every rank's bits: this rank's own slot must equal what it decoded, and every OTHER slot must carry
+            # the checksums (ones count, position-weighted sum) its owner computed from its own decode and published by all-reduce
+            full = np.empty((world, B, L), dtype=np.uint8)
+            _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(full), d_full, full.nbytes))
+            w = (np.arange(L, dtype=np.int64) % 251) + 1
 
-        def cks(a):
-            return [int(a.sum(dtype=np.int64)), int((a.sum(axis=0, dtype=np.int64) * w).sum())]
+            def cks(a):
+                return [int(a.sum(dtype=np.int64)), int((a.sum(axis=0, dtype=np.int64) * w).sum())]
 
-        mine = np.zeros((world, 2), np.int64)
-        mine[rank] = cks(bits)
-        published = allreduce_i64(mine.reshape(-1)).reshape(world, 2)
-        gather_ok = bool(np.array_equal(full[rank], bits) and
-                         all(cks(full[r]) == list(published[r]) for r in range(world)))
-        gather_ok = bool(allreduce_i64([0 if gather_ok else 1])[0] == 0)         # true only if it held on EVERY rank
-    ber = nerr / float(world * B * MSG_BITS)
+            mine = np.zeros((world, 2), np.int64)
+            mine[rank] = cks(bits)
+            published = allreduce_i64(mine.reshape(-1)).reshape(world, 2)
+            gather_ok = bool(np.array_equal(full[rank], bits) and
+                             all(cks(full[r]) == list(published[r]) for r in range(world)))
+            gather_ok = bool(allreduce_i64([0 if gather_ok else 1])[0] == 0)         # true only if it held on EVERY rank
+        ber = nerr / float(world * B * MSG_BITS)
     out = None
     if rank == 0:
-        import oracle
-        # parity of what was timed: 16384 codewords (first / middle / last 5462 of the batch: every wavefront position of
-        # the first, middle and last workgroups) against the oracle, decoded on the host threads
-        ns = min(B, 5462)
-        starts = sorted({0, max(0, B // 2 - ns // 2), B - ns})
-        mism, checked = 0, 0
-        llr_s = None
-        for lo in starts:
-            blk = np.empty((ns, LEN))
-            _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(blk), ctypes.c_void_p(d_llr.value + lo * LEN * 8), blk.nbytes))
-            want = oracle.viterbi_decode_mt(blk, tr, None, "soft", usable_cores())
-            mism += int(np.sum(want != bits[lo:lo + ns]))
-            checked += ns
-            if lo == 0:
-                llr_s = blk
-        llr_ref = oracle.demodulate(md.constellation, y[0], "soft", N0)
-        demod_err = float(np.max(np.abs(llr_ref - llr_s[0])))
+        mism = checked = demod_err = llr_s = ns = None
+        if args.full:
+            import oracle
+            # parity of what was timed: 16384 codewords (first / middle / last 5462 of the batch: every wavefront position of
+            # the first, middle and last workgroups) against the oracle, decoded on the host threads
+            ns = min(B, 5462)
+            starts = sorted({0, max(0, B // 2 - ns // 2), B - ns})
+            mism, checked = 0, 0
+            for lo in starts:
+                blk = np.empty((ns, LEN))
+                _lib.check(lib.cpx_memcpy_d2h(_lib.ptr(blk), ctypes.c_void_p(d_llr.value + lo * LEN * 8), blk.nbytes))
+                want = oracle.viterbi_decode_mt(blk, tr, None, "soft", usable_cores())
+                mism += int(np.sum(want != bits[lo:lo + ns]))
+                checked += ns
+                if lo == 0:
+                    llr_s = blk
+            llr_ref = oracle.demodulate(md.constellation, y[0], "soft", N0)
+            demod_err = float(np.max(np.abs(llr_ref - llr_s[0])))
         kavg = float(np.mean(kernel_ms))
         achieved = ALG_BYTES_PER_CW * B / (kavg * 1e-3) / 1e9
         value = world * B * MSG_BITS * args.steps / elapsed
@@ -718,6 +736,7 @@ def main():
                            world, "; `value_with_gather`: + one RCCL all-gather of the decoded bits (%d B per rank) per step"
                            % (B * L) if args.gather else ""),
                        "collectives": "engine RCCL binding (cpx_comm_*)" if comm is not None else "none (single process)"},
+            "full": args.full,                                     # false: the fields only --full fills below are null
             "ber": ber, "oracle_mismatched_bits": mism, "oracle_sample_codewords": checked, "kernel_path_check": path_check, "build_id": build,
             "git_head": _git_head()[0], "git_head_source": _git_head()[1],
             "demod_max_abs_err_vs_oracle": demod_err,
@@ -753,16 +772,16 @@ def main():
                 "note": "HIP events on rank 0 around decode + ncclAllGather (in place, [world][B][L] uint8 on every GPU)"}
             out["comm_world"] = comm_world
             out["launcher"] = "bench.py (subprocess per rank)" if os.environ.get("CPX_COMM_NONCE") else "external (RANK/WORLD_SIZE set)"
-        # the other decoders north_star names, on their own configurations (N = 1 only; the headline fields above are final)
+        # the other decoders north_star names, on their own configurations (--full, N = 1 only; the headline fields above are final)
         out["other_configs"] = None
-        if world == 1 and not args.no_other_configs and args.precision == "fp64-parity":
+        if args.full and world == 1 and not args.no_other_configs and args.precision == "fp64-parity":
             for d in (d_y, d_llr, d_full):
                 _lib.check(lib.cpx_free(d))
             d_y = d_llr = d_full = None
             from benchmarks import other_configs
             out["other_configs"] = other_configs.run(lib, args.steps, args.warmup,
                                                      log=(lambda m: print(m, file=sys.stderr)) if os.environ.get("BENCH_DEBUG") else None)
-        if not args.no_cpu_baseline and world == 1:                # reported at N = 1 only; the other ranks would idle
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N = 1 only; the other ranks would idle
             out["cpu_baseline"] = cpu_baseline(tr, llr_s, bits[:ns, :].astype(np.int64))
         else:
             out["cpu_baseline"] = None

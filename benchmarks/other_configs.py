@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """The decoders north_star names next to the Viterbi headline, on their BASELINE.json configurations, as lines that the
-DRIVER's one `bench.py` run carries (round 5: until now only the builder had ever timed them).
+DRIVER's one `bench.py --full` run carries (round 5: until now only the builder had ever timed them).
 
-    run(lib, steps, warmup) -> list of dicts          (bench.py puts it into the JSON line as `other_configs`)
+    run(lib, steps, warmup) -> list of dicts          (bench.py --full puts it into the JSON line as `other_configs`)
     python benchmarks/other_configs.py [--steps K]    (the same lines on their own, one JSON object per line)
 
 Every entry is device-resident, timed with HIP events on the launch stream for the same number of steps as the headline,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """rocprofv3 evidence for one workload: kernel-trace stats + separate PMC passes, summarised per kernel into JSON.
 
-    python scripts/collect_pmc.py --out gpurun_out/r02 --name viterbi_c2 --match viterbi -- python bench.py --steps 3 ...
+    python scripts/collect_pmc.py --out <dir> --name viterbi_c2 --match viterbi -- python bench.py --steps 3 --full ...
 
 Runs the command once under `rocprofv3 --kernel-trace --stats` and once per counter group under
 `rocprofv3 --pmc <group> --kernel-trace` (counters in their own runs, never mixed with other trace domains;

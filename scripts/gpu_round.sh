@@ -22,12 +22,12 @@ if [[ $SEC == *s* ]]; then
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 | tee $OUT/smoke.txt
 fi
 if [[ $SEC == *b* ]]; then
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 2>&1 | tail -3 | tee $OUT/bench_n1.json
-  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline --precision fp32-fast 2>&1 | tail -1 | tee $OUT/bench_fp32_fast.json | cut -c1-400
+  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>&1 | tail -3 | tee $OUT/bench_n1.json
+  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 3 --full --no-cpu-baseline --precision fp32-fast 2>&1 | tail -1 | tee $OUT/bench_fp32_fast.json | cut -c1-400
 fi
 if [[ $SEC == *d* ]]; then
   timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 \
-      bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --gather 2>&1 | tail -5 | tee $OUT/bench_torchrun_n1.txt
+      bench.py --gpus 1 --steps 5 --warmup 2 --full --no-cpu-baseline --gather 2>&1 | tail -5 | tee $OUT/bench_torchrun_n1.txt
 fi
 if [[ $SEC == *k* ]]; then
   timeout 1200 python benchmarks/bench_kernels.py 2>&1 | tee $OUT/bench_kernels.jsonl | cut -c1-250
@@ -42,7 +42,7 @@ if [[ $SEC == *l* ]]; then
 fi
 if [[ $SEC == *v* ]]; then
   timeout 1500 python scripts/collect_pmc.py --out $OUT --name viterbi_c2 --match viterbi --batch 65536 -- \
-      python $R/bench.py --steps 25 --warmup 5 --no-cpu-baseline --no-other-configs --sustain-seconds 0 2>&1 | tail -40
+      python $R/bench.py --steps 25 --warmup 5 --full --no-cpu-baseline --no-other-configs --sustain-seconds 0 2>&1 | tail -40
 fi
 if [[ $SEC == *u* ]]; then
   timeout 1500 python scripts/collect_pmc.py --out $OUT --name turbo_c3 --match _kernel --fetch-scale 2 -- \

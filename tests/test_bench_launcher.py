@@ -123,28 +123,33 @@ def test_id_exchange_rejects_a_file_of_another_launch(tmp_path):
     assert parallel._launcher_start_ticks().isdigit() and int(parallel._launcher_start_ticks()) > 0
 
 
-def test_bench_gpus_2_end_to_end_against_the_host_stand_in(tmp_path):
-    """`bench.py --gpus 2` has never run with two ranks on hardware (one GPU per lease; SCALE_r01..r04 skipped).  Here its rank
-    path runs END TO END in two real processes started by bench.py's own launcher, against tests/fake_engine.py -- a host
-    stand-in for the C-ABI that lives in tests/ only (the product has no CPU fallback): RankComm's nonce rendezvous,
-    cpx_comm_init_rank -> allgather_dev -> allreduce -> cpx_comm_info, the in-place gather layout and its checksum exchange, and
-    the N > 1 fields of the JSON line."""
+def _bench_gpus_2_on_the_host_stand_in(tmp_path, *extra):
+    """`bench.py --gpus 2 --steps 2 --warmup 1 --batch 48` against tests/fake_engine.py, two ranks started by bench.py's own
+    launcher; returns rank 0's JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "CPX_COMM_NONCE")}
     env["CPX_FAKE_DIR"] = str(tmp_path)
     env["CPX_FAKE_DEVICES"] = "2"
     out_path = tmp_path / "stdout.txt"
     with open(out_path, "w") as fo:
-        import contextlib
         argv = [sys.executable, os.path.join(ROOT, "tests", "fake_engine.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                "--batch", "48", "--no-cpu-baseline"]
+                "--batch", "48"] + list(extra)
         # bench.launch_ranks inherits stdout: run it in a child so that rank 0's line lands in a file
         code = ("import sys; sys.path.insert(0, %r); import bench; sys.exit(bench.launch_ranks(2, %r, timeout=240))" % (ROOT, argv))
         r = subprocess.run([sys.executable, "-c", code], env=env, stdout=fo, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in open(out_path).read().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines                                      # ONE line, from rank 0
-    j = json.loads(lines[0])
-    assert j["n_gpus"] == 2 and j["steps"] == 2 and j["scaling"] == "weak"
+    return json.loads(lines[0])
+
+
+def test_bench_gpus_2_end_to_end_against_the_host_stand_in(tmp_path):
+    """`bench.py --gpus 2` has never run with two ranks on hardware (one GPU per lease; SCALE_r01..r04 skipped).  Here its rank
+    path runs END TO END in two real processes started by bench.py's own launcher, against tests/fake_engine.py -- a host
+    stand-in for the C-ABI that lives in tests/ only (the product has no CPU fallback): RankComm's nonce rendezvous,
+    cpx_comm_init_rank -> allgather_dev -> allreduce -> cpx_comm_info, the in-place gather layout and its checksum exchange, and
+    the N > 1 fields of the JSON line (the all-gather region and the checks are --full)."""
+    j = _bench_gpus_2_on_the_host_stand_in(tmp_path, "--no-cpu-baseline", "--full")
+    assert j["n_gpus"] == 2 and j["steps"] == 2 and j["scaling"] == "weak" and j["full"] is True
     assert j["config"]["batch_per_gpu"] == 48 and "x2" in j["config"]["parallelism"]
     assert j["config"]["collectives"] == "engine RCCL binding (cpx_comm_*)"
     assert j["value"] > 0 and j["value_with_gather"] > 0 and j["ms_per_step_with_gather"] > 0
@@ -162,14 +167,37 @@ def test_bench_gpus_2_end_to_end_against_the_host_stand_in(tmp_path):
         assert ("cpx_comm_unique_id" in calls) == (rank == 0)          # rank 0 makes the id, rank 1 reads it from the nonce-keyed file
 
 
-def _bench_single_on_the_host_stand_in(tmp_path, *extra):
+def test_bench_gpus_2_plain_run_times_the_decode_and_nothing_else(tmp_path):
+    """Without --full an N > 1 run forms the communicator, times the K decode steps (max over ranks) and prints the line: no
+    all-gather region, no checks after it; the fields only --full fills are there as null."""
+    j = _bench_gpus_2_on_the_host_stand_in(tmp_path)
+    assert j["n_gpus"] == 2 and j["steps"] == 2 and j["full"] is False
+    assert j["value"] > 0 and j["ms_per_step"] > 0 and j["unit"] == "info-bits/s" and j["higher_is_better"] is True
+    assert j["dtype"] == "f64" and j["roofline"]["kernel_ms_avg"] > 0
+    assert j["comm_world"] == {"nranks": 2, "this_rank": 0, "source": "ncclCommCount / ncclCommUserRank"}
+    assert j["kernel_path_check"]["mismatching_bits_between_repeats"] == 0
+    assert "all-gather" not in j["config"]["parallelism"]
+    for key in ("value_with_gather", "ms_per_step_with_gather", "gather", "ber", "oracle_mismatched_bits", "oracle_sample_codewords",
+                "demod_max_abs_err_vs_oracle", "other_configs", "cpu_baseline"):
+        assert j[key] is None, key
+    assert j["roofline"]["clock"] is None and j["roofline"]["sustained"] is None
+    for rank in (0, 1):
+        calls = json.load(open(tmp_path / ("calls_rank%d.json" % rank)))
+        assert "cpx_comm_init_rank" in calls and "cpx_comm_allreduce_f64" in calls and "cpx_comm_destroy" in calls
+        assert "cpx_comm_allgather_u8" not in calls, rank
+
+
+def _bench_single_on_the_host_stand_in(tmp_path, *extra, opt_outs=True):
     """`bench.py --gpus 1` against tests/fake_engine.py (host stand-in for the C-ABI, tests/ only); returns (exit code, JSON line or
-    None, stderr)."""
+    None, stderr).  opt_outs: leave out the path check and what --full would add that the stand-in cannot serve or that takes
+    seconds (cpu_baseline, other_configs, the sustained phase)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "CPX_COMM_NONCE")}
     env["CPX_FAKE_DIR"] = str(tmp_path)
     env["CPX_FAKE_DEVICES"] = "1"
-    argv = [sys.executable, os.path.join(ROOT, "tests", "fake_engine.py"), "--gpus", "1", "--batch", "40", "--no-cpu-baseline",
-            "--no-other-configs", "--no-path-check", "--sustain-seconds", "0"] + list(extra)
+    argv = [sys.executable, os.path.join(ROOT, "tests", "fake_engine.py"), "--gpus", "1", "--batch", "40"]
+    if opt_outs:
+        argv += ["--no-cpu-baseline", "--no-other-configs", "--no-path-check", "--sustain-seconds", "0"]
+    argv += list(extra)
     r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) <= 1, lines
@@ -178,16 +206,17 @@ def _bench_single_on_the_host_stand_in(tmp_path, *extra):
 
 def test_bench_dump_outputs_writes_the_timed_decode_and_is_reproducible(tmp_path):
     """--dump-outputs DIR: after the timed steps, the bits the last timed step decoded land in DIR as float32 / float64 .npy
-    (a fixed, seeded sample of rows plus a checksum of every codeword), identical from run to run with the same arguments;
-    --steps is the number of timed steps and the line carries ms_per_step."""
+    (a fixed, seeded sample of rows plus a checksum of every codeword), identical from run to run with the same arguments and
+    with or without --full; --steps is the number of timed steps and the line carries ms_per_step."""
     import numpy as np
     runs = []
-    for k, steps in enumerate((3, 4)):
+    for k, (steps, full) in enumerate(((3, []), (4, ["--full"]))):
         out_dir = tmp_path / ("dump%d" % k)
         code, j, err = _bench_single_on_the_host_stand_in(tmp_path, "--steps", str(steps), "--warmup", "1",
-                                                          "--dump-outputs", str(out_dir))
+                                                          "--dump-outputs", str(out_dir), *full)
         assert code == 0, err[-2000:]
-        assert j["steps"] == steps and j["ms_per_step"] > 0 and j["oracle_mismatched_bits"] == 0
+        assert j["steps"] == steps and j["ms_per_step"] > 0 and j["full"] is bool(full)
+        assert j["oracle_mismatched_bits"] == (0 if full else None)    # the oracle sample is a check of --full
         assert sorted(j["dump_outputs"]["files"]) == ["decoded_bits.npy", "decoded_bits_rows.npy", "decoded_bits_weighted_sum.npy"]
         arrays = {f: np.load(out_dir / f) for f in j["dump_outputs"]["files"]}
         assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
@@ -198,11 +227,28 @@ def test_bench_dump_outputs_writes_the_timed_decode_and_is_reproducible(tmp_path
     assert set(np.unique(bits)) <= {0.0, 1.0} and bits.sum() > 0
     assert np.array_equal(wsum, bits @ np.arange(1, 1031, dtype=np.float32))
     for f in runs[0]:
-        assert np.array_equal(runs[0][f], runs[1][f]), f             # same inputs, same outputs, whatever the number of steps
+        assert np.array_equal(runs[0][f], runs[1][f]), f             # same inputs, same outputs, whatever the number of steps or --full
     # a larger batch than the sample: a seeded subset of rows, the same every time
     assert np.array_equal(bench.dump_sample_rows(65536), bench.dump_sample_rows(65536))
     assert len(bench.dump_sample_rows(65536)) == bench.DUMP_SAMPLE_CODEWORDS
     assert bench.dump_bytes(65536, 1030) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_bench_plain_run_leaves_out_what_only_full_adds(tmp_path):
+    """Without --full and without any opt-out a one-GPU run sets up, runs the kernel-path check, warms up, times the steps and
+    prints the line: none of the checks after the timed region, the clock probe, the sustained phase, `other_configs` (which
+    the stand-in cannot serve) or `cpu_baseline` runs; their fields are null."""
+    code, j, err = _bench_single_on_the_host_stand_in(tmp_path, "--steps", "2", "--warmup", "1", opt_outs=False)
+    assert code == 0, err[-2000:]
+    assert j["full"] is False and j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1
+    assert j["value"] > 0 and j["ms_per_step"] > 0 and j["dtype"] == "f64" and j["unit"] == "info-bits/s"
+    assert j["metric"] == "decoded info-bits/s at fixed Eb/N0 (Viterbi K=7 r=1/2, 1024b); BER match" and j["higher_is_better"] is True
+    assert j["kernel_path_check"]["codewords"] == 40 and j["kernel_path_check"]["mismatching_bits_between_repeats"] == 0
+    assert j["roofline"]["kernel"].startswith("viterbi_cw_fused_kernel") and j["roofline"]["kernel_ms_avg"] > 0
+    for key in ("ber", "oracle_mismatched_bits", "oracle_sample_codewords", "demod_max_abs_err_vs_oracle", "other_configs", "cpu_baseline"):
+        assert j[key] is None, key
+    assert j["roofline"]["clock"] is None and j["roofline"]["sustained"] is None
+    assert "dump_outputs" not in j
 
 
 def test_bench_refuses_zero_steps(tmp_path):

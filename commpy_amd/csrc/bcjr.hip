@@ -1371,21 +1371,16 @@ int cpx_map_decode_batch(const cpx_trellis *t, const double *sys, const double *
     if (rc) return rc;
     if (B == 0 || N == 0) return CPX_OK;
     const size_t nb = sizeof(double) * (size_t)(B * N);
-    DevBuf ds, dp, dl, dout, dbits;
-    if ((rc = ds.alloc(nb)) || (rc = dp.alloc(nb)) || (rc = dl.alloc(nb)) || (rc = dout.alloc(nb)) ||
-        (rc = dbits.alloc((size_t)(B * N))))
+    HostStage s;
+    const double *ds, *dp, *dl;
+    double *dout;
+    uint8_t *dbits;
+    if ((rc = s.in(sys, nb, &ds)) || (rc = s.in(par, nb, &dp)) || (rc = s.in(L_int, nb, &dl)) || (rc = s.out(nb, &dout)) ||
+        (rc = s.out((size_t)(B * N), &dbits)) ||
+        (rc = cpx_map_decode_batch_dev(t, ds, dp, dl, B, N, noise_variance, want_bits, dout, dbits, s.st)) ||
+        (rc = s.get(L_ext, dout, nb)))
         return rc;
-    hipStream_t st = lib_stream();
-    CPX_HIP(hipMemcpyAsync(ds.p, sys, nb, hipMemcpyHostToDevice, st));
-    CPX_HIP(hipMemcpyAsync(dp.p, par, nb, hipMemcpyHostToDevice, st));
-    CPX_HIP(hipMemcpyAsync(dl.p, L_int, nb, hipMemcpyHostToDevice, st));
-    rc = cpx_map_decode_batch_dev(t, ds.as<double>(), dp.as<double>(), dl.as<double>(), B, N, noise_variance, want_bits,
-                                  dout.as<double>(), dbits.as<uint8_t>(), st);
-    if (rc) return rc;
-    if ((rc = d2h_pageable(L_ext, dout.p, nb, st))) return rc;
-    CPX_HIP(hipMemcpyAsync(bits, dbits.p, (size_t)(B * N), hipMemcpyDeviceToHost, st));
-    CPX_HIP(hipStreamSynchronize(st));
-    return CPX_OK;
+    return s.get(bits, dbits, (size_t)(B * N));
 }
 
 int cpx_turbo_decode_batch(const cpx_trellis *t, const double *sys, const double *p1, const double *p2,
@@ -1399,24 +1394,16 @@ int cpx_turbo_decode_batch(const cpx_trellis *t, const double *sys, const double
     for (int64_t i = 0; i < N; i++)
         CPX_REQUIRE(perm[i] >= 0 && perm[i] < N, CPX_EINVAL, "turbo_decode: interleaver index out of range");
     const size_t nb = sizeof(double) * (size_t)(B * N);
-    DevBuf ds, d1, d2, dl, dperm, dbits;
-    if ((rc = ds.alloc(nb)) || (rc = d1.alloc(nb)) || (rc = d2.alloc(nb)) || (rc = dperm.alloc(sizeof(int32_t) * N)) ||
-        (rc = dbits.alloc((size_t)(B * N))))
+    HostStage s;
+    const double *ds, *d1, *d2, *dl = nullptr;
+    const int32_t *dperm;
+    uint8_t *dbits;
+    if ((rc = s.in(sys, nb, &ds)) || (rc = s.in(p1, nb, &d1)) || (rc = s.in(p2, nb, &d2)) ||
+        (rc = s.in(perm, sizeof(int32_t) * N, &dperm)) || (L_int_or_null && (rc = s.in(L_int_or_null, nb, &dl))) ||
+        (rc = s.out((size_t)(B * N), &dbits)) ||
+        (rc = cpx_turbo_decode_batch_dev(t, ds, d1, d2, dl, dperm, B, N, noise_variance, n_iter, dbits, s.st)))
         return rc;
-    if (L_int_or_null && (rc = dl.alloc(nb))) return rc;
-    hipStream_t st = lib_stream();
-    CPX_HIP(hipMemcpyAsync(ds.p, sys, nb, hipMemcpyHostToDevice, st));
-    CPX_HIP(hipMemcpyAsync(d1.p, p1, nb, hipMemcpyHostToDevice, st));
-    CPX_HIP(hipMemcpyAsync(d2.p, p2, nb, hipMemcpyHostToDevice, st));
-    CPX_HIP(hipMemcpyAsync(dperm.p, perm, sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-    if (L_int_or_null) CPX_HIP(hipMemcpyAsync(dl.p, L_int_or_null, nb, hipMemcpyHostToDevice, st));
-    rc = cpx_turbo_decode_batch_dev(t, ds.as<double>(), d1.as<double>(), d2.as<double>(),
-                                    L_int_or_null ? dl.as<double>() : nullptr, dperm.as<int32_t>(), B, N, noise_variance,
-                                    n_iter, dbits.as<uint8_t>(), st);
-    if (rc) return rc;
-    CPX_HIP(hipMemcpyAsync(bits, dbits.p, (size_t)(B * N), hipMemcpyDeviceToHost, st));
-    CPX_HIP(hipStreamSynchronize(st));
-    return CPX_OK;
+    return s.get(bits, dbits, (size_t)(B * N));
 }
 
 }  // extern "C"

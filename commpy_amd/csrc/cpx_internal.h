@@ -144,17 +144,59 @@ int viterbi_generic(const ::cpx_trellis *t, const double *d_coded, int64_t B, in
 
 inline hipStream_t pick_stream(void *s) { return s ? reinterpret_cast<hipStream_t>(s) : lib_stream(); }
 
-// RAII device buffer for the host-buffer entry points.
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        if (bytes == 0) bytes = 8;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); p = nullptr; return CPX_ENOMEM; }
+// a handle's device table: hipMalloc + hipMemcpy of `bytes` into *d ("<what>: ..." set, CPX_ENOMEM / CPX_EHIP, on failure; *d stays
+// null if the allocation failed, so the handle's own destroy releases what was built)
+int upload(void **d, const void *h, size_t bytes, const char *what);
+
+// a HIP event (no timing) for the lifetime of the object; e is null if it could not be created
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() { if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) e = nullptr; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+};
+
+// Device staging of the host-buffer entry points, on the library stream: `in` allocates and queues the upload of `host`, `out`
+// allocates, `get` downloads (blocking, through d2h_pageable; nothing for zero bytes); the destructor frees every buffer.  Allocations
+// are fresh per call (a zero-byte request still gets 8 bytes); copies run inside CPX_TRACE ranges, and with tracing on an upload is
+// waited for so that the ranges do not overlap.
+class HostStage {
+public:
+    const hipStream_t st = lib_stream();
+    HostStage() = default;
+    HostStage(const HostStage &) = delete;
+    HostStage &operator=(const HostStage &) = delete;
+    ~HostStage() { for (void *p : bufs_) (void)hipFree(p); }
+    template <class T> int out(size_t bytes, T **d) {
+        void *p;
+        int rc = alloc(bytes, &p);
+        *d = static_cast<T *>(p);
+        return rc;
+    }
+    template <class T> int in(const void *host, size_t bytes, T **d) {
+        CPX_TRACE("H2D");
+        void *p;
+        if (int rc = alloc(bytes, &p)) return rc;
+        *d = static_cast<T *>(p);
+        CPX_HIP(hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, st));
+        if (trace_enabled()) CPX_HIP(hipStreamSynchronize(st));
         return CPX_OK;
     }
-    template <class T> T *as() { return reinterpret_cast<T *>(p); }
+    int get(void *host, const void *d, size_t bytes) {
+        if (bytes == 0) return CPX_OK;
+        CPX_TRACE("D2H");
+        return d2h_pageable(host, d, bytes, st);
+    }
+private:
+    int alloc(size_t bytes, void **d) {
+        if (bytes == 0) bytes = 8;
+        hipError_t e = hipMalloc(d, bytes);
+        if (e != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); *d = nullptr; return CPX_ENOMEM; }
+        bufs_.push_back(*d);
+        return CPX_OK;
+    }
+    std::vector<void *> bufs_;
 };
 
 // a block of the scratch arena (not owned: released by cpx_release_workspace)

@@ -882,8 +882,10 @@ int cpx_modem_create(const double *constellation_re_im, int M, cpx_modem **out) 
     m->nbits = 0;
     while ((1 << m->nbits) < M) m->nbits++;
     (void)hipGetDevice(&m->device);
-    CPX_HIP(hipMalloc((void **)&m->d_const, sizeof(double) * 2 * M));
-    CPX_HIP(hipMemcpy(m->d_const, constellation_re_im, sizeof(double) * 2 * M, hipMemcpyHostToDevice));
+    if ((rc = upload((void **)&m->d_const, constellation_re_im, sizeof(double) * 2 * M, "cpx_modem_create"))) {
+        cpx_modem_destroy(m);
+        return rc;
+    }
     // axis-separable?  label = (a << nh) | b, real part a function of a only, imaginary part of b only (exactly)
     if (m->nbits % 2 == 0 && m->nbits >= 2 && m->nbits <= 8) {
         const int nh = m->nbits / 2, R = 1 << nh;
@@ -898,8 +900,10 @@ int cpx_modem_create(const double *constellation_re_im, int M, cpx_modem **out) 
             for (int b = a + 1; b < R; b++)
                 if (axes[a] == axes[b] || axes[R + a] == axes[R + b]) sep = false;
         if (sep) {
-            CPX_HIP(hipMalloc((void **)&m->d_axes, sizeof(double) * 2 * R));
-            CPX_HIP(hipMemcpy(m->d_axes, axes.data(), sizeof(double) * 2 * R, hipMemcpyHostToDevice));
+            if ((rc = upload((void **)&m->d_axes, axes.data(), sizeof(double) * 2 * R, "cpx_modem_create"))) {
+                cpx_modem_destroy(m);
+                return rc;
+            }
             m->separable = true;
             // equally spaced levels in reflected Gray order (what QAMModem builds)?  level j = p0 + j d has label j ^ (j >> 1)
             bool gp = R >= 2;
@@ -927,7 +931,7 @@ int cpx_demod_set_path(const char *mode) { return set_mode(Switch::demod, mode);
 int cpx_modem_destroy(cpx_modem *m) {
     if (!m) return CPX_OK;
     (void)hipFree(m->d_const);
-    if (m->d_axes) (void)hipFree(m->d_axes);
+    (void)hipFree(m->d_axes);
     delete m;
     return CPX_OK;
 }
@@ -1070,16 +1074,14 @@ int cpx_demod_soft(const cpx_modem *m, const double *y_re_im, int64_t Ns, double
     int rc = ensure_device();
     if (rc) return rc;
     if (Ns == 0) return CPX_OK;
-    DevBuf din, dout;
     const size_t out_bytes = sizeof(double) * (size_t)Ns * m->nbits;
-    if ((rc = din.alloc(sizeof(double) * 2 * (size_t)Ns))) return rc;
-    if ((rc = dout.alloc(out_bytes))) return rc;
-    hipStream_t st = lib_stream();
-    CPX_HIP(hipMemcpyAsync(din.p, y_re_im, sizeof(double) * 2 * (size_t)Ns, hipMemcpyHostToDevice, st));
-    if ((rc = cpx_demod_soft_dev(m, din.as<double>(), Ns, noise_var, dout.as<double>(), st))) return rc;
-    if ((rc = d2h_pageable(llr, dout.p, out_bytes, st))) return rc;
-    CPX_HIP(hipStreamSynchronize(st));
-    return CPX_OK;
+    HostStage s;
+    const double *din;
+    double *dout;
+    if ((rc = s.in(y_re_im, sizeof(double) * 2 * (size_t)Ns, &din)) || (rc = s.out(out_bytes, &dout)) ||
+        (rc = cpx_demod_soft_dev(m, din, Ns, noise_var, dout, s.st)))
+        return rc;
+    return s.get(llr, dout, out_bytes);
 }
 
 int cpx_demod_hard(const cpx_modem *m, const double *y_re_im, int64_t Ns, int8_t *bits) {
@@ -1088,16 +1090,14 @@ int cpx_demod_hard(const cpx_modem *m, const double *y_re_im, int64_t Ns, int8_t
     int rc = ensure_device();
     if (rc) return rc;
     if (Ns == 0) return CPX_OK;
-    DevBuf din, dout;
     const size_t out_bytes = (size_t)Ns * m->nbits;
-    if ((rc = din.alloc(sizeof(double) * 2 * (size_t)Ns))) return rc;
-    if ((rc = dout.alloc(out_bytes))) return rc;
-    hipStream_t st = lib_stream();
-    CPX_HIP(hipMemcpyAsync(din.p, y_re_im, sizeof(double) * 2 * (size_t)Ns, hipMemcpyHostToDevice, st));
-    if ((rc = cpx_demod_hard_dev(m, din.as<double>(), Ns, dout.as<int8_t>(), st))) return rc;
-    CPX_HIP(hipMemcpyAsync(bits, dout.p, out_bytes, hipMemcpyDeviceToHost, st));
-    CPX_HIP(hipStreamSynchronize(st));
-    return CPX_OK;
+    HostStage s;
+    const double *din;
+    int8_t *dout;
+    if ((rc = s.in(y_re_im, sizeof(double) * 2 * (size_t)Ns, &din)) || (rc = s.out(out_bytes, &dout)) ||
+        (rc = cpx_demod_hard_dev(m, din, Ns, dout, s.st)))
+        return rc;
+    return s.get(bits, dout, out_bytes);
 }
 
 // ---- fused link front end (link_front_kernel) ----------------------------------------------------------------------------------
@@ -1155,21 +1155,17 @@ int cpx_link_front_create(const cpx_trellis *t, const cpx_modem *m, int64_t nbit
     CPX_REQUIRE(lf, CPX_ENOMEM, "link_front: out of memory");
     lf->t = t; lf->m = m; lf->device = t->device; lf->nbits = (int)nbits; lf->mem = mem; lf->ntx = (int)ntx; lf->nsym = (int)nsym; lf->nde = (int)nde;
     lf->lead = (int)lead;
-    auto up = [&](const std::vector<int32_t> &h, int32_t **d) -> int {
-        if (hipMalloc((void **)d, sizeof(int32_t) * h.size()) != hipSuccess) return CPX_ENOMEM;
-        return hipMemcpy(*d, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice) == hipSuccess ? CPX_OK : CPX_EHIP;
-    };
-    int rc = up(jo, &lf->d_jo);
-    if (!rc) rc = up(pg, &lf->d_pg);
-    if (rc) { cpx_link_front_destroy(lf); set_error("link_front: table upload failed"); return rc; }
+    int rc = upload((void **)&lf->d_jo, jo.data(), sizeof(int32_t) * jo.size(), "link_front");
+    if (!rc) rc = upload((void **)&lf->d_pg, pg.data(), sizeof(int32_t) * pg.size(), "link_front");
+    if (rc) { cpx_link_front_destroy(lf); return rc; }
     *out = lf;
     return CPX_OK;
 }
 
 int cpx_link_front_destroy(cpx_link_front *lf) {
     if (!lf) return CPX_OK;
-    if (lf->d_jo) (void)hipFree(lf->d_jo);
-    if (lf->d_pg) (void)hipFree(lf->d_pg);
+    (void)hipFree(lf->d_jo);
+    (void)hipFree(lf->d_pg);
     delete lf;
     return CPX_OK;
 }

@@ -355,17 +355,17 @@ int cpx_ldpc_encoder_create(const uint8_t *gen_bits, int64_t m, int64_t k, cpx_l
         for (int64_t j = 0; j < k; j++)
             if (src[j] & 1) dst[(j >> 5) * 64] |= 1u << (j & 31);
     }
-    hipError_t er = hipMalloc((void **)&e->d_gen, h.size() * sizeof(uint32_t));
-    if (er != hipSuccess) { delete e; set_error("ldpc_encoder_create: hipMalloc failed: %s", hipGetErrorString(er)); return CPX_ENOMEM; }
-    er = hipMemcpy(e->d_gen, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (er != hipSuccess) { (void)hipFree(e->d_gen); delete e; set_error("ldpc_encoder_create: upload failed: %s", hipGetErrorString(er)); return CPX_EHIP; }
+    if ((rc = upload((void **)&e->d_gen, h.data(), h.size() * sizeof(uint32_t), "ldpc_encoder_create"))) {
+        cpx_ldpc_encoder_destroy(e);
+        return rc;
+    }
     *out = e;
     return CPX_OK;
 }
 
 int cpx_ldpc_encoder_destroy(cpx_ldpc_encoder *e) {
     if (!e) return CPX_OK;
-    if (e->d_gen) (void)hipFree(e->d_gen);
+    (void)hipFree(e->d_gen);
     delete e;
     return CPX_OK;
 }

@@ -970,16 +970,9 @@ int cpx_ldpc_create_from_blob(const void *blob, size_t nbytes, cpx_ldpc **out) {
         {&c->d_col_ptr, v.col_ptr, (size_t)h->n_v + 1}, {&c->d_col_edge, v.col_edge, (size_t)E},
         {&c->d_col_cj, v.col_cj, (size_t)E}, {&c->d_row_pad, v.row_pad, v.n_row_pad},
         {&c->d_col_pad_edge, v.col_pad_edge, v.n_col_pad}, {&c->d_col_pad_cj, v.col_pad_cj, v.n_col_pad}};
-    for (auto &u : ups) {
-        hipError_t e1 = hipMalloc((void **)u.dst, sizeof(int32_t) * u.n);
-        hipError_t e2 = e1 == hipSuccess ? hipMemcpy(*u.dst, u.src, sizeof(int32_t) * u.n, hipMemcpyHostToDevice) : e1;
-        if (e2 != hipSuccess) {
-            set_error("cpx_ldpc_create: device upload failed: %s", hipGetErrorString(e2));
-            cpx_ldpc_destroy(c);
-            return CPX_EHIP;
-        }
-    }
-    if ((rc = ldpc_resident_tables(c, v.row_ptr, v.row_pad, v.col_ptr, v.col_pad_cj))) {
+    for (auto &u : ups)
+        if ((rc = upload((void **)u.dst, u.src, sizeof(int32_t) * u.n, "cpx_ldpc_create"))) break;
+    if (rc || (rc = ldpc_resident_tables(c, v.row_ptr, v.row_pad, v.col_ptr, v.col_pad_cj))) {
         cpx_ldpc_destroy(c);
         return rc;
     }
@@ -1161,37 +1154,28 @@ static int ldpc_decode_host(const cpx_ldpc *c, double *llr, int64_t B, int alg, 
     if (rc) return rc;
     if (B == 0) return CPX_OK;
     const size_t nvb = (size_t)((int64_t)c->n_v * B);
-    DevBuf d_llr, d_dec, d_out, d_it, d_flag;
-    if ((rc = d_llr.alloc(sizeof(double) * nvb))) return rc;
-    if ((rc = d_dec.alloc(nvb))) return rc;
-    if ((rc = d_out.alloc(sizeof(double) * nvb))) return rc;
-    if ((rc = d_it.alloc(sizeof(int32_t) * (size_t)B))) return rc;
-    if ((rc = d_flag.alloc(sizeof(int)))) return rc;
-    hipStream_t st = lib_stream();
-    CPX_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(int), st));
-    {
-        CPX_TRACE("H2D llr");
-        CPX_HIP(hipMemcpyAsync(d_llr.p, llr, sizeof(double) * nvb, hipMemcpyHostToDevice, st));
-        if (trace_enabled()) CPX_HIP(hipStreamSynchronize(st));
-    }
-    rc = ldpc_decode_impl(c, d_llr.as<double>(), B, alg, n_iters, d_dec.as<int8_t>(), d_out.as<double>(), block_major,
-                          d_it.as<int32_t>(), d_flag.as<int>(), st);
-    if (rc) return rc;
+    HostStage s;
+    double *d_llr, *d_out;
+    int8_t *d_dec;
+    int32_t *d_it;
+    int *d_flag;
+    if ((rc = s.out(sizeof(int), &d_flag))) return rc;
+    CPX_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), s.st));
+    if ((rc = s.in(llr, sizeof(double) * nvb, &d_llr)) || (rc = s.out(nvb, &d_dec)) || (rc = s.out(sizeof(double) * nvb, &d_out)) ||
+        (rc = s.out(sizeof(int32_t) * (size_t)B, &d_it)) ||
+        (rc = ldpc_decode_impl(c, d_llr, B, alg, n_iters, d_dec, d_out, block_major, d_it, d_flag, s.st)))
+        return rc;
     // in-place clip (:186): the caller's array only changes if a value lay outside +-500 (or is NaN) -- the kernels say so,
     // and the 8-byte-per-LLR copy back (a third of this call's PCIe traffic) is skipped otherwise
     int clipped = 0;
     {
         CPX_TRACE("decode (wait) + clip flag");
-        CPX_HIP(hipMemcpyAsync(&clipped, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        CPX_HIP(hipStreamSynchronize(st));
+        if ((rc = s.get(&clipped, d_flag, sizeof(int)))) return rc;
     }
-    CPX_TRACE("D2H results");
-    if (clipped && (rc = d2h_pageable(llr, d_llr.p, sizeof(double) * nvb, st))) return rc;
-    if (dec_word && (rc = d2h_pageable(dec_word, d_dec.p, nvb, st))) return rc;
-    if (out_llrs && (rc = d2h_pageable(out_llrs, d_out.p, sizeof(double) * nvb, st))) return rc;
-    if (iters_done) CPX_HIP(hipMemcpyAsync(iters_done, d_it.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
-    CPX_HIP(hipStreamSynchronize(st));
-    return CPX_OK;
+    if (clipped && (rc = s.get(llr, d_llr, sizeof(double) * nvb))) return rc;
+    if (dec_word && (rc = s.get(dec_word, d_dec, nvb))) return rc;
+    if (out_llrs && (rc = s.get(out_llrs, d_out, sizeof(double) * nvb))) return rc;
+    return iters_done ? s.get(iters_done, d_it, sizeof(int32_t) * (size_t)B) : CPX_OK;
 }
 
 int cpx_ldpc_bp_decode_batch(const cpx_ldpc *c, double *llr, int64_t B, int alg, int n_iters, int8_t *dec_word,

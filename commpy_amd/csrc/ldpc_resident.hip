@@ -837,11 +837,8 @@ int ldpc_resident_tables(cpx_ldpc *c, const int32_t *row_ptr, const int32_t *row
     for (size_t i = 0; i < cr.size(); i++) cr32[i] = roff / 2 + (cr[i] - roff) / 2;
     struct Up { int32_t **dst; std::vector<int32_t> *src; } ups[] = {{&c->d_res_row_q32, &rq32}, {&c->d_res_col_r32, &cr32}, {&c->d_res_row_deg, &dg}, {&c->d_res_row_q, &rq},
                                                                      {&c->d_res_col_r, &cr}, {&c->d_res_vgrp, &vg}};
-    for (auto &u : ups) {
-        hipError_t e1 = hipMalloc((void **)u.dst, sizeof(int32_t) * u.src->size());
-        hipError_t e2 = e1 == hipSuccess ? hipMemcpy(*u.dst, u.src->data(), sizeof(int32_t) * u.src->size(), hipMemcpyHostToDevice) : e1;
-        if (e2 != hipSuccess) { set_error("cpx_ldpc_create: device upload failed: %s", hipGetErrorString(e2)); return CPX_EHIP; }
-    }
+    for (auto &u : ups)
+        if (int rc = upload((void **)u.dst, u.src->data(), sizeof(int32_t) * u.src->size(), "cpx_ldpc_create")) return rc;
     return CPX_OK;
 }
 

@@ -642,26 +642,21 @@ int bf_run(const cpx_modem *md, const double *d_y, const double *d_h, int h_batc
     return CPX_OK;
 }
 
-// host-buffer wrapper: upload y and H, run `dev`, download `out_bytes` (and `out2_bytes`)
-template <class F>
-int mimo_host(const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, void *out, size_t out_bytes, void *out2,
-              size_t out2_bytes, F dev) {
-    int rc = ensure_device();
-    if (rc) return rc;
+// the host-buffer wrappers' checks, ensure_device() first
+int mimo_host_check(const double *y, const double *h, int64_t B, int nr, int nt, const void *out) {
+    if (int rc = ensure_device()) return rc;
     CPX_REQUIRE(B >= 0 && nr >= 1 && nt >= 1, CPX_EINVAL, "mimo: need B >= 0, nr >= 1, nt >= 1");
     CPX_REQUIRE((y && h && out) || B == 0, CPX_EINVAL, "mimo: null pointer");
-    if (B == 0) return dev(nullptr, nullptr, nullptr, nullptr, lib_stream());
-    const size_t ybytes = 16 * size_t(B) * nr, hbytes = 16 * size_t(nr) * nt * (h_batched ? size_t(B) : 1);
-    DevBuf dy, dh, dout, dout2;
-    if ((rc = dy.alloc(ybytes)) || (rc = dh.alloc(hbytes)) || (rc = dout.alloc(out_bytes)) || (rc = dout2.alloc(out2_bytes))) return rc;
-    hipStream_t st = lib_stream();
-    CPX_HIP(hipMemcpyAsync(dy.p, y, ybytes, hipMemcpyHostToDevice, st));
-    CPX_HIP(hipMemcpyAsync(dh.p, h, hbytes, hipMemcpyHostToDevice, st));
-    if ((rc = dev(dy.as<double>(), dh.as<double>(), dout.p, dout2.p, st))) return rc;
-    if ((rc = d2h_pageable(out, dout.p, out_bytes, st))) return rc;
-    if (out2 && out2_bytes) CPX_HIP(hipMemcpyAsync(out2, dout2.p, out2_bytes, hipMemcpyDeviceToHost, st));
-    CPX_HIP(hipStreamSynchronize(st));
     return CPX_OK;
+}
+
+// y and H staged; an empty batch stages neither (its device entry point gets null y and H, and its outputs are empty downloads)
+int mimo_in(HostStage &s, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, const double **dy,
+            const double **dh) {
+    *dy = *dh = nullptr;
+    if (B == 0) return CPX_OK;
+    if (int rc = s.in(y, 16 * size_t(B) * nr, dy)) return rc;
+    return s.in(h, 16 * size_t(nr) * nt * (h_batched ? size_t(B) : 1), dh);
 }
 
 }  // namespace
@@ -695,10 +690,16 @@ int cpx_mimo_ml_dev(const cpx_modem *md, const double *d_y, const double *d_h, i
 
 int cpx_mimo_ml(const cpx_modem *md, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, int32_t *idx) {
     CPX_TRACE("cpx_mimo_ml");
-    return mimo_host(y, h, h_batched, B, nr, nt, idx, 4 * size_t(B) * nt, nullptr, 0,
-                     [&](const double *dy, const double *dh, void *o, void *, hipStream_t st) {
-                         return cpx_mimo_ml_dev(md, dy, dh, h_batched, B, nr, nt, static_cast<int32_t *>(o), st);
-                     });
+    if (int rc = mimo_host_check(y, h, B, nr, nt, idx)) return rc;
+    HostStage s;
+    const double *dy, *dh;
+    int32_t *d_idx;
+    const size_t n = 4 * size_t(B) * nt;
+    int rc;
+    if ((rc = mimo_in(s, y, h, h_batched, B, nr, nt, &dy, &dh)) || (rc = s.out(n, &d_idx)) ||
+        (rc = cpx_mimo_ml_dev(md, dy, dh, h_batched, B, nr, nt, d_idx, s.st)))
+        return rc;
+    return s.get(idx, d_idx, n);
 }
 
 int cpx_kbest_hard_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt, int K,
@@ -709,10 +710,16 @@ int cpx_kbest_hard_dev(const cpx_modem *md, const double *d_y, const double *d_h
 
 int cpx_kbest_hard(const cpx_modem *md, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, int K, int32_t *idx) {
     CPX_TRACE("cpx_kbest_hard");
-    return mimo_host(y, h, h_batched, B, nr, nt, idx, 4 * size_t(B) * nt, nullptr, 0,
-                     [&](const double *dy, const double *dh, void *o, void *, hipStream_t st) {
-                         return cpx_kbest_hard_dev(md, dy, dh, h_batched, B, nr, nt, K, static_cast<int32_t *>(o), st);
-                     });
+    if (int rc = mimo_host_check(y, h, B, nr, nt, idx)) return rc;
+    HostStage s;
+    const double *dy, *dh;
+    int32_t *d_idx;
+    const size_t n = 4 * size_t(B) * nt;
+    int rc;
+    if ((rc = mimo_in(s, y, h, h_batched, B, nr, nt, &dy, &dh)) || (rc = s.out(n, &d_idx)) ||
+        (rc = cpx_kbest_hard_dev(md, dy, dh, h_batched, B, nr, nt, K, d_idx, s.st)))
+        return rc;
+    return s.get(idx, d_idx, n);
 }
 
 int cpx_kbest_soft_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt, int K,
@@ -724,11 +731,16 @@ int cpx_kbest_soft_dev(const cpx_modem *md, const double *d_y, const double *d_h
 int cpx_kbest_soft(const cpx_modem *md, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, int K,
                    double noise_var, double *llr) {
     CPX_TRACE("cpx_kbest_soft");
-    const size_t nbits = md ? size_t(md->nbits) : 0;
-    return mimo_host(y, h, h_batched, B, nr, nt, llr, 8 * size_t(B) * nt * nbits, nullptr, 0,
-                     [&](const double *dy, const double *dh, void *o, void *, hipStream_t st) {
-                         return cpx_kbest_soft_dev(md, dy, dh, h_batched, B, nr, nt, K, noise_var, static_cast<double *>(o), st);
-                     });
+    if (int rc = mimo_host_check(y, h, B, nr, nt, llr)) return rc;
+    HostStage s;
+    const double *dy, *dh;
+    double *d_llr;
+    const size_t n = 8 * size_t(B) * nt * (md ? size_t(md->nbits) : 0);
+    int rc;
+    if ((rc = mimo_in(s, y, h, h_batched, B, nr, nt, &dy, &dh)) || (rc = s.out(n, &d_llr)) ||
+        (rc = cpx_kbest_soft_dev(md, dy, dh, h_batched, B, nr, nt, K, noise_var, d_llr, s.st)))
+        return rc;
+    return s.get(llr, d_llr, n);
 }
 
 int cpx_kbest_list_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int nr, int nt, int K,
@@ -741,12 +753,17 @@ int cpx_kbest_list(const cpx_modem *md, const double *y, const double *h, int h_
                    int32_t *cand, int32_t *count) {
     CPX_TRACE("cpx_kbest_list");
     CPX_REQUIRE(md && K >= 1 && nt >= 1, CPX_EINVAL, "kbest: null modem, K < 1 or nt < 1");
-    const size_t ke = size_t(kbest_effective_K(K, md->M, nt));
-    return mimo_host(y, h, h_batched, B, nr, nt, cand, 4 * size_t(B) * ke * nt, count, 4 * size_t(B),
-                     [&](const double *dy, const double *dh, void *o, void *o2, hipStream_t st) {
-                         return cpx_kbest_list_dev(md, dy, dh, h_batched, B, nr, nt, K, static_cast<int32_t *>(o),
-                                                   static_cast<int32_t *>(o2), st);
-                     });
+    const size_t n = 4 * size_t(B) * size_t(kbest_effective_K(K, md->M, nt)) * nt;
+    if (int rc = mimo_host_check(y, h, B, nr, nt, cand)) return rc;
+    HostStage s;
+    const double *dy, *dh;
+    int32_t *d_cand, *d_count;
+    int rc;
+    if ((rc = mimo_in(s, y, h, h_batched, B, nr, nt, &dy, &dh)) || (rc = s.out(n, &d_cand)) ||
+        (rc = s.out(4 * size_t(B), &d_count)) ||
+        (rc = cpx_kbest_list_dev(md, dy, dh, h_batched, B, nr, nt, K, d_cand, d_count, s.st)) || (rc = s.get(cand, d_cand, n)))
+        return rc;
+    return count ? s.get(count, d_count, 4 * size_t(B)) : CPX_OK;
 }
 
 }  // extern "C"
@@ -770,20 +787,21 @@ int cpx_best_first(const cpx_modem *md, const double *y, const double *h, int h_
     if (labels)
         for (int i = 0; i < md->M * nbits; i++)
             CPX_REQUIRE(labels[i] <= 1, CPX_EINVAL, "best_first: label table entry %d is %d, not 0 or 1", i, int(labels[i]));
-    int rc = ensure_device();
-    if (rc) return rc;
-    DevBuf dl;
-    if (labels && B > 0) {
-        if ((rc = dl.alloc(size_t(md->M) * nbits))) return rc;
-        CPX_HIP(hipMemcpy(dl.p, labels, size_t(md->M) * nbits, hipMemcpyHostToDevice));
-    }
+    if (int rc = mimo_host_check(y, h, B, nr, nt, llr)) return rc;
+    HostStage s;
+    const double *dy, *dh;
+    uint8_t *d_labels = nullptr;
+    double *d_llr;
+    int32_t *d_iters;
     std::vector<int32_t> iters(size_t(B > 0 ? B : 0));
-    rc = mimo_host(y, h, h_batched, B, nr, nt, llr, 8 * size_t(B) * nr * nbits, iters.data(), 4 * iters.size(),
-                   [&](const double *dy, const double *dh, void *o, void *o2, hipStream_t st) {
-                       return cpx_best_first_dev(md, dy, dh, h_batched, B, nr, nt, stack_size, llr_max, dl.as<uint8_t>(),
-                                                 static_cast<double *>(o), static_cast<int32_t *>(o2), st);
-                   });
-    if (rc) return rc;
+    const size_t n = 8 * size_t(B) * nr * nbits;
+    int rc;
+    if ((rc = mimo_in(s, y, h, h_batched, B, nr, nt, &dy, &dh)) ||
+        (labels && B > 0 && (rc = s.in(labels, size_t(md->M) * nbits, &d_labels))) || (rc = s.out(n, &d_llr)) ||
+        (rc = s.out(4 * iters.size(), &d_iters)) ||
+        (rc = cpx_best_first_dev(md, dy, dh, h_batched, B, nr, nt, stack_size, llr_max, d_labels, d_llr, d_iters, s.st)) ||
+        (rc = s.get(llr, d_llr, n)) || (rc = s.get(iters.data(), d_iters, 4 * iters.size())))
+        return rc;
     for (int64_t b = 0; b < B; b++)
         CPX_REQUIRE(iters[b] >= 0, CPX_EHIP, "best_first: vector %lld hit the search's iteration cap (an engine fault)", (long long)b);
     return CPX_OK;

@@ -152,16 +152,9 @@ int cpx_mimo_channel_create(int nr, int nt, const double *sqrt_rr, const double 
     (void)hipGetDevice(&ch->device);
     ch->a_identity = is_identity(sqrt_rr, nr);
     ch->b_identity = is_identity(sqrt_rt_T, nt);
-    if (hipMalloc((void **)&ch->d_mats, 8 * host.size()) != hipSuccess) {
-        delete ch;
-        set_error("mimo_channel: hipMalloc of %zu bytes failed", 8 * host.size());
-        return CPX_ENOMEM;
-    }
-    if (hipMemcpy(ch->d_mats, host.data(), 8 * host.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(ch->d_mats);
-        delete ch;
-        set_error("mimo_channel: upload of the fading matrices failed");
-        return CPX_EHIP;
+    if ((rc = upload((void **)&ch->d_mats, host.data(), 8 * host.size(), "mimo_channel"))) {
+        cpx_mimo_channel_destroy(ch);
+        return rc;
     }
     *out = ch;
     return CPX_OK;
@@ -169,7 +162,7 @@ int cpx_mimo_channel_create(int nr, int nt, const double *sqrt_rr, const double 
 
 int cpx_mimo_channel_destroy(cpx_mimo_channel *ch) {
     if (!ch) return CPX_OK;
-    if (ch->d_mats) (void)hipFree(ch->d_mats);
+    (void)hipFree(ch->d_mats);
     delete ch;
     return CPX_OK;
 }

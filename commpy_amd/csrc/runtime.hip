@@ -245,21 +245,20 @@ int d2h_pageable(void *dst, const void *d_src, size_t bytes, hipStream_t st) {
     std::lock_guard<std::mutex> lk(mu);
     for (int i = 0; i < 2; i++)
         if (!pin[i]) CPX_HIP(hipHostMalloc((void **)&pin[i], CH, hipHostMallocDefault));
-    hipEvent_t ev[2];
-    CPX_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
-    CPX_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
+    Event ev[2];
+    CPX_REQUIRE(ev[0].e && ev[1].e, CPX_EHIP, "download: hipEventCreate failed");
     const size_t n = (bytes + CH - 1) / CH;
     auto issue = [&](size_t c) -> hipError_t {
         const size_t len = std::min(CH, bytes - c * CH);
         hipError_t e = hipMemcpyAsync(pin[c & 1], static_cast<const unsigned char *>(d_src) + c * CH, len, hipMemcpyDeviceToHost, st);
-        return e != hipSuccess ? e : hipEventRecord(ev[c & 1], st);
+        return e != hipSuccess ? e : hipEventRecord(ev[c & 1].e, st);
     };
     unsigned nt = std::thread::hardware_concurrency();
     nt = nt > 8 ? 8 : (nt < 1 ? 1 : nt);
     hipError_t err = issue(0);
     for (size_t c = 0; c < n && err == hipSuccess; c++) {
         if (c + 1 < n) err = issue(c + 1);                        // its pinned block was emptied in the previous round
-        if (err == hipSuccess) err = hipEventSynchronize(ev[c & 1]);
+        if (err == hipSuccess) err = hipEventSynchronize(ev[c & 1].e);
         if (err != hipSuccess) break;
         const size_t len = std::min(CH, bytes - c * CH);
         unsigned char *to = static_cast<unsigned char *>(dst) + c * CH;
@@ -270,9 +269,15 @@ int d2h_pageable(void *dst, const void *d_src, size_t bytes, hipStream_t st) {
         work(0);
         for (auto &x : th) x.join();
     }
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
     if (err != hipSuccess) { set_error("download failed: %s", hipGetErrorString(err)); (void)hipStreamSynchronize(st); return CPX_EHIP; }
+    return CPX_OK;
+}
+
+int upload(void **d, const void *h, size_t bytes, const char *what) {
+    hipError_t e = hipMalloc(d, bytes);
+    if (e != hipSuccess) { *d = nullptr; set_error("%s: hipMalloc(%zu) failed: %s", what, bytes, hipGetErrorString(e)); return CPX_ENOMEM; }
+    e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_error("%s: upload of %zu bytes failed: %s", what, bytes, hipGetErrorString(e)); return CPX_EHIP; }
     return CPX_OK;
 }
 

@@ -680,17 +680,21 @@ int cpx_trellis_create(int k, int n, int n_states, int n_inputs, const int32_t *
     int32_t **dst[5] = {&t->d_next, &t->d_out, &t->d_pred_state, &t->d_pred_input, &t->d_pred_code};
     const int32_t *src[5] = {t->next_state.data(), t->output.data(), t->pred_state.data(), t->pred_input.data(),
                              t->pred_code.data()};
-    for (int i = 0; i < 5; i++) {
-        CPX_HIP(hipMalloc((void **)dst[i], bytes));
-        CPX_HIP(hipMemcpy(*dst[i], src[i], bytes, hipMemcpyHostToDevice));
-    }
+    for (int i = 0; i < 5; i++)
+        if ((rc = upload((void **)dst[i], src[i], bytes, "cpx_trellis_create"))) {
+            cpx_trellis_destroy(t);
+            return rc;
+        }
     *out = t;
     return CPX_OK;
 }
 
 int cpx_trellis_destroy(cpx_trellis *t) {
     if (!t) return CPX_OK;
-    if (t->spec_mod) (void)hipModuleUnload(t->spec_mod);
+    if (t->spec_mod) {
+        (void)hipDeviceSynchronize();                             // nothing may still run from the module
+        (void)hipModuleUnload(t->spec_mod);
+    }
     (void)hipFree(t->d_next); (void)hipFree(t->d_out);
     (void)hipFree(t->d_pred_state); (void)hipFree(t->d_pred_input); (void)hipFree(t->d_pred_code);
     delete t;
@@ -858,6 +862,11 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
         }
         return rc;
     };
+    auto launch_error = [] {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) set_error("viterbi: kernel launch failed: %s", hipGetErrorString(e));
+        return e != hipSuccess ? CPX_EHIP : CPX_OK;
+    };
     if (!dm) {   // large batches of the standard rate-1/2 codes: one codeword per lane (viterbi_cw.hip).  That path runs in rounds
         // of one wavefront of 64 codewords per SIMD, each as long as a full one; a last round that would fill less than 45 % of
         // the chip is cheaper on the wave kernels below, whose time is proportional to the batch (config 2: 54 us per 1000
@@ -920,7 +929,7 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
         if (t->S == 256) hipLaunchKernelGGL((viterbi_wide_kernel<4, 2>), dim3((unsigned)B), dim3(64), lds, st_rem, p);
         else if (t->I == 2) hipLaunchKernelGGL((viterbi_wide_kernel<2, 2>), dim3((unsigned)B), dim3(64), lds, st_rem, p);
         else hipLaunchKernelGGL((viterbi_wide_kernel<2, 4>), dim3((unsigned)B), dim3(64), lds, st_rem, p);
-        CPX_HIP(hipGetLastError());
+        if (int rcl = launch_error()) return join(rcl);
         if (p.nanflags) if (int rcr = launch_redo(t, p, B, st_rem)) return join(rcr);
         note_kernel("viterbi_wide_kernel<%d,%d>", t->S / 64, t->I);
         return join(CPX_OK);
@@ -949,7 +958,7 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
     }
 #undef VIT_CASE
 #undef VIT_LAUNCH
-    CPX_HIP(hipGetLastError());
+    if (int rcl = launch_error()) return join(rcl);
     if (p.nanflags) if (int rcr = launch_redo(t, p, nblocks, st_rem)) return join(rcr);
     {
         char first[160];                                         // a leading round on the codeword path, if any
@@ -988,16 +997,13 @@ int cpx_demod_hard_viterbi_batch(const cpx_modem *m, const cpx_trellis *t, const
     int rc = ensure_device();
     if (rc) return rc;
     if (B == 0 || L == 0) return CPX_OK;
-    DevBuf din, dout;
-    if ((rc = din.alloc(sizeof(double) * 2 * (size_t)(B * nsym)))) return rc;
-    if ((rc = dout.alloc((size_t)(B * L)))) return rc;
-    hipStream_t st = lib_stream();
-    CPX_HIP(hipMemcpyAsync(din.p, y_re_im, sizeof(double) * 2 * (size_t)(B * nsym), hipMemcpyHostToDevice, st));
-    rc = cpx_demod_hard_viterbi_batch_dev(m, t, din.as<double>(), B, nsym, L, n_steps, tb_depth, dout.as<uint8_t>(), st);
-    if (rc) return rc;
-    CPX_HIP(hipMemcpyAsync(bits, dout.p, (size_t)(B * L), hipMemcpyDeviceToHost, st));
-    CPX_HIP(hipStreamSynchronize(st));
-    return CPX_OK;
+    HostStage s;
+    const double *dy;
+    uint8_t *dbits;
+    if ((rc = s.in(y_re_im, sizeof(double) * 2 * (size_t)(B * nsym), &dy)) || (rc = s.out((size_t)(B * L), &dbits)) ||
+        (rc = cpx_demod_hard_viterbi_batch_dev(m, t, dy, B, nsym, L, n_steps, tb_depth, dbits, s.st)))
+        return rc;
+    return s.get(bits, dbits, (size_t)(B * L));
 }
 
 int cpx_viterbi_decode_batch(const cpx_trellis *t, const double *coded, int64_t B, int64_t len, int64_t L,
@@ -1007,17 +1013,13 @@ int cpx_viterbi_decode_batch(const cpx_trellis *t, const double *coded, int64_t 
     int rc = ensure_device();
     if (rc) return rc;
     if (B == 0 || L == 0) return CPX_OK;
-    DevBuf din, dout;
-    if ((rc = din.alloc(sizeof(double) * (size_t)(B * len)))) return rc;
-    if ((rc = dout.alloc((size_t)(B * L)))) return rc;
-    hipStream_t st = lib_stream();
-    CPX_HIP(hipMemcpyAsync(din.p, coded, sizeof(double) * (size_t)(B * len), hipMemcpyHostToDevice, st));
-    rc = cpx_viterbi_decode_batch_dev(t, din.as<double>(), B, len, L, n_steps, tb_depth, decoding_type,
-                                      dout.as<uint8_t>(), st);
-    if (rc) return rc;
-    CPX_HIP(hipMemcpyAsync(bits, dout.p, (size_t)(B * L), hipMemcpyDeviceToHost, st));
-    CPX_HIP(hipStreamSynchronize(st));
-    return CPX_OK;
+    HostStage s;
+    const double *din;
+    uint8_t *dbits;
+    if ((rc = s.in(coded, sizeof(double) * (size_t)(B * len), &din)) || (rc = s.out((size_t)(B * L), &dbits)) ||
+        (rc = cpx_viterbi_decode_batch_dev(t, din, B, len, L, n_steps, tb_depth, decoding_type, dbits, s.st)))
+        return rc;
+    return s.get(bits, dbits, (size_t)(B * L));
 }
 
 int cpx_viterbi_decode_batch_i64(const cpx_trellis *t, const double *coded, int64_t B, int64_t len, int64_t L,
@@ -1086,19 +1088,10 @@ int cpx_viterbi_decode_batch_i64(const cpx_trellis *t, const double *coded, int6
             CPX_HIP(hipStreamCreateWithFlags(&s_cmp[dev], hipStreamNonBlocking));
             CPX_HIP(hipStreamCreateWithFlags(&s_dn[dev], hipStreamNonBlocking));
         }
-        std::vector<hipEvent_t> ev_up(nch, nullptr), ev_cmp(nch, nullptr), ev_dn(nch, nullptr);
-        bool ev_ok = true;
-        for (int c = 0; c < nch && ev_ok; c++)
-            ev_ok = hipEventCreateWithFlags(&ev_up[c], hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&ev_cmp[c], hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&ev_dn[c], hipEventDisableTiming) == hipSuccess;
-        if (!ev_ok) {                                              // nothing is in flight yet: release what was created
-            for (int c = 0; c < nch; c++)
-                for (hipEvent_t e : {ev_up[c], ev_cmp[c], ev_dn[c]})
-                    if (e) (void)hipEventDestroy(e);
-            set_error("viterbi: hipEventCreate failed");
-            return CPX_EHIP;
-        }
+        // (declared before the widener thread, so that they outlive it)
+        std::vector<Event> ev_up(nch), ev_cmp(nch), ev_dn(nch);
+        for (int c = 0; c < nch; c++)
+            CPX_REQUIRE(ev_up[c].e && ev_cmp[c].e && ev_dn[c].e, CPX_EHIP, "viterbi: hipEventCreate failed");
         auto cw_lo = [&](int c) { return B * c / nch; };
         int issued = 0, wrc = CPX_OK;
         std::mutex qmu;
@@ -1111,7 +1104,7 @@ int cpx_viterbi_decode_batch_i64(const cpx_trellis *t, const double *coded, int6
                     qcv.wait(ql, [&] { return issued > c || issued < 0; });
                     if (issued < 0) return;
                 }
-                if (hipEventSynchronize(ev_dn[c]) != hipSuccess) { wrc = CPX_EHIP; return; }
+                if (hipEventSynchronize(ev_dn[c].e) != hipSuccess) { wrc = CPX_EHIP; return; }
                 CPX_TRACE("widen chunk (worker thread)");
                 widen((size_t)(cw_lo(c) * L), (size_t)(cw_lo(c + 1) * L), nt > 2 ? nt - 1 : 1);
             }
@@ -1121,7 +1114,6 @@ int cpx_viterbi_decode_batch_i64(const cpx_trellis *t, const double *coded, int6
             qcv.notify_all();
             widener.join();
             (void)hipDeviceSynchronize();
-            for (int c = 0; c < nch; c++) { (void)hipEventDestroy(ev_up[c]); (void)hipEventDestroy(ev_cmp[c]); (void)hipEventDestroy(ev_dn[c]); }
             return code;
         };
         for (int c = 0; c < nch; c++) {
@@ -1130,22 +1122,21 @@ int cpx_viterbi_decode_batch_i64(const cpx_trellis *t, const double *coded, int6
                 CPX_TRACE("H2D chunk");
                 if (hipMemcpyAsync(din.as<double>() + lo * len, coded + lo * len, sizeof(double) * (size_t)(n * len),
                                    hipMemcpyHostToDevice, s_up[dev]) != hipSuccess ||
-                    hipEventRecord(ev_up[c], s_up[dev]) != hipSuccess) { set_error("viterbi: upload failed"); return fail(CPX_EHIP); }
+                    hipEventRecord(ev_up[c].e, s_up[dev]) != hipSuccess) { set_error("viterbi: upload failed"); return fail(CPX_EHIP); }
             }
-            if (hipStreamWaitEvent(s_cmp[dev], ev_up[c], 0) != hipSuccess) { set_error("viterbi: stream wait failed"); return fail(CPX_EHIP); }
+            if (hipStreamWaitEvent(s_cmp[dev], ev_up[c].e, 0) != hipSuccess) { set_error("viterbi: stream wait failed"); return fail(CPX_EHIP); }
             viterbi_prefer_cw(true);                               // see viterbi_cw.hip: the chunk's round hides behind the next upload
             rc = cpx_viterbi_decode_batch_dev(t, din.as<double>() + lo * len, n, len, L, n_steps, tb_depth, decoding_type,
                                               dout.as<uint8_t>() + lo * L, s_cmp[dev]);
             viterbi_prefer_cw(false);
             if (rc) return fail(rc);
-            if (hipEventRecord(ev_cmp[c], s_cmp[dev]) != hipSuccess || hipStreamWaitEvent(s_dn[dev], ev_cmp[c], 0) != hipSuccess ||
+            if (hipEventRecord(ev_cmp[c].e, s_cmp[dev]) != hipSuccess || hipStreamWaitEvent(s_dn[dev], ev_cmp[c].e, 0) != hipSuccess ||
                 hipMemcpyAsync(stage + lo * L, dout.as<uint8_t>() + lo * L, (size_t)(n * L), hipMemcpyDeviceToHost, s_dn[dev]) != hipSuccess ||
-                hipEventRecord(ev_dn[c], s_dn[dev]) != hipSuccess) { set_error("viterbi: download failed"); return fail(CPX_EHIP); }
+                hipEventRecord(ev_dn[c].e, s_dn[dev]) != hipSuccess) { set_error("viterbi: download failed"); return fail(CPX_EHIP); }
             { std::lock_guard<std::mutex> ql(qmu); issued = c + 1; }
             qcv.notify_all();
         }
         widener.join();
-        for (int c = 0; c < nch; c++) { (void)hipEventDestroy(ev_up[c]); (void)hipEventDestroy(ev_cmp[c]); (void)hipEventDestroy(ev_dn[c]); }
         if (wrc) { set_error("viterbi: download failed"); return wrc; }
         CPX_HIP(hipStreamSynchronize(s_cmp[dev]));
         return CPX_OK;

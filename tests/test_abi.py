@@ -130,3 +130,62 @@ def test_ldpc_design_blob_host_only(tmp_path, monkeypatch):
     i32p = ctypes.POINTER(ctypes.c_int32)
     e1, e2 = np.array([1, 0], np.int32), np.array([0, 0], np.int32)
     assert lib.cpx_ldpc_blob_build(4, 2, 2, e1.ctypes.data_as(i32p), e2.ctypes.data_as(i32p), None, 0, ctypes.byref(need)) == _lib.CPX_EINVAL
+
+
+# every host-buffer entry point (host arrays in, host arrays out): (name, arguments with a null handle, null data and a
+# non-empty batch, the same with an empty batch)
+_HOST_BUFFER_CALLS = [
+    ("cpx_viterbi_decode_batch", (None, None, 2, 8, 4, 4, 5, 1, None), (None, None, 0, 8, 4, 4, 5, 1, None)),
+    ("cpx_viterbi_decode_batch_i64", (None, None, 2, 8, 4, 4, 5, 1, None), (None, None, 0, 8, 4, 4, 5, 1, None)),
+    ("cpx_demod_hard_viterbi_batch", (None, None, None, 2, 4, 4, 4, 5, None), (None, None, None, 0, 4, 4, 4, 5, None)),
+    ("cpx_map_decode_batch", (None, None, None, None, 2, 8, 1.0, 1, None, None),
+     (None, None, None, None, 0, 8, 1.0, 1, None, None)),
+    ("cpx_turbo_decode_batch", (None, None, None, None, None, None, 2, 8, 1.0, 2, None),
+     (None, None, None, None, None, None, 0, 8, 1.0, 2, None)),
+    ("cpx_demod_soft", (None, None, 2, 1.0, None), (None, None, 0, 1.0, None)),
+    ("cpx_demod_hard", (None, None, 2, None), (None, None, 0, None)),
+    ("cpx_ldpc_bp_decode_batch", (None, None, 2, 0, 2, None, None, None), (None, None, 0, 0, 2, None, None, None)),
+    ("cpx_ldpc_bp_decode_batch_bm", (None, None, 2, 0, 2, None, None, None), (None, None, 0, 0, 2, None, None, None)),
+    ("cpx_mimo_ml", (None, None, None, 0, 2, 2, 2, None), (None, None, None, 0, 0, 2, 2, None)),
+    ("cpx_kbest_hard", (None, None, None, 0, 2, 2, 2, 4, None), (None, None, None, 0, 0, 2, 2, 4, None)),
+    ("cpx_kbest_soft", (None, None, None, 0, 2, 2, 2, 4, 1.0, None), (None, None, None, 0, 0, 2, 2, 4, 1.0, None)),
+    ("cpx_kbest_list", (None, None, None, 0, 2, 2, 2, 4, None, None), (None, None, None, 0, 0, 2, 2, 4, None, None)),
+    ("cpx_best_first", (None, None, None, 0, 2, 2, 2, None, 1.0, None, None),
+     (None, None, None, 0, 0, 2, 2, None, 1.0, None, None)),
+]
+
+_NODEV = "no HIP device available"      # ensure_device()'s message (the runtime's own reason follows it)
+# what each entry point returns for both rows of _HOST_BUFFER_CALLS: the null checks of the MIMO detectors (best-first and the
+# K-best list aside, which need the modem's size first) come after ensure_device()
+_HOST_BUFFER_EXPECTED = {
+    "cpx_viterbi_decode_batch": (-1, "viterbi: null pointer"),
+    "cpx_viterbi_decode_batch_i64": (-1, "viterbi: null pointer"),
+    "cpx_demod_hard_viterbi_batch": (-1, "demod_hard_viterbi: null pointer"),
+    "cpx_map_decode_batch": (-1, "map_decode: null pointer"),
+    "cpx_turbo_decode_batch": (-1, "turbo_decode: null pointer"),
+    "cpx_demod_soft": (-1, "demod: null pointer"),
+    "cpx_demod_hard": (-1, "demod: null pointer"),
+    "cpx_ldpc_bp_decode_batch": (-1, "ldpc: null pointer"),
+    "cpx_ldpc_bp_decode_batch_bm": (-1, "ldpc: null pointer"),
+    "cpx_mimo_ml": (-4, _NODEV),
+    "cpx_kbest_hard": (-4, _NODEV),
+    "cpx_kbest_soft": (-4, _NODEV),
+    "cpx_kbest_list": (-1, "kbest: null modem, K < 1 or nt < 1"),
+    "cpx_best_first": (-1, "best_first: null modem"),
+}
+
+
+def test_host_buffer_entry_points_check_order_without_device():
+    """Null handle and null data, with a non-empty and an empty batch: every host-buffer entry point keeps its return code and
+    message, i.e. the order of its null checks and ensure_device()."""
+    if _lib.device_count() > 0:
+        pytest.skip("a HIP device is present")
+    lib = _lib.load()
+    assert set(_HOST_BUFFER_EXPECTED) == {name for name, _, _ in _HOST_BUFFER_CALLS}
+    for name, full, empty in _HOST_BUFFER_CALLS:
+        want_rc, want_msg = _HOST_BUFFER_EXPECTED[name]
+        for args in (full, empty):
+            rc = getattr(lib, name)(*args)
+            msg = _lib.last_error()
+            assert rc == want_rc, (name, args, rc, msg)
+            assert msg == want_msg if want_rc != -4 else msg.startswith(want_msg + " ("), (name, args, msg)

@@ -100,6 +100,12 @@ SYMBOLS = {
     "cpx_demod_soft_scaled_dev": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p]),
     "cpx_demod_hard": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "cpx_demod_hard_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cpx_ofdm_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
+    "cpx_ofdm_destroy": (c_int, [c_void_p]),
+    "cpx_ofdm_tx": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "cpx_ofdm_tx_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "cpx_ofdm_rx": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "cpx_ofdm_rx_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "cpx_kbest_set_path": (c_int, [c_char_p]),
     "cpx_mimo_ml": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
     "cpx_mimo_ml_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),

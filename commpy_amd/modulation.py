@@ -6,10 +6,11 @@ the host; ``demodulate`` ('hard' and 'soft') runs on the GPU through ``cpx_demod
 ``cpx_demod_soft`` (csrc/demod.hip).  The MIMO detectors ``mimo_ml`` and ``kbest`` (modulation.py:299-406) run on the
 GPU too (csrc/mimo.hip), with batched forms ``mimo_ml_batch`` / ``kbest_batch`` for throughput; The soft-output
 ``best_first_detector`` (modulation.py:422-565) runs on the GPU as well, with ``best_first_batch`` as its batched form.
-``max_log_approx`` and ``bit_lvl_repr`` are small host functions.  The OFDM helpers of the reference module are out of scope
-(SURVEY section 2, row 7).
+``max_log_approx`` and ``bit_lvl_repr`` are small host functions.  ``ofdm_tx`` / ``ofdm_rx`` (modulation.py:265-296) run on the
+GPU too (csrc/ofdm.hip), float64 only, with the symbol-major batched forms ``ofdm_tx_batch`` / ``ofdm_rx_batch``.
 """
 import ctypes
+import numbers
 import operator
 
 import numpy as np
@@ -18,7 +19,7 @@ from commpy_amd import _lib
 from commpy_amd.utilities import signal_power
 
 __all__ = ['PSKModem', 'QAMModem', 'Modem', 'mimo_ml', 'kbest', 'max_log_approx', 'bit_lvl_repr', 'mimo_ml_batch',
-           'kbest_batch', 'best_first_detector', 'best_first_batch']
+           'kbest_batch', 'best_first_detector', 'best_first_batch', 'ofdm_tx', 'ofdm_rx', 'ofdm_tx_batch', 'ofdm_rx_batch']
 
 
 def _gray_rank(m):
@@ -366,3 +367,124 @@ def bit_lvl_repr(H, w):
     if len(w) % 2:
         raise ValueError('Beta (length of w) must be even.')
     return np.asarray(H).dot(np.kron(np.identity(np.shape(H)[1]), w))
+
+
+# ---- OFDM (csrc/ofdm.hip) -----------------------------------------------------------------------------------------------------
+OFDM_MAX_NFFT = 65536
+
+
+def _whole(value, name):
+    """``value`` as an int: integers, and floats holding a whole number (the reference casts its sizes to float)."""
+    if isinstance(value, (bool, np.bool_)):
+        raise ValueError('%s must be a whole number, got %r' % (name, value))
+    if isinstance(value, numbers.Integral):
+        return int(value)
+    if isinstance(value, numbers.Real) and np.isfinite(value) and float(value) == int(value):
+        return int(value)
+    raise ValueError('%s must be a whole number, got %r' % (name, value))
+
+
+def _ofdm_sizes(nfft, nsc, cp_length):
+    """(nfft, nsc, cp_length) as ints, checked as the engine checks them (ValueError, no device needed)."""
+    nfft, nsc, cp_length = _whole(nfft, 'nfft'), _whole(nsc, 'nsc'), _whole(cp_length, 'cp_length')
+    if nfft < 2:
+        raise ValueError('nfft = %d, need at least 2' % nfft)
+    if nfft > OFDM_MAX_NFFT:
+        raise ValueError('nfft = %d is above the engine limit of %d' % (nfft, OFDM_MAX_NFFT))
+    if nsc < 2 or nsc % 2:
+        raise ValueError('nsc = %d, need an even number >= 2' % nsc)
+    if nsc // 2 > nfft - 1:
+        raise ValueError('nsc / 2 = %d subcarriers per side do not fit nfft = %d (at most nfft - 1)' % (nsc // 2, nfft))
+    if cp_length < 0:
+        raise ValueError('cp_length = %d is negative' % cp_length)
+    return nfft, nsc, cp_length
+
+
+def ofdm_prefix_length(nfft, cp_length):
+    """Samples of prefix in front of each transmitted symbol: ``cp_length`` if 0 < cp_length < nfft, else nfft -- the length of
+    the reference's ``t[-cp_length:]``, which takes the whole symbol for cp_length = 0 and for cp_length >= nfft."""
+    return cp_length if 0 < cp_length < nfft else nfft
+
+
+class _OfdmPlan:
+    """The engine's plan of one (nfft, nsc, cp_length): twiddles and kernel choice, one handle per device."""
+
+    def __init__(self, nfft, nsc, cp_length):
+        self.nfft, self.nsc, self.cp_length = nfft, nsc, cp_length
+
+        def create():
+            h = ctypes.c_void_p()
+            _lib.check(_lib.load().cpx_ofdm_create(nfft, nsc, cp_length, ctypes.byref(h)))
+            return h
+        self._handles = _lib.DeviceHandles(create, 'cpx_ofdm_destroy')
+
+    def handle(self):
+        return self._handles.get()
+
+
+_ofdm_plans = {}
+
+
+def _ofdm_plan(nfft, nsc, cp_length):
+    key = (nfft, nsc, cp_length)
+    plan = _ofdm_plans.get(key)
+    if plan is None:
+        if len(_ofdm_plans) > 64:
+            _ofdm_plans.clear()
+        plan = _ofdm_plans[key] = _OfdmPlan(nfft, nsc, cp_length)
+    return plan
+
+
+def ofdm_tx_batch(symbols, nfft, cp_length):
+    """``ofdm_tx`` for B streams at once, symbol-major: ``symbols [B, nsym, nsc]`` (what ``modulate(bits).reshape(B, nsym, nsc)``
+    gives) -> complex128 ``[B, nsym * (P + nfft)]``, P = ``ofdm_prefix_length(nfft, cp_length)``."""
+    x = np.asarray(symbols)
+    if x.ndim != 3:
+        raise ValueError('symbols must be [B, nsym, nsc], got %d dimensions' % x.ndim)
+    B, nsym, nsc = x.shape
+    nfft, nsc, cp_length = _ofdm_sizes(nfft, nsc, cp_length)
+    per = ofdm_prefix_length(nfft, cp_length) + nfft
+    out = np.zeros((B, nsym * per), dtype=np.complex128)
+    if out.size:
+        x = np.ascontiguousarray(x, dtype=np.complex128)
+        _lib.check(_lib.load().cpx_ofdm_tx(_ofdm_plan(nfft, nsc, cp_length).handle(), _lib.ptr(x), B, nsym, _lib.ptr(out)))
+    return out
+
+
+def ofdm_rx_batch(y, nfft, nsc, cp_length):
+    """``ofdm_rx`` for B streams at once: ``y [B, n]`` -> complex128 ``[B, n // (nfft + cp_length), nsc]`` (symbol-major)."""
+    y = np.asarray(y)
+    if y.ndim != 2:
+        raise ValueError('y must be [B, n], got %d dimensions' % y.ndim)
+    nfft, nsc, cp_length = _ofdm_sizes(nfft, nsc, cp_length)
+    B, n = y.shape
+    out = np.zeros((B, n // (nfft + cp_length), nsc), dtype=np.complex128)
+    if out.size:
+        y = np.ascontiguousarray(y, dtype=np.complex128)
+        _lib.check(_lib.load().cpx_ofdm_rx(_ofdm_plan(nfft, nsc, cp_length).handle(), _lib.ptr(y), B, n, _lib.ptr(out)))
+    return out
+
+
+def ofdm_tx(x, nfft, nsc, cp_length):
+    """OFDM transmit (modulation.py:265): ``x [nsc, nsym]``, column i = symbol i -> complex128 of length nsym * (P + nfft).
+    Per symbol, bins 1..nsc/2 carry ``x[nsc/2:, i]`` and the top nsc/2 bins ``x[:nsc/2, i]`` (the second wins where they
+    overlap), every other bin is 0; the block is the last P samples of ``ifft`` of that, then all nfft of them.
+    P = cp_length if 0 < cp_length < nfft, else nfft (the reference's ``t[-cp_length:]``)."""
+    nfft, nsc, cp_length = _ofdm_sizes(nfft, nsc, cp_length)
+    x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError('x must be [nsc, nsym], got %d dimensions' % x.ndim)
+    if x.shape[0] != nsc:
+        raise ValueError('x has %d rows, nsc = %d' % (x.shape[0], nsc))
+    return ofdm_tx_batch(x.T[None], nfft, cp_length)[0]
+
+
+def ofdm_rx(y, nfft, nsc, cp_length):
+    """OFDM receive (modulation.py:286): ``y`` 1-D -> complex128 ``[nsc, len(y) // (nfft + cp_length)]``.  Symbol i is the fft of
+    the nfft samples after the first cp_length of its block; column i holds its top nsc/2 bins, then bins 1..nsc/2.  Samples
+    past the last whole block are ignored."""
+    nfft, nsc, cp_length = _ofdm_sizes(nfft, nsc, cp_length)
+    y = np.asarray(y)
+    if y.ndim != 1:
+        raise ValueError('y must be 1-D, got %d dimensions' % y.ndim)
+    return np.ascontiguousarray(ofdm_rx_batch(y[None], nfft, nsc, cp_length)[0].T)

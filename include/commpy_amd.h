@@ -306,6 +306,29 @@ int cpx_demod_hard(const cpx_modem *m, const double *y_re_im, int64_t Ns, int8_t
 int cpx_demod_hard_dev(const cpx_modem *m, const double *d_y_re_im, int64_t Ns, int8_t *d_bits,
                        void *stream);
 
+/* ---- OFDM transmit / receive -------------------------------------------------------
+ * ofdm_tx / ofdm_rx, commpy/modulation.py:265-296, with h = nsc / 2, float64 only (cpx_set_precision does not apply):
+ *   TX, symbol i:  F = zeros(nfft); F[1:h+1] = x_i[h:]; F[nfft-h:] = x_i[:h] -- where the two ranges overlap (nsc > nfft - 1)
+ *                  the second write wins; t = ifft(F) (1/nfft scaling); the block is t[nfft-P:] followed by t, where
+ *                  P = cp_length if 0 < cp_length < nfft and P = nfft otherwise: the reference's t[-cp_length:] takes the whole
+ *                  symbol for cp_length = 0 and for cp_length >= nfft, and that is reproduced, not corrected.
+ *   RX, symbol i:  S = nfft + cp_length, X = fft(y[i S + cp_length : i S + cp_length + nfft]); x_hat_i = X[nfft-h:] ++ X[1:h+1];
+ *                  ny / S symbols per row, leftover samples at the end are ignored.
+ * cpx_ofdm_create: the plan of one (nfft, nsc, cp_length) on the current device: the twiddles (host-computed in long double from
+ *   exactly reduced angles), the bin map and the kernel: power-of-two nfft up to 8192 take an LDS-resident Stockham FFT, every
+ *   other size a direct DFT.  CPX_EINVAL for nfft < 2, nsc odd or < 2, h > nfft - 1, cp_length < 0; CPX_ELIMIT for nfft > 65536.
+ * cpx_ofdm_tx:  x [B][nsym][nsc] complex128 (symbol-major: a modulated bit stream reshaped) -> out [B][nsym (P + nfft)].
+ * cpx_ofdm_rx:  y [B][ny] complex128 -> out [B][ny / S][nsc].
+ * Every symbol's output is bit-identical whatever the batch size, its place in the batch or the stream.
+ */
+typedef struct cpx_ofdm cpx_ofdm;
+int cpx_ofdm_create(int nfft, int nsc, int cp_length, cpx_ofdm **out);
+int cpx_ofdm_destroy(cpx_ofdm *plan);
+int cpx_ofdm_tx(const cpx_ofdm *plan, const double *x_re_im, int64_t B, int64_t nsym, double *out_re_im);
+int cpx_ofdm_tx_dev(const cpx_ofdm *plan, const double *d_x_re_im, int64_t B, int64_t nsym, double *d_out_re_im, void *stream);
+int cpx_ofdm_rx(const cpx_ofdm *plan, const double *y_re_im, int64_t B, int64_t ny, double *out_re_im);
+int cpx_ofdm_rx_dev(const cpx_ofdm *plan, const double *d_y_re_im, int64_t B, int64_t ny, double *d_out_re_im, void *stream);
+
 /* ---- MIMO detection ------------------------------------------------------------------------------
  * Replace mimo_ml / kbest of commpy/modulation.py:299-406 (with max_log_approx :599-646 for the soft output) for a batch of B
  * received vectors.  The constellation is the modem's (cpx_modem_create), float64 throughout.

@@ -17,8 +17,12 @@
 //     still formed as those products so that the reference's underflow pattern at very high SNR
 //     (log(0/x) = -inf, 0/0 = NaN, modulation.py:134-137) is kept; finite values differ from the
 //     sequential sums by O(1e-16) relative (tolerance 1e-5).  Hard decisions decompose per axis
-//     exactly (nearest grid point, first minimum = lowest label); symbols whose two best axis
-//     distances are closer than 1e-12 relative are re-decided with the reference's full hypot scan.
+//     exactly (nearest grid point, first minimum = lowest label); symbols with a NaN / inf component
+//     and symbols whose two best axis distances are closer than 1e-12 relative are re-decided with the
+//     reference's full hypot scan (demod_dev.h).
+// Hard-decision contract (tests/test_demod_edges_gpu.py): a symbol with a NaN or inf component gets the
+// reference's label 0; exact ties go to the lowest label; where only rounding separates the candidates
+// -- several labels within 2 ulps of the minimum distance -- the label is one of them.
 #include "cpx_internal.h"
 #include "cpx_math.h"
 #include "demod_dev.h"
@@ -339,14 +343,15 @@ __device__ __forceinline__ void sep_symbol(const SepCtx &c, const double2 cur, d
         // Two levels per axis (QPSK / 4-QAM): LLR(bit of the real axis) = log(e[1] sy / (e[0] sy)) = (dx0^2 - dx1^2) / N0 -- no
         // exp, no log, no division; the kernel is then bound by its 32 bytes per symbol.  Valid while every one of the four
         // point probabilities exp(-(dx^2 + dy^2) / N0) the reference adds up is a normal number with room to spare: all four
-        // exponents below 650 (e^-650 = 1e-282).  Beyond that -- far outliers, Es/N0 above ~22 dB -- the reference's sums
-        // underflow in its own pattern (-inf, NaN) and the symbol is decided point by point below, as before.
+        // exponents below 650 in magnitude (e^-650 = 1e-282).  Beyond that -- far outliers, Es/N0 above ~22 dB, or a negative
+        // noise_var whose positive exponents overflow -- the reference's sums underflow or overflow in its own pattern (-inf, NaN)
+        // and the symbol is decided point by point below, as before.
         const double dx0 = cur.x - c.ax[0], dx1 = cur.x - c.ax[1], dy0 = cur.y - c.ax[R], dy1 = cur.y - c.ax[R + 1];
         const double qx0 = dx0 * dx0, qx1 = dx1 * dx1, qy0 = dy0 * dy0, qy1 = dy1 * dy1;
         const double worst = RCP ? (fmax(qx0, qx1) + fmax(qy0, qy1)) * -c.ninv : (fmax(qx0, qx1) + fmax(qy0, qy1)) / c.noise_var;
         out[1] = RCP ? (qx1 - qx0) * c.ninv : (qx0 - qx1) / c.noise_var;           // label bit 1 = real-axis index
         out[0] = RCP ? (qy1 - qy0) * c.ninv : (qy0 - qy1) / c.noise_var;           // label bit 0 = imag-axis index
-        if (!(worst < 650.0)) {
+        if (!(fabs(worst) < 650.0)) {                               // (a negative noise_var: the exponents are positive)
             double num[NB] = {0.0, 0.0}, den[NB] = {0.0, 0.0};
             for (int m = 0; m < R * R; m++) {
                 const double h = hypot(cur.x - c.ax[m >> NH], cur.y - c.ax[R + (m & (R - 1))]);
@@ -706,6 +711,11 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_soft_sep_f32_kernel(const d
             if (!(nx >= F32_TINY) || !(qx >= F32_TINY)) out[NH + b] = lse2_subset<R, 1>(tx, b) - lse2_subset<R, 0>(tx, b);
             if (!(ny >= F32_TINY) || !(qy >= F32_TINY)) out[b] = lse2_subset<R, 1>(ty, b) - lse2_subset<R, 0>(ty, b);
         }
+        // a NaN / inf component (after the cast: anything beyond the float range) leaves every distance inf or NaN, every
+        // exponential of the reference 0 or NaN and every LLR NaN; the per-axis form above would keep the other axis' LLRs finite
+        const float poison = (x - x) + (yy - yy);                 // 0, or NaN
+#pragma unroll
+        for (int b = 0; b < NB; b++) out[b] += poison;
         store_rows_f32<NB>(out, sc, i0, Ns, llr, stage);
     }
 }

@@ -17,9 +17,15 @@ __device__ __forceinline__ int hard_scan(const double2 *c, int M, double2 cur) {
 }
 
 // Axis-separable square constellations (what QAMModem builds): label = (a << NH) | b, point = xs[a] + 1j*ys[b],
-// axes = [xs | ys].  The nearest grid line per axis gives the nearest point; a symbol whose two best distances on an axis
-// are closer than 1e-12 (relative) is re-decided with the reference's full hypot scan, so the first-minimum rule of
-// argmin holds on decision boundaries too.
+// axes = [xs | ys].  The nearest grid line per axis gives the nearest point in exact arithmetic.  A symbol is re-decided with
+// the reference's full hypot scan (first minimum) unless the two best distances of each axis are more than 1e-12 apart
+// (relative): exact ties on decision boundaries go to the lowest label, and a NaN or +-inf component -- where the per-axis
+// distances are inf - inf or NaN and the reference answers label 0, every distance being inf or every one NaN -- fails the
+// comparison and takes the scan too.
+// Contract (tests/test_demod_edges_gpu.py): non-finite symbols and exact ties get the reference's label; where only rounding
+// separates candidates -- several labels whose exact distances lie within 2 ulps of the minimum, e.g. 5e-7 from a 16-QAM
+// boundary under an imaginary part of 1e4, where the reference's own hypot rounding makes a near-tie a tie -- the label is one
+// of that band (here the exact nearest; the scan's device hypot is not promised to round like the host's either).
 template <int NH>
 __device__ __forceinline__ int hard_sep(const double2 *c, const double *axes, double2 cur) {
     constexpr int R = 1 << NH;
@@ -32,7 +38,7 @@ __device__ __forceinline__ int hard_sep(const double2 *c, const double *axes, do
         if (dy < db) { db2 = db; db = dy; ib = a; } else if (dy < db2) db2 = dy;
     }
     int best = (ia << NH) | ib;
-    if (da2 - da <= 1e-12 * da2 || db2 - db <= 1e-12 * db2) best = hard_scan(c, R * R, cur);
+    if (!(da2 - da > 1e-12 * da2 && db2 - db > 1e-12 * db2)) best = hard_scan(c, R * R, cur);   // (NaN: the scan)
     return best;
 }
 

@@ -1,14 +1,17 @@
-"""commpy_amd -- MI355X-native channel-decoding / demodulation engine with CommPy's Python API.
+"""commpy_amd -- MI355X-native communication-link engine with CommPy's Python API.
 
-Scope: the batched decoding hot path of veeresht/CommPy 0.8.0 -- Viterbi,
-BCJR/MAP + turbo, LDPC belief propagation and PSK/QAM hard/soft demodulation -- re-implemented as
-hand-written HIP kernels for gfx950 behind a ctypes C-ABI (include/commpy_amd.h), plus the host-side
-code descriptions either side of it (Trellis, interleavers, LDPC design files, constellations,
-encoders).  No PyTorch, no Triton, no CPU fallback: the decoders raise if the HIP library or the
-GPU is missing.
+The modules of veeresht/CommPy 0.8.0, re-implemented as hand-written HIP kernels for gfx950 behind a ctypes C-ABI
+(include/commpy_amd.h) where they have a hot path -- Viterbi, BCJR/MAP + turbo, LDPC belief propagation, PSK/QAM modulation and
+hard/soft demodulation, MIMO detection, the fading channels and links, OFDM, and pulse shaping / matched filtering / frequency
+offset of sampled waveforms -- with the host-side descriptions either side of them (Trellis, interleavers, LDPC design files,
+constellations, encoders, filter taps, PN and Zadoff-Chu sequences).  No PyTorch, no Triton, no CPU fallback: the device entry
+points raise if the HIP library or the GPU is missing.
 
     from commpy_amd.channelcoding import Trellis, viterbi_decode, map_decode, turbo_decode, ldpc_bp_decode
-    from commpy_amd.modulation import PSKModem, QAMModem
+    from commpy_amd.modulation import PSKModem, QAMModem, ofdm_tx, ofdm_rx
+    from commpy_amd.filters import rrcosfilter, pulse_shape, matched_filter
+    from commpy_amd.sequences import pnsequence, zcsequence
+    from commpy_amd.impairments import add_frequency_offset
 """
 __version__ = "0.3.0"
 
@@ -48,4 +51,4 @@ class precision:
         return False
 
 
-__all__ = ["channelcoding", "modulation", "utilities", "parallel", "set_precision", "precision"]
+__all__ = ["channelcoding", "modulation", "utilities", "parallel", "filters", "sequences", "impairments", "set_precision", "precision"]

@@ -106,6 +106,14 @@ SYMBOLS = {
     "cpx_ofdm_tx_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "cpx_ofdm_rx": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "cpx_ofdm_rx_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "cpx_fir_create": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
+    "cpx_fir_destroy": (c_int, [c_void_p]),
+    "cpx_fir_interp": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "cpx_fir_interp_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "cpx_fir_decim": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p]),
+    "cpx_fir_decim_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p]),
+    "cpx_freq_offset": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
+    "cpx_freq_offset_dev": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "cpx_kbest_set_path": (c_int, [c_char_p]),
     "cpx_mimo_ml": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
     "cpx_mimo_ml_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),

@@ -329,6 +329,34 @@ int cpx_ofdm_tx_dev(const cpx_ofdm *plan, const double *d_x_re_im, int64_t B, in
 int cpx_ofdm_rx(const cpx_ofdm *plan, const double *y_re_im, int64_t B, int64_t ny, double *out_re_im);
 int cpx_ofdm_rx_dev(const cpx_ofdm *plan, const double *d_y_re_im, int64_t B, int64_t ny, double *d_out_re_im, void *stream);
 
+/* ---- FIR filtering and frequency offset of sampled waveforms ------------------------------
+ * What commpy/filters.py, utilities.upsample and impairments.py leave to numpy.convolve and numpy.exp, batched; complex128 data,
+ * float64 arithmetic only (cpx_set_precision does not apply).
+ * cpx_fir_create: a plan holding `ntaps` taps on the current device, real (taps_complex = 0: ntaps doubles) or complex
+ *   (taps_complex = 1: ntaps interleaved re/im pairs).  1 <= ntaps <= 8192 (CPX_ELIMIT above); taps must be finite.
+ * cpx_fir_interp:  x [B][n] -> out [B][n sps + ntaps - 1], row b = convolve(upsample(x[b], sps), taps), polyphase (the zeros
+ *   between symbols are never formed); sps >= 1, sps = 1 is a plain full convolution.
+ * cpx_fir_decim:   y [B][n] -> out [B][ceil((n + ntaps - 1 - offset) / sps)], row b = convolve(y[b], taps)[offset::sps] for
+ *   0 <= offset < n + ntaps - 1; only the kept samples are computed.
+ * cpx_freq_offset: out[b][k] = x[b][k] (cos t + i sin t), t = step k rounded once to float64, step = step[0] for the whole batch
+ *   (step_batched = 0) or step[b] per row (step_batched = 1); the caller computes step = (2 pi)(delta_f / Fs).  In the _dev form
+ *   `d_step` is a DEVICE pointer like the data, and out == x (in place) is allowed.
+ * B = 0 succeeds without touching the device; n = 0 with B > 0 is CPX_EINVAL for the filters (numpy.convolve refuses an empty
+ * operand).  Every output sample is summed over its taps in ascending tap index by fused multiply-adds: bit-identical whatever
+ * the batch size, the row's place in the batch or the stream.
+ */
+typedef struct cpx_fir cpx_fir;
+int cpx_fir_create(const double *taps, int ntaps, int taps_complex, cpx_fir **out);
+int cpx_fir_destroy(cpx_fir *plan);
+int cpx_fir_interp(const cpx_fir *plan, const double *x_re_im, int64_t B, int64_t n, int sps, double *out_re_im);
+int cpx_fir_interp_dev(const cpx_fir *plan, const double *d_x_re_im, int64_t B, int64_t n, int sps, double *d_out_re_im, void *stream);
+int cpx_fir_decim(const cpx_fir *plan, const double *y_re_im, int64_t B, int64_t n, int sps, int64_t offset, double *out_re_im);
+int cpx_fir_decim_dev(const cpx_fir *plan, const double *d_y_re_im, int64_t B, int64_t n, int sps, int64_t offset,
+                      double *d_out_re_im, void *stream);
+int cpx_freq_offset(const double *x_re_im, int64_t B, int64_t n, const double *step, int step_batched, double *out_re_im);
+int cpx_freq_offset_dev(const double *d_x_re_im, int64_t B, int64_t n, const double *d_step, int step_batched, double *d_out_re_im,
+                        void *stream);
+
 /* ---- MIMO detection ------------------------------------------------------------------------------
  * Replace mimo_ml / kbest of commpy/modulation.py:299-406 (with max_log_approx :599-646 for the soft output) for a batch of B
  * received vectors.  The constellation is the modem's (cpx_modem_create), float64 throughout.

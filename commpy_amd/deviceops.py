@@ -1,0 +1,358 @@
+"""Device memory and the one-shot host conveniences over the link-simulation stages of the C-ABI.
+
+``DeviceBuf`` is a device allocation for callers that keep data in HBM.  The ``*_gpu`` functions and ``LdpcEncoder.encode`` take
+host arrays, run ONE stage on the GPU (encoders, puncturing, modulation, binary channels, the MIMO fading channel) and return
+host arrays; the device links of ``commpy_amd.devicelink`` chain the same entry points without leaving the device.
+"""
+import contextlib
+import ctypes
+
+import numpy as np
+
+from commpy_amd import _lib
+from commpy_amd.channelcoding.convcode import puncture_keep_mask
+from commpy_amd.channelcoding.ldpc import build_matrix
+
+__all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu', 'mimo_channel_gpu', 'puncturing_gpu',
+           'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder', 'gf2_generator',
+           'triang_ldpc_systematic_encode_gpu']
+
+
+class DeviceBuf:
+    """A device allocation owned through the C-ABI (cpx_malloc / cpx_free)."""
+
+    def __init__(self, nbytes):
+        self.lib = _lib.load()
+        self.nbytes = int(nbytes)
+        self.ptr = ctypes.c_void_p()
+        _lib.check(self.lib.cpx_malloc(ctypes.byref(self.ptr), max(self.nbytes, 8)))
+
+    @classmethod
+    def from_array(cls, arr):
+        arr = np.ascontiguousarray(arr)
+        buf = cls(arr.nbytes)
+        if arr.nbytes:
+            _lib.check(buf.lib.cpx_memcpy_h2d(buf.ptr, _lib.ptr(arr), arr.nbytes))
+        return buf
+
+    def to_array(self, shape, dtype):
+        out = np.empty(shape, dtype=dtype)
+        if out.nbytes:
+            _lib.check(self.lib.cpx_memcpy_d2h(_lib.ptr(out), self.ptr, out.nbytes))
+        return out
+
+    def free(self):
+        if self.ptr:
+            self.lib.cpx_free(self.ptr)
+            self.ptr = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class _OneShot(contextlib.ExitStack):
+    """The device memory of one host-convenience call: ``with _OneShot() as dev`` uploads inputs, allocates outputs and downloads
+    results; everything it allocated is freed when the block ends, also by an exception."""
+
+    lib = property(lambda self: _lib.load())
+
+    def _own(self, buf):
+        self.callback(buf.free)
+        return buf
+
+    def upload(self, arr):
+        """Device pointer of a copy of ``arr``."""
+        return self._own(DeviceBuf.from_array(arr)).ptr
+
+    def alloc(self, nbytes):
+        return self._own(DeviceBuf(nbytes))
+
+    def download(self, buf, shape, dtype):
+        """``buf`` as a host array, once the default stream has finished."""
+        _lib.check(self.lib.cpx_stream_sync(None))
+        return buf.to_array(shape, dtype)
+
+
+def _encoded_length(nmsg, trellis, termination):
+    """number_outbits of conv_encode (convcode.py:505-520)."""
+    k, n, m = trellis.k, trellis.n, trellis.total_memory
+    rate = float(k) / n
+    if termination == 'cont':
+        return int(nmsg / rate)
+    if trellis.code_type == 'rsc':
+        return int((nmsg + k * m) / rate)
+    return int((nmsg + m + m % k) / rate)
+
+
+def conv_encode_gpu(message_bits, trellis, termination='term'):
+    """``conv_encode`` for a batch ``[B, nbits]`` on the GPU (no puncturing); returns int64 ``[B, nout]``."""
+    msgs = np.ascontiguousarray(np.atleast_2d(message_bits), dtype=np.uint8)
+    B, nmsg = msgs.shape
+    nout = _encoded_length(nmsg, trellis, termination)
+    rsc = trellis.code_type == 'rsc'
+    # recursive codes clock a tail for 'term' only (convcode.py:538); other codes append zeros for anything but 'cont'
+    terminate = (termination == 'term') if rsc else (termination != 'cont')
+    with _OneShot() as dev:
+        d_out = dev.alloc(B * nout)
+        _lib.check(dev.lib.cpx_conv_encode_batch_dev(trellis._device_handle(), dev.upload(msgs), B, nmsg, int(terminate),
+                                                     int(rsc), d_out.ptr, nout, None))
+        return dev.download(d_out, (B, nout), np.uint8).astype(np.int64)
+
+
+def modulate_gpu(modem, input_bits):
+    """``Modem.modulate`` on the GPU; returns complex128 symbols."""
+    bits = np.ascontiguousarray(input_bits, dtype=np.uint8).reshape(-1)
+    nsym = bits.size // modem.num_bits_symbol
+    with _OneShot() as dev:
+        d_sym = dev.alloc(nsym * 16)
+        _lib.check(dev.lib.cpx_modulate_dev(modem._device_handle(), dev.upload(bits), nsym, d_sym.ptr, None))
+        return dev.download(d_sym, (nsym,), np.complex128)
+
+
+def puncture_indices(n_positions, punct_vec):
+    """Index table of ``puncturing(message, punct_vec)`` (convcode.py:752-774) for messages of ``n_positions`` bits:
+    ``punctured[j] = message[idx[j]]`` -- what ``cpx_gather_u8_dev`` is given."""
+    return np.flatnonzero(puncture_keep_mask(n_positions, punct_vec)).astype(np.int32)
+
+
+def depuncture_indices(shouldbe, punct_vec, n_punctured):
+    """Index table of ``depuncturing(punctured, punct_vec, shouldbe)`` (convcode.py:777-804): ``out[j] = punctured[idx[j]]`` where
+    ``idx[j] >= 0`` and 0.0 where it is -1 -- what ``cpx_gather_f64_dev`` is given.  ``IndexError`` like the reference's
+    ``punctured[idx - shift2]`` when ``n_punctured`` values cannot fill the pattern."""
+    keep = puncture_keep_mask(shouldbe, punct_vec)
+    if keep.sum() > n_punctured:
+        raise IndexError('depuncturing: message too short for the puncturing pattern')
+    de = -np.ones(int(shouldbe), dtype=np.int32)
+    de[keep] = np.arange(keep.sum(), dtype=np.int32)
+    return de
+
+
+def _gather_gpu(entry, rows, idx, dtype):
+    """``out[b, j] = rows[b, idx[j]]`` (0 where ``idx[j]`` is -1) through ``cpx_gather_u8_dev`` / ``cpx_gather_f64_dev``."""
+    B, n = rows.shape
+    with _OneShot() as dev:
+        d_out = dev.alloc(B * len(idx) * np.dtype(dtype).itemsize)
+        _lib.check(getattr(dev.lib, entry)(dev.upload(rows), B, n, dev.upload(idx), len(idx), d_out.ptr, None))
+        return dev.download(d_out, (B, len(idx)), dtype)
+
+
+def puncturing_gpu(messages, punct_vec):
+    """``puncturing`` for a batch ``[B, n]`` of bit rows on the GPU (``cpx_gather_u8_dev``); returns uint8 ``[B, n_kept]``."""
+    msgs = np.ascontiguousarray(np.atleast_2d(messages), dtype=np.uint8)
+    return _gather_gpu("cpx_gather_u8_dev", msgs, puncture_indices(msgs.shape[1], punct_vec), np.uint8)
+
+
+def depuncturing_gpu(punctured, punct_vec, shouldbe):
+    """``depuncturing`` for a batch ``[B, n_punctured]`` of float rows on the GPU (``cpx_gather_f64_dev``); float64 ``[B, shouldbe]``."""
+    rows = np.ascontiguousarray(np.atleast_2d(punctured), dtype=np.float64)
+    return _gather_gpu("cpx_gather_f64_dev", rows, depuncture_indices(shouldbe, punct_vec, rows.shape[1]), np.float64)
+
+
+def _binary_channel_gpu(which, input_bits, p, seed, stream_id):
+    bits = np.ascontiguousarray(input_bits, dtype=np.uint8)
+    with _OneShot() as dev:
+        d_out = dev.alloc(bits.size)
+        _lib.check(getattr(dev.lib, which)(dev.upload(bits), bits.size, float(p), int(seed), int(stream_id), d_out.ptr, None, None))
+        return dev.download(d_out, bits.shape, np.int8)
+
+
+def bsc_gpu(input_bits, p_t, seed=0, stream_id=0):
+    """``bsc(input_bits, p_t)`` (channels.py:652-673) on the GPU: every bit flipped with probability ``p_t``.  The draws come
+    from the Philox stream ``(seed, stream_id)``, not from NumPy's global generator: statistically, not bit-wise, the reference's."""
+    return _binary_channel_gpu("cpx_bsc_dev", input_bits, p_t, seed, stream_id)
+
+
+def bec_gpu(input_bits, p_e, seed=0, stream_id=0):
+    """``bec(input_bits, p_e)`` (channels.py:630-649) on the GPU: every bit erased (-1) with probability ``p_e``."""
+    return _binary_channel_gpu("cpx_bec_dev", input_bits, p_e, seed, stream_id)
+
+
+def turbo_encode_gpu(msg_bits, trellis1, trellis2, interleaver, mode=0):
+    """``turbo_encode`` (turbo.py:14-59) for a batch ``[B, N]`` of messages on the GPU.
+
+    Returns ``[sys, p1, p2]`` as int64 arrays ``[B, N]``, ``[B, N]`` and ``[B, 2(N+m2)-m2]``: row ``b`` of each equals
+    what the reference returns for ``msg_bits[b]`` (the second parity stream keeps ``conv_encode``'s
+    unpunctured length with a zero tail -- use ``p2[:, :N]``).  ``mode``: 0 auto, 1 walk, 2 scan kernel.
+    """
+    msgs = np.ascontiguousarray(np.atleast_2d(msg_bits), dtype=np.uint8)
+    B, N = msgs.shape
+    if trellis1.code_type != 'rsc' or trellis2.code_type != 'rsc':
+        # a non-recursive trellis makes conv_encode clock a zero tail (convcode.py:516-520) whose outputs the
+        # reference leaves in the second parity stream; only the recursive-systematic case is built
+        raise ValueError("turbo_encode_gpu needs recursive systematic component codes (code_type='rsc')")
+    perm = np.ascontiguousarray(interleaver.p_array, dtype=np.int32)
+    if perm.size != N:
+        raise ValueError('interleaver length must equal the message length')
+    np2 = 2 * (N + trellis2.total_memory) - trellis2.total_memory     # conv_encode's length minus turbo.py:57's cut
+    with _OneShot() as dev:
+        d_sys, d_p1, d_p2 = dev.alloc(B * N), dev.alloc(B * N), dev.alloc(B * np2)
+        _lib.check(dev.lib.cpx_turbo_encode_batch_dev(trellis1._device_handle(), trellis2._device_handle(), dev.upload(msgs), B, N,
+                                                      dev.upload(perm), d_sys.ptr, d_p1.ptr, d_p2.ptr, np2, int(mode), None))
+        return [dev.download(d, (B, cols), np.uint8).astype(np.int64) for d, cols in ((d_sys, N), (d_p1, N), (d_p2, np2))]
+
+
+def gf2_generator(ldpc_code_params):
+    """Systematic generator over GF(2): ``P`` (uint8 ``[m, k]``) with ``H[:, k:] @ P = H[:, :k] (mod 2)``.
+
+    ``build_matrix`` (ldpc.py:44-48) inverts the last ``m`` columns of H over the *reals*, which is only a valid GF(2)
+    inverse for (approximately) triangular codes; this is the same construction done in GF(2) arithmetic, so it
+    also covers codes like the 802.11n (1944,1296) matrix of BASELINE config 4 whose real inverse is not integral.
+    """
+    if ldpc_code_params.get('parity_check_matrix') is None:
+        try:
+            build_matrix(ldpc_code_params)
+        except Exception:       # the real-valued inverse may not exist; H itself is all that is needed here
+            pass
+    H = ldpc_code_params.get('parity_check_matrix')
+    if H is None:
+        n_c, deg = ldpc_code_params['n_cnodes'], ldpc_code_params['max_cnode_deg']
+        adj = np.asarray(ldpc_code_params['cnode_adj_list']).reshape(n_c, deg)
+        Hd = np.zeros((n_c, ldpc_code_params['n_vnodes']), np.uint8)
+        for c in range(n_c):
+            Hd[c, adj[c, :ldpc_code_params['cnode_deg_list'][c]]] = 1
+    else:
+        Hd = (np.asarray(H.todense() if hasattr(H, 'todense') else H) != 0).astype(np.uint8)
+    m, n = Hd.shape
+    k = n - m
+    A = np.concatenate([Hd[:, k:], Hd[:, :k]], axis=1)               # [H_sys | H_par], reduce the left block to I
+    for col in range(m):
+        piv = col + np.flatnonzero(A[col:, col])
+        if piv.size == 0:
+            raise ValueError('the last n_cnodes columns of H are singular over GF(2)')
+        if piv[0] != col:
+            A[[col, piv[0]]] = A[[piv[0], col]]
+        rows = np.flatnonzero(A[:, col])
+        rows = rows[rows != col]
+        A[rows] ^= A[col]
+    return np.ascontiguousarray(A[:, m:])
+
+
+class LdpcEncoder:
+    """Device-resident systematic LDPC encoder: ``code = [msg, G2 @ msg mod 2]`` per block (ldpc.py:302-354).
+
+    ``generator='reference'`` uses ``ldpc_code_params['generator_matrix']`` exactly as
+    ``triang_ldpc_systematic_encode`` does (built by ``build_matrix`` if absent) and requires its entries to be
+    integers, so that ``G.dot(msg) % 2`` (ldpc.py:353) is GF(2) arithmetic; ``generator='gf2'`` uses
+    :func:`gf2_generator`.
+    """
+
+    def __init__(self, ldpc_code_params, generator='reference'):
+        self.lib = lib = _lib.load()
+        if generator == 'gf2':
+            G2 = gf2_generator(ldpc_code_params)
+        elif generator == 'reference':
+            if ldpc_code_params.get('generator_matrix') is None or ldpc_code_params.get('parity_check_matrix') is None:
+                build_matrix(ldpc_code_params)
+            G = ldpc_code_params['generator_matrix']
+            G = np.asarray(G.todense() if hasattr(G, 'todense') else G, dtype=np.float64)
+            if not np.all(np.abs(G - np.rint(G)) < 1e-9):
+                raise ValueError("generator_matrix is not integer valued (the code is not triangular); "
+                                 "use generator='gf2'")
+            G2 = (np.rint(G).astype(np.int64) % 2).astype(np.uint8)
+        else:
+            raise ValueError("generator must be 'reference' or 'gf2'")
+        self.G2 = G2 = np.ascontiguousarray(G2, dtype=np.uint8)
+        self.m, self.k = m, k = G2.shape
+        self.n = self.m + self.k
+
+        def create():
+            h = ctypes.c_void_p()
+            _lib.check(lib.cpx_ldpc_encoder_create(_lib.ptr(G2), m, k, ctypes.byref(h)))
+            return h
+        self._handles = _lib.DeviceHandles(create, 'cpx_ldpc_encoder_destroy')
+        self._handles.get()                 # now, so that a missing device or a refused generator fails the constructor
+
+    @property
+    def h(self):
+        """Opaque cpx_ldpc_encoder* of the current device (one per device, created on first use there)."""
+        return self._handles.get()
+
+    def encode_dev(self, d_msg, B, d_code, stream=None):
+        """msg ``[B][k]`` uint8 (device) -> code ``[B][n]`` uint8 (device); asynchronous on ``stream``."""
+        _lib.check(self.lib.cpx_ldpc_encode_batch_dev(self.h, d_msg, int(B), d_code, stream))
+
+    def encode(self, msgs):
+        """Host convenience: uint8/int ``[B, k]`` -> int8 ``[B, n]``."""
+        msgs = np.ascontiguousarray(np.atleast_2d(msgs), dtype=np.uint8)
+        B, k = msgs.shape
+        if k != self.k:
+            raise ValueError('messages must have %d bits' % self.k)
+        with _OneShot() as dev:
+            d_code = dev.alloc(B * self.n)
+            self.encode_dev(dev.upload(msgs), B, d_code.ptr)
+            return dev.download(d_code, (B, self.n), np.int8)
+
+
+def triang_ldpc_systematic_encode_gpu(message_bits, ldpc_code_params, pad=True, generator='reference'):
+    """``triang_ldpc_systematic_encode`` (ldpc.py:302-354) on the GPU: same arguments, padding rule, ``ValueError``
+    and return layout (int8 ``(n, n_blocks)``, squeezed; block ``j`` = ``message_bits[j*k:(j+1)*k]``)."""
+    enc = ldpc_code_params.get('_cpx_ldpc_enc_' + generator)
+    if enc is None:
+        enc = LdpcEncoder(ldpc_code_params, generator)
+        ldpc_code_params['_cpx_ldpc_enc_' + generator] = enc
+    message_bits = np.asarray(message_bits)
+    modulo = len(message_bits) % enc.k
+    if modulo:
+        if pad:
+            message_bits = np.concatenate((message_bits, np.zeros(enc.k - modulo, message_bits.dtype)))
+        else:
+            raise ValueError('Padding is disable but message length is not a multiple of block length.')
+    return enc.encode(message_bits.reshape(-1, enc.k)).T.squeeze().astype(np.int8)
+
+
+# ---- the MIMO fading channel --------------------------------------------------------------------------------------------------
+
+def _fading_matrices(channel):
+    """(sqrtm(Rr) [nr, nr], sqrtm(Rt).T [nt, nt], mean [nr, nt]) as complex128 C arrays: the three matrices
+    ``MIMOFlatChannel.propagate`` multiplies G with, computed once on the host."""
+    from scipy.linalg import sqrtm
+    mean, rt, rr = channel.fading_param
+    return (np.ascontiguousarray(sqrtm(rr), dtype=np.complex128), np.ascontiguousarray(sqrtm(rt).T, dtype=np.complex128),
+            np.ascontiguousarray(np.broadcast_to(mean, (channel.nb_rx, channel.nb_tx)), dtype=np.complex128))
+
+
+def _channel_handles(channel):
+    """cpx_mimo_channel handles (one per device) of the channel's current fading_param."""
+    lib = _lib.load()
+    a, bt, mean = _fading_matrices(channel)
+
+    def create():
+        h = ctypes.c_void_p()
+        _lib.check(lib.cpx_mimo_channel_create(channel.nb_rx, channel.nb_tx, _lib.ptr(a), _lib.ptr(bt), _lib.ptr(mean),
+                                               ctypes.byref(h)))
+        return h
+    return _lib.DeviceHandles(create, 'cpx_mimo_channel_destroy')
+
+
+def _require_complex(channel):
+    if not channel.isComplex:
+        raise ValueError('the device MIMO channel is complex valued: call uncorr_rayleigh_fading(complex) or give a complex fading_param')
+
+
+def mimo_channel_gpu(channel, modem, bits, seed=0, stream_id=0):
+    """``MIMOFlatChannel.propagate(modem.modulate(bits))`` on the GPU: returns ``(y [V, nr], H [V, nr, nt])`` for the
+    ``V = len(bits) / (nt * num_bits_symbol)`` vectors the bits fill (a partial vector is a ValueError).  The fading G and the noise
+    come from the Philox streams ``(seed, 2 stream_id)`` and ``(seed, 2 stream_id + 1)`` instead of NumPy's generator (statistically,
+    not bit-wise, the reference's); ``H = sqrtm(Rr) G sqrtm(Rt).T + mean`` and the noise of per-component std ``noise_std / 2``
+    follow channels.py (quirk B7)."""
+    _require_complex(channel)
+    if channel.noise_std is None:
+        raise AssertionError('Noise standard deviation must be set before propagation.')
+    nr, nt, nb = channel.nb_rx, channel.nb_tx, modem.num_bits_symbol
+    flat = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+    if flat.size % (nt * nb):
+        raise ValueError('%d bits do not fill whole vectors of %d symbols of %d bits' % (flat.size, nt, nb))
+    V = flat.size // (nt * nb)
+    handles = _channel_handles(channel)
+    try:
+        with _OneShot() as dev:
+            d_y, d_h = dev.alloc(V * nr * 16), dev.alloc(V * nr * nt * 16)
+            _lib.check(dev.lib.cpx_mimo_channel_run_dev(handles.get(), modem._device_handle(), dev.upload(flat), V, 0,
+                                                        float(channel.noise_std) * 0.5, int(seed), 2 * int(stream_id),
+                                                        2 * int(stream_id) + 1, d_y.ptr, d_h.ptr, None))
+            return dev.download(d_y, (V, nr), np.complex128), dev.download(d_h, (V, nr, nt), np.complex128)
+    finally:
+        handles.drop()

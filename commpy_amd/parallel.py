@@ -31,6 +31,7 @@ import time
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd.deviceops import DeviceBuf
 
 __all__ = ['shard_bounds', 'shard_counts', 'pad_shard', 'unpad_gathered', 'sharded_decode', 'reduce_counters',
            'exchange_unique_id', 'launch_nonce', 'RankComm', 'DeviceGroup']
@@ -224,7 +225,6 @@ class RankComm:
 
     # -- host-array collectives (the Collective protocol of sharded_decode / reduce_counters) -------------------------
     def allgather_rows(self, local, n_total):
-        from commpy_amd.devicelink import DeviceBuf
         local = np.ascontiguousarray(local)
         padded = pad_shard(local, n_total, self.rank, self.world)
         nb = padded.nbytes
@@ -237,7 +237,6 @@ class RankComm:
         return unpad_gathered(full, n_total, self.world)
 
     def allreduce(self, arr, op='sum'):
-        from commpy_amd.devicelink import DeviceBuf
         a = np.ascontiguousarray(arr)
         if a.dtype not in (np.int64, np.float64):
             raise TypeError('allreduce: int64 or float64 arrays')
@@ -347,7 +346,6 @@ class DeviceGroup:
     def allreduce_counters(self, per_device_counters):
         """Sum one int64 counter array per device over the group with an RCCL all-reduce; returns the total (read back
         from the first device)."""
-        from commpy_amd.devicelink import DeviceBuf
         arrs = [np.ascontiguousarray(c, dtype=np.int64) for c in per_device_counters]
         if len(arrs) != self.G or any(a.shape != arrs[0].shape for a in arrs):
             raise ValueError('allreduce_counters: one equally shaped array per device')
@@ -368,7 +366,6 @@ class DeviceGroup:
         ``gather=True``: the decoded bits are all-gathered over xGMI so that every GPU holds the whole result (read
         back from the first); ``gather=False``: no collective, every shard comes back from its own GPU."""
         from commpy_amd.channelcoding.convcode import _VIT_TYPES, _viterbi_sizes
-        from commpy_amd.devicelink import DeviceBuf
         if decoding_type not in _VIT_TYPES:
             raise ValueError('The available decoding types are "hard", "soft" and "unquantized')
         x = _lib.as_f64(np.atleast_2d(coded_bits))
@@ -414,7 +411,6 @@ class DeviceGroup:
         32768 per GPU).  Returns ``(dec_word int8 (n, B), out_llrs float64 (n, B))`` like the reference; ``dec_word`` is
         all-gathered over xGMI (``gather=True``), ``out_llrs`` (8 bytes per bit) stays sharded and is read back from each GPU."""
         from commpy_amd.channelcoding.ldpc import _device_code
-        from commpy_amd.devicelink import DeviceBuf
         if decoder_algorithm not in ('SPA', 'MSA'):
             raise NameError('Please input a valid decoder_algorithm string (meanning "SPA" or "MSA").')
         n_v = int(ldpc_code_params['n_vnodes'])

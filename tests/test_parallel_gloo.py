@@ -125,7 +125,7 @@ def test_sharded_decode_world2_gloo(tmp_path):
 def test_parallel_module_is_torch_free():
     """north_star: no PyTorch in the product -- the collective layer is the engine's own RCCL binding."""
     import ast
-    for mod in ("parallel.py", "_lib.py", "devicelink.py"):
+    for mod in ("parallel.py", "_lib.py", "devicelink.py", "deviceops.py"):
         tree = ast.parse(open(os.path.join(ROOT, "commpy_amd", mod)).read())
         names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
         names += [n.module or "" for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]

@@ -129,6 +129,16 @@ SYMBOLS = {
     "cpx_best_first": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_double, c_void_p, c_void_p]),
     "cpx_best_first_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_double, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
+    "cpx_mimo_list_dist": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "cpx_mimo_list_dist_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                       c_void_p]),
+    "cpx_mimo_list_llr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_double, c_double,
+                                  c_void_p]),
+    "cpx_mimo_list_llr_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_double, c_double,
+                                      c_void_p, c_void_p]),
+    "cpx_mimo_idd_exchange_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_double,
+                                          c_double, c_int, c_void_p]),
+    "cpx_mimo_llr_hard_dev": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "cpx_mimo_channel_create": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "cpx_mimo_channel_destroy": (c_int, [c_void_p]),
     "cpx_mimo_channel_run_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_uint64, c_double, c_uint64, c_uint64, c_uint64,

@@ -13,7 +13,8 @@ to the host.  The random streams are Philox-based, so results are statistically 
 comparable with the reference; the deterministic stages are bit-exact (tests/test_devicelink_gpu.py).
 
 ``DeviceMimoLink`` does the same for a MIMO link over a ``MIMOFlatChannel`` (bits -> [LDPC encode] -> Kronecker fading channel ->
-ML / K-best / best-first detector -> [LDPC decode] -> error count), the device counterpart of ``LinkModel`` with ``mimo_receiver``.
+ML / K-best / best-first detector -> [LDPC decode] -> error count), the device counterpart of ``LinkModel`` with ``mimo_receiver``;
+with ``idd_iters`` it closes the loop between a list detector with priors and the LDPC decoder (``links.idd_decoder`` on the device).
 
 ``DeviceBscLink`` is BASELINE config 1 (hard-decision Viterbi over a BSC).  The two sweep rules the links share are
 ``_fixed_budget_ber`` and ``_sequential_ber``.  ``DeviceBuf``, the one-shot ``*_gpu`` host conveniences and ``LdpcEncoder`` live in
@@ -332,20 +333,32 @@ class DeviceMimoLink:
     ``noise_std / 2`` while the detector is told ``noise_std**2`` (quirk B7).  Random streams are Philox (seed, call, stage), so
     BERs are statistically, not bit-wise, the host link's.
 
+    ``idd_iters >= 1`` (LDPC-coded 'kbest' with 'soft' output only) runs iterative detection and decoding, ``links.idd_decoder``
+    with a list detector: the K-best list is searched once and its distances computed once, a first detector pass without prior
+    (LLRs clipped to ``idd_clip``) fills the decoder's input, then ``idd_iters`` rounds of LDPC decode and detector / decoder
+    exchange (``cpx_mimo_idd_exchange_dev``) follow.  ``idd_decision``: 'hard' takes the sign of the final LLRs, 'decode' one more
+    LDPC decode of them; the first k bits of each block are counted.  ``idd_iters=0`` is the one-pass link.
+    The exchange subtracts the decoder's extrinsic LLRs unclipped (links.py:404) while the detector reads them clipped to
+    ``idd_clip``: a clip below the extrinsic magnitudes (min-sum sums reach several times the decoder's own 500) makes the
+    detector's output disagree with the decoder by the difference, and the default 500 then loses to one pass on this link;
+    ``idd_clip=float('inf')`` keeps ``posterior - ext`` the detector's extrinsic.
+
     Refusals (``ValueError``, before anything is launched): other detector / code combinations, a real channel, a shape the
     detector refuses, a ``send_chunk`` that does not fill whole vectors (or whole codewords).
     """
 
     def __init__(self, modem, channel, detector='kbest', K=16, output_type='hard', stack_size=(1, 3, 5), llr_max=500,
-                 ldpc_params=None, ldpc_alg='MSA', ldpc_iters=15, send_chunk=720, seed=1):
+                 ldpc_params=None, ldpc_alg='MSA', ldpc_iters=15, send_chunk=720, seed=1, idd_iters=0, idd_clip=500.0,
+                 idd_decision='decode'):
         self.modem, self.channel = modem, channel
         self.detector, self.output_type = detector, output_type
         self.K, self.llr_max = int(K), float(llr_max)
         self.seed = int(seed)
         self.ldpc_params, self.ldpc_iters = ldpc_params, int(ldpc_iters)
-        self._plan(detector, output_type, stack_size, ldpc_params, ldpc_alg, send_chunk)
+        self._plan(detector, output_type, stack_size, ldpc_params, ldpc_alg, send_chunk, idd_iters, idd_clip, idd_decision)
         self.tx_batch = max(1, _VECTORS_PER_LAUNCH // self.vectors_per_tx)
-        self.keep_rx = False               # tests: keep the last batch's y, H, detector output and messages (self.last_rx)
+        self.keep_rx = False               # tests: keep the last batch's y, H, detector output and messages (self.last_rx);
+                                           # an IDD link also keeps its final LLRs and the candidate list
         self.last_rx = None
         self._calls = 0
         self._bufs = {}
@@ -360,9 +373,10 @@ class DeviceMimoLink:
             self._code = _device_code(ldpc_params)
 
     # -- the plan: every check that needs no device ------------------------------------------------------------------------------
-    def _plan(self, detector, output_type, stack_size, ldpc_params, ldpc_alg, send_chunk):
+    def _plan(self, detector, output_type, stack_size, ldpc_params, ldpc_alg, send_chunk, idd_iters=0, idd_clip=500.0,
+              idd_decision='decode'):
         from commpy_amd.channels import MIMOFlatChannel
-        from commpy_amd.modulation import _bf_stacks
+        from commpy_amd.modulation import _bf_stacks, _list_checks
         if not isinstance(self.channel, MIMOFlatChannel):
             raise ValueError('DeviceMimoLink needs a MIMOFlatChannel')
         _require_complex(self.channel)
@@ -377,6 +391,14 @@ class DeviceMimoLink:
             raise ValueError("detector %r with output %r %s an LDPC code is not a device MIMO link: uncoded links take 'ml' or "
                              "'kbest' with 'hard' output, coded ones 'kbest' with 'soft' output or 'best_first'"
                              % (detector, output_type, 'and' if self.coded else 'without'))
+        self.idd_iters, self.idd_clip, self.idd_decision = _whole(idd_iters), float(idd_clip), idd_decision
+        if self.idd_iters < 0:
+            raise ValueError('idd_iters must be 0 (one detection pass) or a positive number of rounds')
+        if self.idd_iters:
+            if not (self.coded and detector == 'kbest' and output_type == 'soft'):
+                raise ValueError("iterative detection and decoding needs an LDPC code and detector='kbest' with output_type='soft'")
+            if idd_decision not in ('hard', 'decode'):
+                raise ValueError("idd_decision must be 'hard' or 'decode'")
         self.stacks = None
         if detector == 'ml':
             if nb * nt > 31:
@@ -390,6 +412,9 @@ class DeviceMimoLink:
                 raise ValueError('kbest: K must be a positive integer')
             if min(self.K, m ** nt) * m >= 2 ** 31:
                 raise ValueError('kbest: K * m above 2^31 children')
+            if self.idd_iters:
+                _list_checks(self.modem, self.K, self.idd_clip, nr, nt)
+                self.Ke = min(self.K, m ** nt)
         else:
             self.stacks = _bf_stacks(nr, nt, stack_size)
             if nr > 64:
@@ -435,6 +460,8 @@ class DeviceMimoLink:
             B = T * self.codewords_per_tx
             bufs.update(code=DeviceBuf(B * self.n), llr=DeviceBuf(B * self.n * 8), dec=DeviceBuf(B * self.n),
                         out=DeviceBuf(B * self.n * 8), blk_errs=DeviceBuf(B * 4))
+            if self.idd_iters:
+                bufs.update(cand=DeviceBuf(V * self.Ke * self.nt * 4), count=DeviceBuf(V * 4), dist=DeviceBuf(V * self.Ke * 8))
         else:
             bufs['idx'] = DeviceBuf(V * self.nt * 4)
         return bufs
@@ -443,7 +470,8 @@ class DeviceMimoLink:
     def run_batch(self, snr_db, T, mark=None):
         """Bit errors per transmission (int32 ``[T]``) of ``T`` transmissions at ``snr_db``; every call draws from fresh
         streams.  ``mark(stage, start)`` (benchmarks) is called around the stages 'source' (bits, encoder), 'channel', 'detector',
-        'decoder' (coded links) and 'count'."""
+        'decoder' (coded links) and 'count'; an IDD link has 'list' (search, distances, first pass) and 'idd' (the rounds) in place of
+        'detector', and 'decoder' only for the 'decode' decision."""
         T = _whole(T)
         if T < 1:
             raise ValueError('T must be at least 1')
@@ -466,6 +494,8 @@ class DeviceMimoLink:
         ck(lib.cpx_mimo_channel_run_dev(self._chan.get(), md, tx.ptr, V, 0, noise_std * 0.5, self.seed, s_fade, s_noise,
                                         bufs['y'].ptr, bufs['h'].ptr, None))
         mark('channel', False)
+        if self.idd_iters:
+            return self._run_idd(bufs, T, noise_std, snr_db, mark)
         mark('detector', True)
         if self.detector == 'ml':
             ck(lib.cpx_mimo_ml_dev(md, bufs['y'].ptr, bufs['h'].ptr, 1, V, nr, nt, bufs['idx'].ptr, None))
@@ -510,6 +540,50 @@ class DeviceMimoLink:
                 rx['tx'] = rx['msg']
                 rx['idx'] = bufs['idx'].to_array((V, nt), np.int32)
             self.last_rx = rx
+        return errs
+
+    def _run_idd(self, bufs, T, noise_std, snr_db, mark):
+        """The receiver of an IDD link on the batch the channel left in ``bufs``: links.py:396-405 with the list detector as
+        ``detector`` and the LDPC decoder's out_llrs as ``decoder``, every buffer block-major on the device."""
+        lib, ck = self.lib, _lib.check
+        md = self.modem._device_handle()
+        V, nr, nt, Ke, B = T * self.vectors_per_tx, self.nr, self.nt, self.Ke, T * self.codewords_per_tx
+        nv, clip = noise_std ** 2, self.idd_clip
+        y, h, a, out = bufs['y'].ptr, bufs['h'].ptr, bufs['llr'].ptr, bufs['out'].ptr
+        cand, count, dist = bufs['cand'].ptr, bufs['count'].ptr, bufs['dist'].ptr
+        mark('list', True)
+        ck(lib.cpx_kbest_list_dev(md, y, h, 1, V, nr, nt, self.K, cand, count, None))
+        ck(lib.cpx_mimo_list_dist_dev(md, y, h, 1, V, nr, nt, cand, count, Ke, dist, None))
+        ck(lib.cpx_mimo_list_llr_dev(md, cand, count, dist, V, nt, Ke, None, nv, clip, a, None))
+        mark('list', False)
+        mark('idd', True)
+        for it in range(self.idd_iters):
+            ck(lib.cpx_ldpc_bp_decode_batch_bm_dev(self._code, a, B, self.alg, self.ldpc_iters, bufs['dec'].ptr, out, None, None))
+            ck(lib.cpx_mimo_idd_exchange_dev(md, cand, count, dist, V, nt, Ke, a, out, nv, clip, int(it == self.idd_iters - 1), None))
+        mark('idd', False)
+        final = None
+        if self.keep_rx:                           # the last decode clips its input in place: keep what the loop gave
+            final = DeviceBuf(B * self.n * 8)
+            ck(lib.cpx_memcpy_d2d_async(final.ptr, a, B * self.n * 8, None))
+        if self.idd_decision == 'decode':
+            mark('decoder', True)
+            ck(lib.cpx_ldpc_bp_decode_batch_bm_dev(self._code, a, B, self.alg, self.ldpc_iters, bufs['dec'].ptr, out, None, None))
+            mark('decoder', False)
+        else:
+            ck(lib.cpx_mimo_llr_hard_dev(a, B * self.n, bufs['dec'].ptr, None))
+        mark('count', True)
+        ck(lib.cpx_count_errors_dev(bufs['msg'].ptr, self.k, bufs['dec'].ptr, self.n, B, 1, self.k, bufs['blk_errs'].ptr, None))
+        mark('count', False)
+        ck(lib.cpx_stream_sync(None))
+        errs = bufs['blk_errs'].to_array((T, self.codewords_per_tx), np.int32).sum(axis=1, dtype=np.int32)
+        if self.keep_rx:
+            self.last_rx = {
+                'snr_db': float(snr_db), 'noise_std': noise_std, 'msg': bufs['msg'].to_array((T, self.send_chunk), np.uint8),
+                'y': bufs['y'].to_array((V, nr), np.complex128), 'h': bufs['h'].to_array((V, nr, nt), np.complex128),
+                'errs': errs.copy(), 'tx': bufs['code'].to_array((T, self.tx_bits), np.uint8),
+                'idd_llr': final.to_array((V, nt * self.nb), np.float64), 'dec': bufs['dec'].to_array((B, self.n), np.int8),
+                'cand': bufs['cand'].to_array((V, Ke, nt), np.int32), 'count': bufs['count'].to_array((V,), np.int32)}
+            final.free()
         return errs
 
     # -- sweeps ----------------------------------------------------------------------------------------------------------------

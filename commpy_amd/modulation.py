@@ -6,6 +6,8 @@ the host; ``demodulate`` ('hard' and 'soft') runs on the GPU through ``cpx_demod
 ``cpx_demod_soft`` (csrc/demod.hip).  The MIMO detectors ``mimo_ml`` and ``kbest`` (modulation.py:299-406) run on the
 GPU too (csrc/mimo.hip), with batched forms ``mimo_ml_batch`` / ``kbest_batch`` for throughput; The soft-output
 ``best_first_detector`` (modulation.py:422-565) runs on the GPU as well, with ``best_first_batch`` as its batched form.
+``list_apriori_batch`` is a max-log list detector that takes a-priori LLRs (csrc/mimo_idd.hip), ``apriori_detector`` its form
+for ``links.idd_decoder``.
 ``max_log_approx`` and ``bit_lvl_repr`` are small host functions.  ``ofdm_tx`` / ``ofdm_rx`` (modulation.py:265-296) run on the
 GPU too (csrc/ofdm.hip), float64 only, with the symbol-major batched forms ``ofdm_tx_batch`` / ``ofdm_rx_batch``.
 """
@@ -19,7 +21,7 @@ from commpy_amd import _lib
 from commpy_amd.utilities import signal_power
 
 __all__ = ['PSKModem', 'QAMModem', 'Modem', 'mimo_ml', 'kbest', 'max_log_approx', 'bit_lvl_repr', 'mimo_ml_batch',
-           'kbest_batch', 'best_first_detector', 'best_first_batch', 'ofdm_tx', 'ofdm_rx', 'ofdm_tx_batch', 'ofdm_rx_batch']
+           'kbest_batch', 'best_first_detector', 'best_first_batch', 'list_apriori_batch', 'apriori_detector', 'ofdm_tx', 'ofdm_rx', 'ofdm_tx_batch', 'ofdm_rx_batch']
 
 
 def _gray_rank(m):
@@ -346,6 +348,80 @@ def best_first_batch(y, h, modem, stack_size, llr_max, labels=None):
     [B, nr * num_bits_symbol] with the bits of ``labels`` ([m, num_bits_symbol] 0/1, default: the modem's labels, what
     ``demode = modem.demodulate(., 'hard')`` gives); a row of NaN marks a vector that reached no leaf."""
     return _best_first(y, h, modem, stack_size, llr_max, labels)
+
+
+LIST_MAX_BITS = 64        # bits per vector the list detector carries (one lane each, mimo_idd.hip)
+LIST_MAX_KE = 4064        # candidates whose costs and labels fit the kernel's LDS
+
+
+def _list_checks(modem, K, llr_clip, nr=None, nt=None):
+    """The refusals of the list detector that need no device (the engine repeats them): ``(K, llr_clip)`` as int and float."""
+    K, clip = operator.index(K), float(llr_clip)
+    if K < 1:
+        raise ValueError('K must be a positive integer')
+    if not clip > 0:
+        raise ValueError('llr_clip must be positive (got %r)' % (llr_clip,))
+    if modem.m != 1 << modem.num_bits_symbol:
+        raise ValueError('the modem must have 2^num_bits_symbol points')
+    if nt is not None:
+        if nt > nr:
+            raise ValueError('h has more columns than rows')
+        if nt * modem.num_bits_symbol > LIST_MAX_BITS:
+            raise ValueError('%d x %d bits per vector above the list detector\'s %d' % (nt, modem.num_bits_symbol, LIST_MAX_BITS))
+        ke = min(K, modem.m ** nt)
+        if ke > LIST_MAX_KE:
+            raise ValueError('a list of %d candidates exceeds the list detector\'s %d' % (ke, LIST_MAX_KE))
+        if ke * modem.m >= 2 ** 31:
+            raise ValueError('kbest: K * m above 2^31 children')
+    return K, clip
+
+
+def list_apriori_batch(y, h, modem, K, noise_var, a_priori=None, llr_clip=500.0):
+    """Max-log list detection with a-priori LLRs of every row of ``y [B, nr]``; ``h`` is [nr, nt] or [B, nr, nt].  Returns the
+    posterior LLRs ``[B, nt * num_bits_symbol]`` (positive: bit 0; the modem's labels, MSB first, antenna after antenna).
+
+    The candidate list is ``kbest``'s final list (K-best search on the channel metric, on the device; the priors do not steer the
+    search -- list sphere detection).  With ``La`` = ``a_priori`` clipped to ``[-llr_clip, llr_clip]`` (None: zeros), the cost of a
+    candidate is ``|y - h x|^2 / (2 noise_var) + sum of La over its bits 1`` and the LLR of a bit the minimum cost with that bit 1
+    minus the minimum with it 0, clipped to ``[-llr_clip, llr_clip]``; a bit value no candidate carries counts as +inf.
+    ``K >= m^nt`` keeps every hypothesis: the exhaustive max-log MAP detector.  ``a_priori=None`` and ``llr_clip=inf`` give
+    ``kbest_batch(..., 'soft')`` bit for bit.  A NaN in a vector's y, h or prior makes that vector's LLRs NaN."""
+    from commpy_amd.deviceops import _OneShot
+    y2, hh, hb, B, nr, nt = _mimo_inputs(y, h)
+    K, clip = _list_checks(modem, K, llr_clip, nr, nt)
+    nbt = nt * modem.num_bits_symbol
+    noise_var = float(noise_var)
+    if not 0.0 < noise_var < np.inf:
+        raise ValueError('noise_var must be positive and finite, got %r' % noise_var)
+    prior = None
+    if a_priori is not None:
+        prior = np.ascontiguousarray(a_priori, dtype=np.float64)
+        if prior.shape != (B, nbt):
+            raise ValueError('a_priori must be [%d, %d], got %s' % (B, nbt, prior.shape))
+    if B == 0:
+        return np.zeros((0, nbt))
+    ke = min(K, modem.m ** nt)
+    md = modem._device_handle()
+    with _OneShot() as dev:
+        lib, ck = dev.lib, _lib.check
+        d_y, d_h = dev.upload(y2), dev.upload(hh)
+        d_cand, d_count, d_dist, d_llr = dev.alloc(B * ke * nt * 4), dev.alloc(B * 4), dev.alloc(B * ke * 8), dev.alloc(B * nbt * 8)
+        ck(lib.cpx_kbest_list_dev(md, d_y, d_h, hb, B, nr, nt, K, d_cand.ptr, d_count.ptr, None))
+        ck(lib.cpx_mimo_list_dist_dev(md, d_y, d_h, hb, B, nr, nt, d_cand.ptr, d_count.ptr, ke, d_dist.ptr, None))
+        ck(lib.cpx_mimo_list_llr_dev(md, d_cand.ptr, d_count.ptr, d_dist.ptr, B, nt, ke, None if prior is None else dev.upload(prior),
+                                     noise_var, clip, d_llr.ptr, None))
+        return dev.download(d_llr, (B, nbt), np.float64)
+
+
+def apriori_detector(modem, K, llr_clip=500.0):
+    """``detector(y, h, constellation, noise_var, a_priori)`` for ``links.idd_decoder``: ``list_apriori_batch`` on one vector.
+    The bits are ``modem``'s labels; ``constellation`` is what ``LinkModel`` passes along and is not read."""
+    K, llr_clip = _list_checks(modem, K, llr_clip)
+
+    def detector(y, h, constellation, noise_var, a_priori):
+        return list_apriori_batch(np.asarray(y).reshape(1, -1), np.asarray(h), modem, K, noise_var,
+                                  np.asarray(a_priori, dtype=np.float64).reshape(1, -1), llr_clip)[0]
+    return detector
 
 
 def max_log_approx(y, h, noise_var, pts_list, demode):

@@ -415,6 +415,42 @@ int cpx_best_first_dev(const cpx_modem *m, const double *d_y_re_im, const double
                        int nt, const int32_t *stack_size, double llr_max, const uint8_t *d_labels, double *d_llr,
                        int32_t *d_iters, void *stream);
 
+/* ---- list detection with a-priori LLRs, iterative detection and decoding (csrc/mimo_idd.hip) -------------------------------
+ * A max-log soft MIMO detector over a candidate list that accepts priors, and the detector / decoder exchange of
+ * commpy/links.py:345-407 (idd_decoder) on device buffers.  The list -- cand [B][Ke][nt] int32 constellation indices and count [B],
+ * exactly what cpx_kbest_list writes -- is searched once on the channel metric; the priors reweigh it, they do not re-run the
+ * tree search.  float64 only: cpx_set_precision is ignored and there is no path switch.  Bits are the modem's labels, MSB first,
+ * antenna after antenna; an LLR is positive for bit 0.
+ *   cpx_mimo_list_dist  dist [B][Ke] = norm(y - H x_c)^2 of every candidate (+inf past count[b]), summed as cpx_kbest_soft sums it:
+ *                       per receive antenna r ascending, hx = 0 + sum_t H[r][t] x[t] (t ascending), s = 0 + sum_r |y_r - hx|^2,
+ *                       sqrt(s) squared.  One thread per candidate: the order depends on nothing else.
+ *   cpx_mimo_list_llr   with La_k = the prior clipped to [-clip, clip] (null: no prior) and S_c = the sum of La_k over the bits 1 of
+ *                       candidate c (k ascending), cost_c = dist_c + 2 noise_var S_c and
+ *                       llr_k = -(min_{c: b_k = 0} cost_c - min_{c: b_k = 1} cost_c) / (2 noise_var), clipped to [-clip, clip]; a bit
+ *                       value no candidate carries counts as +inf (llr = +-clip).  This is min_{b_k = 1} - min_{b_k = 0} of
+ *                       dist_c / (2 noise_var) + S_c, scaled by 2 noise_var so that a null or zero prior with clip = inf reproduces
+ *                       cpx_kbest_soft bit for bit.  A NaN in a vector's y, H or prior makes all LLRs of that vector NaN.
+ *   cpx_mimo_idd_exchange_dev   one IDD round in one launch: ext = dec_out - dec_in (the decoder's extrinsic LLRs),
+ *                       post = the detector above with prior ext, dec_in <- post - ext (last != 0: dec_in <- post, what the
+ *                       decision receives).  dec_in is the block-major buffer cpx_ldpc_bp_decode_batch_bm_dev clipped in place,
+ *                       dec_out its out_llrs; both [B][nt nbits] seen per vector.
+ *   cpx_mimo_llr_hard_dev       bits[i] = signbit(llr[i]) (int8), the hard decision on final LLRs.
+ * CPX_EINVAL: clip <= 0 or NaN, noise_var not positive and finite, Ke < 1, a null pointer with B > 0, a modem without 2^nbits points; CPX_ELIMIT:
+ * nt * nbits > 64 bits per vector, or a list whose costs and labels exceed 64 KB of LDS (Ke > 4064).  Ke is the row count of
+ * cand, min(K, m^nt) for a list from cpx_kbest_list.  cpx_last_kernel names what ran. */
+int cpx_mimo_list_dist(const cpx_modem *m, const double *y_re_im, const double *h_re_im, int h_batched, int64_t B, int nr, int nt,
+                       const int32_t *cand, const int32_t *count, int Ke, double *dist);
+int cpx_mimo_list_dist_dev(const cpx_modem *m, const double *d_y_re_im, const double *d_h_re_im, int h_batched, int64_t B, int nr,
+                           int nt, const int32_t *d_cand, const int32_t *d_count, int Ke, double *d_dist, void *stream);
+int cpx_mimo_list_llr(const cpx_modem *m, const int32_t *cand, const int32_t *count, const double *dist, int64_t B, int nt, int Ke,
+                      const double *prior_or_null, double noise_var, double clip, double *llr);
+int cpx_mimo_list_llr_dev(const cpx_modem *m, const int32_t *d_cand, const int32_t *d_count, const double *d_dist, int64_t B, int nt,
+                          int Ke, const double *d_prior_or_null, double noise_var, double clip, double *d_llr, void *stream);
+int cpx_mimo_idd_exchange_dev(const cpx_modem *m, const int32_t *d_cand, const int32_t *d_count, const double *d_dist, int64_t B,
+                              int nt, int Ke, double *d_dec_in_inout, const double *d_dec_out, double noise_var, double clip,
+                              int last, void *stream);
+int cpx_mimo_llr_hard_dev(const double *d_llr, int64_t n, int8_t *d_bits, void *stream);
+
 /* ---- MIMO link stages on the device ---------------------------------------------------
  * The MIMO flat-fading channel of commpy/channels.py:242-330 (MIMOFlatChannel.propagate, Kronecker model) and the hard-decision
  * error count of a MIMO link, so that a Monte-Carlo MIMO point never leaves HBM.  Device pointers, asynchronous on `stream`.

@@ -133,6 +133,26 @@ __device__ __forceinline__ void bit_metrics_cw(int type, double r, double &m0, d
     }
 }
 
+// The fused kernel's form of the 'soft' clip and metrics (cw_step<..., LEAN = true>): the same values with fewer instructions.
+//  * clip: fmin(fmax(r, -500), 500) compiles to three instructions -- the kernels run in IEEE mode (the code object's kernel descriptor
+//    has ieee_mode = 1, dx10_clamp = 1), where v_max_f64 / v_min_f64 turn a SIGNALLING NaN operand into a quiet NaN instead of returning
+//    the other operand, so the compiler quiets r first (v_max_f64 r, r).  For every number and for a quiet NaN -- what NumPy, torch and
+//    the engine's own generators produce -- the two instructions below return the same value: r clipped, NaN -> -500 (v_max_f64 returns
+//    the non-NaN operand).  A signalling NaN comes out as +500 instead of -500; that value is never seen: nan_or flags the codeword
+//    (v_cmp_u_f64 is true for either kind of NaN) and the NaN-exact redo launch decodes it again and overwrites all of its bits; the clip
+//    only has to keep the arithmetic of the discarded pass finite.  The constants sit in scalar registers, as the compiler keeps them.
+//  * exp_pm500 / fast_log<false, false, true>: cpx_math.h, bit-identical on the clipped range.
+__device__ __forceinline__ double clip500(double r) {
+    double c;
+    asm("v_max_f64 %0, %1, %2\n\tv_min_f64 %0, %0, %3" : "=&v"(c) : "v"(r), "s"(-500.0), "s"(500.0));
+    return c;
+}
+__device__ __forceinline__ void soft_metrics_lean(double r, double &m0, double &m1) {
+    const double nll0 = fast_log<false, false, true>(exp_pm500(r) + 1.0);   // |r| <= 500: the argument is finite and >= 1
+    m0 = nll0;
+    m1 = nll0 - r;
+}
+
 // One traceback hop: the decision bit of state st is bit 63 - st of the step's word, i.e. the top bit of (w << st)
 // (v_lshlrev_b64 uses the low 6 bits of st only); st' = (st << 1) | bit in one v_alignbit_b32.  The high bits of st are
 // never masked on the way -- only st mod S is meaningful (for S < 64 the shift amount is masked explicitly).
@@ -158,23 +178,40 @@ struct NoHook {
 // so one 2-bit number per butterfly describes the code; it arrives packed in scalar registers (goff) and selects the branch metric by
 // VGPR index mode (round 5, see the GEN branch below; rounds 3 / 4: an LDS table [4][64 lanes] of pairs (metric of c, metric of c ^ 3) and
 // every butterfly reads its pair from there: 32 16-byte LDS reads + 32 address adds per step more than the compiled-in codes.
-template <int LGS, unsigned G0, unsigned G1, int TYPE, int R, class Hook = NoHook>
+// LEAN (the fused kernel): clip500 / soft_metrics_lean above, and the branch metrics without the leading "0.0 +" of NumPy's add.reduce.
+// Adding +0.0 changes exactly one value, -0.0 (to +0.0; a NaN stays the NaN it was: the per-bit metrics are results of arithmetic,
+// already quiet), and no per-bit metric is ever -0.0: 'hard' converts an integer (never -0.0), 'unquantized' takes a square (sign +),
+// 'soft' m0 = log(x), x >= 1, ends in a subtraction a - b that is -0.0 only for a = -0.0, b = +0.0 -- a = dk ln2_hi is +0.0 or >= 0.69 --
+// and m1 = m0 - r is -0.0 only for m0 = -0.0 (x - x is +0.0 in round-to-nearest).  The other kernels keep the literal form.
+template <int LGS, unsigned G0, unsigned G1, int TYPE, int R, bool LEAN = false, class Hook = NoHook>
 __device__ __forceinline__ void cw_step(double (&pm)[1 << LGS], double r0, double r1, unsigned long long &word, int &best,
                                         const Hook &hook = Hook(), unsigned char *bml = nullptr, const unsigned *gidx = nullptr) {
     constexpr int type = TYPE;
     using C = SrCode<LGS, G0, G1>;
     constexpr bool GEN = G0 == 0 && G1 == 0;
     constexpr int S = 1 << LGS, H = S / 2;
-    if (type == CPX_VIT_SOFT) {                                    // coded_bits.clip(-500, 500) (:719)
-        r0 = fmin(fmax(r0, -500.0), 500.0);
-        r1 = fmin(fmax(r1, -500.0), 500.0);
-    }
     double m00, m01, m10, m11;
-    bit_metrics_cw(type, r0, m00, m01);
-    bit_metrics_cw(type, r1, m10, m11);
+    if constexpr (LEAN && TYPE == CPX_VIT_SOFT) {                  // coded_bits.clip(-500, 500) (:719)
+        r0 = clip500(r0);
+        r1 = clip500(r1);
+        soft_metrics_lean(r0, m00, m01);
+        soft_metrics_lean(r1, m10, m11);
+    } else {
+        if (type == CPX_VIT_SOFT) {
+            r0 = fmin(fmax(r0, -500.0), 500.0);
+            r1 = fmin(fmax(r1, -500.0), 500.0);
+        }
+        bit_metrics_cw(type, r0, m00, m01);
+        bit_metrics_cw(type, r1, m10, m11);
+    }
     double bmv[4];                                                 // NumPy add.reduce, n < 8: sequential from 0
-    bmv[0] = (0.0 + m00) + m10; bmv[1] = (0.0 + m00) + m11;
-    bmv[2] = (0.0 + m01) + m10; bmv[3] = (0.0 + m01) + m11;
+    if constexpr (LEAN) {
+        bmv[0] = m00 + m10; bmv[1] = m00 + m11;
+        bmv[2] = m01 + m10; bmv[3] = m01 + m11;
+    } else {
+        bmv[0] = (0.0 + m00) + m10; bmv[1] = (0.0 + m00) + m11;
+        bmv[2] = (0.0 + m01) + m10; bmv[3] = (0.0 + m01) + m11;
+    }
     unsigned da = 0, db = 0;                                       // decisions of states 0..H-1 / H..S-1
     hook.template at<0>();
     auto butterfly = [&](int j, double m_a0, double m_a1, double m_b0, double m_b1) {
@@ -371,7 +408,7 @@ __device__ __forceinline__ void bit_metrics_f32(int type, double r, float &m0, f
     }
 }
 
-template <int LGS, unsigned G0, unsigned G1, int TYPE, int R, class Hook = NoHook>
+template <int LGS, unsigned G0, unsigned G1, int TYPE, int R, bool LEAN = false, class Hook = NoHook>   // (LEAN: float64 only, ignored here)
 __device__ __forceinline__ void cw_step(float (&pm)[1 << LGS], double r0, double r1, unsigned long long &word, int &best,
                                         const Hook &hook = Hook(), unsigned char * = nullptr, const unsigned * = nullptr) {
     using C = SrCode<LGS, G0, G1>;
@@ -632,30 +669,52 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
     walk.hr = H;
 
     // writes the decoded bits staged in tile entries 0 .. n-1: entry li holds the result of the walk of step tc0 + li - 1,
-    // i.e. output step tc0 + li - 1 - H
+    // i.e. output step so = tc0 + li - 1 - H, and is written when 1 <= so <= min(T - H, L).  Those bounds are wave-uniform, so the
+    // entries to write are one range [lo, hi) per flush, worked out on the scalar unit; a lane's two entries (lane, lane + 64) get one
+    // predicate each per flush instead of five terms per store, and a store's address is a scalar row pointer (advanced by L per
+    // codeword) plus a 32-bit lane offset.  (Before: 64-bit vector index arithmetic and the whole predicate in front of each of the 128
+    // byte stores, ~220 instructions per round of eight codewords.)
+    const int so_max = (int)((p.L < (int64_t)(T - H)) ? p.L : (int64_t)(T - H));   // last output step the flushes write (may be < 1)
     auto flush = [&](int tc0, int n) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         // the tile rows are complete (same wave wrote them)
         const int64_t cwb = grp * 64;
         const int ncw = (int)((p.B - cwb < 64) ? (p.B - cwb) : 64);
-        // eight codewords per round: their LDS reads are all in flight before the first store waits for one (one codeword
-        // per round put an LDS round trip in front of every store: ~19 k cycles per 96 steps, 5 % of the kernel)
-        for (int c0 = 0; c0 < 64; c0 += 8) {
-            unsigned char v[8][2];
+        const int so0 = tc0 - 1 - H;                                               // output step of entry 0
+        const int lo = so0 >= 1 ? 0 : 1 - so0;
+        const int hi = (so_max - so0 + 1 < n) ? so_max - so0 + 1 : n;
+        if (lo < hi) {
+            const bool w0 = lane >= lo && lane < hi, w1 = lane + 64 >= lo && lane + 64 < hi;
+            const unsigned o0 = (unsigned)(lane - lo), o1 = o0 + 64u;              // byte offsets from entry lo (used where w0 / w1 hold)
+            const int l1 = (lane + 64 < FR_OBPAD) ? lane + 64 : FR_OBPAD - 1;      // entries >= n are never written: read inside the row
+            unsigned char *row = p.bits + cwb * p.L + (so0 + lo - 1);              // entry lo of the group's first codeword
+            // eight codewords per round: their LDS reads are all in flight before the first store waits for one (one codeword
+            // per round put an LDS round trip in front of every store: ~19 k cycles per 96 steps, 5 % of the kernel)
+            for (int c0 = 0; c0 < ncw; c0 += 8) {
+                unsigned char v[8][2];
 #pragma unroll
-            for (int u = 0; u < 8; u++)
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const int li = lane + 64 * h;
-                    v[u][h] = (li < n) ? obuf[(c0 + u) * FR_OBPAD + li] : (unsigned char)0;
+                for (int u = 0; u < 8; u++) {
+                    v[u][0] = obuf[(c0 + u) * FR_OBPAD + lane];
+                    v[u][1] = obuf[(c0 + u) * FR_OBPAD + l1];
                 }
+                if (c0 + 8 <= ncw) {                                               // (always, but for the batch's last group)
+                    if (w0) {
 #pragma unroll
-            for (int u = 0; u < 8; u++)
+                        for (int u = 0; u < 8; u++) row[(int64_t)u * p.L + o0] = v[u][0];
+                    }
+                    if (w1) {
 #pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const int li = lane + 64 * h, so = tc0 + li - 1 - H;
-                    if (c0 + u < ncw && li < n && so >= 1 && so <= T - H && so - 1 < p.L)
-                        p.bits[(cwb + c0 + u) * p.L + so - 1] = v[u][h];
+                        for (int u = 0; u < 8; u++) row[(int64_t)u * p.L + o1] = v[u][1];
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 8; u++)
+                        if (c0 + u < ncw) {
+                            if (w0) row[(int64_t)u * p.L + o0] = v[u][0];
+                            if (w1) row[(int64_t)u * p.L + o1] = v[u][1];
+                        }
                 }
+                row += 8 * p.L;
+            }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         // tile read before the next chunk overwrites it
     };
@@ -680,7 +739,7 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
                 unsigned long long word;
                 int bst;
                 if constexpr (TYPE == CPX_VIT_SOFT) nan_or(nanmask, cur[R].x, cur[R].y);   // (steps > tmax re-read step tmax)
-                cw_step<LGS, G0, G1, TYPE, R>(pm, r0, r1, word, bst, walk, nullptr, gidx);   // + hops 0 .. 3/4 H of the walk of step tt - 1
+                cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, walk, nullptr, gidx);   // + hops 0 .. 3/4 H of the walk of step tt - 1
                 walk.finish();
                 myrow[g * LGS + R] = (unsigned char)((walk.st >> (LGS - 1)) & 1u);   // input bit of the branch into the state at step tt - 1 - H
                 // ring slot of step tt and (mirrored ring) its copy RING slots above; the (at most LGS - 1) steps > T of the last group

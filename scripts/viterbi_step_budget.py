@@ -5,7 +5,16 @@
 
 Disassembles commpy_amd/csrc/build/viterbi_cw.o (device part, gfx950), finds the kernel's step loop (the smallest backward branch that spans
 a whole trellis step), counts the steps of one trip of it by the first-equal scans it contains (64 v_cmp_eq_f64 per step) and
-sorts every instruction of the loop body into the phases of cw_step (csrc/viterbi_cw.hip) by opcode -- the table of DESIGN.md 4.1."""
+sorts every instruction of the loop body into the phases of cw_step (csrc/viterbi_cw.hip) by opcode -- the table of DESIGN.md 4.1.
+
+Two more tables:
+* the same instructions BY POSITION in the step.  The fused kernel pins the four batches of traceback LDS reads between the phases of
+  cw_step (WalkHook::at, sched_barrier), and a step ends with the byte it stores into the output tile, so the read batches cut a step
+  into: LLR -> branch metrics | butterflies, first half | second half | minimum tree | first-equal scan and the step's tail.  The
+  traceback's own instructions (hops, LDS, waits for LDS) are listed apart wherever they sit.  An opcode table cannot tell the
+  v_add_f64 of exp / log from those of the add-compare-select; this one can.
+* the code of a 96-step chunk OUTSIDE the hot loop: the loop around it (chunk set-up, the pending walk of the last chunk) and, inside
+  that, the rounds of the output flush (eight codewords each, eight rounds per flush), as static instruction counts."""
 import argparse
 import collections
 import os
@@ -73,6 +82,71 @@ def classify(op, args):
     return "other (" + op + ")"
 
 
+TRACEBACK = ("v_lshlrev_b64", "v_alignbit_b32", "ds_", "s_waitcnt")
+PHASES = ["LLR -> branch metrics (clip, exp, log, sums; pad select, NaN detect, loads, the previous step's ring / tile addresses)",
+          "add-compare-select, butterflies 0 .. S/4 - 1", "add-compare-select, butterflies S/4 .. S/2 - 1",
+          "minimum tree", "first-equal scan, decision word, ring slot"]
+
+
+def position_table(loop, steps):
+    """Instructions per step by position: a step ends at its ds_write_b8 (output tile); inside it every batch of traceback reads
+    (ds_read* more than 20 instructions after the previous one) starts the next phase."""
+    cnt, tb = collections.Counter(), collections.Counter()
+    phase, since, nsteps = 0, 10 ** 6, 0
+    for _, op, args in loop:
+        if op.startswith("ds_read"):
+            if since > 20:
+                phase = min(phase + 1, len(PHASES) - 1)
+            since = 0
+        else:
+            since += 1
+        if op.startswith(TRACEBACK):
+            tb["traceback + tile: " + ("LDS" if op.startswith("ds_") else "s_waitcnt" if op.startswith("s_waitcnt") else "hops")] += 1
+        else:
+            cnt[phase] += 1
+        if op == "ds_write_b8":
+            phase, nsteps = 0, nsteps + 1
+    out = ["", "by position in the step (%d tile stores = steps found per trip):" % nsteps, "",
+           "| phase of cw_step, by position | instructions per trellis step |", "|---|---|"]
+    for ph in range(len(PHASES)):
+        out.append("| %s | %.1f |" % (PHASES[ph], cnt[ph] / steps))
+    for k in sorted(tb):
+        out.append("| %s | %.1f |" % (k, tb[k] / steps))
+    return out
+
+
+def chunk_table(body, addr, hot):
+    """Static counts of the per-chunk code around the hot loop `hot` = (first, last) and of the flush rounds inside it."""
+    def loops():
+        for i, (ad, op, args) in enumerate(body):
+            if op.startswith("s_cbranch") or op == "s_branch":
+                m = re.search(r"\+0x([0-9a-f]+)>\s*$", args)
+                j = addr.get(body[0][0] + int(m.group(1), 16)) if m else None
+                if j is not None and j < i:
+                    yield j, i
+    outer = min(((j, i) for j, i in loops() if j < hot[0] and i > hot[1]), key=lambda ji: ji[1] - ji[0], default=None)
+    out = ["", "per 96-step chunk, outside the hot loop (static counts; the hot loop runs 16 trips per chunk):", ""]
+    if outer is None:
+        return out + ["(no loop around the hot loop found)"]
+    rounds = [(j, i) for j, i in loops() if outer[0] <= j and i <= outer[1] and (i < hot[0] or j > hot[1]) and
+              any(o.startswith("global_store") for _, o, _ in body[j:i + 1])]
+    rnd = min(rounds, key=lambda ji: ji[1] - ji[0], default=None)
+    n_outer = outer[1] - outer[0] + 1 - (hot[1] - hot[0] + 1)
+    out += ["| block | instructions |", "|---|---|"]
+    if rnd:
+        seg = body[rnd[0]:rnd[1] + 1]
+        n_rnd = len(seg)
+        out.append("| flush, one round of eight codewords (x 8 per chunk): %d LDS reads, %d stores, %d branches | %d |" %
+                   (sum(o.startswith("ds_read") for _, o, _ in seg), sum(o.startswith("global_store") for _, o, _ in seg),
+                    sum(o.startswith(("s_cbranch", "s_branch")) for _, o, _ in seg), n_rnd))
+        out.append("| chunk set-up, flush set-up, the last chunk's pending walk | %d |" % (n_outer - n_rnd))
+        out.append("| **per chunk, every flush instruction executed** | **%d** = %.1f per trellis step |" %
+                   (n_outer - n_rnd + 8 * n_rnd, (n_outer - n_rnd + 8 * n_rnd) / 96.0))
+    else:
+        out.append("| all of it (no flush round loop found) | %d |" % n_outer)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernel", default=DEFAULT)
@@ -109,6 +183,7 @@ def main():
     for k, v in sorted(cnt.items(), key=lambda kv: -kv[1]):
         lines.append("| %s | %.1f |" % (k, v / steps))
     lines += ["| **all** | **%.1f** (vector ALU: %.1f) |" % (len(loop) / steps, valu / steps)]
+    lines += position_table(loop, steps) + chunk_table(body, addr, best)
     text = "\n".join(lines)
     print(text)
     if a.md:

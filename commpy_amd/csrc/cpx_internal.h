@@ -72,10 +72,42 @@ int workspace(hipStream_t stream, int slot, size_t bytes, void **out, bool *fres
         }                                       \
     } while (0)
 
-// codeword-per-lane Viterbi path (viterbi_cw.hip): true when it handled the call (*rc = status)
+// What the Viterbi dispatch needs to know about a trellis: worked out once, by cpx_trellis_create (viterbi.hip)
+struct TrellisClass {
+    int lgS = 0;                     // S = 1 << lgS
+    // feed-forward, k = 1: predecessor j of state s is ((s << 1) & (S - 1)) | j, its input s >> (lgS - 1) => arithmetic traceback
+    bool shift_register = false;
+    // ... of rate 1/2 and 4 .. 64 states, AND a linear code: g0, g1 = its generators in the kernel template's convention (bit lgS taps
+    // the input, viterbi_cw.hip SrCode); what the compiled-in pairs and the per-pair code objects are keyed by
+    bool linear_half = false;
+    unsigned g0 = 0, g1 = 0;
+    // ... of rate 1/2 and 4 .. 64 states whose butterflies have the form (c, c ^ 3, c ^ 3, c) -- both generators tap the input and the
+    // oldest register bit: the table-driven fused kernel (cw_step, G0 = G1 = 0).  goff: field j = 2 c_j of butterfly j
+    bool end_tap = false;
+    unsigned goff[4] = {0u, 0u, 0u, 0u};
+};
+
+// The codeword-per-lane path runs in rounds of one wavefront of 64 codewords per SIMD (65536 codewords on 256 CUs), each as long as a
+// full one; the state-per-lane kernels' time is proportional to the batch.  A round filled below 45 % is cheaper on the latter (config
+// 2: 54 us per 1000 codewords against 1.55 ms per round, break-even at 0.44 of a round -- scripts/micro/split_probe.py: 30 000
+// codewords 1.63 ms on the wave kernels, 1.53 ms as a round; 99 536: 3.59 ms as round + wave kernels, 3.01 as two rounds)
+inline int64_t viterbi_round() { return (int64_t)device_cus() * 4 * 64; }
+inline bool viterbi_round_pays(int64_t codewords, int64_t round) { return 20 * codewords >= 9 * round; }
+
+// codeword-per-lane Viterbi path (viterbi_cw.hip): what it launched, if anything
+enum class CwFlavour { none, mirrored, deep, lean, small, code_object, table, two_kernels };
+struct CwResult {
+    bool handled = false;            // false: the caller uses the state-per-lane kernels
+    int rc = CPX_OK;                 // handled: the call's status
+    CwFlavour flavour = CwFlavour::none;
+};
+// any_batch_size: take this path whatever the batch size (a chunk of the host-buffer pipeline: its round costs the same however full
+// it is and hides behind the next chunk's upload; the fused kernel -- and with it the precision mode -- then serves the host API exactly
+// as it serves the device API).  lean_ring: the 64-state built-in pairs take the ring stored once where that flavour exists ('soft',
+// default depth, float64): the caller runs a remainder beside the round(s).
 // nanflags ('soft' only, else null): [B] bytes, set to 1 for every codeword that received a NaN (viterbi.hip re-decodes those)
-bool viterbi_codeword_path(const ::cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L, int64_t T,
-                           int tb, int type, uint8_t *d_bits, uint8_t *nanflags, hipStream_t st, int *rc);
+CwResult viterbi_codeword_path(const ::cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L, int64_t T, int tb,
+                               int type, uint8_t *d_bits, uint8_t *nanflags, hipStream_t st, bool any_batch_size, bool lean_ring);
 
 // LDS-resident LDPC path (ldpc_resident.hip): true when it handled the call (*rc = status)
 int ldpc_resident_tables(::cpx_ldpc *c, const int32_t *row_ptr, const int32_t *row_pad, const int32_t *col_ptr,
@@ -133,8 +165,6 @@ inline int ldpc_forced_path() { return mode_of(Switch::ldpc_path); }
 // CPX_LDPC_SPA=exact: sum-product check rows always by the exact-order sequence (ldpc_dev.h)
 inline bool ldpc_spa_exact() { return mode_of(Switch::ldpc_spa) == 1; }
 
-void viterbi_lean_ring(bool on);   // thread-local: the next 64-state rounds of this thread take the unmirrored ring where that flavour exists
-void viterbi_prefer_cw(bool on);   // thread-local: the next dispatches of this thread take the codeword path whatever the batch size
 // cpx_viterbi_set_path / CPX_VITERBI_PATH: bit 0 wave only, bit 1 codeword path forced, bit 2 strict ("!": fail instead of
 // falling back), bit 3 two-kernel form even where the fused kernel applies, bit 4 general kernel (viterbi_generic.hip)
 inline int viterbi_path_flags() { return mode_of(Switch::viterbi_path); }
@@ -229,6 +259,7 @@ struct cpx_trellis {
     hipFunction_t spec_fn[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
     int spec_lg = 0;
     unsigned spec_g0 = 0, spec_g1 = 0;
+    cpx::TrellisClass cls;                                   // filled by cpx_trellis_create, read by the Viterbi dispatch
 };
 
 struct cpx_ldpc {

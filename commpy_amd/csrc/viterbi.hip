@@ -35,6 +35,7 @@
 #include <condition_variable>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace cpx;
@@ -634,6 +635,63 @@ int next_pow2(int v) {
 
 }  // namespace
 
+// What the dispatch reads from the handle (cpx_internal.h TrellisClass): one walk over the predecessor tables, at creation.
+static void classify(cpx_trellis *t) {
+    cpx::TrellisClass &c = t->cls;
+    while ((1 << c.lgS) < t->S) c.lgS++;
+    const int S = t->S, lg = c.lgS, H = S / 2;
+    if (!(t->I == 2 && t->k == 1 && lg >= 1)) return;
+    for (int s = 0; s < S; s++)
+        for (int j = 0; j < 2; j++)
+            if (t->pred_state[s * 2 + j] != (((s << 1) & (S - 1)) | j) || t->pred_input[s * 2 + j] != (s >> (lg - 1))) return;
+    c.shift_register = true;
+    if (t->n != 2 || lg < 2 || lg > 6) return;
+    // a linear code: the output of a unit register [input bit | predecessor state] is the generators' bit i ...
+    for (int i = 0; i <= lg; i++) {
+        const int pred = (1 << i) & (S - 1), b = (1 << i) >> lg;
+        const int code = t->pred_code[((pred >> 1) | (b << (lg - 1))) * 2 + (pred & 1)];
+        c.g0 |= (unsigned)((code >> 1) & 1) << i;
+        c.g1 |= (unsigned)(code & 1) << i;
+    }
+    // ... and every branch carries the parities of its register under them (the formula of SrCode::code, viterbi_cw.hip)
+    c.linear_half = true;
+    for (int s = 0; s < S; s++)
+        for (int j = 0; j < 2; j++) {
+            const unsigned reg = ((unsigned)(s >> (lg - 1)) << lg) | (unsigned)(((s << 1) & (S - 1)) | j);
+            const int want = ((__builtin_popcount(reg & c.g0) & 1) << 1) | (__builtin_popcount(reg & c.g1) & 1);
+            if (t->pred_code[s * 2 + j] != want) c.linear_half = false;
+        }
+    if (!c.linear_half) c.g0 = c.g1 = 0;
+    c.end_tap = true;
+    for (int j = 0; j < H && c.end_tap; j++) {
+        const int code = t->pred_code[j * 2 + 0];
+        c.end_tap = t->pred_code[j * 2 + 1] == (code ^ 3) && t->pred_code[(j + H) * 2 + 0] == (code ^ 3) && t->pred_code[(j + H) * 2 + 1] == code;
+        c.goff[j >> 3] |= (2u * (unsigned)code) << (4 * (j & 7));
+    }
+    if (!c.end_tap) for (unsigned &g : c.goff) g = 0u;
+}
+
+// The state-per-lane template of a trellis of 2 .. 64 states: calls f(lgS, I, SR) with its template arguments as integral constants
+// (SR: shift register => arithmetic traceback, no predecessor table lookups); false: no such template.
+template <class Fn>
+static bool with_wave_template(const cpx_trellis *t, Fn &&f) {
+    auto with_lg = [&](auto lg) {
+        if (t->I == 4) f(lg, std::integral_constant<int, 4>{}, std::false_type{});
+        else if (t->cls.shift_register) f(lg, std::integral_constant<int, 2>{}, std::true_type{});
+        else f(lg, std::integral_constant<int, 2>{}, std::false_type{});
+        return true;
+    };
+    switch (t->cls.lgS) {
+        case 1: return with_lg(std::integral_constant<int, 1>{});
+        case 2: return with_lg(std::integral_constant<int, 2>{});
+        case 3: return with_lg(std::integral_constant<int, 3>{});
+        case 4: return with_lg(std::integral_constant<int, 4>{});
+        case 5: return with_lg(std::integral_constant<int, 5>{});
+        case 6: return with_lg(std::integral_constant<int, 6>{});
+        default: set_error("viterbi: unsupported number of states %d", t->S); return false;
+    }
+}
+
 extern "C" {
 
 int cpx_trellis_create(int k, int n, int n_states, int n_inputs, const int32_t *next_state_table,
@@ -675,6 +733,7 @@ int cpx_trellis_create(int k, int n, int n_states, int n_inputs, const int32_t *
                   "pmetrics[number_inputs], convcode.py:604-629)", I);
         return CPX_EINVAL;
     }
+    classify(t);
     (void)hipGetDevice(&t->device);
     size_t bytes = sizeof(int32_t) * S * I;
     int32_t **dst[5] = {&t->d_next, &t->d_out, &t->d_pred_state, &t->d_pred_input, &t->d_pred_code};
@@ -699,18 +758,6 @@ int cpx_trellis_destroy(cpx_trellis *t) {
     (void)hipFree(t->d_pred_state); (void)hipFree(t->d_pred_input); (void)hipFree(t->d_pred_code);
     delete t;
     return CPX_OK;
-}
-
-// shift-register structure (feed-forward, k = 1): predecessor j of state s is ((s << 1) & (S - 1)) | j, input s >> (lgS - 1)
-static bool shift_register(const cpx_trellis *t) {
-    int lgS = 0;
-    while ((1 << lgS) < t->S) lgS++;
-    if (!(t->I == 2 && t->k == 1 && lgS >= 1)) return false;
-    for (int s2 = 0; s2 < t->S; s2++)
-        for (int j = 0; j < 2; j++)
-            if (t->pred_state[s2 * 2 + j] != (((s2 << 1) & (t->S - 1)) | j) || t->pred_input[s2 * 2 + j] != (s2 >> (lgS - 1)))
-                return false;
-    return true;
 }
 
 // ring size and dynamic LDS of the state-per-lane kernels for this trellis and p.tb (sets p.RS)
@@ -746,19 +793,11 @@ static int launch_redo(const cpx_trellis *t, VitParams p, int64_t nitems, hipStr
         if (t->S == 256) hipLaunchKernelGGL((viterbi_wide_redo_kernel<4, 2>), grid, block, lds, st, p, nitems);
         else if (t->I == 2) hipLaunchKernelGGL((viterbi_wide_redo_kernel<2, 2>), grid, block, lds, st, p, nitems);
         else hipLaunchKernelGGL((viterbi_wide_redo_kernel<2, 4>), grid, block, lds, st, p, nitems);
-    } else {
-        const bool sr = shift_register(t);
-#define REDO_CASE(LG)                                                                                              \
-    case LG:                                                                                                       \
-        if (t->I == 4) hipLaunchKernelGGL((viterbi_wave_redo_kernel<LG, 4, false>), grid, block, lds, st, p, nitems);   \
-        else if (sr) hipLaunchKernelGGL((viterbi_wave_redo_kernel<LG, 2, true>), grid, block, lds, st, p, nitems);      \
-        else hipLaunchKernelGGL((viterbi_wave_redo_kernel<LG, 2, false>), grid, block, lds, st, p, nitems);             \
-        break;
-        switch (p.lgS) {
-            REDO_CASE(1) REDO_CASE(2) REDO_CASE(3) REDO_CASE(4) REDO_CASE(5) REDO_CASE(6)
-            default: set_error("viterbi: unsupported number of states %d", t->S); return CPX_ELIMIT;
-        }
-#undef REDO_CASE
+    } else if (!with_wave_template(t, [&](auto lg, auto it, auto sr) {
+                   hipLaunchKernelGGL((viterbi_wave_redo_kernel<decltype(lg)::value, decltype(it)::value, decltype(sr)::value>), grid, block,
+                                      lds, st, p, nitems);
+               })) {
+        return CPX_ELIMIT;
     }
     CPX_HIP(hipGetLastError());
     return CPX_OK;
@@ -803,8 +842,10 @@ static int side_stream(hipStream_t *st, hipEvent_t *fork, hipEvent_t *join) {
     return CPX_OK;
 }
 
-static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const DemodSrc *dm, int64_t B, int64_t len, int64_t L,
-                            int64_t n_steps, int tb_depth, int decoding_type, uint8_t *d_bits, void *stream) {
+// ---- viterbi_dispatch: validate, plan, run --------------------------------------------------------------------------------------
+// Validate.  CPX_OK: *general = the request takes viterbi_generic.hip, not the specialised kernels.
+static int viterbi_validate(const cpx_trellis *t, const DemodSrc *dm, int64_t B, int64_t len, int64_t L, int tb_depth, int decoding_type,
+                            bool *general) {
     CPX_REQUIRE(t, CPX_EINVAL, "viterbi: null trellis");
     if (int rcd = check_handle_device(t->device, "viterbi")) return rcd;
     CPX_REQUIRE(decoding_type >= 0 && decoding_type <= 2, CPX_EINVAL,
@@ -812,18 +853,52 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
     CPX_REQUIRE(B >= 0 && len >= 0 && L >= 0, CPX_EINVAL, "viterbi: negative size");
     CPX_REQUIRE(tb_depth >= 2, CPX_EINVAL, "viterbi: tb_depth must be >= 2");
     CPX_REQUIRE((L / t->k) * (int64_t)t->n <= len, CPX_EINVAL, "viterbi: L inconsistent with len");
-    // what the specialised kernels below are instantiated for; every other trellis / window takes viterbi_generic.hip
+    // what the specialised kernels are instantiated for; every other trellis / window takes viterbi_generic.hip
     // (256 states with k = 1 -- K = 9, round 4 -- run four states per lane on the wide kernel: its tables hold 8-bit state numbers)
-    bool general = !(t->I == 2 || t->I == 4) || t->n > CPX_MAX_N || t->S < 2 || (t->S > 128 && !(t->S == 256 && t->I == 2));
-    if (!general) {
+    *general = !(t->I == 2 || t->I == 4) || t->n > CPX_MAX_N || t->S < 2 || (t->S > 128 && !(t->S == 256 && t->I == 2));
+    if (!*general) {
         VitParams q;
         q.tb = tb_depth; q.NC = 1 << t->n;
         size_t need = 0;
-        general = wave_lds_bytes(t, q, &need) > 64 * 1024;       // the traceback ring of the state-per-lane kernels lives in LDS
+        *general = wave_lds_bytes(t, q, &need) > 64 * 1024;      // the traceback ring of the state-per-lane kernels lives in LDS
     }
     if (dm) {
-        CPX_REQUIRE(!general, CPX_ELIMIT, "demod_hard_viterbi: this trellis / traceback depth takes the two-call path (demodulate, then viterbi_decode)");
+        CPX_REQUIRE(!*general, CPX_ELIMIT, "demod_hard_viterbi: this trellis / traceback depth takes the two-call path (demodulate, then viterbi_decode)");
     }
+    return CPX_OK;
+}
+
+// Plan: how the batch is split between the two kernel families.  (Which state-per-lane template serves the rest: with_wave_template.)
+struct VitPlan {
+    int64_t Bcw = 0;                 // leading codewords offered to the codeword-per-lane path (viterbi_cw.hip); the rest: state per lane
+    bool armed = false;              // the rest is to run BESIDE the round(s): side stream and events below, fork recorded
+    hipStream_t st_side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+};
+static VitPlan viterbi_plan(const cpx_trellis *t, int64_t B, int tb_depth, int decoding_type, hipStream_t st) {
+    // large batches of the standard rate-1/2 codes: one codeword per lane.  Whole rounds go there, and a last round that pays
+    // (viterbi_round_pays, cpx_internal.h); a smaller remainder goes to the state-per-lane kernels
+    VitPlan pl;
+    const int64_t round = viterbi_round();
+    pl.Bcw = B;
+    if (!(viterbi_path_flags() & 2) && B > round && !viterbi_round_pays(B % round, round)) pl.Bcw = B / round * round;
+    // Round 6: the remainder runs BESIDE the rounds.  The rounds take the 32-slot ring stored once (the Lean32 flavour: 93 instead of
+    // 157 KB of LDS per workgroup, priority 3), which leaves the remainder's state-per-lane waves room on every CU; they are issued on a
+    // lowest-priority side stream, forked from `st` before the rounds are launched (same inputs) and joined behind them, so that the
+    // dispatcher places the round's 256 workgroups first -- one per CU -- and the remainder around them.  'soft', default depth, float64,
+    // built-in 64-state pairs only (where the lean flavour exists); CPX_VITERBI_OVERLAP=0 keeps one stream and the mirrored ring.
+    if (pl.Bcw < B && overlap_enabled() && t->S == 64 && decoding_type == CPX_VIT_SOFT && tb_depth == 30 && !precision_fast()) {
+        pl.armed = side_stream(&pl.st_side, &pl.ev_fork, &pl.ev_join) == CPX_OK && hipEventRecord(pl.ev_fork, st) == hipSuccess;
+        if (!pl.armed) (void)hipGetLastError();
+    }
+    return pl;
+}
+
+// any_batch_size: see viterbi_codeword_path (cpx_internal.h)
+static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const DemodSrc *dm, int64_t B, int64_t len, int64_t L,
+                            int64_t n_steps, int tb_depth, int decoding_type, uint8_t *d_bits, void *stream, bool any_batch_size = false) {
+    bool general = false;
+    if (int rcv = viterbi_validate(t, dm, B, len, L, tb_depth, decoding_type, &general)) return rcv;
     if (B == 0 || L == 0) return CPX_OK;
     hipStream_t st = pick_stream(stream);
     if (n_steps <= 0 || n_steps * t->k < L) CPX_HIP(hipMemsetAsync(d_bits, 0, (size_t)(B * L), st));
@@ -847,15 +922,13 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
         p.k = t->k; p.n = t->n; p.I = t->I; p.NC = 1 << t->n; p.type = decoding_type; p.tb = tb_depth;
         p.ysym = nullptr; p.cst = nullptr; p.axes = nullptr; p.nsym = 0; p.M = 0; p.nb = 1; p.nh = 0;
         p.nanflags = flags;
-        int lg = 0;
-        while ((1 << lg) < t->S) lg++;
-        p.lgS = lg;
+        p.lgS = t->cls.lgS;
     };
+    const VitPlan pl = dm ? VitPlan() : viterbi_plan(t, B, tb_depth, decoding_type, st);
     hipStream_t st_rem = st;                                     // the stream of the state-per-lane launches below
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool overlapped = false;
     auto join = [&](int rc) {                                    // every exit below the fork: `st` continues behind the side stream
-        if (overlapped && (hipEventRecord(ev_join, st_rem) != hipSuccess || hipStreamWaitEvent(st, ev_join, 0) != hipSuccess)) {
+        if (overlapped && (hipEventRecord(pl.ev_join, st_rem) != hipSuccess || hipStreamWaitEvent(st, pl.ev_join, 0) != hipSuccess)) {
             (void)hipStreamSynchronize(st_rem);
             set_error("viterbi: joining the side stream failed");
             return rc ? rc : CPX_EHIP;
@@ -867,48 +940,28 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
         if (e != hipSuccess) set_error("viterbi: kernel launch failed: %s", hipGetErrorString(e));
         return e != hipSuccess ? CPX_EHIP : CPX_OK;
     };
-    if (!dm) {   // large batches of the standard rate-1/2 codes: one codeword per lane (viterbi_cw.hip).  That path runs in rounds
-        // of one wavefront of 64 codewords per SIMD, each as long as a full one; a last round that would fill less than 45 % of
-        // the chip is cheaper on the wave kernels below, whose time is proportional to the batch (config 2: 54 us per 1000
-        // codewords against 1.55 ms per round, break-even at 0.44 of a round -- scripts/micro/split_probe.py: 30 000
-        // codewords 1.63 ms on the wave kernels, 1.53 ms as a round; 99 536: 3.59 ms as round + wave kernels, 3.01 as two rounds)
-        const int64_t round = (int64_t)device_cus() * 4 * 64;
-        int64_t Bcw = B;
-        if (!(viterbi_path_flags() & 2) && B > round && 20 * (B % round) < 9 * round) Bcw = B / round * round;
-        // Round 6: the remainder runs BESIDE the rounds.  The rounds take the 32-slot ring stored once (launch_fused_lean: 93 instead of
-        // 157 KB of LDS per workgroup, priority 3), which leaves the remainder's state-per-lane waves room on every CU; they are issued on a
-        // lowest-priority side stream, forked from `st` before the rounds are launched (same inputs) and joined behind them, so that the
-        // dispatcher places the round's 256 workgroups first -- one per CU -- and the remainder around them.  'soft', default depth, float64,
-        // built-in 64-state pairs only (where the lean flavour exists); CPX_VITERBI_OVERLAP=0 keeps one stream and the mirrored ring.
-        hipStream_t st_side = nullptr;
-        bool armed = false;
-        if (Bcw < B && overlap_enabled() && t->S == 64 && decoding_type == CPX_VIT_SOFT && tb_depth == 30 && !precision_fast()) {
-            armed = side_stream(&st_side, &ev_fork, &ev_join) == CPX_OK && hipEventRecord(ev_fork, st) == hipSuccess;
-            if (!armed) (void)hipGetLastError();
-        }
-        int rc_cw = CPX_OK;
-        viterbi_lean_ring(armed);
-        const bool took_cw = viterbi_codeword_path(t, d_coded, Bcw, len, L, n_steps, tb_depth, decoding_type, d_bits, nanflags, st, &rc_cw);
-        viterbi_lean_ring(false);
-        if (took_cw) {
-            if (rc_cw != CPX_OK) return rc_cw;
+    if (pl.Bcw > 0) {
+        const CwResult cw = viterbi_codeword_path(t, d_coded, pl.Bcw, len, L, n_steps, tb_depth, decoding_type, d_bits, nanflags, st,
+                                                  any_batch_size, pl.armed);
+        if (cw.handled) {
+            if (cw.rc != CPX_OK) return cw.rc;
             if (nanflags) {
                 // codeword path: one flag per item of the redo kernel -- 64 / S consecutive codewords, the codewords of one
                 // wavefront of the state-per-lane kernel (one codeword for 64 states)
-                const int64_t items = (Bcw + (64 / t->S) - 1) / (64 / t->S);
+                const int64_t items = (pl.Bcw + (64 / t->S) - 1) / (64 / t->S);
                 VitParams q;
-                wave_params(q, d_coded, d_bits, Bcw, nanflags);
+                wave_params(q, d_coded, d_bits, pl.Bcw, nanflags);
                 if (int rcr = launch_redo(t, q, items, st)) return rcr;
                 nanflags += items;
             }
-            if (Bcw == B) return CPX_OK;
-            if (armed && strstr(last_kernel_name(), "ring stored once")) {   // (the rounds are in `st`'s queue already: dispatched first)
-                if (hipStreamWaitEvent(st_side, ev_fork, 0) == hipSuccess) { st_rem = st_side; overlapped = true; }
+            if (pl.Bcw == B) return CPX_OK;
+            if (cw.flavour == CwFlavour::lean) {                     // (the rounds are in `st`'s queue already: dispatched first)
+                if (hipStreamWaitEvent(pl.st_side, pl.ev_fork, 0) == hipSuccess) { st_rem = pl.st_side; overlapped = true; }
                 else (void)hipGetLastError();
             }
-            d_coded += Bcw * len;
-            d_bits += Bcw * L;
-            B -= Bcw;
+            d_coded += pl.Bcw * len;
+            d_bits += pl.Bcw * L;
+            B -= pl.Bcw;
         }
     }
 
@@ -921,7 +974,6 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
         p.nsym = dm->nsym; p.M = dm->m->M; p.nb = dm->m->nbits; p.nh = dm->m->separable ? dm->m->nbits / 2 : 0;
         CPX_REQUIRE(t->S <= 64, CPX_ELIMIT, "demod_hard_viterbi: trellises above 64 states take the two-call path");
     }
-    const int lgS = p.lgS;
     size_t lds = 0;
     if (int rcl = wave_lds(t, p, &lds)) return join(rcl);
     if (t->S > 64) {                                             // 128 states: two states per lane
@@ -937,38 +989,28 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
     const int S = t->S, G = 64 / S;
     const int64_t nblocks = (B + G - 1) / G;
     if (nblocks >= (1ll << 31)) { set_error("viterbi: batch too large"); return join(CPX_ELIMIT); }
-    dim3 grid((unsigned)nblocks), block(64);
-    const bool sr = shift_register(t);                       // => arithmetic traceback (no predecessor table lookups)
-#define VIT_LAUNCH(LG, IT, SRV)                                                                             \
-    do {                                                                                                    \
-        if (dm) hipLaunchKernelGGL((viterbi_wave_kernel<LG, IT, SRV, 0, true>), grid, block, lds, st_rem, p);    \
-        else if (t->n == 2) hipLaunchKernelGGL((viterbi_wave_kernel<LG, IT, SRV, 2>), grid, block, lds, st_rem, p);    \
-        else if (t->n == 3) hipLaunchKernelGGL((viterbi_wave_kernel<LG, IT, SRV, 3>), grid, block, lds, st_rem, p); \
-        else hipLaunchKernelGGL((viterbi_wave_kernel<LG, IT, SRV, 0>), grid, block, lds, st_rem, p);             \
-    } while (0)
-#define VIT_CASE(LG)                                       \
-    case LG:                                               \
-        if (t->I == 4) VIT_LAUNCH(LG, 4, false);           \
-        else if (sr) VIT_LAUNCH(LG, 2, true);              \
-        else VIT_LAUNCH(LG, 2, false);                     \
-        break;
-    switch (lgS) {
-        VIT_CASE(1) VIT_CASE(2) VIT_CASE(3) VIT_CASE(4) VIT_CASE(5) VIT_CASE(6)
-        default: set_error("viterbi: unsupported number of states %d", S); return join(CPX_ELIMIT);
-    }
-#undef VIT_CASE
-#undef VIT_LAUNCH
+    const dim3 grid((unsigned)nblocks), block(64);
+    if (!with_wave_template(t, [&](auto lg, auto it, auto sr) {
+            constexpr int LG = decltype(lg)::value, IT = decltype(it)::value;
+            constexpr bool SR = decltype(sr)::value;
+            if (dm) hipLaunchKernelGGL((viterbi_wave_kernel<LG, IT, SR, 0, true>), grid, block, lds, st_rem, p);
+            else if (t->n == 2) hipLaunchKernelGGL((viterbi_wave_kernel<LG, IT, SR, 2>), grid, block, lds, st_rem, p);
+            else if (t->n == 3) hipLaunchKernelGGL((viterbi_wave_kernel<LG, IT, SR, 3>), grid, block, lds, st_rem, p);
+            else hipLaunchKernelGGL((viterbi_wave_kernel<LG, IT, SR, 0>), grid, block, lds, st_rem, p);
+        }))
+        return join(CPX_ELIMIT);
     if (int rcl = launch_error()) return join(rcl);
     if (p.nanflags) if (int rcr = launch_redo(t, p, nblocks, st_rem)) return join(rcr);
     {
         char first[160];                                         // a leading round on the codeword path, if any
         snprintf(first, sizeof(first), "%s", last_kernel_name());
-        note_kernel("%s%sviterbi_wave_kernel<%d,%d,%s,%d%s>%s", first, first[0] ? " + " : "", lgS, t->I,
-                    (t->I == 2 && sr) ? "true" : "false", (!dm && (t->n == 2 || t->n == 3)) ? t->n : 0, dm ? ",demod" : "",
+        note_kernel("%s%sviterbi_wave_kernel<%d,%d,%s,%d%s>%s", first, first[0] ? " + " : "", p.lgS, t->I,
+                    (t->I == 2 && t->cls.shift_register) ? "true" : "false", (!dm && (t->n == 2 || t->n == 3)) ? t->n : 0, dm ? ",demod" : "",
                     overlapped ? " (beside the round, side stream)" : "");
     }
     return join(CPX_OK);
 }
+
 
 int cpx_viterbi_decode_batch_dev(const cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L,
                                  int64_t n_steps, int tb_depth, int decoding_type, uint8_t *d_bits, void *stream) {
@@ -1125,10 +1167,12 @@ int cpx_viterbi_decode_batch_i64(const cpx_trellis *t, const double *coded, int6
                     hipEventRecord(ev_up[c].e, s_up[dev]) != hipSuccess) { set_error("viterbi: upload failed"); return fail(CPX_EHIP); }
             }
             if (hipStreamWaitEvent(s_cmp[dev], ev_up[c].e, 0) != hipSuccess) { set_error("viterbi: stream wait failed"); return fail(CPX_EHIP); }
-            viterbi_prefer_cw(true);                               // see viterbi_cw.hip: the chunk's round hides behind the next upload
-            rc = cpx_viterbi_decode_batch_dev(t, din.as<double>() + lo * len, n, len, L, n_steps, tb_depth, decoding_type,
-                                              dout.as<uint8_t>() + lo * L, s_cmp[dev]);
-            viterbi_prefer_cw(false);
+            {
+                CPX_TRACE("cpx_viterbi_decode_batch_dev");
+                // the codeword path whatever the chunk's size: its round hides behind the next upload (viterbi_codeword_path)
+                rc = viterbi_dispatch(t, din.as<double>() + lo * len, nullptr, n, len, L, n_steps, tb_depth, decoding_type,
+                                      dout.as<uint8_t>() + lo * L, s_cmp[dev], true);
+            }
             if (rc) return fail(rc);
             if (hipEventRecord(ev_cmp[c].e, s_cmp[dev]) != hipSuccess || hipStreamWaitEvent(s_dn[dev], ev_cmp[c].e, 0) != hipSuccess ||
                 hipMemcpyAsync(stage + lo * L, dout.as<uint8_t>() + lo * L, (size_t)(n * L), hipMemcpyDeviceToHost, s_dn[dev]) != hipSuccess ||

@@ -634,7 +634,7 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
     const int64_t grp = (int64_t)blockIdx.x * ACS_WAVES + wv;
     const int64_t cw = grp * 64 + lane;
     if (grp * 64 >= p.B) return;                                                   // whole wave beyond the batch
-    if constexpr (LGS == 6 && !MIR && !GEN && RING == FR_RING) __builtin_amdgcn_s_setprio(3);   // launch_fused_lean: another kernel's waves share the SIMD
+    if constexpr (LGS == 6 && !MIR && !GEN && RING == FR_RING) __builtin_amdgcn_s_setprio(3);   // the Lean32 flavour: another kernel's waves share the SIMD
     const bool valid = cw < p.B;
     const double *x = p.coded + (valid ? cw : 0) * p.len;
     static_assert(!GEN || (!MIR && std::is_same<F, double>::value), "table-driven codes: unmirrored ring, float64");
@@ -865,184 +865,79 @@ __global__ __launch_bounds__(TB_THREADS) void viterbi_cw_tb_kernel(CwParams p) {
     }
 }
 
-template <int LGS, unsigned G0, unsigned G1>
-bool tables_match(const cpx_trellis *t) {
-    using C = SrCode<LGS, G0, G1>;
-    if (t->S != (1 << LGS) || t->I != 2 || t->k != 1 || t->n != 2) return false;
-    for (int s = 0; s < t->S; s++)
-        for (int j = 0; j < 2; j++) {
-            if (t->pred_state[s * 2 + j] != (((s << 1) & (t->S - 1)) | j)) return false;
-            if (t->pred_input[s * 2 + j] != (s >> (LGS - 1))) return false;
-            if (t->pred_code[s * 2 + j] != C::code(s, j)) return false;
-        }
-    return true;
-}
-
-// Table-driven codes (cw_step, G0 = G1 = 0): a 2^LGS-state shift-register trellis of rate 1/2 whose butterflies have the form
-// (c, c ^ 3, c ^ 3, c) -- both generators tap the input and the oldest register bit.  Fills goff: field j = 2 c_j.
-template <int LGS>
-bool generic_match(const cpx_trellis *t, unsigned (&goff)[4]) {
-    static_assert((1 << LGS) / 2 <= 32, "goff holds 32 butterflies");
-    const int S = 1 << LGS, H = S / 2;
-    for (unsigned &g : goff) g = 0u;
-    if (t->S != S || t->I != 2 || t->k != 1 || t->n != 2) return false;
-    for (int s = 0; s < S; s++)
-        for (int j = 0; j < 2; j++) {
-            if (t->pred_state[s * 2 + j] != (((s << 1) & (S - 1)) | j)) return false;
-            if (t->pred_input[s * 2 + j] != (s >> (LGS - 1))) return false;
-        }
-    for (int j = 0; j < H; j++) {
-        const int c = t->pred_code[j * 2 + 0];
-        if (c < 0 || c > 3) return false;
-        if (t->pred_code[j * 2 + 1] != (c ^ 3) || t->pred_code[(j + H) * 2 + 0] != (c ^ 3) || t->pred_code[(j + H) * 2 + 1] != c) return false;
-        goff[j >> 3] |= (2u * (unsigned)c) << (4 * (j & 7));
-    }
-
-    return true;
-}
-
-template <int LGS, int TYPE, bool RT>
-int launch_fused_generic_typed(const CwParams &p, hipStream_t st) {
-    constexpr int RING = 5 * LGS - 1 <= 16 ? 16 : 32;              // a ring cut to the depth (see launch_fused_small_typed)
-    auto *fn = viterbi_cw_fused_kernel<LGS, 0u, 0u, TYPE, 5 * LGS - 2, RT, double, RING, false>;
-    const size_t lds = ACS_WAVES * fused_wave_lds<RING, false, true>();
-    static bool raised[64] = {};
-    static std::mutex raised_mu;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    std::lock_guard<std::mutex> lk(raised_mu);
-    if (!raised[dev]) {
-        if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            (void)hipGetLastError();
-            return 0;
-        }
-        raised[dev] = true;
-    }
-    const unsigned groups = (unsigned)((p.B + 63) / 64), blocks = (groups + ACS_WAVES - 1) / ACS_WAVES;
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * ACS_WAVES), lds, st, p);
-    return 1;
-}
-
-// the default depth runs the compile-time walk; smaller depths the same kernel with a run-time hop count (round 4)
-template <int LGS>
-int launch_fused_generic(const CwParams &p, hipStream_t st) {
-    const bool rt = p.tb != 5 * LGS;
-    if (p.type == CPX_VIT_HARD) return rt ? launch_fused_generic_typed<LGS, CPX_VIT_HARD, true>(p, st) : launch_fused_generic_typed<LGS, CPX_VIT_HARD, false>(p, st);
-    if (p.type == CPX_VIT_SOFT) return rt ? launch_fused_generic_typed<LGS, CPX_VIT_SOFT, true>(p, st) : launch_fused_generic_typed<LGS, CPX_VIT_SOFT, false>(p, st);
-    return rt ? launch_fused_generic_typed<LGS, CPX_VIT_UNQUANTIZED, true>(p, st) : launch_fused_generic_typed<LGS, CPX_VIT_UNQUANTIZED, false>(p, st);
-}
-
-template <int LGS, unsigned G0, unsigned G1>
-void launch(const CwParams &p, size_t tb_lds, hipStream_t st) {
-    const unsigned groups = (unsigned)((p.B + 63) / 64), ablocks = (groups + ACS_WAVES - 1) / ACS_WAVES;
-    const dim3 ab(64 * ACS_WAVES);
-    if (p.type == CPX_VIT_HARD) hipLaunchKernelGGL((viterbi_cw_acs_kernel<LGS, G0, G1, CPX_VIT_HARD>), dim3(ablocks), ab, 0, st, p);
-    else if (p.type == CPX_VIT_SOFT) hipLaunchKernelGGL((viterbi_cw_acs_kernel<LGS, G0, G1, CPX_VIT_SOFT>), dim3(ablocks), ab, 0, st, p);
-    else hipLaunchKernelGGL((viterbi_cw_acs_kernel<LGS, G0, G1, CPX_VIT_UNQUANTIZED>), dim3(ablocks), ab, 0, st, p);
-    hipLaunchKernelGGL((viterbi_cw_tb_kernel<LGS>), dim3(groups), dim3(TB_THREADS), tb_lds, st, p);
-}
-
-// fused kernel: the walk is compiled for the reference's default traceback depth, tb_depth = 5 * total_memory
-// (convcode.py:701); every smaller depth runs it with a run-time hop count
+// ---- host side: one launcher for every flavour of the fused kernel ---------------------------------------------------------------
+// A flavour = ring slots, mirrored or stored once, and the hop count the walk is compiled for (tb_depth - 2 of the deepest window it
+// serves; shallower windows run the same flavour with a run-time hop count, RT).
+template <int RING_, bool MIR_, int HOPS_>
+struct Flavour {
+    static constexpr int RING = RING_, HOPS = HOPS_;
+    static constexpr bool MIR = MIR_;
+};
+// the reference's default traceback depth, tb_depth = 5 * total_memory (convcode.py:701) ...
 template <int LGS> constexpr int fused_tb() { return 5 * LGS; }
-
-// ... and up to this depth on the deep ring (run-time hop count, float64 metrics only)
+// ... and the deepest window of the deep ring (run-time hop count, float64 metrics only)
 template <int LGS> constexpr int fused_tb_deep() { return 8 * LGS; }
-
-template <int LGS, unsigned G0, unsigned G1, int TYPE, bool RT, class F, bool DEEP = false>
-int launch_fused_typed(const CwParams &p, hipStream_t st) {
-    constexpr int RING = DEEP ? FR_RING_DEEP : FR_RING;
-    auto *fn = viterbi_cw_fused_kernel<LGS, G0, G1, TYPE, (DEEP ? fused_tb_deep<LGS>() : fused_tb<LGS>()) - 2, RT, F, RING, !DEEP>;
-    const size_t lds = ACS_WAVES * fused_wave_lds<RING, !DEEP>();
-    static bool raised[64] = {};                                 // > 64 KiB of dynamic LDS is opt-in, once per kernel and device
-    static std::mutex raised_mu;                                 // host threads may launch concurrently (ctypes drops the GIL)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    std::lock_guard<std::mutex> lk(raised_mu);
-    if (!raised[dev]) {
-        if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            (void)hipGetLastError();                             // a device with less LDS: the two-kernel form is used
-            return 0;
-        }
-        raised[dev] = true;
-    }
-    const unsigned groups = (unsigned)((p.B + 63) / 64), blocks = (groups + ACS_WAVES - 1) / ACS_WAVES;
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * ACS_WAVES), lds, st, p);
-    return 1;
-}
-
+// 64 states up to the default depth: 157 KB of LDS per workgroup
+template <int LGS> using Mirrored32 = Flavour<FR_RING, true, fused_tb<LGS>() - 2>;
+// 64 states, tb_depth 31 .. 48 (see FR_RING_DEEP)
+template <int LGS> using Deep64 = Flavour<FR_RING_DEEP, false, fused_tb_deep<LGS>() - 2>;
 // 64 states on the 32-slot ring stored ONCE ('soft', default depth, float64): 93 KB of LDS per workgroup instead of 157, one more
 // instruction per traceback hop.  Used for the round(s) of a batch that ALSO has a remainder on the state-per-lane kernels
 // (viterbi_dispatch, round 6): with the mirrored ring a round's workgroup holds the CU's whole LDS and the remainder's workgroups are
 // not placed until it retires (profiles/r06_viterbi_remainder_overlap_ab.txt); with this one they run beside it.
-template <int LGS, unsigned G0, unsigned G1>
-int launch_fused_lean(const CwParams &p, hipStream_t st) {
-    auto *fn = viterbi_cw_fused_kernel<LGS, G0, G1, CPX_VIT_SOFT, fused_tb<LGS>() - 2, false, double, FR_RING, false>;
-    const size_t lds = ACS_WAVES * fused_wave_lds<FR_RING, false>();
-    static bool raised[64] = {};
-    static std::mutex raised_mu;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    std::lock_guard<std::mutex> lk(raised_mu);
-    if (!raised[dev]) {
-        if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            (void)hipGetLastError();
-            return 0;
-        }
-        raised[dev] = true;
-    }
-    const unsigned groups = (unsigned)((p.B + 63) / 64), blocks = (groups + ACS_WAVES - 1) / ACS_WAVES;
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * ACS_WAVES), lds, st, p);
-    return 1;
-}
+template <int LGS> using Lean32 = Flavour<FR_RING, false, fused_tb<LGS>() - 2>;
+// Small trellises (4 .. 32 states) and every table-driven code, up to the default depth: a 16- or 32-slot unmirrored ring cut to the
+// depth -- 14.6 / 22.8 KB of LDS per wave instead of 39, so that two workgroups fit a CU (the one-wave-per-SIMD structure of the
+// 64-state kernel leaves a 4-state step, ~60 instructions, waiting for its own latencies: 0.77 ms on BASELINE config 1 where the
+// state-per-lane kernel takes 0.56; with the small ring 0.42 ms).
+template <int LGS> using Small = Flavour<(fused_tb<LGS>() - 1 <= 16 ? 16 : 32), false, fused_tb<LGS>() - 2>;
 
-// Small trellises (4 and 16 states) at their default depth: the same fused kernel on a 16- or 32-slot unmirrored ring -- 14.6 /
-// 22.8 KB of LDS per wave instead of 39, so that two workgroups fit a CU (the one-wave-per-SIMD structure of the 64-state kernel
-// leaves a 4-state step, ~60 instructions, waiting for its own latencies: 0.77 ms on BASELINE config 1 where the state-per-lane
-// kernel takes 0.56; with the small ring 0.42 ms).
-template <int LGS, unsigned G0, unsigned G1, int TYPE, bool RT>
-int launch_fused_small_typed(const CwParams &p, hipStream_t st) {
-    constexpr int RING = fused_tb<LGS>() - 1 <= 16 ? 16 : 32;
-    auto *fn = viterbi_cw_fused_kernel<LGS, G0, G1, TYPE, fused_tb<LGS>() - 2, RT, double, RING, false>;
-    const size_t lds = ACS_WAVES * fused_wave_lds<RING, false>();
-    if (lds > 64 * 1024) {                                        // (32-slot ring: 91 KB) dynamic LDS above 64 KiB is opt-in, once per kernel and device
+// Launches ONE instantiation; false (nothing launched) on a device that cannot give it its LDS: the caller tries the next form.
+template <class FL, int LGS, unsigned G0, unsigned G1, int TYPE, bool RT, class F>
+bool launch_fused_kernel(const CwParams &p, hipStream_t st) {
+    auto *fn = viterbi_cw_fused_kernel<LGS, G0, G1, TYPE, FL::HOPS, RT, F, FL::RING, FL::MIR>;
+    constexpr size_t lds = ACS_WAVES * fused_wave_lds<FL::RING, FL::MIR, G0 == 0 && G1 == 0>();
+    if (lds > 64 * 1024) {                                       // > 64 KiB of dynamic LDS is opt-in, once per kernel and device
         static bool raised[64] = {};
-        static std::mutex raised_mu;
+        static std::mutex raised_mu;                             // host threads may launch concurrently (ctypes drops the GIL)
         int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
         std::lock_guard<std::mutex> lk(raised_mu);
         if (!raised[dev]) {
             if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                (void)hipGetLastError();
-                return 0;
+                (void)hipGetLastError();                         // a device with less LDS
+                return false;
             }
             raised[dev] = true;
         }
     }
     const unsigned groups = (unsigned)((p.B + 63) / 64), blocks = (groups + ACS_WAVES - 1) / ACS_WAVES;
     hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * ACS_WAVES), lds, st, p);
-    return 1;
-}
-template <int LGS, unsigned G0, unsigned G1>
-int launch_fused_small(const CwParams &p, hipStream_t st) {
-    const bool rt = p.tb != fused_tb<LGS>();                       // below the default depth: run-time hop count (round 4)
-    if (p.type == CPX_VIT_HARD) return rt ? launch_fused_small_typed<LGS, G0, G1, CPX_VIT_HARD, true>(p, st) : launch_fused_small_typed<LGS, G0, G1, CPX_VIT_HARD, false>(p, st);
-    if (p.type == CPX_VIT_SOFT) return rt ? launch_fused_small_typed<LGS, G0, G1, CPX_VIT_SOFT, true>(p, st) : launch_fused_small_typed<LGS, G0, G1, CPX_VIT_SOFT, false>(p, st);
-    return rt ? launch_fused_small_typed<LGS, G0, G1, CPX_VIT_UNQUANTIZED, true>(p, st) : launch_fused_small_typed<LGS, G0, G1, CPX_VIT_UNQUANTIZED, false>(p, st);
+    return true;
 }
 
-// the default depth runs the compile-time walk; smaller depths the same kernel with a run-time hop count
-template <int LGS, unsigned G0, unsigned G1, class F>
-int launch_fused(const CwParams &p, hipStream_t st) {
-    if (p.tb > fused_tb<LGS>()) {
-        if (p.type == CPX_VIT_HARD) return launch_fused_typed<LGS, G0, G1, CPX_VIT_HARD, true, double, true>(p, st);
-        if (p.type == CPX_VIT_SOFT) return launch_fused_typed<LGS, G0, G1, CPX_VIT_SOFT, true, double, true>(p, st);
-        return launch_fused_typed<LGS, G0, G1, CPX_VIT_UNQUANTIZED, true, double, true>(p, st);
-    }
-    const bool rt = p.tb != fused_tb<LGS>();
-    if (p.type == CPX_VIT_HARD) return rt ? launch_fused_typed<LGS, G0, G1, CPX_VIT_HARD, true, F>(p, st) : launch_fused_typed<LGS, G0, G1, CPX_VIT_HARD, false, F>(p, st);
-    if (p.type == CPX_VIT_SOFT) return rt ? launch_fused_typed<LGS, G0, G1, CPX_VIT_SOFT, true, F>(p, st) : launch_fused_typed<LGS, G0, G1, CPX_VIT_SOFT, false, F>(p, st);
-    return rt ? launch_fused_typed<LGS, G0, G1, CPX_VIT_UNQUANTIZED, true, F>(p, st) : launch_fused_typed<LGS, G0, G1, CPX_VIT_UNQUANTIZED, false, F>(p, st);
+// decoding type -> template argument; RT: the walk takes its hop count from p.tb
+template <class FL, int LGS, unsigned G0, unsigned G1, class F, bool RT>
+bool launch_fused_rt(const CwParams &p, hipStream_t st) {
+    if (p.type == CPX_VIT_HARD) return launch_fused_kernel<FL, LGS, G0, G1, CPX_VIT_HARD, RT, F>(p, st);
+    if (p.type == CPX_VIT_SOFT) return launch_fused_kernel<FL, LGS, G0, G1, CPX_VIT_SOFT, RT, F>(p, st);
+    return launch_fused_kernel<FL, LGS, G0, G1, CPX_VIT_UNQUANTIZED, RT, F>(p, st);
+}
+// the default depth runs the compile-time walk; smaller depths the same kernel with a run-time hop count (round 4)
+template <class FL, int LGS, unsigned G0, unsigned G1, class F = double>
+bool launch_fused(const CwParams &p, hipStream_t st) {
+    return p.tb != FL::HOPS + 2 ? launch_fused_rt<FL, LGS, G0, G1, F, true>(p, st) : launch_fused_rt<FL, LGS, G0, G1, F, false>(p, st);
+}
+
+// the two-kernel form: decision words through HBM (p.dec, p.best)
+template <int LGS, unsigned G0, unsigned G1>
+void launch_two_kernels(const CwParams &p, size_t tb_lds, hipStream_t st) {
+    const unsigned groups = (unsigned)((p.B + 63) / 64), ablocks = (groups + ACS_WAVES - 1) / ACS_WAVES;
+    const dim3 ab(64 * ACS_WAVES);
+    if (p.type == CPX_VIT_HARD) hipLaunchKernelGGL((viterbi_cw_acs_kernel<LGS, G0, G1, CPX_VIT_HARD>), dim3(ablocks), ab, 0, st, p);
+    else if (p.type == CPX_VIT_SOFT) hipLaunchKernelGGL((viterbi_cw_acs_kernel<LGS, G0, G1, CPX_VIT_SOFT>), dim3(ablocks), ab, 0, st, p);
+    else hipLaunchKernelGGL((viterbi_cw_acs_kernel<LGS, G0, G1, CPX_VIT_UNQUANTIZED>), dim3(ablocks), ab, 0, st, p);
+    hipLaunchKernelGGL((viterbi_cw_tb_kernel<LGS>), dim3(groups), dim3(TB_THREADS), tb_lds, st, p);
 }
 
 }  // namespace
@@ -1055,8 +950,8 @@ int launch_fused(const CwParams &p, hipStream_t st) {
 // this file yields a code object that holds nothing but the six fused kernels of THAT pair (three decoding types x {default depth,
 // run-time hop count}), generators as template arguments like the built-in pairs; commpy_amd/jit.py builds and caches it,
 // cpx_trellis_attach_viterbi_code loads it (hipModuleLoadData) and viterbi_codeword_path launches it in place of the table-driven
-// kernel.  Generators in the template's convention ("MSB taps the input", see CPX_TRY below).  64 states: the mirrored 32-slot ring of
-// launch_fused_typed; fewer: the small unmirrored ring of launch_fused_small_typed.
+// kernel.  Generators in the template's convention ("MSB taps the input", see BUILTIN_PAIRS below).  64 states: the Mirrored32
+// flavour; fewer: Small.
 namespace {
 constexpr int SPEC_LG = CPX_VIT_SPEC_LG;
 constexpr int SPEC_RING = SPEC_LG == 6 ? FR_RING : (5 * SPEC_LG - 1 <= 16 ? 16 : 32);
@@ -1070,130 +965,176 @@ CPX_SPEC(CPX_VIT_UNQUANTIZED, false) CPX_SPEC(CPX_VIT_UNQUANTIZED, true)
 }  // namespace
 #else
 
+namespace {
+
+// The generator pairs with kernels of their own, in the template's convention: bit lg taps the input.  commpy's default
+// polynomial_format='MSB' makes the LEAST significant bit of the octal number the D^0 tap (convcode.py:211-222), i.e. the bit-reversed
+// number here: (133,171) -> (155,117).
+struct Pair { int lg; unsigned g0, g1; };
+constexpr Pair BUILTIN_PAIRS[] = {
+    {6, 0155u, 0117u},     // K = 7 (133,171), commpy default format: 802.11 / BASELINE configs 2 and 5
+    {6, 0117u, 0155u},     // K = 7 (171,133)
+    {6, 0133u, 0171u},     // K = 7 (133,171) written with polynomial_format='LSB' (convcode.py:216-222)
+    {6, 0171u, 0133u},     // K = 7 (171,133), 'LSB'
+    // Wifi80211 as shipped: its generators are written in DECIMAL, (133, 171), and dec2bitarray wraps them to (5, 43)
+    // (wifi80211.py:49, utilities.py:81-85, SURVEY B1) -- 0000101 / 0101011, bit-reversed 0120 / 0152.  The reference's
+    // own link simulation (BASELINE config 5 with default arguments) decodes this 64-state code.
+    {6, 0120u, 0152u},
+    {2, 05u, 07u},         // K = 3 (5,7) -- BASELINE config 1
+    {4, 031u, 027u},       // K = 5 (23,35)
+};
+constexpr int N_BUILTIN = sizeof(BUILTIN_PAIRS) / sizeof(BUILTIN_PAIRS[0]);
+
+int builtin_index(const TrellisClass &c) {
+    if (c.linear_half)
+        for (int i = 0; i < N_BUILTIN; i++)
+            if (BUILTIN_PAIRS[i].lg == c.lgS && BUILTIN_PAIRS[i].g0 == c.g0 && BUILTIN_PAIRS[i].g1 == c.g1) return i;
+    return -1;
+}
+
+const char *type_name(int type) { return type == CPX_VIT_HARD ? "hard" : type == CPX_VIT_SOFT ? "soft" : "unquantized"; }
+
+// what one call of viterbi_codeword_path works with
+struct CwCall {
+    CwParams p;
+    hipStream_t st;
+    size_t tb_lds;           // traceback window of the two-kernel form
+    int64_t groups;
+    bool lean_ring, two_kernels, f32;
+};
+
+CwResult done(CwFlavour f, const char *form) {
+    if (hipGetLastError() == hipSuccess) return {true, CPX_OK, f};
+    set_error("viterbi (%scodeword path): launch failed", form);
+    return {true, CPX_EHIP, f};
+}
+
+// A built-in pair.  64 states: always handled here -- the fused kernel up to tb_depth 48, else (or on request) two kernels.
+// Fewer states: the small ring up to the default depth; not handled otherwise.
+template <int LG, unsigned GA, unsigned GB>
+CwResult run_builtin(CwCall &c) {
+    CwParams &p = c.p;
+    const int tb = p.tb, type = p.type;
+    if constexpr (LG == 6) {
+        if (c.lean_ring && type == CPX_VIT_SOFT && tb == fused_tb<LG>() && !c.two_kernels && !c.f32 &&
+            launch_fused_kernel<Lean32<LG>, LG, GA, GB, CPX_VIT_SOFT, false, double>(p, c.st)) {
+            const CwResult r = done(CwFlavour::lean, "fused ");
+            note_kernel("viterbi_cw_fused_kernel<%d,0%o,0%o,%s,%d,ring stored once>", LG, GA, GB, type_name(type), fused_tb<LG>() - 2);
+            return r;
+        }
+        const bool deep = tb > fused_tb<LG>();
+        if (tb >= 2 && tb <= fused_tb_deep<LG>() && !c.two_kernels &&
+            (deep ? launch_fused_rt<Deep64<LG>, LG, GA, GB, double, true>(p, c.st)
+                  : c.f32 ? launch_fused<Mirrored32<LG>, LG, GA, GB, float>(p, c.st) : launch_fused<Mirrored32<LG>, LG, GA, GB, double>(p, c.st))) {
+            const CwResult r = done(deep ? CwFlavour::deep : CwFlavour::mirrored, "fused ");
+            note_kernel("viterbi_cw_fused_kernel<%d,0%o,0%o,%s,%d%s%s>", LG, GA, GB, type_name(type),
+                        (deep ? fused_tb_deep<LG>() : fused_tb<LG>()) - 2,
+                        deep ? ",runtime hops,64-slot ring" : tb == fused_tb<LG>() ? "" : ",runtime hops", (c.f32 && !deep) ? ",f32" : "");
+            return r;
+        }
+        void *w0 = nullptr, *w1 = nullptr;
+        p.Tp = (p.T + LG - 1) / LG * LG;
+        if (int rc = workspace(c.st, 0, sizeof(unsigned long long) * (size_t)(c.groups * p.Tp * 64), &w0)) return {true, rc, CwFlavour::two_kernels};
+        if (int rc = workspace(c.st, 1, (size_t)(c.groups * p.Tp * 64), &w1)) return {true, rc, CwFlavour::two_kernels};
+        p.dec = static_cast<unsigned long long *>(w0);
+        p.best = static_cast<unsigned char *>(w1);
+        launch_two_kernels<LG, GA, GB>(p, c.tb_lds, c.st);
+        const CwResult r = done(CwFlavour::two_kernels, "");
+        note_kernel("viterbi_cw_acs_kernel<%d,0%o,0%o,%s> + viterbi_cw_tb_kernel<%d>", LG, GA, GB, type_name(type), LG);
+        return r;
+    } else {
+        if (tb >= 2 && tb <= fused_tb<LG>() && !c.two_kernels && !c.f32 && launch_fused<Small<LG>, LG, GA, GB>(p, c.st)) {
+            const CwResult r = done(CwFlavour::small, "small fused ");
+            note_kernel("viterbi_cw_fused_kernel<%d,0%o,0%o,%s,%d,small ring%s>", LG, GA, GB, type_name(type), fused_tb<LG>() - 2,
+                        tb == fused_tb<LG>() ? "" : ",runtime hops");
+            return r;
+        }
+        return {};
+    }
+}
+template <int I = 0>
+CwResult run_builtin_at(int i, CwCall &c) {
+    if constexpr (I < N_BUILTIN) {
+        constexpr Pair P = BUILTIN_PAIRS[I];
+        return i == I ? run_builtin<P.lg, P.g0, P.g1>(c) : run_builtin_at<I + 1>(i, c);
+    } else {
+        return {};
+    }
+}
+
+// any other end-tap code (4 .. 64 states), up to its default depth: the table-driven kernel, G0 = G1 = 0 (cw_step reads p.goff)
+template <int LG = 6>
+CwResult run_table(int lg, CwCall &c) {
+    if constexpr (LG >= 2) {
+        if (lg != LG) return run_table<LG - 1>(lg, c);
+        if (!launch_fused<Small<LG>, LG, 0u, 0u>(c.p, c.st)) return {};
+        const CwResult r = done(CwFlavour::table, "table-driven ");
+        note_kernel("viterbi_cw_fused_kernel<%d,table-driven,%s,%d%s>", LG, type_name(c.p.type), fused_tb<LG>() - 2,
+                    c.p.tb == fused_tb<LG>() ? "" : ",runtime hops");
+        return r;
+    } else {
+        return {};
+    }
+}
+
+}  // namespace
+
 namespace cpx {
 
-// Set by the host-buffer pipeline (viterbi.hip) around its per-chunk calls: a chunk of a large batch takes the codeword path
-// whatever its own size (a round costs the same however full it is and hides behind the next chunk's upload; the fused
-// kernel -- and with it the precision mode -- then serves the host API exactly as it serves the device API).
-static thread_local bool tl_prefer_cw = false;
-void viterbi_prefer_cw(bool on) { tl_prefer_cw = on; }
-// Set by viterbi_dispatch around the round(s) of a batch whose remainder it runs beside them: the 64-state built-in pairs then take
-// the unmirrored ring (launch_fused_lean) where that flavour exists ('soft', default depth, float64).
-static thread_local bool tl_lean_ring = false;
-void viterbi_lean_ring(bool on) { tl_lean_ring = on; }
-
-static const char *type_name(int type) { return type == CPX_VIT_HARD ? "hard" : type == CPX_VIT_SOFT ? "soft" : "unquantized"; }
-
-// Returns true when the call was handled here (*rc = status); false -> the caller uses the state-per-lane kernels.
-bool viterbi_codeword_path(const cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L, int64_t T,
-                           int tb, int type, uint8_t *d_bits, uint8_t *nanflags, hipStream_t st, int *rc) {
-    *rc = CPX_OK;
+CwResult viterbi_codeword_path(const cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L, int64_t T,
+                               int tb, int type, uint8_t *d_bits, uint8_t *nanflags, hipStream_t st, bool any_batch_size, bool lean_ring) {
     // path override (cpx_viterbi_set_path / CPX_VITERBI_PATH): "wave" = state-per-lane kernels; "cw" = this path whatever
     // the batch size; "cw!" = fail instead of falling back; "cw2", "cw2!" = the two-kernel form even where the fused
     // kernel applies
     const int pf = viterbi_path_flags();
-    if (pf & 1) return false;
-    const bool forced = (pf & 2) || tl_prefer_cw, strict = pf & 4, two_kernels = pf & 8;
-    auto reject = [&](const char *why) {
-        if (!strict) return false;
+    if (pf & 1) return {};
+    const bool forced = (pf & 2) || any_batch_size, strict = pf & 4;
+    auto reject = [&](const char *why) -> CwResult {
+        if (!strict) return {};
         set_error("viterbi (codeword path): %s", why);
-        *rc = CPX_ELIMIT;
-        return true;
+        return {true, CPX_ELIMIT, CwFlavour::none};
     };
-    // one wavefront of 64 codewords per SIMD needs 65536 codewords on 256 CUs; below 45 % of that the wave kernels win
-    // (their time is proportional to the batch, a round of this path costs the same however full it is: break-even 0.44)
-    if (!forced && 20 * B < 9 * (int64_t)device_cus() * 4 * 64) return false;
+    if (!forced && !viterbi_round_pays(B, viterbi_round())) return {};
+    const TrellisClass &k = t->cls;
     if (t->I != 2 || t->k != 1 || t->n != 2 || T < 1) return reject("needs a rate-1/2, k = 1 trellis");
     if ((len & 1) || ((uintptr_t)d_coded & 15)) return reject("rows must be 16-byte aligned");
-    const size_t tb_lds = (size_t)(64 + tb - 2) * (TB_STRIDE * 8 + 64);
-    if (tb_lds > 64 * 1024) return reject("traceback window exceeds 64 KiB of LDS");
-    const int64_t groups = (B + 63) / 64;
-    if (groups >= (1ll << 31) || T >= (1ll << 31) - 64) return reject("batch too large / block too long");
-    CwParams p;
+    CwCall c;
+    c.st = st;
+    c.tb_lds = (size_t)(64 + tb - 2) * (TB_STRIDE * 8 + 64);
+    if (c.tb_lds > 64 * 1024) return reject("traceback window exceeds 64 KiB of LDS");
+    c.groups = (B + 63) / 64;
+    if (c.groups >= (1ll << 31) || T >= (1ll << 31) - 64) return reject("batch too large / block too long");
+    CwParams &p = c.p;
     p.coded = d_coded; p.bits = d_bits; p.B = B; p.len = len; p.L = L; p.T = T; p.Lk = L;   // k = 1
     p.type = type; p.tb = tb; p.nanflags = nanflags;
     if (type == CPX_VIT_SOFT && !nanflags) return reject("'soft' needs the NaN flag array");
-    // float32 path metrics when the caller selected "fp32-fast" (cpx_set_precision) -- fused kernel only.  ('hard' metrics
-    // of 0/1 inputs are Hamming distances <= 2 T, exact in float32: there the fast mode returns identical bits.)
-    const bool f32 = precision_fast() && T < (1ll << 22);
-#define CPX_TRY(LG, GA, GB)                                                                                         \
-    if (tables_match<LG, GA, GB>(t)) {                                                                              \
-        if (tl_lean_ring && type == CPX_VIT_SOFT && tb == fused_tb<LG>() && !two_kernels && !f32 && launch_fused_lean<LG, GA, GB>(p, st)) { \
-            if (hipGetLastError() != hipSuccess) { set_error("viterbi (fused codeword path): launch failed"); *rc = CPX_EHIP; } \
-            note_kernel("viterbi_cw_fused_kernel<%d,0%o,0%o,%s,%d,ring stored once>", LG, GA, GB, type_name(type), fused_tb<LG>() - 2); \
-            return true;                                                                                            \
-        }                                                                                                           \
-        if (tb >= 2 && tb <= fused_tb_deep<LG>() && !two_kernels &&                                                 \
-            (f32 ? launch_fused<LG, GA, GB, float>(p, st) : launch_fused<LG, GA, GB, double>(p, st))) {                 \
-            const bool deep = tb > fused_tb<LG>();                                                                  \
-            if (hipGetLastError() != hipSuccess) { set_error("viterbi (fused codeword path): launch failed"); *rc = CPX_EHIP; } \
-            note_kernel("viterbi_cw_fused_kernel<%d,0%o,0%o,%s,%d%s%s>", LG, GA, GB, type_name(type),                    \
-                        (deep ? fused_tb_deep<LG>() : fused_tb<LG>()) - 2,                                            \
-                        deep ? ",runtime hops,64-slot ring" : tb == fused_tb<LG>() ? "" : ",runtime hops",              \
-                        (f32 && !deep) ? ",f32" : "");                                                              \
-            return true;                                                                                            \
-        }                                                                                                           \
-        void *w0 = nullptr, *w1 = nullptr;                                                                          \
-        p.Tp = (T + LG - 1) / LG * LG;                                                                              \
-        if ((*rc = workspace(st, 0, sizeof(unsigned long long) * (size_t)(groups * p.Tp * 64), &w0))) return true;  \
-        if ((*rc = workspace(st, 1, (size_t)(groups * p.Tp * 64), &w1))) return true;                               \
-        p.dec = static_cast<unsigned long long *>(w0);                                                              \
-        p.best = static_cast<unsigned char *>(w1);                                                                  \
-        launch<LG, GA, GB>(p, tb_lds, st);                                                                          \
-        if (hipGetLastError() != hipSuccess) { set_error("viterbi (codeword path): launch failed"); *rc = CPX_EHIP; } \
-        note_kernel("viterbi_cw_acs_kernel<%d,0%o,0%o,%s> + viterbi_cw_tb_kernel<%d>", LG, GA, GB, type_name(type), LG); \
-        return true;                                                                                                \
-    }
-    // Template generators are in "MSB taps the input" order.  commpy's default polynomial_format='MSB' makes the
-    // LEAST significant bit of the octal number the D^0 tap (convcode.py:211-222), i.e. the bit-reversed number here:
-    // (133,171) -> (155,117).
-    CPX_TRY(6, 0155u, 0117u)      // K = 7 (133,171), commpy default format: 802.11 / BASELINE configs 2 and 5
-    CPX_TRY(6, 0117u, 0155u)      // K = 7 (171,133)
-    CPX_TRY(6, 0133u, 0171u)      // K = 7 (133,171) written with polynomial_format='LSB' (convcode.py:216-222)
-    CPX_TRY(6, 0171u, 0133u)      // K = 7 (171,133), 'LSB'
-    // Wifi80211 as shipped: its generators are written in DECIMAL, (133, 171), and dec2bitarray wraps them to (5, 43)
-    // (wifi80211.py:49, utilities.py:81-85, SURVEY B1) -- 0000101 / 0101011, bit-reversed 0120 / 0152.  The reference's
-    // own link simulation (BASELINE config 5 with default arguments) decodes this 64-state code.
-    CPX_TRY(6, 0120u, 0152u)
-#undef CPX_TRY
-    // K = 3 (5,7) -- BASELINE config 1 -- and K = 5 (23,35) up to their default depths: the small-ring flavour of the fused kernel
-#define CPX_TRY_SMALL(LG, GA, GB)                                                                                       \
-    if (tb >= 2 && tb <= fused_tb<LG>() && !two_kernels && !f32 && tables_match<LG, GA, GB>(t) && launch_fused_small<LG, GA, GB>(p, st)) { \
-        if (hipGetLastError() != hipSuccess) { set_error("viterbi (small fused codeword path): launch failed"); *rc = CPX_EHIP; } \
-        note_kernel("viterbi_cw_fused_kernel<%d,0%o,0%o,%s,%d,small ring%s>", LG, GA, GB, type_name(type), fused_tb<LG>() - 2,   \
-                    tb == fused_tb<LG>() ? "" : ",runtime hops");                                                       \
-        return true;                                                                                                    \
-    }
-    CPX_TRY_SMALL(2, 05u, 07u)
-    CPX_TRY_SMALL(4, 031u, 027u)
-#undef CPX_TRY_SMALL
+    c.lean_ring = lean_ring;
+    c.two_kernels = pf & 8;
+    // float32 path metrics when the caller selected "fp32-fast" (cpx_set_precision) -- fused kernel of the built-in 64-state pairs only.
+    // ('hard' metrics of 0/1 inputs are Hamming distances <= 2 T, exact in float32: there the fast mode returns identical bits.)
+    c.f32 = precision_fast() && T < (1ll << 22);
+    if (const CwResult r = run_builtin_at(builtin_index(k), c); r.handled) return r;
+    // every other flavour: up to the default depth, fused, float64 (deeper windows, and the fp32-fast mode, go to the state-per-lane kernels)
+    const bool plain = tb >= 2 && !c.two_kernels && !c.f32;
     // a code object compiled for this code's generators (cpx_trellis_attach_viterbi_code): the built-in pairs' kernel, from a module
-    if (t->spec_mod && tb >= 2 && tb <= 5 * t->spec_lg && !two_kernels && !f32) {
+    if (t->spec_mod && plain && tb <= 5 * t->spec_lg) {
         const bool rt = tb != 5 * t->spec_lg;
         hipFunction_t fn = t->spec_fn[type][rt ? 1 : 0];
-        const unsigned groups32 = (unsigned)groups, blocks = (groups32 + ACS_WAVES - 1) / ACS_WAVES;
+        const unsigned groups32 = (unsigned)c.groups, blocks = (groups32 + ACS_WAVES - 1) / ACS_WAVES;
         void *args[] = {(void *)&p};
         if (hipModuleLaunchKernel(fn, blocks, 1, 1, 64 * ACS_WAVES, 1, 1, 0, st, args, nullptr) != hipSuccess) {
             (void)hipGetLastError();
             set_error("viterbi (per-pair code object): launch failed");
-            *rc = CPX_EHIP;
-            return true;
+            return {true, CPX_EHIP, CwFlavour::code_object};
         }
         note_kernel("viterbi_cw_fused_kernel<%d,0%o,0%o,%s,%d%s> (code object of this pair)", t->spec_lg, t->spec_g0, t->spec_g1,
                     type_name(type), 5 * t->spec_lg - 2, rt ? ",runtime hops" : "");
-        return true;
+        return {true, CPX_OK, CwFlavour::code_object};
     }
-    // any other rate-1/2 shift-register code of full constraint length (4 .. 64 states), up to its default traceback depth: the
-    // table-driven fused kernel (deeper windows, and the fp32-fast mode, go to the state-per-lane kernels)
-#define CPX_TRY_TABLE(LG)                                                                                               \
-    if (tb >= 2 && tb <= fused_tb<LG>() && !two_kernels && !f32 && generic_match<LG>(t, p.goff) && launch_fused_generic<LG>(p, st)) { \
-        if (hipGetLastError() != hipSuccess) { set_error("viterbi (table-driven codeword path): launch failed"); *rc = CPX_EHIP; } \
-        note_kernel("viterbi_cw_fused_kernel<%d,table-driven,%s,%d%s>", LG, type_name(type), fused_tb<LG>() - 2,              \
-                    tb == fused_tb<LG>() ? "" : ",runtime hops");                                                       \
-        return true;                                                                                                    \
+    if (k.end_tap && plain && tb <= 5 * k.lgS) {
+        memcpy(p.goff, k.goff, sizeof(p.goff));
+        if (const CwResult r = run_table(k.lgS, c); r.handled) return r;
     }
-    CPX_TRY_TABLE(6) CPX_TRY_TABLE(5) CPX_TRY_TABLE(4) CPX_TRY_TABLE(3) CPX_TRY_TABLE(2)
-#undef CPX_TRY_TABLE
     return reject("no instantiation for this trellis");
 }
 
@@ -1202,53 +1143,13 @@ bool viterbi_codeword_path(const cpx_trellis *t, const double *d_coded, int64_t 
 extern "C" int cpx_viterbi_set_path(const char *mode) { return cpx::set_mode(cpx::Switch::viterbi_path, mode); }
 
 // ---- per-pair code objects (round 6): query and attach -------------------------------------------------------------------------
-namespace {
-// generators of a rate-1/2, k = 1 shift-register trellis in the kernel template's convention (bit lg = the input tap), or false
-bool runtime_generators(const cpx_trellis *t, int &lg, unsigned &g0, unsigned &g1) {
-    lg = 0;
-    while ((1 << lg) < t->S) lg++;
-    if (t->I != 2 || t->k != 1 || t->n != 2 || (1 << lg) != t->S || lg < 2 || lg > 6) return false;
-    const int S = t->S;
-    auto code_of = [&](unsigned reg) -> int {                    // reg = [input bit | predecessor state]
-        const int pred = (int)(reg & (unsigned)(S - 1)), b = (int)(reg >> lg);
-        const int s = (pred >> 1) | (b << (lg - 1)), j = pred & 1;
-        return t->pred_code[s * 2 + j];
-    };
-    g0 = g1 = 0;
-    for (int i = 0; i <= lg; i++) {                               // a linear code: the output of a unit register is the generators' bit i
-        const int c = code_of(1u << i);
-        if (c < 0 || c > 3) return false;
-        g0 |= (unsigned)((c >> 1) & 1) << i;
-        g1 |= (unsigned)(c & 1) << i;
-    }
-    for (int s = 0; s < S; s++)
-        for (int j = 0; j < 2; j++) {
-            if (t->pred_state[s * 2 + j] != (((s << 1) & (S - 1)) | j) || t->pred_input[s * 2 + j] != (s >> (lg - 1))) return false;
-            const unsigned reg = ((unsigned)(s >> (lg - 1)) << lg) | (unsigned)(((s << 1) & (S - 1)) | j);
-            const int want = ((__builtin_popcount(reg & g0) & 1) << 1) | (__builtin_popcount(reg & g1) & 1);
-            if (t->pred_code[s * 2 + j] != want) return false;
-        }
-    return true;
-}
-bool builtin_pair(const cpx_trellis *t) {
-    return tables_match<6, 0155u, 0117u>(t) || tables_match<6, 0117u, 0155u>(t) || tables_match<6, 0133u, 0171u>(t) ||
-           tables_match<6, 0171u, 0133u>(t) || tables_match<6, 0120u, 0152u>(t) || tables_match<2, 05u, 07u>(t) ||
-           tables_match<4, 031u, 027u>(t);
-}
-}  // namespace
-
 extern "C" int cpx_trellis_viterbi_spec_query(const cpx_trellis *t, int *lg, unsigned *g0, unsigned *g1) {
     CPX_REQUIRE(t && lg && g0 && g1, CPX_EINVAL, "cpx_trellis_viterbi_spec_query: null pointer");
     *lg = 0; *g0 = 0; *g1 = 0;
-    int l = 0;
-    unsigned a = 0, b = 0;
-    unsigned goff[4];
+    const cpx::TrellisClass &k = t->cls;
     // what the table-driven kernel serves today and a compiled pair would serve faster: full-constraint-length codes that are not built in
-    const bool table = (t->S == 64 && generic_match<6>(t, goff)) || (t->S == 32 && generic_match<5>(t, goff)) ||
-                       (t->S == 16 && generic_match<4>(t, goff)) || (t->S == 8 && generic_match<3>(t, goff)) ||
-                       (t->S == 4 && generic_match<2>(t, goff));
-    if (!table || builtin_pair(t) || t->spec_mod || !runtime_generators(t, l, a, b)) return CPX_OK;
-    *lg = l; *g0 = a; *g1 = b;
+    if (!k.end_tap || !k.linear_half || builtin_index(k) >= 0 || t->spec_mod) return CPX_OK;
+    *lg = k.lgS; *g0 = k.g0; *g1 = k.g1;
     return CPX_OK;
 }
 
@@ -1256,10 +1157,10 @@ extern "C" int cpx_trellis_attach_viterbi_code(cpx_trellis *t, const void *image
     CPX_REQUIRE(t && image && bytes >= 64, CPX_EINVAL, "cpx_trellis_attach_viterbi_code: null / empty image");
     if (int rcd = cpx::check_handle_device(t->device, "attach_viterbi_code")) return rcd;
     CPX_REQUIRE(!t->spec_mod, CPX_EINVAL, "cpx_trellis_attach_viterbi_code: the trellis already has a code object");
-    int lg = 0;
-    unsigned g0 = 0, g1 = 0;
-    CPX_REQUIRE(runtime_generators(t, lg, g0, g1), CPX_EINVAL,
+    CPX_REQUIRE(t->cls.linear_half, CPX_EINVAL,
                 "cpx_trellis_attach_viterbi_code: not a rate-1/2 shift-register code of 4 .. 64 states");
+    const int lg = t->cls.lgS;
+    const unsigned g0 = t->cls.g0, g1 = t->cls.g1;
     hipModule_t mod = nullptr;
     if (hipModuleLoadData(&mod, image) != hipSuccess) {
         (void)hipGetLastError();

@@ -1092,6 +1092,23 @@ def gen_fingerprints():
 GENS["fingerprints"] = gen_fingerprints
 
 
+def gen_viterbi_dispatch_names():
+    """tests/golden/viterbi_dispatch_names.json for tests/test_viterbi_dispatch_gpu.py: the cpx_last_kernel() note (or the error) of
+    every request that test lists, from the ENGINE as built in this tree -- no reference involved, needs the GPU.  Recorded once, at the
+    commit before the Viterbi host dispatch was reorganised; regenerate only from a library whose dispatch is known to be right."""
+    import json
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_viterbi_dispatch_gpu as vd
+    with open(vd.NAMES_JSON, "w") as f:
+        json.dump(vd.record(), f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("wrote %s (%.1f kB)" % (vd.NAMES_JSON, os.path.getsize(vd.NAMES_JSON) / 1e3))
+
+
+GENS["viterbi_dispatch_names"] = gen_viterbi_dispatch_names
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)

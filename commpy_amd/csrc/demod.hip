@@ -33,6 +33,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 using namespace cpx;
 
@@ -40,6 +41,28 @@ namespace {
 
 constexpr int DEMOD_BLOCK = 256;
 constexpr int MAX_M = 256;
+
+// The reference's formula as it is written (modulation.py:125-137), for one symbol: |y - c_m| by hypot, exp of the quotient by noise_var
+// (RCP: of the product with ninv = -1 / noise_var), the two sums per bit in increasing label m, the logarithm of their quotient
+// (label bit b in out[b], unscaled).  `point(m)`: constellation point m.  The redo blocks of demod_soft_gen_kernel and sep_symbol
+// are this formula too and stay written out: folded into this function they cost those kernels registers and occupancy.
+template <int NB, bool RCP, class P>
+__device__ __forceinline__ void literal_llrs(const double2 cur, int M, P point, double noise_var, double ninv, double (&out)[NB]) {
+    double num[NB], den[NB];
+#pragma unroll
+    for (int b = 0; b < NB; b++) { num[b] = 0.0; den[b] = 0.0; }
+    for (int m = 0; m < M; m++) {
+        const double2 c = point(m);
+        const double a = hypot(cur.x - c.x, cur.y - c.y);           // abs(current_symbol - symbol)
+        const double e = exp(RCP ? (a * a) * ninv : (-(a * a)) / noise_var);   // exp((-abs(..)**2)/noise_var) (:134,136)
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            if ((m >> b) & 1) num[b] += e; else den[b] += e;
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; b++) out[b] = fast_log(num[b] / den[b]);
+}
 
 // `scale` multiplies every LLR on its way out (1.0: exact identity; -1.0: the sign flip between Modem.demodulate -- log P1/P0 --
 // and ldpc_bp_decode -- log P0/P1 --, test_ldpc.py:53-54, without a second pass over the LLRs).
@@ -52,21 +75,10 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_soft_kernel(const double2 *
     __syncthreads();
     const double ninv = -1.0 / noise_var;                             // RCP: see demod_soft_sep_kernel
     for (int64_t i = (int64_t)blockIdx.x * DEMOD_BLOCK + threadIdx.x; i < Ns; i += (int64_t)gridDim.x * DEMOD_BLOCK) {
-        const double2 cur = y[i];
-        double num[NB], den[NB];
+        double out[NB];
+        literal_llrs<NB, RCP>(y[i], M, [&](int m) { return c_s[m]; }, noise_var, ninv, out);
 #pragma unroll
-        for (int b = 0; b < NB; b++) { num[b] = 0.0; den[b] = 0.0; }
-        for (int m = 0; m < M; m++) {
-            const double2 c = c_s[m];
-            const double a = hypot(cur.x - c.x, cur.y - c.y);       // abs(current_symbol - symbol)
-            const double e = exp(RCP ? (a * a) * ninv : (-(a * a)) / noise_var);   // exp((-abs(..)**2)/noise_var) (:134,136)
-#pragma unroll
-            for (int b = 0; b < NB; b++) {
-                if ((m >> b) & 1) num[b] += e; else den[b] += e;
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < NB; b++) llr[i * NB + NB - 1 - b] = fast_log(num[b] / den[b]) * scale;   // (:137)
+        for (int b = 0; b < NB; b++) llr[i * NB + NB - 1 - b] = out[b] * scale;   // (:137)
     }
 }
 
@@ -122,6 +134,23 @@ __device__ const double DEMOD_TAB[96] = {
     -0x1.fe89139dbd565p-4, -0x1.b6ac88dad5b1dp-4, -0x1.700d30aeac0e8p-4, -0x1.2aa04a44717a1p-4,
     -0x1.ccb73cdddb2d0p-5, -0x1.466aed42de3f9p-5, -0x1.8492528c8cac5p-6, -0x1.010157588de69p-7
 };
+
+// Block-wide staging into LDS (the caller's __syncthreads() follows): the 2 R axis levels of a separable constellation, the exp / log tables
+__device__ __forceinline__ void stage_axes(double *ax_s, const double *axes, int n) {
+    for (int m = threadIdx.x; m < n; m += DEMOD_BLOCK) ax_s[m] = axes[m];
+}
+
+template <bool TAB>
+__device__ __forceinline__ void stage_tab(double *tab_s) {
+    if (TAB) for (int m = threadIdx.x; m < 96; m += DEMOD_BLOCK) tab_s[m] = DEMOD_TAB[m];
+}
+
+// Around a wave's use of its private LDS tile: what its lanes wrote is visible to the others behind this, and read before they overwrite it
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 __device__ __forceinline__ double tab_exp(double x, const double *__restrict__ tab) {
     constexpr double INV_L32 = 0x1.71547652b82fep+5, L32_HI = 0x1.62e42fefa39efp-6, L32_LO = 0x1.ac00000000000p-61;
@@ -216,7 +245,7 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_soft_gen_kernel(const doubl
         c_s[m] = c;
         if (RCP) cn_s[m] = make_double2(c.x * rs, c.y * rs);
     }
-    for (int m = threadIdx.x; m < 96; m += DEMOD_BLOCK) tab_s[m] = DEMOD_TAB[m];
+    stage_tab<true>(tab_s);
     __syncthreads();
     double pend[NB];
     auto symbol = [&](const double2 cur) __attribute__((always_inline)) {
@@ -281,9 +310,7 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_soft_gen_kernel(const doubl
     auto flush = [&](const int64_t base, const bool full) __attribute__((always_inline)) {   // base: the wave's first symbol of that trip
 #pragma unroll
         for (int b = 0; b < NB; b++) tile[lane * NB + NB - 1 - b] = pend[b];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const int64_t total = Ns * NB, g0 = base * NB;
 #pragma unroll
         for (int k = 0; k < (NB + 1) / 2; k++) {
@@ -294,9 +321,7 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_soft_gen_kernel(const doubl
                 else if (g0 + e < total) llr[g0 + e] = v.x;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     };
     // the software pipeline of demod_soft_sep_kernel: next symbol requested and previous LLRs stored at the top of a trip
     const int64_t stride = (int64_t)gridDim.x * DEMOD_BLOCK;
@@ -427,9 +452,8 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_soft_sep_kernel(const doubl
     constexpr int R = 1 << NH, NB = 2 * NH;
     __shared__ double ax_s[2 * R];
     __shared__ double tab_s[TAB ? 96 : 1];
-    for (int m = threadIdx.x; m < 2 * R; m += DEMOD_BLOCK) ax_s[m] = axes[m];
-    if (TAB)
-        for (int m = threadIdx.x; m < 96; m += DEMOD_BLOCK) tab_s[m] = DEMOD_TAB[m];
+    stage_axes(ax_s, axes, 2 * R);
+    stage_tab<TAB>(tab_s);
     __syncthreads();
     const SepCtx ctx = sep_ctx<GP>(ax_s, tab_s, noise_var, step_x, step_y);
     // One symbol: cur -> NB LLRs in `pend` (two levels per axis: stored at once).
@@ -459,9 +483,7 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_soft_sep_kernel(const doubl
         if (DEFER) {
 #pragma unroll
             for (int b = 0; b < NB; b++) tile[lane * NB + NB - 1 - b] = pend[DEFER ? b : 0];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             const int64_t total = Ns * NB, g0 = base * NB;
 #pragma unroll
             for (int k = 0; k < NB / 2; k++) {
@@ -470,12 +492,11 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_soft_sep_kernel(const doubl
                 if (full || g0 + e + 1 < total) *reinterpret_cast<double2 *>(llr + g0 + e) = v;   // (16-byte aligned: the host sends a
                 else if (g0 + e < total) llr[g0 + e] = v.x;                                         //  caller's odd pointer to demod_soft_kernel)
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
         }
     };
-    // Software pipeline over a wave's symbols (round 5).  The load sat at the top of the loop body with its wait right behind it and
+    // Software pipeline over a wave's symbols (round 5; demod_soft_gen_kernel has its own copy of this skeleton: merged, the two
+    // kernels' register counts move).  The load sat at the top of the loop body with its wait right behind it and
     // the stores at the bottom, in front of the loop header's vmcnt(0).  Now the next symbol is requested and the previous trip's LLRs
     // are stored at the TOP of a trip -- both complete while the current symbol is computed.  The first trip is peeled off (a store
     // that is there on one path into the loop header and not on the other makes the compiler wait for the worst case on both), and
@@ -539,9 +560,8 @@ __global__ __launch_bounds__(DEMOD_BLOCK, (NH <= 3 ? 4 : 3)) void link_front_ker
     __shared__ double tab_s[TAB ? 96 : 1];
     __shared__ int32_t out_s[128];
     __shared__ double xpose[WAVES * 64 * NB];
-    for (int m = threadIdx.x; m < 2 * R; m += DEMOD_BLOCK) ax_s[m] = p.axes[m];
-    if (TAB)
-        for (int m = threadIdx.x; m < 96; m += DEMOD_BLOCK) tab_s[m] = DEMOD_TAB[m];
+    stage_axes(ax_s, p.axes, 2 * R);
+    stage_tab<TAB>(tab_s);
     for (int m = threadIdx.x; m < (2 << p.mem); m += DEMOD_BLOCK) out_s[m] = p.out_tab[m];
     __syncthreads();
     const SepCtx ctx = sep_ctx<GP>(ax_s, tab_s, p.noise_var, p.step_x, p.step_y);
@@ -596,9 +616,7 @@ __global__ __launch_bounds__(DEMOD_BLOCK, (NH <= 3 ? 4 : 3)) void link_front_ker
         sep_symbol<NH, RCP, GP, TAB>(ctx, y, out);
 #pragma unroll
         for (int b = 0; b < NB; b++) tile[lane * NB + NB - 1 - b] = out[b] * p.llr_scale;   // (:137)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         // ---- transmitted-bit order -> decoder-input positions, zeros behind (and, for bit 0, in front of) the kept ones ----
         const uint32_t left = (Ns - wbase) * NB;                    // transmitted bits from the wave's first one to the end (>= 1)
 #pragma unroll
@@ -617,9 +635,7 @@ __global__ __launch_bounds__(DEMOD_BLOCK, (NH <= 3 ? 4 : 3)) void link_front_ker
                     for (int z = 1; z <= p.lead; z++) o[-z] = 0.0;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
 }
 
@@ -799,7 +815,7 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_hard_sep_kernel(const doubl
     __shared__ double2 c_s[M];
     __shared__ double ax_s[2 * R];
     for (int m = threadIdx.x; m < M; m += DEMOD_BLOCK) c_s[m] = cst[m];
-    for (int m = threadIdx.x; m < 2 * R; m += DEMOD_BLOCK) ax_s[m] = axes[m];
+    stage_axes(ax_s, axes, 2 * R);
     __syncthreads();
     for (int64_t i = (int64_t)blockIdx.x * DEMOD_BLOCK + threadIdx.x; i < Ns; i += (int64_t)gridDim.x * DEMOD_BLOCK) {
         const int best = hard_sep<NH>(c_s, ax_s, y[i]);
@@ -837,21 +853,10 @@ __global__ __launch_bounds__(DEMOD_BLOCK) void demod_soft_any_kernel(const doubl
                                                                      const double2 *__restrict__ cst, int M,
                                                                      double noise_var, double scale, double *__restrict__ llr) {
     for (int64_t i = (int64_t)blockIdx.x * DEMOD_BLOCK + threadIdx.x; i < Ns; i += (int64_t)gridDim.x * DEMOD_BLOCK) {
-        const double2 cur = y[i];
-        double num[NB], den[NB];
+        double out[NB];
+        literal_llrs<NB, false>(y[i], M, [&](int m) { return cst[m]; }, noise_var, 0.0, out);
 #pragma unroll
-        for (int b = 0; b < NB; b++) { num[b] = 0.0; den[b] = 0.0; }
-        for (int m = 0; m < M; m++) {
-            const double2 c = cst[m];
-            const double a = hypot(cur.x - c.x, cur.y - c.y);       // abs(current_symbol - symbol)
-            const double e = exp((-(a * a)) / noise_var);           // (:134,136)
-#pragma unroll
-            for (int b = 0; b < NB; b++) {
-                if ((m >> b) & 1) num[b] += e; else den[b] += e;
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < NB; b++) llr[i * NB + NB - 1 - b] = fast_log(num[b] / den[b]) * scale;   // (:137)
+        for (int b = 0; b < NB; b++) llr[i * NB + NB - 1 - b] = out[b] * scale;   // (:137)
     }
 }
 
@@ -875,6 +880,101 @@ unsigned grid_for(int64_t Ns) {
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     return (unsigned)blocks;
+}
+
+// ---- which kernel serves a soft request: decided in classify_soft and nowhere else ---------------------------------------------------
+enum class SoftFamily { Any, SepF32, GenF32, Sep, Gen, Literal };
+const char *const SOFT_KERNEL[] = {"demod_soft_any_kernel", "demod_soft_sep_f32_kernel", "demod_soft_f32_kernel", "demod_soft_sep_kernel", "demod_soft_gen_kernel", "demod_soft_kernel"};
+
+struct SoftVariant {
+    SoftFamily family;
+    int n;                  // the kernel's template integer: NH (bits per axis) of the separable families, NB (bits per symbol) of the others
+    bool rcp, gp, tab;      // RCP of the float64 LDS kernels; GP and TAB of Sep (false elsewhere)
+};
+
+// The separable kernel's form by bits per symbol, in the default mode: two levels per axis have a closed form and eight or more the
+// progression (both GP, if the modem's levels allow it), the latter with table-driven exp / log (TAB); four levels: R exponentials.
+constexpr bool sep_wants_gp(int nbits) { return nbits >= 6 || nbits == 2; }
+constexpr bool sep_wants_tab(int nbits) { return nbits >= 6; }
+
+// `mode`: demod_mode(); `d_llr`: the fast float64 kernels store 16 bytes per lane (link_front_kernel does not: it passes null)
+SoftVariant classify_soft(const cpx_modem *m, double noise_var, double scale, const void *d_llr, bool fast, int mode) {
+    SoftVariant v = {SoftFamily::Literal, m->nbits, noise_var > 1e-290 && noise_var < 1e290, false, false};   // rcp: 1 / noise_var is a normal number
+    const bool al16 = ((uintptr_t)d_llr & 15) == 0;
+    if (m->M > MAX_M) v.family = SoftFamily::Any;                 // table too large for the LDS kernels
+    else if (fast && noise_var > 1e-30 && noise_var < 1e30 && std::isfinite(scale))       // float32 log-sum-exp variants
+        v.family = m->separable ? SoftFamily::SepF32 : SoftFamily::GenF32;
+    else if (m->separable && al16) {
+        v.family = SoftFamily::Sep;
+        v.gp = m->gp && sep_wants_gp(m->nbits) && mode != 1;       // "plain": no progression
+        v.tab = v.gp && sep_wants_tab(m->nbits) && mode != 2;      // "libm" keeps the library's exp / log
+    } else if (mode != 2 && al16) v.family = SoftFamily::Gen;     // generic constellations: the table-driven kernel unless "libm"
+    if (v.family == SoftFamily::SepF32 || v.family == SoftFamily::Sep) v.n = m->nbits / 2;
+    return v;
+}
+
+void note_soft(const SoftVariant &v) {
+    const char *name = SOFT_KERNEL[(int)v.family];
+    switch (v.family) {
+        case SoftFamily::Any: note_kernel("%s<%d> (%d points, division form)", name, v.n, 1 << v.n); break;
+        case SoftFamily::SepF32: case SoftFamily::GenF32: note_kernel("%s<%d>", name, v.n); break;
+        default: note_kernel("%s<%d,%s%s%s>", name, v.n, v.rcp ? "rcp" : "div", v.gp ? ",gp" : "", v.tab ? ",tab" : "");
+    }
+}
+
+// f(std::integral_constant<int, N>) for the N in LO .. HI that equals n; false when there is none
+template <int LO, int HI, class F>
+bool with_int(int n, F &&f) {
+    if constexpr (LO > HI) return false;
+    else return n == LO ? (f(std::integral_constant<int, LO>{}), true) : with_int<LO + 1, HI>(n, f);
+}
+
+// The separable kernels that exist: two levels per axis plain or closed form (GP), four plain, eight and sixteen plain, progression
+// (GP) or progression with tables (GP, TAB).  Null for any other combination (classify_soft does not produce one).
+using SepKernel = void (*)(const double2 *, int64_t, const double *, double, double, double, double, double *);
+template <int NH, bool RCP>
+SepKernel sep_kernel(bool gp, bool tab) {
+    if constexpr (NH >= 3) if (gp && tab) return demod_soft_sep_kernel<NH, RCP, true, true>;
+    if constexpr (NH != 2) if (gp && !tab) return demod_soft_sep_kernel<NH, RCP, true, false>;
+    return gp || tab ? nullptr : demod_soft_sep_kernel<NH, RCP, false, false>;
+}
+
+// One launch per family; false: no kernel for v.n bits.
+bool launch_soft(const SoftVariant &v, const cpx_modem *m, const double2 *y, int64_t Ns, double noise_var, double scale, double *llr, hipStream_t st) {
+    const double2 *c = reinterpret_cast<const double2 *>(m->d_const);
+    const dim3 grid(grid_for(Ns)), block(DEMOD_BLOCK);
+    const unsigned rows = (unsigned)std::min<int64_t>((Ns + 63) / 64, (int64_t)256 * 16 * (DEMOD_BLOCK / 64));
+    const dim3 gridf((rows + DEMOD_BLOCK / 64 - 1) / (DEMOD_BLOCK / 64));           // the float32 kernels walk whole waves
+    auto launch = [&](auto kernel, dim3 g, auto... table) { hipLaunchKernelGGL(kernel, g, block, 0, st, y, Ns, table..., noise_var, scale, llr); };
+    switch (v.family) {
+        case SoftFamily::Any: return with_int<9, 16>(v.n, [&](auto nb) { launch(demod_soft_any_kernel<nb()>, grid, c, m->M); });
+        case SoftFamily::SepF32: return with_int<1, 4>(v.n, [&](auto nh) { launch(demod_soft_sep_f32_kernel<nh()>, gridf, m->d_axes); });
+        case SoftFamily::GenF32: return with_int<1, 8>(v.n, [&](auto nb) { launch(demod_soft_f32_kernel<nb()>, gridf, c, m->M); });
+        case SoftFamily::Gen: return with_int<1, 8>(v.n, [&](auto nb) { launch(v.rcp ? demod_soft_gen_kernel<nb(), true> : demod_soft_gen_kernel<nb(), false>, grid, c); });
+        case SoftFamily::Literal: return with_int<1, 8>(v.n, [&](auto nb) { launch(v.rcp ? demod_soft_kernel<nb(), true> : demod_soft_kernel<nb(), false>, grid, c, m->M); });
+        case SoftFamily::Sep: {
+            SepKernel k = nullptr;
+            with_int<1, 4>(v.n, [&](auto nh) { k = v.rcp ? sep_kernel<nh(), true>(v.gp, v.tab) : sep_kernel<nh(), false>(v.gp, v.tab); });
+            if (k) hipLaunchKernelGGL(k, grid, block, 0, st, y, Ns, m->d_axes, noise_var, scale, m->gp_step[0], m->gp_step[1], llr);
+            return k != nullptr;
+        }
+    }
+    return false;
+}
+
+// The host-array entry points: symbols up, `run(d_y, d_out, stream)` (a *_dev entry point), nbits values of T per symbol down
+template <class T, class F>
+int demod_host(const cpx_modem *m, const double *y_re_im, int64_t Ns, T *out, F run) {
+    CPX_REQUIRE(m && (y_re_im || Ns == 0) && (out || Ns == 0), CPX_EINVAL, "demod: null pointer");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (Ns == 0) return CPX_OK;
+    const size_t out_bytes = sizeof(T) * (size_t)Ns * m->nbits;
+    HostStage s;
+    const double *din;
+    T *dout;
+    if ((rc = s.in(y_re_im, sizeof(double) * 2 * (size_t)Ns, &din)) || (rc = s.out(out_bytes, &dout)) || (rc = run(din, dout, s.st))) return rc;
+    return s.get(out, dout, out_bytes);
 }
 
 }  // namespace
@@ -957,92 +1057,13 @@ int cpx_demod_soft_scaled_dev(const cpx_modem *m, const double *d_y, int64_t Ns,
     if (int rcd = check_handle_device(m->device, "demod")) return rcd;
     CPX_REQUIRE(Ns >= 0, CPX_EINVAL, "demod: negative size");
     if (Ns == 0) return CPX_OK;
-    hipStream_t st = pick_stream(stream);
-    const double2 *y = reinterpret_cast<const double2 *>(d_y);
-    const double2 *c = reinterpret_cast<const double2 *>(m->d_const);
-    dim3 grid(grid_for(Ns)), block(DEMOD_BLOCK);
-    const bool rcp = noise_var > 1e-290 && noise_var < 1e290;     // 1 / noise_var is a normal number
-    if (m->M > MAX_M) {                                           // table too large for the LDS kernels
-        switch (m->nbits) {
-#define CASE(NB) case NB: hipLaunchKernelGGL(demod_soft_any_kernel<NB>, grid, block, 0, st, y, Ns, c, m->M, noise_var, scale, d_llr); break;
-            CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16)
-#undef CASE
-            default: set_error("demod: unsupported bits per symbol %d", m->nbits); return CPX_ELIMIT;
-        }
-        CPX_HIP(hipGetLastError());
-        note_kernel("demod_soft_any_kernel<%d> (%d points, division form)", m->nbits, m->M);
-        return CPX_OK;
-    }
-    if (precision_fast() && noise_var > 1e-30 && noise_var < 1e30 && std::isfinite(scale)) {   // float32 log-sum-exp variants
-        const unsigned rows = (unsigned)std::min<int64_t>((Ns + 63) / 64, (int64_t)256 * 16 * (DEMOD_BLOCK / 64));
-        dim3 gridf((rows + DEMOD_BLOCK / 64 - 1) / (DEMOD_BLOCK / 64));
-        if (m->separable) {
-            switch (m->nbits / 2) {
-#define CASE(NH) case NH: hipLaunchKernelGGL(demod_soft_sep_f32_kernel<NH>, gridf, block, 0, st, y, Ns, m->d_axes, noise_var, scale, d_llr); break;
-                CASE(1) CASE(2) CASE(3) CASE(4)
-#undef CASE
-                default: set_error("demod: unsupported bits per symbol %d", m->nbits); return CPX_ELIMIT;
-            }
-            CPX_HIP(hipGetLastError());
-            note_kernel("demod_soft_sep_f32_kernel<%d>", m->nbits / 2);
-        } else {
-            switch (m->nbits) {
-#define CASE(NB) case NB: hipLaunchKernelGGL(demod_soft_f32_kernel<NB>, gridf, block, 0, st, y, Ns, c, m->M, noise_var, scale, d_llr); break;
-                CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-                default: set_error("demod: unsupported bits per symbol %d", m->nbits); return CPX_ELIMIT;
-            }
-            CPX_HIP(hipGetLastError());
-            note_kernel("demod_soft_f32_kernel<%d>", m->nbits);
-        }
-        return CPX_OK;
-    }
-    const bool al16 = ((uintptr_t)d_llr & 15) == 0;                // the fast kernels store 16 bytes per lane
-    const bool gen = demod_mode() != 2 && al16;                   // generic constellations: the table-driven kernel unless "libm"
-    const bool gp = m->gp && (m->nbits >= 6 || m->nbits == 2) && demod_mode() != 1;
-    const bool tab = gp && m->nbits >= 6 && demod_mode() != 2;       // table-driven exp / log (round 5); "libm" keeps the library's
-    if (m->separable && al16) {
-        switch (m->nbits / 2) {
-#define LAUNCH(NH, RC, GPV) hipLaunchKernelGGL((demod_soft_sep_kernel<NH, RC, GPV>), grid, block, 0, st, y, Ns, m->d_axes, noise_var, \
-                                               scale, m->gp_step[0], m->gp_step[1], d_llr)
-#define CASE(NH) case NH:                                         \
-        if (rcp) LAUNCH(NH, true, false); else LAUNCH(NH, false, false);  \
-        break;
-#define CASE_GP(NH) case NH:                                      \
-        if (gp) { if (rcp) LAUNCH(NH, true, true); else LAUNCH(NH, false, true); }       \
-        else { if (rcp) LAUNCH(NH, true, false); else LAUNCH(NH, false, false); }        \
-        break;
-#define LAUNCH_T(NH, RC) hipLaunchKernelGGL((demod_soft_sep_kernel<NH, RC, true, true>), grid, block, 0, st, y, Ns, m->d_axes, noise_var, \
-                                            scale, m->gp_step[0], m->gp_step[1], d_llr)
-#define CASE_GT(NH) case NH:                                      \
-        if (tab) { if (rcp) LAUNCH_T(NH, true); else LAUNCH_T(NH, false); }              \
-        else if (gp) { if (rcp) LAUNCH(NH, true, true); else LAUNCH(NH, false, true); }  \
-        else { if (rcp) LAUNCH(NH, true, false); else LAUNCH(NH, false, false); }        \
-        break;
-            CASE_GP(1) CASE(2) CASE_GT(3) CASE_GT(4)              // two levels: closed form; 8 and 16 levels: progression (4 exp instead of R)
-#undef CASE
-#undef CASE_GP
-#undef CASE_GT
-#undef LAUNCH_T
-#undef LAUNCH
-            default: set_error("demod: unsupported bits per symbol %d", m->nbits); return CPX_ELIMIT;
-        }
-    } else {
-        switch (m->nbits) {
-#define CASE(NB) case NB:                                                                                                \
-        if (gen && rcp) hipLaunchKernelGGL((demod_soft_gen_kernel<NB, true>), grid, block, 0, st, y, Ns, c, noise_var, scale, d_llr);   \
-        else if (gen) hipLaunchKernelGGL((demod_soft_gen_kernel<NB, false>), grid, block, 0, st, y, Ns, c, noise_var, scale, d_llr);   \
-        else if (rcp) hipLaunchKernelGGL((demod_soft_kernel<NB, true>), grid, block, 0, st, y, Ns, c, m->M, noise_var, scale, d_llr);   \
-        else hipLaunchKernelGGL((demod_soft_kernel<NB, false>), grid, block, 0, st, y, Ns, c, m->M, noise_var, scale, d_llr);   \
-        break;
-            CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-            default: set_error("demod: unsupported bits per symbol %d", m->nbits); return CPX_ELIMIT;
-        }
+    const SoftVariant v = classify_soft(m, noise_var, scale, d_llr, precision_fast(), demod_mode());
+    if (!launch_soft(v, m, reinterpret_cast<const double2 *>(d_y), Ns, noise_var, scale, d_llr, pick_stream(stream))) {
+        set_error("demod: unsupported bits per symbol %d", m->nbits);
+        return CPX_ELIMIT;
     }
     CPX_HIP(hipGetLastError());
-    if (m->separable && al16) note_kernel("demod_soft_sep_kernel<%d,%s%s%s>", m->nbits / 2, rcp ? "rcp" : "div", gp ? ",gp" : "", tab ? ",tab" : "");
-    else note_kernel("%s<%d,%s>", gen ? "demod_soft_gen_kernel" : "demod_soft_kernel", m->nbits, rcp ? "rcp" : "div");
+    note_soft(v);
     return CPX_OK;
 }
 
@@ -1080,34 +1101,12 @@ int cpx_demod_hard_dev(const cpx_modem *m, const double *d_y, int64_t Ns, int8_t
 
 int cpx_demod_soft(const cpx_modem *m, const double *y_re_im, int64_t Ns, double noise_var, double *llr) {
     CPX_TRACE("cpx_demod_soft");
-    CPX_REQUIRE(m && (y_re_im || Ns == 0) && (llr || Ns == 0), CPX_EINVAL, "demod: null pointer");
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (Ns == 0) return CPX_OK;
-    const size_t out_bytes = sizeof(double) * (size_t)Ns * m->nbits;
-    HostStage s;
-    const double *din;
-    double *dout;
-    if ((rc = s.in(y_re_im, sizeof(double) * 2 * (size_t)Ns, &din)) || (rc = s.out(out_bytes, &dout)) ||
-        (rc = cpx_demod_soft_dev(m, din, Ns, noise_var, dout, s.st)))
-        return rc;
-    return s.get(llr, dout, out_bytes);
+    return demod_host(m, y_re_im, Ns, llr, [&](const double *din, double *dout, void *st) { return cpx_demod_soft_dev(m, din, Ns, noise_var, dout, st); });
 }
 
 int cpx_demod_hard(const cpx_modem *m, const double *y_re_im, int64_t Ns, int8_t *bits) {
     CPX_TRACE("cpx_demod_hard");
-    CPX_REQUIRE(m && (y_re_im || Ns == 0) && (bits || Ns == 0), CPX_EINVAL, "demod: null pointer");
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (Ns == 0) return CPX_OK;
-    const size_t out_bytes = (size_t)Ns * m->nbits;
-    HostStage s;
-    const double *din;
-    int8_t *dout;
-    if ((rc = s.in(y_re_im, sizeof(double) * 2 * (size_t)Ns, &din)) || (rc = s.out(out_bytes, &dout)) ||
-        (rc = cpx_demod_hard_dev(m, din, Ns, dout, s.st)))
-        return rc;
-    return s.get(bits, dout, out_bytes);
+    return demod_host(m, y_re_im, Ns, bits, [&](const double *din, int8_t *dout, void *st) { return cpx_demod_hard_dev(m, din, Ns, dout, st); });
 }
 
 // ---- fused link front end (link_front_kernel) ----------------------------------------------------------------------------------
@@ -1137,7 +1136,7 @@ int cpx_link_front_create(const cpx_trellis *t, const cpx_modem *m, int64_t nbit
     if (!ff) { set_error("link_front: not a feed-forward k = 1 shift-register trellis of <= 64 states"); return CPX_ELIMIT; }
     const int nb = m->nbits;
     if (!m->separable || (nb != 2 && nb != 4 && nb != 6 && nb != 8)) { set_error("link_front: modem is not a square QAM of 4..256 points"); return CPX_ELIMIT; }
-    if ((nb >= 6 || nb == 2) && !m->gp) { set_error("link_front: axis levels are not equally spaced Gray levels"); return CPX_ELIMIT; }
+    if (sep_wants_gp(nb) && !m->gp) { set_error("link_front: axis levels are not equally spaced Gray levels"); return CPX_ELIMIT; }
     if (ntx % nb) { set_error("link_front: %lld transmitted bits are not a whole number of symbols", (long long)ntx); return CPX_ELIMIT; }
     const int64_t nsym = ntx / nb, ncoded = nbits * t->n;
     if (nbits >= (1 << 24) || nde >= (1 << 26) || nbits * nsym >= (1ll << 31)) { set_error("link_front: frame too long"); return CPX_ELIMIT; }
@@ -1190,9 +1189,10 @@ int cpx_link_front_run_dev(const cpx_link_front *lf, int64_t T, double noise_var
     if (T == 0) return CPX_OK;
     if (T * (int64_t)lf->nsym >= (1ll << 31) / 8) { set_error("link_front: %lld transmissions in one call (limit: 2^28 symbols)", (long long)T); return CPX_ELIMIT; }
     const cpx_modem *m = lf->m;
-    // the demodulator variant the staged path would run for this modem and mode (cpx_demod_soft_scaled_dev); other modes: staged
-    const bool rcp = noise_var > 1e-290 && noise_var < 1e290;
-    if (!rcp || precision_fast() || demod_mode() != 0) {
+    // The variant the staged path would run (classify_soft).  The fused kernel exists for the default float64 one only: separable, reciprocal
+    // exponent, the form sep_wants_gp / _tab name (cpx_link_front_create saw to it that the modem's levels allow it); anything else: staged
+    const SoftVariant v = classify_soft(m, noise_var, llr_scale, nullptr, precision_fast(), demod_mode());
+    if (demod_mode() != 0 || v.family != SoftFamily::Sep || !v.rcp || v.gp != sep_wants_gp(m->nbits) || v.tab != sep_wants_tab(m->nbits)) {
         set_error("link_front: only the default float64 demodulator path is fused (noise_var %g, mode %d)", noise_var, demod_mode());
         return CPX_ELIMIT;
     }
@@ -1204,14 +1204,11 @@ int cpx_link_front_run_dev(const cpx_link_front *lf, int64_t T, double noise_var
     p.msg = d_msg; p.llr = d_llr; p.rx = reinterpret_cast<double2 *>(d_rx_re_im);
     dim3 grid(grid_for(T * (int64_t)lf->nsym)), block(DEMOD_BLOCK);
     hipStream_t st = pick_stream(stream);
-    switch (m->nbits / 2) {                                       // <NH, RCP, GP, TAB> as in cpx_demod_soft_scaled_dev's default mode
-        case 1: hipLaunchKernelGGL((link_front_kernel<1, true, true, false>), grid, block, 0, st, p); break;
-        case 2: hipLaunchKernelGGL((link_front_kernel<2, true, false, false>), grid, block, 0, st, p); break;
-        case 3: hipLaunchKernelGGL((link_front_kernel<3, true, true, true>), grid, block, 0, st, p); break;
-        default: hipLaunchKernelGGL((link_front_kernel<4, true, true, true>), grid, block, 0, st, p); break;
-    }
+    with_int<1, 4>(v.n, [&](auto nh) {
+        hipLaunchKernelGGL((link_front_kernel<nh(), true, sep_wants_gp(2 * nh()), sep_wants_tab(2 * nh())>), grid, block, 0, st, p);
+    });
     CPX_HIP(hipGetLastError());
-    note_kernel("link_front_kernel<%d> (bits, conv_encode, puncture, modulate, AWGN, soft demod, depuncture fused)", m->nbits / 2);
+    note_kernel("link_front_kernel<%d> (bits, conv_encode, puncture, modulate, AWGN, soft demod, depuncture fused)", v.n);
     return CPX_OK;
 }
 

@@ -1109,6 +1109,24 @@ def gen_viterbi_dispatch_names():
 GENS["viterbi_dispatch_names"] = gen_viterbi_dispatch_names
 
 
+def gen_demod_dispatch_names():
+    """tests/golden/demod_dispatch_names.json for tests/test_demod_dispatch_gpu.py: the cpx_last_kernel() note and the SHA-1 of the
+    output (or the error) of every request that test lists, from the ENGINE as built in this tree -- no reference involved, needs the
+    GPU.  Recorded once, at the commit before the demodulator's host dispatch was reorganised; regenerate only from a library whose
+    dispatch and kernels are known to be right."""
+    import json
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_demod_dispatch_gpu as dd
+    with open(dd.NAMES_JSON, "w") as f:
+        json.dump(dd.record(), f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("wrote %s (%.1f kB)" % (dd.NAMES_JSON, os.path.getsize(dd.NAMES_JSON) / 1e3))
+
+
+GENS["demod_dispatch_names"] = gen_demod_dispatch_names
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)

@@ -316,55 +316,88 @@ __device__ __forceinline__ void cw_step(double (&pm)[1 << LGS], double r0, doubl
         }
     }
     hook.template at<2>();
-    // first-argmin state (:645): the minimum (v_min_f64 tree, as viterbi.hip's cross-lane tree) and the first state equal to it
-    double m0 = pm[0], m1 = pm[1 % S], m2 = pm[2 % S], m3 = pm[3 % S];
-    if constexpr (S == 64) {
-        // 60 v_min_f64 as three statements of four interleaved chains (viterbi_cw_asm.h: one statement per instruction cost an
-        // s_nop per dependent pair and serialised the chains)
-#define CPX_V4(a) "v"(pm[a]), "v"(pm[(a) + 1]), "v"(pm[(a) + 2]), "v"(pm[(a) + 3])
-        asm(CPX_MIN_BLOCK24 : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3)
-            : CPX_V4(4), CPX_V4(8), CPX_V4(12), CPX_V4(16), CPX_V4(20), CPX_V4(24));
-        asm(CPX_MIN_BLOCK24 : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3)
-            : CPX_V4(28), CPX_V4(32), CPX_V4(36), CPX_V4(40), CPX_V4(44), CPX_V4(48));
-        asm(CPX_MIN_BLOCK12 : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3) : CPX_V4(52), CPX_V4(56), CPX_V4(60));
-#undef CPX_V4
-    } else {
-#pragma unroll
-        for (int s = 4; s < S; s += 4) {
-            m0 = vmin(m0, pm[s]); m1 = vmin(m1, pm[s + 1]); m2 = vmin(m2, pm[s + 2]); m3 = vmin(m3, pm[s + 3]);
-        }
-    }
-    const double mn = vmin(vmin(m0, m1), vmin(m2, m3));
-    hook.template at<3>();
     int bst = 0;
-    if constexpr (S == 64) {
-        // first state equal to the minimum, scanned downwards (a later, lower state overwrites): per four states four compares
-        // into four SGPR pairs, then the four selects with inline-constant state numbers -- three instructions always sit
-        // between a float64 compare and the select that reads its mask (back to back the pair needs two wait states).  Three
-        // statements of 24 / 24 / 16 states (30 operands is the limit of one).
-        unsigned long long k0, k1, k2, k3;
-#define CPX_S4(a) "v"(pm[rotl<LGS>((a), R + 1)]), "v"(pm[rotl<LGS>((a) - 1, R + 1)]), "v"(pm[rotl<LGS>((a) - 2, R + 1)]), "v"(pm[rotl<LGS>((a) - 3, R + 1)])
-        asm(CPX_SCAN_BLOCK0 : "+v"(bst), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3)
-            : "v"(mn), CPX_S4(63), CPX_S4(59), CPX_S4(55), CPX_S4(51), CPX_S4(47), CPX_S4(43));
-        asm(CPX_SCAN_BLOCK1 : "+v"(bst), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3)
-            : "v"(mn), CPX_S4(39), CPX_S4(35), CPX_S4(31), CPX_S4(27), CPX_S4(23), CPX_S4(19));
-        asm(CPX_SCAN_BLOCK2 : "+v"(bst), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3)
-            : "v"(mn), CPX_S4(15), CPX_S4(11), CPX_S4(7), CPX_S4(3));
-#undef CPX_S4
-    } else if constexpr (S % 4 == 0) {
+    // 'soft', 64 states: FIRST-ARGMIN ON THE HIGH DWORDS.  The step needs the first-argmin state only, not the minimum, and every 'soft'
+    // path metric is +0.0, a positive number or +inf -- never NaN, never negative, never -0.0 (the clip maps a NaN input to -500, the
+    // per-bit metrics are >= +0.0 and never -0.0, see LEAN above, and metrics are only added and selected, see acs_min).  For such
+    // doubles the numeric order IS the unsigned order of the 64-bit patterns, equal values have equal patterns, and +inf (0x7ff00000
+    // 00000000) is simply the largest pattern in the domain.  Hence the minimum's high dword is the unsigned minimum of the 64 high dwords,
+    // and the first-argmin state is one of the states whose high dword equals it (the "hits"): with exactly one hit that state IS the
+    // first-argmin, whatever the low dwords hold.  With two or more hits in any lane (an exact tie, or metrics that differ only in the low
+    // dword) the whole wave runs the float64 tree and first-equal scan below and takes their result -- on the benchmark's input 0.54 % of
+    // the wave-steps, 0.48 % of them the five all-tie steps of the zero tail (profiles/viterbi_argmin32_tie_rate.txt).  The branch is
+    // wave-uniform (an SGPR pair written by one compare) and marked unlikely: the float64 block sits out of line, the step's hot path has
+    // no taken branch, and the hook calls stay unconditional and in order.  (Measured issue costs: profiles/viterbi_argmin32_issue_cost.txt.)
+    constexpr bool ARGMIN32 = LEAN && S == 64 && TYPE == CPX_VIT_SOFT && !GEN;   // the fused kernel, compiled-in generators
+    unsigned long long tie = ~0ull;                                // lanes with more than one hit
+    if constexpr (ARGMIN32) {
+        unsigned h0, h1, h2, h3;
+#define CPX_H4(a) "v"(__double2hiint(pm[a])), "v"(__double2hiint(pm[(a) + 1])), "v"(__double2hiint(pm[(a) + 2])), "v"(__double2hiint(pm[(a) + 3]))
+        asm(CPX_HMIN_BLOCK0 : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3) : CPX_H4(0), CPX_H4(4), CPX_H4(8), CPX_H4(12), CPX_H4(16));
+        asm(CPX_HMIN_BLOCK1 : "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3) : CPX_H4(20), CPX_H4(24), CPX_H4(28), CPX_H4(32), CPX_H4(36), CPX_H4(40));
+        asm(CPX_HMIN_BLOCK2 : "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3) : CPX_H4(44), CPX_H4(48), CPX_H4(52), CPX_H4(56), CPX_H4(60));
+#undef CPX_H4
+        hook.template at<3>();
+        // hit words in logical state order (state s sits in register rotl(s, R + 1)): ha = states 0 .. 31, hb = states 32 .. 63
+        unsigned ha, hb, tmp;
+#define CPX_P1(a) "v"(__double2hiint(pm[rotl<LGS>((a), R + 1)])), "v"(__double2hiint(pm[rotl<LGS>((a) + 32, R + 1)]))
+#define CPX_P4(a) CPX_P1(a), CPX_P1((a) + 1), CPX_P1((a) + 2), CPX_P1((a) + 3)
+        asm(CPX_HIT_BLOCK0 : "=&v"(ha), "=&v"(hb) : "v"(h0), CPX_P4(0), CPX_P4(4), CPX_P4(8) : "vcc");
+        asm(CPX_HIT_BLOCK1 : "+v"(ha), "+v"(hb) : "v"(h0), CPX_P4(12), CPX_P4(16), CPX_P4(20) : "vcc");
+        asm(CPX_HIT_BLOCK2 : "+v"(ha), "+v"(hb), "=&v"(bst), "=&v"(tmp), "=&s"(tie) : "v"(h0), CPX_P4(24), CPX_P4(28) : "vcc");
+#undef CPX_P4
+#undef CPX_P1
+    }
+    if (__builtin_expect(tie != 0, !ARGMIN32)) {
+        // first-argmin state (:645): the minimum (v_min_f64 tree, as viterbi.hip's cross-lane tree) and the first state equal to it
+        double m0 = pm[0], m1 = pm[1 % S], m2 = pm[2 % S], m3 = pm[3 % S];
+        if constexpr (S == 64) {
+            // 60 v_min_f64 as three statements of four interleaved chains (viterbi_cw_asm.h: one statement per instruction cost an
+            // s_nop per dependent pair and serialised the chains)
+#define CPX_V4(a) "v"(pm[a]), "v"(pm[(a) + 1]), "v"(pm[(a) + 2]), "v"(pm[(a) + 3])
+            asm(CPX_MIN_BLOCK24 : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3)
+                : CPX_V4(4), CPX_V4(8), CPX_V4(12), CPX_V4(16), CPX_V4(20), CPX_V4(24));
+            asm(CPX_MIN_BLOCK24 : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3)
+                : CPX_V4(28), CPX_V4(32), CPX_V4(36), CPX_V4(40), CPX_V4(44), CPX_V4(48));
+            asm(CPX_MIN_BLOCK12 : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3) : CPX_V4(52), CPX_V4(56), CPX_V4(60));
+#undef CPX_V4
+        } else {
 #pragma unroll
-        for (int s = S - 4; s >= 0; s -= 4) {
-            unsigned long long k0, k1, k2, k3;
-            asm("v_cmp_eq_f64 %1, %5, %9\n\tv_cmp_eq_f64 %2, %6, %9\n\tv_cmp_eq_f64 %3, %7, %9\n\tv_cmp_eq_f64 %4, %8, %9\n\t"
-                "v_cndmask_b32 %0, %0, %10, %1\n\tv_cndmask_b32 %0, %0, %11, %2\n\tv_cndmask_b32 %0, %0, %12, %3\n\t"
-                "v_cndmask_b32 %0, %0, %13, %4"
-                : "+v"(bst), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3)
-                : "v"(pm[rotl<LGS>(s + 3, R + 1)]), "v"(pm[rotl<LGS>(s + 2, R + 1)]), "v"(pm[rotl<LGS>(s + 1, R + 1)]),
-                  "v"(pm[rotl<LGS>(s, R + 1)]), "v"(mn), "n"(s + 3), "n"(s + 2), "n"(s + 1), "n"(s));   // inline constants
+            for (int s = 4; s < S; s += 4) {
+                m0 = vmin(m0, pm[s]); m1 = vmin(m1, pm[s + 1]); m2 = vmin(m2, pm[s + 2]); m3 = vmin(m3, pm[s + 3]);
+            }
         }
-    } else {
+        const double mn = vmin(vmin(m0, m1), vmin(m2, m3));
+        if constexpr (!ARGMIN32) hook.template at<3>();
+        if constexpr (S == 64) {
+            // first state equal to the minimum, scanned downwards (a later, lower state overwrites): per four states four compares
+            // into four SGPR pairs, then the four selects with inline-constant state numbers -- three instructions always sit
+            // between a float64 compare and the select that reads its mask (back to back the pair needs two wait states).  Three
+            // statements of 24 / 24 / 16 states (30 operands is the limit of one).
+            unsigned long long k0, k1, k2, k3;
+#define CPX_S4(a) "v"(pm[rotl<LGS>((a), R + 1)]), "v"(pm[rotl<LGS>((a) - 1, R + 1)]), "v"(pm[rotl<LGS>((a) - 2, R + 1)]), "v"(pm[rotl<LGS>((a) - 3, R + 1)])
+            asm(CPX_SCAN_BLOCK0 : "+v"(bst), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3)
+                : "v"(mn), CPX_S4(63), CPX_S4(59), CPX_S4(55), CPX_S4(51), CPX_S4(47), CPX_S4(43));
+            asm(CPX_SCAN_BLOCK1 : "+v"(bst), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3)
+                : "v"(mn), CPX_S4(39), CPX_S4(35), CPX_S4(31), CPX_S4(27), CPX_S4(23), CPX_S4(19));
+            asm(CPX_SCAN_BLOCK2 : "+v"(bst), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3)
+                : "v"(mn), CPX_S4(15), CPX_S4(11), CPX_S4(7), CPX_S4(3));
+#undef CPX_S4
+        } else if constexpr (S % 4 == 0) {
 #pragma unroll
-        for (int s = S - 1; s >= 0; s--) bst = (pm[rotl<LGS>(s, R + 1)] == mn) ? s : bst;
+            for (int s = S - 4; s >= 0; s -= 4) {
+                unsigned long long k0, k1, k2, k3;
+                asm("v_cmp_eq_f64 %1, %5, %9\n\tv_cmp_eq_f64 %2, %6, %9\n\tv_cmp_eq_f64 %3, %7, %9\n\tv_cmp_eq_f64 %4, %8, %9\n\t"
+                    "v_cndmask_b32 %0, %0, %10, %1\n\tv_cndmask_b32 %0, %0, %11, %2\n\tv_cndmask_b32 %0, %0, %12, %3\n\t"
+                    "v_cndmask_b32 %0, %0, %13, %4"
+                    : "+v"(bst), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3)
+                    : "v"(pm[rotl<LGS>(s + 3, R + 1)]), "v"(pm[rotl<LGS>(s + 2, R + 1)]), "v"(pm[rotl<LGS>(s + 1, R + 1)]),
+                      "v"(pm[rotl<LGS>(s, R + 1)]), "v"(mn), "n"(s + 3), "n"(s + 2), "n"(s + 1), "n"(s));   // inline constants
+            }
+        } else {
+#pragma unroll
+            for (int s = S - 1; s >= 0; s--) bst = (pm[rotl<LGS>(s, R + 1)] == mn) ? s : bst;
+        }
     }
     // shifting the decisions in in increasing state order leaves state j of a half at bit H-1-j of its word; placing the
     // lower half on top puts state s at bit 63 - s of the 64-bit word: the traceback reads it as the top bit of (w << s)

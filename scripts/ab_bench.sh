@@ -12,6 +12,6 @@ for r in $(seq 1 $ROUNDS); do
     timeout 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 j = json.loads(sys.stdin.read())
-print(json.dumps({'lib': '$lib', 'round': $r, 'ms_per_step': round(j['ms_per_step'], 4), 'kernel_ms_avg': round(j['roofline']['kernel_ms_avg'], 4), 'mismatch': j['oracle_mismatched_bits'], 'ber': j['ber']}))" | tee -a $OUT/ab.jsonl
+print(json.dumps({'lib': '$lib', 'round': $r, 'ms_per_step': round(j['ms_per_step'], 4), 'kernel_ms_avg': round(j['roofline']['kernel_ms_avg'], 4), 'kernel_ms_median': round(j['roofline']['kernel_ms_median'], 4), 'mismatch': j['oracle_mismatched_bits'], 'path_check': j.get('kernel_path_check'), 'ber': j['ber']}))" | tee -a $OUT/ab.jsonl
   done
 done

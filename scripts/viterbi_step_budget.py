@@ -4,8 +4,11 @@
     python scripts/viterbi_step_budget.py [--kernel "viterbi_cw_fused_kernel<6, 109u, 79u, 1, 28, false, double, 32, true>"] [--md out.md]
 
 Disassembles commpy_amd/csrc/build/viterbi_cw.o (device part, gfx950), finds the kernel's step loop (the smallest backward branch that spans
-a whole trellis step), counts the steps of one trip of it by the first-equal scans it contains (64 v_cmp_eq_f64 per step) and
-sorts every instruction of the loop body into the phases of cw_step (csrc/viterbi_cw.hip) by opcode -- the table of DESIGN.md 4.1.
+a whole trellis step), counts the steps of one trip of it by the 64 equality compares per step it contains (v_cmp_eq_u32 of the
+hit words; v_cmp_eq_f64 of the first-equal scan where the 32-bit first-argmin is not compiled in) and sorts every instruction of the
+loop body into the phases of cw_step (csrc/viterbi_cw.hip) by opcode -- the table of DESIGN.md 4.1.  The float64 minimum tree and
+first-equal scan that 'soft' keeps as the fallback of the 32-bit first-argmin are compiled out of line, behind the loop (the branch
+to them is marked unlikely): the loop body counted here is what a step executes when no lane of the wave ties.
 
 Two more tables:
 * the same instructions BY POSITION in the step.  The fused kernel pins the four batches of traceback LDS reads between the phases of
@@ -52,7 +55,15 @@ def kernel_body(dis, name):
     return out
 
 
-def classify(op, args):
+ARGMIN32 = "first-argmin on the high dwords: v_min3_u32 tree, v_cmp_eq_u32 + v_addc_co_u32 hit words, index, tie test"
+
+
+def classify(op, args, prev=None):
+    # (only in a kernel that has the 32-bit first-argmin compiled in, main(): elsewhere these opcodes belong to the traceback)
+    if EQ[0] == "v_cmp_eq_u32" and (
+            op in ("v_min3_u32", "v_min_u32", "v_cmp_eq_u32", "v_ffbh_u32", "v_bcnt_u32_b32", "v_cmp_lt_u32") or
+            (prev == "v_cmp_eq_u32" and (op.startswith("v_addc_co") or op == "v_cndmask_b32"))):
+        return ARGMIN32
     if op in ("v_add_f64",):
         return "add-compare-select: v_add_f64 (path metric + branch metric)"
     if op == "v_cmp_lt_f64" or op.startswith("v_addc_co"):
@@ -85,7 +96,8 @@ def classify(op, args):
 TRACEBACK = ("v_lshlrev_b64", "v_alignbit_b32", "ds_", "s_waitcnt")
 PHASES = ["LLR -> branch metrics (clip, exp, log, sums; pad select, NaN detect, loads, the previous step's ring / tile addresses)",
           "add-compare-select, butterflies 0 .. S/4 - 1", "add-compare-select, butterflies S/4 .. S/2 - 1",
-          "minimum tree", "first-equal scan, decision word, ring slot"]
+          "minimum tree (of the high dwords where the 32-bit first-argmin is compiled in)",
+          "first-equal scan / hit words and index, decision word, ring slot"]
 
 
 def position_table(loop, steps):
@@ -117,13 +129,16 @@ def position_table(loop, steps):
 
 def chunk_table(body, addr, hot):
     """Static counts of the per-chunk code around the hot loop `hot` = (first, last) and of the flush rounds inside it."""
-    def loops():
+    def branches():
         for i, (ad, op, args) in enumerate(body):
             if op.startswith("s_cbranch") or op == "s_branch":
                 m = re.search(r"\+0x([0-9a-f]+)>\s*$", args)
                 j = addr.get(body[0][0] + int(m.group(1), 16)) if m else None
-                if j is not None and j < i:
+                if j is not None:
                     yield j, i
+
+    def loops():
+        return ((j, i) for j, i in branches() if j < i)
     outer = min(((j, i) for j, i in loops() if j < hot[0] and i > hot[1]), key=lambda ji: ji[1] - ji[0], default=None)
     out = ["", "per 96-step chunk, outside the hot loop (static counts; the hot loop runs 16 trips per chunk):", ""]
     if outer is None:
@@ -131,8 +146,21 @@ def chunk_table(body, addr, hot):
     rounds = [(j, i) for j, i in loops() if outer[0] <= j and i <= outer[1] and (i < hot[0] or j > hot[1]) and
               any(o.startswith("global_store") for _, o, _ in body[j:i + 1])]
     rnd = min(rounds, key=lambda ji: ji[1] - ji[0], default=None)
-    n_outer = outer[1] - outer[0] + 1 - (hot[1] - hot[0] + 1)
+    # the float64 fallback of the 32-bit first-argmin: blocks behind the hot loop that a forward branch out of the loop enters and
+    # that end with a branch back into it, each holding a first-equal scan (64 v_cmp_eq_f64).  A step runs one only when a lane of
+    # its wave has a high-dword tie; they are not part of what a chunk executes besides its steps.
+    cold = []
+    for t, i in branches():
+        if hot[0] <= i <= hot[1] and outer[1] >= t > hot[1]:
+            e = next((k for j, k in branches() if k >= t and hot[0] <= j <= hot[1]), None)
+            if e is not None and sum(1 for _, o, _ in body[t:e + 1] if o == "v_cmp_eq_f64") >= 64 and (t, e) not in cold:
+                cold.append((t, e))
+    n_cold = sum(e - t + 1 for t, e in cold)
+    n_outer = outer[1] - outer[0] + 1 - (hot[1] - hot[0] + 1) - n_cold
     out += ["| block | instructions |", "|---|---|"]
+    if cold:
+        out.append("| float64 fallback of the first-argmin, %d blocks out of line behind the loop (one per unrolled step; a step runs its block "
+                   "only when a lane of the wave has a high-dword tie): NOT part of the rows below | %d |" % (len(cold), n_cold))
     if rnd:
         seg = body[rnd[0]:rnd[1] + 1]
         n_rnd = len(seg)
@@ -147,6 +175,14 @@ def chunk_table(body, addr, hot):
     return out
 
 
+EQ = ["v_cmp_eq_f64"]          # main(): "v_cmp_eq_u32" for a kernel that has the 32-bit first-argmin (its float64 scan is the cold fallback)
+
+
+def eq_compares(seg):
+    """Equality compares of the step's first-argmin in a stretch of code: 64 per trellis step."""
+    return sum(1 for _, o, _ in seg if o == EQ[0])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernel", default=DEFAULT)
@@ -157,25 +193,27 @@ def main():
     if not body:
         sys.exit("kernel not found: " + a.kernel)
     addr = {ad: i for i, (ad, _, _) in enumerate(body)}
-    best = None
+    if sum(1 for _, o, _ in body if o == "v_cmp_eq_u32") >= 64:
+        EQ[0] = "v_cmp_eq_u32"
+    # the step loop: of the backward branches whose span holds the most trellis steps (64 equality compares each), the SMALLEST span.
+    # (The loop around it, which flushes the output tile every 96 steps, holds the same steps in a larger span; the out-of-line
+    # fallback blocks of the 32-bit first-argmin sit behind the loop and branch back into it: their spans hold fewer steps.)
+    cands = []
     for i, (ad, op, args) in enumerate(body):
         if op.startswith("s_cbranch") or op == "s_branch":
             m = re.search(r"\+0x([0-9a-f]+)>\s*$", args)
             if not m:
                 continue
             # the operand is printed relative to the kernel symbol: resolve through the first instruction's address
-            tgt = body[0][0] + int(m.group(1), 16)
-            j = addr.get(tgt)
-            # the step loop: the SMALLEST backward branch whose span holds at least one whole trellis step (64 first-equal compares);
-            # the loop around it flushes the output tile every 96 steps
-            if j is not None and j < i and sum(1 for _, o, _ in body[j:i + 1] if o == "v_cmp_eq_f64") >= 64 and \
-                    (best is None or i - j < best[1] - best[0]):
-                best = (j, i)
+            j = addr.get(body[0][0] + int(m.group(1), 16))
+            if j is not None and j < i and eq_compares(body[j:i + 1]) >= 64:
+                cands.append((-(eq_compares(body[j:i + 1]) // 64), i - j, j, i))
+    best = min(cands)[2:] if cands else None
     if best is None:
         sys.exit("no loop found")
     loop = body[best[0]:best[1] + 1]
-    steps = sum(1 for _, op, _ in loop if op == "v_cmp_eq_f64") // 64
-    cnt = collections.Counter(classify(op, args) for _, op, args in loop)
+    steps = eq_compares(loop) // 64
+    cnt = collections.Counter(classify(op, args, loop[k - 1][1] if k else None) for k, (_, op, args) in enumerate(loop))
     valu = sum(v for k, v in cnt.items() if not k.startswith(("LDS", "memory", "s_", "scalar")))
     lines = ["kernel: %s" % a.kernel,
              "hot loop: %d instructions per trip, %d trellis steps per trip (kernel: %d instructions)" % (len(loop), steps, len(body)), "",

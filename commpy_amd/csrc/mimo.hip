@@ -114,7 +114,9 @@ __device__ __forceinline__ void householder_qr(double2 *A, int nr, int w, int ke
         const double2 alpha = make_double2(-ph.x * nx, -ph.y * nx);
         const double2 v0 = csub(x0, alpha);
         const double vn2 = abs2(v0) + tail;
-        const bool reflect = nx > 0.0 && vn2 > 0.0;
+        // a zero column is skipped; a NaN column reflects, so that the NaN reaches every later column and Q^H y as it does in
+        // LAPACK's QR (skipping it would leave a finite R and y behind a NaN entry of H)
+        const bool reflect = !(nx <= 0.0) && !(vn2 <= 0.0);
         if (reflect) {
             for (int j = k + 1 + lane; j < w; j += WAVE) {
                 double2 s = make_double2(v0.x * A[k * w + j].x + v0.y * A[k * w + j].y, v0.x * A[k * w + j].y - v0.y * A[k * w + j].x);

@@ -129,6 +129,10 @@ SYMBOLS = {
     "cpx_best_first": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_double, c_void_p, c_void_p]),
     "cpx_best_first_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_double, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
+    "cpx_mimo_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "cpx_mimo_linear_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
     "cpx_mimo_list_dist": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "cpx_mimo_list_dist_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                        c_void_p]),

@@ -229,6 +229,14 @@ private:
     std::vector<void *> bufs_;
 };
 
+// the MIMO entry points' shared checks and staging (mimo.hip; also used by mimo_linear.hip)
+int mimo_check(const ::cpx_modem *md, int64_t B, int nr, int nt, const char *what);   // handle, device and sizes
+// the host-buffer wrappers' checks, ensure_device() first
+int mimo_host_check(const double *y, const double *h, int64_t B, int nr, int nt, const void *out);
+// y and H staged; an empty batch stages neither
+int mimo_in(HostStage &s, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, const double **dy,
+            const double **dh);
+
 // a block of the scratch arena (not owned: released by cpx_release_workspace)
 struct ArenaBuf {
     void *p = nullptr;

@@ -24,6 +24,35 @@
 
 using namespace cpx;
 
+// shared with mimo_linear.hip (cpx_internal.h)
+namespace cpx {
+
+int mimo_check(const cpx_modem *md, int64_t B, int nr, int nt, const char *what) {
+    CPX_REQUIRE(md, CPX_EINVAL, "%s: null modem", what);
+    if (int rc = check_handle_device(md->device, what)) return rc;
+    CPX_REQUIRE(B >= 0 && nr >= 1 && nt >= 1, CPX_EINVAL, "%s: need B >= 0, nr >= 1, nt >= 1", what);
+    return CPX_OK;
+}
+
+// the host-buffer wrappers' checks, ensure_device() first
+int mimo_host_check(const double *y, const double *h, int64_t B, int nr, int nt, const void *out) {
+    if (int rc = ensure_device()) return rc;
+    CPX_REQUIRE(B >= 0 && nr >= 1 && nt >= 1, CPX_EINVAL, "mimo: need B >= 0, nr >= 1, nt >= 1");
+    CPX_REQUIRE((y && h && out) || B == 0, CPX_EINVAL, "mimo: null pointer");
+    return CPX_OK;
+}
+
+// y and H staged; an empty batch stages neither (its device entry point gets null y and H, and its outputs are empty downloads)
+int mimo_in(HostStage &s, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, const double **dy,
+            const double **dh) {
+    *dy = *dh = nullptr;
+    if (B == 0) return CPX_OK;
+    if (int rc = s.in(y, 16 * size_t(B) * nr, dy)) return rc;
+    return s.in(h, 16 * size_t(nr) * nt * (h_batched ? size_t(B) : 1), dh);
+}
+
+}  // namespace cpx
+
 namespace {
 
 constexpr int WAVE = 64;
@@ -276,13 +305,6 @@ __global__ __launch_bounds__(WAVE) void kbest_kernel(const double2 *__restrict__
 bool kbest_forced_general() { return mode_of(Switch::kbest_path) == 1; }   // cpx_kbest_set_path / CPX_KBEST_PATH
 
 int grid_for(int64_t B) { return int(B < 1048576 ? B : 1048576); }
-
-int mimo_check(const cpx_modem *md, int64_t B, int nr, int nt, const char *what) {
-    CPX_REQUIRE(md, CPX_EINVAL, "%s: null modem", what);
-    if (int rc = check_handle_device(md->device, what)) return rc;
-    CPX_REQUIRE(B >= 0 && nr >= 1 && nt >= 1, CPX_EINVAL, "%s: need B >= 0, nr >= 1, nt >= 1", what);
-    return CPX_OK;
-}
 
 // K clipped to what the search can ever hold (m^nt survivors), saturating
 int kbest_effective_K(int K, int m, int nt) {
@@ -642,23 +664,6 @@ int bf_run(const cpx_modem *md, const double *d_y, const double *d_h, int h_batc
     CPX_HIP(hipGetLastError());
     note_kernel("best_first_kernel<global> (m %d, %dx%d, %zu B per vector)", m, nr, nt, L.bytes);
     return CPX_OK;
-}
-
-// the host-buffer wrappers' checks, ensure_device() first
-int mimo_host_check(const double *y, const double *h, int64_t B, int nr, int nt, const void *out) {
-    if (int rc = ensure_device()) return rc;
-    CPX_REQUIRE(B >= 0 && nr >= 1 && nt >= 1, CPX_EINVAL, "mimo: need B >= 0, nr >= 1, nt >= 1");
-    CPX_REQUIRE((y && h && out) || B == 0, CPX_EINVAL, "mimo: null pointer");
-    return CPX_OK;
-}
-
-// y and H staged; an empty batch stages neither (its device entry point gets null y and H, and its outputs are empty downloads)
-int mimo_in(HostStage &s, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, const double **dy,
-            const double **dh) {
-    *dy = *dh = nullptr;
-    if (B == 0) return CPX_OK;
-    if (int rc = s.in(y, 16 * size_t(B) * nr, dy)) return rc;
-    return s.in(h, 16 * size_t(nr) * nt * (h_batched ? size_t(B) : 1), dh);
 }
 
 }  // namespace

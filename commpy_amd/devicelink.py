@@ -333,6 +333,11 @@ class DeviceMimoLink:
     ``noise_std / 2`` while the detector is told ``noise_std**2`` (quirk B7).  Random streams are Philox (seed, call, stage), so
     BERs are statistically, not bit-wise, the host link's.
 
+    ``detector`` 'zf' or 'mmse' is the linear detector (``cpx_mimo_linear_dev`` on the link's buffers): 'hard' output makes an
+    uncoded link, 'soft' output with ``ldpc_params`` an LDPC-coded one.  Because of quirk B7 the true N0 is ``noise_std**2 / 2``:
+    'mmse' regularises with ``noise_std**2 / (2 Es)``, and the LLRs are scaled with ``noise_std**2`` itself, exactly as the K-best
+    soft path is.  ``idd_iters > 0`` with a linear detector is refused.
+
     ``idd_iters >= 1`` (LDPC-coded 'kbest' with 'soft' output only) runs iterative detection and decoding, ``links.idd_decoder``
     with a list detector: the K-best list is searched once and its distances computed once, a first detector pass without prior
     (LLRs clipped to ``idd_clip``) fills the decoder's input, then ``idd_iters`` rounds of LDPC decode and detector / decoder
@@ -385,11 +390,13 @@ class DeviceMimoLink:
         if m != 1 << nb:
             raise ValueError('the modem must have 2^num_bits_symbol points')
         self.coded = ldpc_params is not None
-        uncoded_ok = detector == 'ml' and output_type == 'hard' or detector == 'kbest' and output_type == 'hard'
-        coded_ok = detector == 'kbest' and output_type == 'soft' or detector == 'best_first'
+        linear = detector in ('zf', 'mmse')
+        uncoded_ok = detector in ('ml', 'kbest', 'zf', 'mmse') and output_type == 'hard'
+        coded_ok = detector in ('kbest', 'zf', 'mmse') and output_type == 'soft' or detector == 'best_first'
         if not (coded_ok if self.coded else uncoded_ok):
-            raise ValueError("detector %r with output %r %s an LDPC code is not a device MIMO link: uncoded links take 'ml' or "
-                             "'kbest' with 'hard' output, coded ones 'kbest' with 'soft' output or 'best_first'"
+            raise ValueError("detector %r with output %r %s an LDPC code is not a device MIMO link: uncoded links take 'ml', "
+                             "'kbest', 'zf' or 'mmse' with 'hard' output, coded ones 'kbest', 'zf' or 'mmse' with 'soft' output or "
+                             "'best_first'"
                              % (detector, output_type, 'and' if self.coded else 'without'))
         self.idd_iters, self.idd_clip, self.idd_decision = _whole(idd_iters), float(idd_clip), idd_decision
         if self.idd_iters < 0:
@@ -415,6 +422,9 @@ class DeviceMimoLink:
             if self.idd_iters:
                 _list_checks(self.modem, self.K, self.idd_clip, nr, nt)
                 self.Ke = min(self.K, m ** nt)
+        elif linear:
+            if nt > 8 and 16 * (m + nr * nt + nr + 2 * nt * nt + 4 * nt) > _ML_LDS:
+                raise ValueError('mimo_linear: the state of one %dx%d vector exceeds the kernel\'s LDS' % (nr, nt))
         else:
             self.stacks = _bf_stacks(nr, nt, stack_size)
             if nr > 64:
@@ -503,6 +513,12 @@ class DeviceMimoLink:
             ck(lib.cpx_kbest_hard_dev(md, bufs['y'].ptr, bufs['h'].ptr, 1, V, nr, nt, self.K, bufs['idx'].ptr, None))
         elif self.detector == 'kbest':
             ck(lib.cpx_kbest_soft_dev(md, bufs['y'].ptr, bufs['h'].ptr, 1, V, nr, nt, self.K, noise_std ** 2, bufs['llr'].ptr, None))
+        elif self.detector in ('zf', 'mmse'):
+            # the true N0 is noise_std^2 / 2 (quirk B7); the LLR scale is what the K-best soft path is given
+            reg = 0.0 if self.detector == 'zf' else noise_std ** 2 / (2.0 * self.modem.Es)
+            ck(lib.cpx_mimo_linear_dev(md, bufs['y'].ptr, bufs['h'].ptr, 1, V, nr, nt, reg, noise_std ** 2,
+                                       None if self.coded else bufs['idx'].ptr, bufs['llr'].ptr if self.coded else None, None, None,
+                                       None))
         else:
             ck(lib.cpx_best_first_dev(md, bufs['y'].ptr, bufs['h'].ptr, 1, V, nr, nt, _lib.ptr(self.stacks), self.llr_max, None,
                                       bufs['llr'].ptr, None, None))

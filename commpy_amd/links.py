@@ -17,7 +17,7 @@ six-argument decoders recognised by arity).
 MIMO channels (``commpy_amd.channels.MIMOFlatChannel``) always run one transmission at a time, as the reference's loop
 does (links.py:229-249).  ``receive`` is then called once per received vector with its channel matrix -- or, when it is
 marked ``batched``, once per transmission with ``y [nb_vect, nr]`` and ``H [nb_vect, nr, nt]`` (one GPU launch);
-``mimo_receiver`` builds such a receiver around the K-best, ML or best-first kernels; ``idd_decoder`` builds the
+``mimo_receiver`` builds such a receiver around the K-best, ML, best-first or linear (ZF / MMSE) kernels; ``idd_decoder`` builds the
 reference's iterative detection-and-decoding decoder from host callbacks.
 """
 import operator
@@ -47,8 +47,25 @@ def mimo_receiver(modem, detector='kbest', K=16, output_type='hard', stack_size=
     ``llr_max``; ``output_type`` is not used).  Bits are the modem's labels, MSB first, antenna after antenna: what
     ``modem.demodulate(kbest(y_i, H_i, constellation, K), 'hard')`` gives vector by vector, and what
     ``best_first_detector(y_i, H_i, constellation, stack_size, noise_var, demode, llr_max)`` gives with
-    ``demode = modem.demodulate(., 'hard')``."""
-    from commpy_amd.modulation import _bf_stacks, best_first_batch, kbest_batch, mimo_ml_batch
+    ``demode = modem.demodulate(., 'hard')``.
+
+    ``detector`` 'zf' or 'mmse' (hard or soft): ``linear_batch``.  The complex channel draws noise of variance ``noise_var / 2``
+    while the receiver is told ``noise_var`` (channels.py, quirk B7), so 'mmse' regularises with ``noise_var / (2 Es)``, the true
+    N0 / Es; the LLR scale is ``noise_var`` itself, exactly as on the K-best soft path."""
+    from commpy_amd.modulation import _bf_stacks, _linear_run, best_first_batch, kbest_batch, mimo_ml_batch
+    if detector in ('zf', 'mmse'):
+        if output_type not in ('hard', 'soft'):
+            raise ValueError('output_type must be "hard" or "soft"')
+        bit_shifts = np.arange(modem.num_bits_symbol - 1, -1, -1)
+
+        def receive_linear(y, h, constellation, noise_var):
+            reg = 0.0 if detector == 'zf' else float(noise_var) / (2.0 * modem.Es)
+            if output_type == 'soft':
+                return _linear_run(np.atleast_2d(y), h, modem, reg, noise_var, ('llr',))['llr'].reshape(-1)
+            idx = _linear_run(np.atleast_2d(y), h, modem, reg, noise_var, ('idx',))['idx']
+            return ((idx[:, :, None] >> bit_shifts) & 1).reshape(-1)
+        receive_linear.batched = True
+        return receive_linear
     if detector == 'best_first':
         sizes = tuple(stack_size)
         if len(sizes) < 1 or min(operator.index(s) for s in sizes) < 1:

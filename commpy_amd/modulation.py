@@ -7,7 +7,8 @@ the host; ``demodulate`` ('hard' and 'soft') runs on the GPU through ``cpx_demod
 GPU too (csrc/mimo.hip), with batched forms ``mimo_ml_batch`` / ``kbest_batch`` for throughput; The soft-output
 ``best_first_detector`` (modulation.py:422-565) runs on the GPU as well, with ``best_first_batch`` as its batched form.
 ``list_apriori_batch`` is a max-log list detector that takes a-priori LLRs (csrc/mimo_idd.hip), ``apriori_detector`` its form
-for ``links.idd_decoder``.
+for ``links.idd_decoder``.  The linear detectors -- zero forcing and MMSE, hard and soft -- are ``zf_detector``, ``mmse_detector``,
+``linear_batch`` and ``linear_equalize_batch`` (csrc/mimo_linear.hip; not in the reference).
 ``max_log_approx`` and ``bit_lvl_repr`` are small host functions.  ``ofdm_tx`` / ``ofdm_rx`` (modulation.py:265-296) run on the
 GPU too (csrc/ofdm.hip), float64 only, with the symbol-major batched forms ``ofdm_tx_batch`` / ``ofdm_rx_batch``.
 """
@@ -21,7 +22,8 @@ from commpy_amd import _lib
 from commpy_amd.utilities import signal_power
 
 __all__ = ['PSKModem', 'QAMModem', 'Modem', 'mimo_ml', 'kbest', 'max_log_approx', 'bit_lvl_repr', 'mimo_ml_batch',
-           'kbest_batch', 'best_first_detector', 'best_first_batch', 'list_apriori_batch', 'apriori_detector', 'ofdm_tx', 'ofdm_rx', 'ofdm_tx_batch', 'ofdm_rx_batch']
+           'kbest_batch', 'best_first_detector', 'best_first_batch', 'list_apriori_batch', 'apriori_detector', 'zf_detector', 'mmse_detector',
+           'linear_batch', 'linear_equalize_batch', 'ofdm_tx', 'ofdm_rx', 'ofdm_tx_batch', 'ofdm_rx_batch']
 
 
 def _gray_rank(m):
@@ -422,6 +424,111 @@ def apriori_detector(modem, K, llr_clip=500.0):
         return list_apriori_batch(np.asarray(y).reshape(1, -1), np.asarray(h), modem, K, noise_var,
                                   np.asarray(a_priori, dtype=np.float64).reshape(1, -1), llr_clip)[0]
     return detector
+
+
+# ---- linear detection: zero forcing and MMSE (csrc/mimo_linear.hip) -----------------------------------------------------------
+def _linear_reg(method, noise_var, Es, reg):
+    """(reg, noise_var) as floats, checked as the engine checks them; ``reg=None``: 0 for 'zf', ``noise_var / Es`` for 'mmse'."""
+    if method not in ('zf', 'mmse'):
+        raise ValueError("method must be 'zf' or 'mmse'")
+    noise_var = float(noise_var)
+    if noise_var != noise_var:
+        raise ValueError('noise_var is NaN')
+    if reg is None:
+        reg = 0.0 if method == 'zf' else noise_var / float(Es)
+    reg = float(reg)
+    if not reg >= 0:
+        raise ValueError('reg must be zero or positive (got %r)' % (reg,))
+    return reg, noise_var
+
+
+def _linear_run(y, h, modem, reg, noise_var, want):
+    """One ``cpx_mimo_linear`` call: ``want`` names the outputs ('idx', 'llr', 'xhat', 'nu'); returns them as a dict."""
+    y2, hh, hb, B, nr, nt = _mimo_inputs(y, h)
+    if modem.m != 1 << modem.num_bits_symbol:
+        raise ValueError('the modem must have 2^num_bits_symbol points')
+    shapes = {'idx': ((B, nt), np.int32), 'llr': ((B, nt * modem.num_bits_symbol), np.float64), 'xhat': ((B, nt), np.complex128),
+              'nu': ((B, nt), np.float64)}
+    out = {k: np.zeros(*shapes[k]) for k in want}
+    if not out:
+        raise ValueError('no output requested')
+    if B:
+        ptrs = [_lib.ptr(out[k]) if k in out else None for k in ('idx', 'llr', 'xhat', 'nu')]
+        _lib.check(_lib.load().cpx_mimo_linear(modem._device_handle(), _lib.ptr(y2), _lib.ptr(hh), hb, B, nr, nt, float(reg),
+                                               float(noise_var), *ptrs))
+    return out
+
+
+def linear_batch(y, h, modem, noise_var, method='mmse', output_type='hard', reg=None):
+    """Linear detection of every row of ``y [B, nr]`` in one launch; ``h`` is [nr, nt] (shared) or [B, nr, nt]; any nr, nt >= 1.
+
+    ``A = h^H h + reg I``, ``z = A^-1 h^H y``, ``a_i = (A^-1)_ii``; the unbiased estimate is ``xhat_i = z_i / (1 - reg a_i)`` and its
+    noise variance ``nu_i = noise_var a_i / (1 - reg a_i)``.  ``reg=None`` means 0 for ``method='zf'`` (``xhat = pinv(h) y``) and
+    ``noise_var / modem.Es`` for 'mmse'.  'hard': symbols [B, nt] of ``modem.constellation``, the nearest point per stream (a tie
+    to the lowest index); 'soft': LLRs [B, nt * num_bits_symbol], per stream ``(min over the points with bit 1 of |xhat_i - s|^2 -
+    min over those with bit 0) / (2 nu_i)`` with the modem's labels, MSB first -- positive: bit 0, the scale of ``kbest_batch``'s
+    soft output.  A vector whose ``A`` is not positive definite (singular h under 'zf', nt > nr with reg = 0) or that holds a NaN /
+    inf gives NaN LLRs and point 0; it affects no other vector."""
+    if output_type not in ('hard', 'soft'):
+        raise ValueError('output_type must be "hard" or "soft"')
+    reg, noise_var = _linear_reg(method, noise_var, modem.Es, reg)
+    if output_type == 'hard':
+        return modem.constellation[_linear_run(y, h, modem, reg, noise_var, ('idx',))['idx']]
+    return _linear_run(y, h, modem, reg, noise_var, ('llr',))['llr']
+
+
+def linear_equalize_batch(y, h, noise_var, method, reg=None, Es=1.0):
+    """The equaliser of ``linear_batch`` alone: ``(xhat [B, nt] complex, nu [B, nt])``, the unbiased estimates and their noise
+    variances.  ``reg=None``: 0 for 'zf', ``noise_var / Es`` for 'mmse'.  Rows of NaN mark a vector that failed."""
+    reg, noise_var = _linear_reg(method, noise_var, Es, reg)
+    out = _linear_run(y, h, _modem_for(np.array([-1.0, 1.0])), reg, noise_var, ('xhat', 'nu'))
+    return out['xhat'], out['nu']
+
+
+def _linear_detector(method, y, h, constellation, noise_var, output_type, demode):
+    h = np.asarray(h)
+    if h.ndim != 2:
+        raise ValueError('h must be [nr, nt]')
+    if output_type not in ('hard', 'soft'):
+        raise ValueError('output_type must be "hard" or "soft"')
+    pts = np.asarray(constellation)
+    kind = complex if isinstance(pts[0], complex) else float
+    md = _modem_for(pts)
+    reg, noise_var = _linear_reg(method, noise_var, md.Es, None)
+    y1 = np.asarray(y).reshape(1, -1)
+    if output_type == 'hard':
+        return pts[_linear_run(y1, h, md, reg, noise_var, ('idx',))['idx'][0]].astype(kind)
+    nb = md.num_bits_symbol
+    index_bits = ((np.arange(md.m)[:, None] >> np.arange(nb - 1, -1, -1)) & 1).astype(np.uint8)
+    labels = index_bits if demode is None else _demode_labels(demode, pts, nb)
+    if np.array_equal(labels, index_bits):
+        return _linear_run(y1, h, md, reg, noise_var, ('llr',))['llr'][0]
+    out = _linear_run(y1, h, md, reg, noise_var, ('xhat', 'nu'))
+    xhat, nu = out['xhat'][0], out['nu'][0]
+    diff = xhat[:, None] - pts.astype(complex)[None, :]
+    dist = diff.real * diff.real + diff.imag * diff.imag                       # [nt, m]
+    llr = np.empty((h.shape[1], nb))
+    with np.errstate(all='ignore'):
+        for k in range(nb):
+            one = labels[:, k] == 1
+            mn1 = np.min(np.where(one[None, :], dist, np.inf), axis=1)
+            mn0 = np.min(np.where(one[None, :], np.inf, dist), axis=1)
+            llr[:, k] = (mn1 - mn0) / (2 * nu)
+    llr[np.isnan(nu)] = np.nan
+    return llr.reshape(-1)
+
+
+def zf_detector(y, h, constellation, noise_var, output_type='hard', demode=None):
+    """Zero-forcing detection of one vector (``linear_batch`` with ``method='zf'``), the argument order of ``kbest``.  'hard': the
+    nearest point of ``xhat = pinv(h) y`` per stream, as the constellation's dtype; 'soft': LLRs [nt * log2 m] with ``demode``'s
+    bits (None: the index bits, MSB first).  A ``demode`` equal to the index bits runs on the device; any other is applied on the
+    host to the device's ``xhat`` and ``nu``, as ``kbest`` does with its list."""
+    return _linear_detector('zf', y, h, constellation, noise_var, output_type, demode)
+
+
+def mmse_detector(y, h, constellation, noise_var, output_type='hard', demode=None):
+    """Unbiased MMSE detection of one vector: ``zf_detector`` with ``reg = noise_var / Es`` (Es: the constellation's mean energy)."""
+    return _linear_detector('mmse', y, h, constellation, noise_var, output_type, demode)
 
 
 def max_log_approx(y, h, noise_var, pts_list, demode):

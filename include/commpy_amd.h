@@ -415,6 +415,33 @@ int cpx_best_first_dev(const cpx_modem *m, const double *d_y_re_im, const double
                        int nt, const int32_t *stack_size, double llr_max, const uint8_t *d_labels, double *d_llr,
                        int32_t *d_iters, void *stream);
 
+/* ---- linear MIMO detection: zero forcing and MMSE (csrc/mimo_linear.hip) -----------------------------------------
+ * Not in the reference.  y, h, h_batched, B, nr, nt and the modem as for the detectors above; any nr >= 1 and nt >= 1 (nt > nr too);
+ * the modem must have m = 2^nbits points.  float64 only: cpx_set_precision is ignored and there is no path switch, nt picks the kernel
+ * (nt <= 8: one vector per lane, registers; above: one wave per vector, LDS).  Per vector, with a regulariser reg >= 0:
+ *   A = H^H H + reg I = L L^H (Cholesky),  z = A^-1 H^H y,  a_i = (A^-1)_ii,  g_i = 1 - reg a_i
+ *   xhat [B][nt] complex  = z_i / g_i, the unbiased estimate;  nu [B][nt] = noise_var a_i / g_i, its noise variance.
+ *   reg = 0 is zero forcing (xhat = H^+ y, nu_i = noise_var a_i), reg = N0 / Es unbiased MMSE: one kernel, only reg differs.
+ *   idx [B][nt]           the first minimum of |xhat_i - s|^2 over the points in index order (strict <: a tie goes to the lowest
+ *                         index, a NaN estimate to index 0, as cpx_mimo_ml's all-NaN metric);
+ *   llr [B][nt * nbits]   (min_{s: bit k = 1} |xhat_i - s|^2 - min_{s: bit k = 0} |xhat_i - s|^2) / (2 nu_i) at [i * nbits + k], bit k
+ *                         of a point = the MSB-first bits of its index (the modem's labels); positive: bit 0; the factor 2 is
+ *                         cpx_kbest_soft's, so that either output feeds the same decoder.
+ * Each output is nullable; at least one must be given.  A vector FAILS when a Cholesky pivot is not a positive finite number
+ * (singular H under zero forcing, nt > nr with reg = 0, NaN / inf in H; positive in float64's terms: the pivot of column j must
+ * exceed 4 (nr + nt) 2^-52 A_jj, what rounding can leave of an exactly singular matrix's pivot), when H^H y is not finite (NaN / inf in y) or when some g_i is
+ * not positive: its xhat, nu and llr are NaN and its idx 0; no other vector is affected.  Every vector goes through the same
+ * operations in the same order: outputs are bit-identical across batch sizes, positions in the batch, streams, shared / replicated H,
+ * the host and device forms and whichever outputs are requested.
+ * CPX_EINVAL: reg negative or NaN, noise_var NaN, no output requested, then a null modem / another device's modem / B < 0 / nr < 1 /
+ * nt < 1, a modem without 2^nbits points, null y or h with B > 0; CPX_ELIMIT: a constellation (nt <= 8) or the state of one vector
+ * (nt >= 9) above 64 KB of LDS.  B = 0 returns CPX_OK without a launch.  cpx_last_kernel names what ran, with nt, nr and m.
+ * cpx_mimo_linear_dev: device pointers, asynchronous on `stream`. */
+int cpx_mimo_linear(const cpx_modem *m, const double *y_re_im, const double *h_re_im, int h_batched, int64_t B, int nr, int nt,
+                    double reg, double noise_var, int32_t *idx, double *llr, double *xhat_re_im, double *nu);
+int cpx_mimo_linear_dev(const cpx_modem *m, const double *d_y_re_im, const double *d_h_re_im, int h_batched, int64_t B, int nr, int nt,
+                        double reg, double noise_var, int32_t *d_idx, double *d_llr, double *d_xhat_re_im, double *d_nu, void *stream);
+
 /* ---- list detection with a-priori LLRs, iterative detection and decoding (csrc/mimo_idd.hip) -------------------------------
  * A max-log soft MIMO detector over a candidate list that accepts priors, and the detector / decoder exchange of
  * commpy/links.py:345-407 (idd_decoder) on device buffers.  The list -- cand [B][Ke][nt] int32 constellation indices and count [B],

@@ -13,6 +13,8 @@ struct Philox {
     uint32_t c[4];
 };
 
+// counter (c0 c1 c2 c3) = (ctr_lo, ctr_hi) = (element index, stream id), key (k0 k1) = seed, each split low word first; the contract is
+// written out in include/commpy_amd.h ("Random streams") and modelled by tests/rng_model.py, which holds the known-answer vectors
 __device__ __forceinline__ Philox philox4x32_10(uint64_t ctr_lo, uint64_t ctr_hi, uint64_t key) {
     uint32_t c0 = (uint32_t)ctr_lo, c1 = (uint32_t)(ctr_lo >> 32), c2 = (uint32_t)ctr_hi, c3 = (uint32_t)(ctr_hi >> 32);
     uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
@@ -27,7 +29,7 @@ __device__ __forceinline__ Philox philox4x32_10(uint64_t ctr_lo, uint64_t ctr_hi
     return Philox{{c0, c1, c2, c3}};
 }
 
-// uniform in (0, 1] with 53 bits
+// uniform in (0, 1] with 53 bits: the top 27 bits of hi above the top 26 bits of lo, plus one, times 2^-53 (exact in float64)
 __device__ __forceinline__ double u01(uint32_t hi, uint32_t lo) {
     const uint64_t m = ((uint64_t)(hi >> 5) << 26) | (uint64_t)(lo >> 6);
     return ((double)m + 1.0) * (1.0 / 9007199254740992.0);

@@ -8,7 +8,8 @@
 //   BSC / BEC          commpy/channels.py:630-673 (one uniform draw per bit; flipped / erased to -1 where it is <= p) -- round 5
 //   error counting     links.py:252-256 (per-chunk XOR popcount)
 // Bit-exact stages (encode, (de)puncture, modulate, error count) are tested against the host mirror and
-// the reference goldens; the random stages are statistical (different generator than the reference).
+// the reference goldens; the random stages are not NumPy's MT19937 draws but an exactly specified function of (seed, stream id,
+// element index) (include/commpy_amd.h, "Random streams"), tested against the NumPy model tests/rng_model.py.
 // All kernels are byte/element-wise streams: HBM bound, one codeword row or one element per lane.
 #include "cpx_internal.h"
 #include "cpx_rng.h"

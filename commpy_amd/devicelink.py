@@ -9,8 +9,11 @@ with the semantics of the reference's ``Wifi80211.link_performance`` chain
 (/root/reference/commpy/wifi80211.py:132-216, links.py:155-267, channels.py:37-74), including quirk B7
 (complex noise of per-component std ``noise_std/2`` while the demodulator is told ``noise_std**2``) and
 quirk B1 (decimal generators) unless ``generator_matrix`` is given.  Only the error counters come back
-to the host.  The random streams are Philox-based, so results are statistically -- not bit-wise --
-comparable with the reference; the deterministic stages are bit-exact (tests/test_devicelink_gpu.py).
+to the host.  The random streams are not NumPy's MT19937 draws: they are an exactly specified function of
+(seed, stream id, element index) (Philox4x32-10; include/commpy_amd.h, "Random streams"), tested against the NumPy
+model tests/rng_model.py, so BERs agree with the reference's in distribution, not bit for bit.  Call number c of a link
+(1, 2, ...) draws its message bits on stream 2 c and its noise on stream 2 c + 1; the deterministic stages are
+bit-exact (tests/test_devicelink_gpu.py).
 
 ``DeviceMimoLink`` does the same for a MIMO link over a ``MIMOFlatChannel`` (bits -> [LDPC encode] -> Kronecker fading channel ->
 ML / K-best / best-first detector -> [LDPC decode] -> error count), the device counterpart of ``LinkModel`` with ``mimo_receiver``;
@@ -62,7 +65,8 @@ def _buffer_set(link, key, build):
 
 class DeviceBscLink:
     """BASELINE config 1 end to end in HBM: random messages -> conv_encode('term') -> BSC(p) -> hard-decision Viterbi -> bit errors
-    (the loop of /root/reference/commpy/channelcoding/tests/test_convcode.py:133-178 with channels.py:652-673 as the channel)."""
+    (the loop of /root/reference/commpy/channelcoding/tests/test_convcode.py:133-178 with channels.py:652-673 as the channel).
+    Call number c draws its messages on stream 2 c and its flips on stream 2 c + 1 of ``seed`` (tests/rng_model.py)."""
 
     def __init__(self, trellis, block_bits=64, tb_depth=None, seed=1):
         self.lib = _lib.load()
@@ -330,8 +334,10 @@ class DeviceMimoLink:
     bits of each block).  A transmission carries ``send_chunk`` message bits, rounded like ``LinkModel._prepare``; coded, that is
     ``send_chunk / k`` codewords sent one after another, as ``triang_ldpc_systematic_encode(...).reshape(-1, order='F')`` lays them
     out.  The SNR convention is channels.py's: ``noise_std = sqrt(2 nt Es / (rate 10^(SNR/10)))``, noise of per-component std
-    ``noise_std / 2`` while the detector is told ``noise_std**2`` (quirk B7).  Random streams are Philox (seed, call, stage), so
-    BERs are statistically, not bit-wise, the host link's.
+    ``noise_std / 2`` while the detector is told ``noise_std**2`` (quirk B7).  The random streams are not NumPy's MT19937 draws
+    but an exactly specified function of (seed, stream id, element index), tested against tests/rng_model.py: call number c draws
+    its message bits on stream 3 c, its fading on 3 c + 1 and its noise on 3 c + 2, so BERs are the host link's in distribution,
+    not bit for bit.
 
     ``detector`` 'zf' or 'mmse' is the linear detector (``cpx_mimo_linear_dev`` on the link's buffers): 'hard' output makes an
     uncoded link, 'soft' output with ``ldpc_params`` an LDPC-coded one.  Because of quirk B7 the true N0 is ``noise_std**2 / 2``:

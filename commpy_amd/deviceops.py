@@ -161,7 +161,8 @@ def _binary_channel_gpu(which, input_bits, p, seed, stream_id):
 
 def bsc_gpu(input_bits, p_t, seed=0, stream_id=0):
     """``bsc(input_bits, p_t)`` (channels.py:652-673) on the GPU: every bit flipped with probability ``p_t``.  The draws come
-    from the Philox stream ``(seed, stream_id)``, not from NumPy's global generator: statistically, not bit-wise, the reference's."""
+    from the Philox stream ``(seed, stream_id)``, not from NumPy's MT19937 generator: an exactly specified function of (seed,
+    stream id, position) (include/commpy_amd.h, "Random streams"), tested against the NumPy model tests/rng_model.py."""
     return _binary_channel_gpu("cpx_bsc_dev", input_bits, p_t, seed, stream_id)
 
 
@@ -335,9 +336,9 @@ def _require_complex(channel):
 def mimo_channel_gpu(channel, modem, bits, seed=0, stream_id=0):
     """``MIMOFlatChannel.propagate(modem.modulate(bits))`` on the GPU: returns ``(y [V, nr], H [V, nr, nt])`` for the
     ``V = len(bits) / (nt * num_bits_symbol)`` vectors the bits fill (a partial vector is a ValueError).  The fading G and the noise
-    come from the Philox streams ``(seed, 2 stream_id)`` and ``(seed, 2 stream_id + 1)`` instead of NumPy's generator (statistically,
-    not bit-wise, the reference's); ``H = sqrtm(Rr) G sqrtm(Rt).T + mean`` and the noise of per-component std ``noise_std / 2``
-    follow channels.py (quirk B7)."""
+    come from the Philox streams ``(seed, 2 stream_id)`` and ``(seed, 2 stream_id + 1)`` instead of NumPy's MT19937 generator (an
+    exactly specified function of seed, stream id and element index, tested against tests/rng_model.py);
+    ``H = sqrtm(Rr) G sqrtm(Rt).T + mean`` and the noise of per-component std ``noise_std / 2`` follow channels.py (quirk B7)."""
     _require_complex(channel)
     if channel.noise_std is None:
         raise AssertionError('Noise standard deviation must be set before propagation.')

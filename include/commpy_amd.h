@@ -528,6 +528,20 @@ int cpx_mimo_hard_errors_dev(const int32_t *d_idx, int nb, const uint8_t *d_msg,
  *   cpx_count_errors_dev      errs[b][c] = sum(msg[b, chunk c] ^ dec[b, chunk c]) (links.py:252-256)
  *   cpx_scale_f64_dev         y = a*x, e.g. the sign flip between Modem.demodulate (log P1/P0) and ldpc_bp_decode
  *                             (log P0/P1), test_ldpc.py:53-54
+ *
+ * Random streams (csrc/cpx_rng.h; modelled by tests/rng_model.py).  The draws are not NumPy's MT19937 stream: every one is an exactly
+ * specified function of (seed, stream_id, element index i), so a kernel may regenerate any of them anywhere.
+ *   words      (w0, w1, w2, w3) = Philox4x32-10 (Salmon et al., SC'11) of the counter (c0, c1, c2, c3) = (i lo, i hi, stream_id lo,
+ *              stream_id hi) under the key (k0, k1) = (seed lo, seed hi): every 64-bit value is split low 32-bit word first.
+ *   uniform    u01(hi, lo) = m 2^-53 with m = ((hi >> 5) << 26 | lo >> 6) + 1 in [1, 2^53]: the top 27 bits of `hi` above the top 26
+ *              bits of `lo`; u01 is in (0, 1] and exact in float64.
+ *   bits       cpx_random_bits_dev: message bit 16 i + j is bit j (LSB first) of the low 16 bits of w0 at counter i.
+ *   bsc / bec  two draws per counter: position 2 i from u01(w0, w1), position 2 i + 1 from u01(w2, w3), both at counter i; a position
+ *              is flipped / erased where (m - 1) 2^-53 <= p, the [0, 1) draw of the reference's `random(n) <= p`.
+ *   awgn       element i: u1 = u01(w0, w1), u2 = u01(w2, w3), rad = sqrt(-2 log u1),
+ *              y.re = x.re + (scale_re * rad) * cos(2 pi u2), y.im = x.im + (scale_im * rad) * sin(2 pi u2), float64 without FMA
+ *              contraction in that order; a zero scale leaves its component of x bit-identical.  log, sqrt and sincospi are the
+ *              device library's: the result is within a few ulp of the noise term of the model's.
  */
 int cpx_random_bits_dev(uint8_t *d_bits, int64_t n, uint64_t seed, uint64_t stream_id, void *stream);
 int cpx_conv_encode_batch_dev(const cpx_trellis *t, const uint8_t *d_msg, int64_t B, int64_t nmsg, int terminate,

@@ -1,5 +1,6 @@
 """Device-side link stages ("next" rows): encoder / modulator bit-exact against the host mirror and the
-reference goldens, Philox noise statistics, and the GPU-resident Wifi80211 chain against reference BER points."""
+reference goldens, moments of the Philox streams (the streams themselves: tests/test_rng_gpu.py), and the GPU-resident Wifi80211
+chain against reference BER points."""
 import ctypes
 
 import numpy as np
@@ -38,6 +39,9 @@ def test_modulate_gpu_exact(gpu):
 
 
 def test_philox_bits_and_awgn_statistics(gpu):
+    """A coarse second net under the random stages.  The streams are not NumPy's MT19937 draws; they are an exactly specified
+    function of (seed, stream id, element index), and tests/test_rng_gpu.py holds the kernels to the NumPy model of it
+    (tests/rng_model.py), whose distribution tests/test_rng_model_host.py checks.  What is asserted here are moments of one stream."""
     from commpy_amd import _lib
     from commpy_amd.devicelink import DeviceBuf
     lib = _lib.load()
@@ -273,7 +277,9 @@ def test_device_puncturing_bit_exact_vs_reference_vectors(gpu):
 
 
 def test_bsc_bec_device(gpu):
-    """cpx_bsc_dev / cpx_bec_dev (channels.py:630-673): structure exactly, rates statistically (Philox, not MT19937)."""
+    """cpx_bsc_dev / cpx_bec_dev (channels.py:630-673): structure, rates and reproducibility of one stream.  The draws are not
+    NumPy's MT19937 stream but an exactly specified function of (seed, stream id, position): tests/test_rng_gpu.py compares every
+    flip and erasure, and the `<= p` threshold, with the NumPy model tests/rng_model.py."""
     from commpy_amd import _lib
     from commpy_amd.devicelink import DeviceBuf, bec_gpu, bsc_gpu
     rs = np.random.RandomState(5)

@@ -114,6 +114,14 @@ SYMBOLS = {
     "cpx_fir_decim_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p]),
     "cpx_freq_offset": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
     "cpx_freq_offset_dev": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "cpx_multipath": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int64, c_int, c_void_p]),
+    "cpx_multipath_dev": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int64, c_int, c_void_p, c_void_p]),
+    "cpx_pilots_create": (c_int, [c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "cpx_pilots_destroy": (c_int, [c_void_p]),
+    "cpx_pilots_map": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "cpx_pilots_map_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cpx_pilots_estimate": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "cpx_pilots_estimate_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cpx_kbest_set_path": (c_int, [c_char_p]),
     "cpx_mimo_ml": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
     "cpx_mimo_ml_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),

@@ -17,7 +17,7 @@ from numpy import abs, absolute, asarray, isrealobj, sqrt, where, zeros
 from scipy.linalg import sqrtm
 from numpy.random import randn, random, standard_normal
 
-__all__ = ['SISOFlatChannel', 'MIMOFlatChannel', 'bec', 'bsc', 'awgn']
+__all__ = ['SISOFlatChannel', 'MIMOFlatChannel', 'bec', 'bsc', 'awgn', 'multipath_batch']
 
 
 class SISOFlatChannel:
@@ -240,3 +240,45 @@ def awgn(input_signal, snr_dB, rate=1.0):
         re, im = randn(n), randn(n)
         return x + (sigma * re + sigma * im * 1j)
     return x + sqrt(2 * per_axis) * randn(n)
+
+
+MULTIPATH_MAX_L = 1024
+MULTIPATH_MAX_TAPS = 2048
+
+
+def multipath_batch(x, g):
+    """Frequency-selective channel on the GPU (csrc/ofdm_chan.hip): ``y[b][r] = sum_t convolve(x[b][t], g[b][r][t])``, full length.
+    ``x [B, nt, n]`` with ``g [B, nr, nt, L]`` or ``[nr, nt, L]`` (shared by all rows) -> complex128 ``[B, nr, n + L - 1]``; the SISO
+    short forms ``x [B, n]`` with ``g [B, L]`` or ``[L]`` -> ``[B, n + L - 1]``.  No noise: add it with ``awgn`` or, on the device,
+    ``cpx_awgn_dev``.  ``L <= 1024`` and ``nr nt L <= 2048``."""
+    from commpy_amd import _lib
+    xa, ga = np.asarray(x), np.asarray(g)
+    for name, a in (('x', xa), ('g', ga)):
+        if a.dtype.kind not in 'biufc':
+            raise ValueError('%s must hold numbers, got dtype %s' % (name, a.dtype))
+    siso = xa.ndim == 2
+    if siso:
+        if ga.ndim not in (1, 2):
+            raise ValueError('x is [B, n]: g must be [L] or [B, L], got shape %s' % (ga.shape,))
+        xa = xa[:, None, :]
+        ga = ga[None, None, :] if ga.ndim == 1 else ga[:, None, None, :]
+    elif xa.ndim != 3:
+        raise ValueError('x must be [B, nt, n] or [B, n], got shape %s' % (xa.shape,))
+    if ga.ndim not in (3, 4):
+        raise ValueError('x is [B, nt, n]: g must be [nr, nt, L] or [B, nr, nt, L], got shape %s' % (ga.shape,))
+    B, nt, n = xa.shape
+    nr, L = ga.shape[-3], ga.shape[-1]
+    if ga.shape[-2] != nt or (ga.ndim == 4 and ga.shape[0] != B):
+        raise ValueError('shape mismatch: x %s, g %s' % (xa.shape, ga.shape))
+    if nt < 1 or nr < 1 or L < 1:
+        raise ValueError('nt = %d, nr = %d, L = %d, need at least 1 of each' % (nt, nr, L))
+    if B and n < 1:
+        raise ValueError('n = 0 (an empty row cannot be convolved)')
+    if L > MULTIPATH_MAX_L or nr * nt * L > MULTIPATH_MAX_TAPS:
+        raise ValueError('L = %d, nr nt L = %d: above the engine limits of %d and %d' % (L, nr * nt * L, MULTIPATH_MAX_L, MULTIPATH_MAX_TAPS))
+    xa = np.ascontiguousarray(xa, dtype=np.complex128)
+    ga = np.ascontiguousarray(ga, dtype=np.complex128)
+    out = np.zeros((B, nr, n + L - 1), dtype=np.complex128)
+    if B:
+        _lib.check(_lib.load().cpx_multipath(_lib.ptr(xa), _lib.ptr(ga), int(ga.ndim == 4), B, nt, nr, n, L, _lib.ptr(out)))
+    return out[:, 0, :] if siso else out

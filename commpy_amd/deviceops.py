@@ -15,7 +15,7 @@ from commpy_amd.channelcoding.ldpc import build_matrix
 
 __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu', 'mimo_channel_gpu', 'puncturing_gpu',
            'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder', 'gf2_generator',
-           'triang_ldpc_systematic_encode_gpu']
+           'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev']
 
 
 class DeviceBuf:
@@ -357,3 +357,34 @@ def mimo_channel_gpu(channel, modem, bits, seed=0, stream_id=0):
             return dev.download(d_y, (V, nr), np.complex128), dev.download(d_h, (V, nr, nt), np.complex128)
     finally:
         handles.drop()
+
+
+# ---- the multipath channel, resource mapping and channel estimation, device resident (csrc/ofdm_chan.hip) -----------------------
+
+def multipath_dev(d_x, d_g, g_batched, B, nt, nr, n, L, stream=None):
+    """``cpx_multipath_dev`` over ``DeviceBuf``s: ``d_x [B][nt][n]``, ``d_g [B][nr][nt][L]`` (``g_batched``) or ``[nr][nt][L]`` ->
+    a new ``DeviceBuf`` ``[B][nr][n + L - 1]`` (complex128), queued on ``stream`` (None: the library's)."""
+    d_y = DeviceBuf(B * nr * (n + L - 1) * 16)
+    _lib.check(d_y.lib.cpx_multipath_dev(d_x.ptr, d_g.ptr, int(bool(g_batched)), B, nt, nr, n, L, d_y.ptr, stream))
+    return d_y
+
+
+def ofdm_map_dev(pilots, d_data, B, stream=None):
+    """``cpx_pilots_map_dev``: ``d_data [B][ndata][nt]`` -> a new ``DeviceBuf`` ``[B][nt][nsym][nsc]``, ``cpx_ofdm_tx_dev``'s input."""
+    d_grid = DeviceBuf(B * pilots.nt * pilots.nsym * pilots.nsc * 16)
+    _lib.check(d_grid.lib.cpx_pilots_map_dev(pilots.handle(), d_data.ptr, B, d_grid.ptr, stream))
+    return d_grid
+
+
+def ofdm_estimate_dev(pilots, d_Y, B, nr, want=('y', 'h'), stream=None):
+    """``cpx_pilots_estimate_dev``: ``d_Y [B][nr][nsym][nsc]`` -> a tuple of new ``DeviceBuf``s, the members of ``(y_data
+    [B][ndata][nr], h_data [B][ndata][nr][nt], h_sc [B][nsc][nr][nt])`` that ``want`` names ('y', 'h', 'h_sc'), in that order:
+    the first two are the ``y`` and ``H`` of the ``cpx_mimo_*_dev`` / ``cpx_kbest_*_dev`` detectors for ``V = B ndata`` vectors."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ('y', 'h', 'h_sc') for w in want):
+        raise ValueError("want must name at least one of 'y', 'h', 'h_sc'")
+    sizes = {'y': pilots.ndata * nr, 'h': pilots.ndata * nr * pilots.nt, 'h_sc': pilots.nsc * nr * pilots.nt}
+    out = {k: DeviceBuf(B * sizes[k] * 16) for k in ('y', 'h', 'h_sc') if k in want}
+    ptrs = [out[k].ptr if k in out else None for k in ('h_sc', 'y', 'h')]
+    _lib.check(_lib.load().cpx_pilots_estimate_dev(pilots.handle(), d_Y.ptr, B, nr, ptrs[0], ptrs[1], ptrs[2], stream))
+    return tuple(out[k] for k in ('y', 'h', 'h_sc') if k in out)

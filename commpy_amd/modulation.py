@@ -11,6 +11,9 @@ for ``links.idd_decoder``.  The linear detectors -- zero forcing and MMSE, hard 
 ``linear_batch`` and ``linear_equalize_batch`` (csrc/mimo_linear.hip; not in the reference).
 ``max_log_approx`` and ``bit_lvl_repr`` are small host functions.  ``ofdm_tx`` / ``ofdm_rx`` (modulation.py:265-296) run on the
 GPU too (csrc/ofdm.hip), float64 only, with the symbol-major batched forms ``ofdm_tx_batch`` / ``ofdm_rx_batch``.
+``OfdmPilots`` describes the pilots of an OFDM frame; ``ofdm_map_batch`` puts data and pilots on the resource grid and
+``ofdm_estimate_batch`` estimates the channel from the received grid and hands ``(y, H)`` to the MIMO detectors in their own layout
+(csrc/ofdm_chan.hip; not in the reference).
 """
 import ctypes
 import numbers
@@ -23,7 +26,8 @@ from commpy_amd.utilities import signal_power
 
 __all__ = ['PSKModem', 'QAMModem', 'Modem', 'mimo_ml', 'kbest', 'max_log_approx', 'bit_lvl_repr', 'mimo_ml_batch',
            'kbest_batch', 'best_first_detector', 'best_first_batch', 'list_apriori_batch', 'apriori_detector', 'zf_detector', 'mmse_detector',
-           'linear_batch', 'linear_equalize_batch', 'ofdm_tx', 'ofdm_rx', 'ofdm_tx_batch', 'ofdm_rx_batch']
+           'linear_batch', 'linear_equalize_batch', 'ofdm_tx', 'ofdm_rx', 'ofdm_tx_batch', 'ofdm_rx_batch', 'OfdmPilots', 'ofdm_map_batch',
+           'ofdm_estimate_batch', 'ofdm_subcarrier_frequencies']
 
 
 def _gray_rank(m):
@@ -671,3 +675,216 @@ def ofdm_rx(y, nfft, nsc, cp_length):
     if y.ndim != 1:
         raise ValueError('y must be 1-D, got %d dimensions' % y.ndim)
     return np.ascontiguousarray(ofdm_rx_batch(y[None], nfft, nsc, cp_length)[0].T)
+
+
+# ---- pilots, resource mapping and channel estimation (csrc/ofdm_chan.hip) ---------------------------------------------------------
+OFDM_MAX_ANTENNAS = 1024
+
+
+def _numeric(a, name, dtype=np.complex128):
+    """``a`` as a C array of ``dtype``; anything but numbers is a ValueError."""
+    arr = np.asarray(a)
+    if arr.dtype.kind not in 'biufc':
+        raise ValueError('%s must hold numbers, got dtype %s' % (name, arr.dtype))
+    return np.ascontiguousarray(arr, dtype=dtype)
+
+
+def _indices(a, name, n):
+    arr = np.asarray(a)
+    if arr.ndim != 1 or arr.shape[0] != n:
+        raise ValueError('%s must be 1-D of length %d, got shape %s' % (name, n, arr.shape))
+    if arr.dtype.kind not in 'iu':
+        raise ValueError('%s must hold integers, got dtype %s' % (name, arr.dtype))
+    return arr.astype(np.int64)
+
+
+def ofdm_subcarrier_frequencies(nsc):
+    """Signed frequency (bin) of each of the ``nsc`` used subcarriers in ``ofdm_tx``'s input order: ``k - nsc/2`` for the lower
+    half, ``k - nsc/2 + 1`` for the upper one (bin 0, DC, is unused)."""
+    k = np.arange(nsc)
+    return np.where(k < nsc // 2, k - nsc // 2, k - nsc // 2 + 1)
+
+
+def _interp_linear(nsc, pk):
+    """W [nsc, len(pk)]: linear interpolation in frequency between the neighbouring pilot subcarriers ``pk`` (ascending), the
+    nearest pilot held outside their range."""
+    f = ofdm_subcarrier_frequencies(nsc).astype(np.float64)
+    fp = f[pk]
+    W = np.zeros((nsc, len(pk)), dtype=np.complex128)
+    j = np.clip(np.searchsorted(fp, f, side='right') - 1, 0, max(len(pk) - 2, 0))
+    rows = np.arange(nsc)
+    if len(pk) == 1:
+        W[:, 0] = 1.0
+        return W
+    a = np.clip((f - fp[j]) / (fp[j + 1] - fp[j]), 0.0, 1.0)
+    W[rows, j] = 1.0 - a
+    W[rows, j + 1] += a
+    return W
+
+
+def _interp_taps(nsc, pk, Lmax, nfft):
+    """W [nsc, len(pk)] = F_all pinv(F_p): the least-squares fit of ``Lmax`` time-domain taps to the pilots' estimates, evaluated on
+    every subcarrier; F[k][l] = exp(-2 pi i f(k) l / nfft)."""
+    if Lmax > len(pk):
+        raise ValueError("interp ('taps', %d, %d): %d taps cannot be fitted to %d pilot subcarriers" % (Lmax, nfft, Lmax, len(pk)))
+    f = ofdm_subcarrier_frequencies(nsc).astype(np.float64)
+    F = np.exp(-2j * np.pi * np.outer(f, np.arange(Lmax)) / nfft)
+    return np.ascontiguousarray(F.dot(np.linalg.pinv(F[pk])))
+
+
+def _default_pilot_values(n):
+    """``n`` unit-modulus QPSK points from the PRBS x^15 + x^14 + 1 (``pnsequence``), two bits per point."""
+    from commpy_amd.sequences import pnsequence
+    bits = pnsequence(15, '1' * 15, '0' * 13 + '11', 2 * n).astype(np.float64)
+    return ((1.0 - 2.0 * bits[0::2]) + 1j * (1.0 - 2.0 * bits[1::2])) * np.sqrt(0.5)
+
+
+class OfdmPilots:
+    """The pilots of a frame of ``nsym`` OFDM symbols x ``nsc`` used subcarriers (``ofdm_tx``'s input order) of ``nt`` transmit
+    antennas.  Pilot i puts ``pil_val[i]`` on resource element ``(pil_sym[i], pil_sc[i])`` of antenna ``pil_tx[i]``; the other
+    antennas are silent there.  Every other resource element carries data: ``ndata`` of them, numbered symbol-major, then by
+    ascending subcarrier (``data_sym``, ``data_sc``).
+
+    ``interp`` gives, per antenna t, the matrix ``W[t] [nsc, np_t]`` that spreads the least-squares estimates at its ``np_t`` distinct
+    pilot subcarriers ``pilot_subcarriers[t]`` (ascending) over all subcarriers: 'linear' (in frequency, the nearest pilot held
+    outside their range), ``('taps', Lmax, nfft)`` (least-squares fit of Lmax time-domain taps, ``F_all pinv(F_p)``) or a list of
+    nt arrays.  Everything is validated here (ValueError) before a device is touched."""
+
+    def __init__(self, nsc, nsym, nt, pil_sym, pil_sc, pil_tx, pil_val, interp='linear'):
+        nsc, nsym, nt = _whole(nsc, 'nsc'), _whole(nsym, 'nsym'), _whole(nt, 'nt')
+        if nsc < 2 or nsc % 2:
+            raise ValueError('nsc = %d, need an even number >= 2' % nsc)
+        if nsym < 1 or nt < 1:
+            raise ValueError('nsym = %d, nt = %d, need at least 1 of each' % (nsym, nt))
+        if nt > OFDM_MAX_ANTENNAS:
+            raise ValueError('nt = %d is above the engine limit of %d' % (nt, OFDM_MAX_ANTENNAS))
+        if nsym * nsc >= 2 ** 30:
+            raise ValueError('a frame of %d resource elements is above the engine limit' % (nsym * nsc))
+        npil = int(np.asarray(pil_sym).shape[0]) if np.asarray(pil_sym).ndim == 1 else -1
+        if npil < 1:
+            raise ValueError('pil_sym must be 1-D with at least one pilot')
+        sym, sc, tx = _indices(pil_sym, 'pil_sym', npil), _indices(pil_sc, 'pil_sc', npil), _indices(pil_tx, 'pil_tx', npil)
+        val = _numeric(pil_val, 'pil_val')
+        if val.shape != (npil,):
+            raise ValueError('pil_val must be 1-D of length %d, got shape %s' % (npil, val.shape))
+        for name, a, hi in (('pil_sym', sym, nsym), ('pil_sc', sc, nsc), ('pil_tx', tx, nt)):
+            if a.min() < 0 or a.max() >= hi:
+                raise ValueError('%s holds an index outside 0 .. %d' % (name, hi - 1))
+        re = sym * nsc + sc
+        if np.unique(re).size != npil:
+            raise ValueError('a resource element appears twice in the pilot list')
+        mag2 = val.real * val.real + val.imag * val.imag
+        if not (np.all(np.isfinite(val)) and np.all(np.isfinite(mag2)) and np.all(mag2 > 0)):
+            raise ValueError('a pilot value is zero or not finite')
+        self.pilot_subcarriers = [np.unique(sc[tx == t]) for t in range(nt)]
+        for t, pk in enumerate(self.pilot_subcarriers):
+            if pk.size == 0:
+                raise ValueError('antenna %d has no pilot' % t)
+        if isinstance(interp, str) and interp == 'linear':
+            W = [_interp_linear(nsc, pk) for pk in self.pilot_subcarriers]
+        elif isinstance(interp, tuple) and len(interp) == 3 and interp[0] == 'taps':
+            Lmax, nfft = _whole(interp[1], 'Lmax'), _whole(interp[2], 'nfft')
+            if Lmax < 1 or nfft < 2:
+                raise ValueError("interp ('taps', Lmax, nfft) needs Lmax >= 1 and nfft >= 2")
+            W = [_interp_taps(nsc, pk, Lmax, nfft) for pk in self.pilot_subcarriers]
+        elif isinstance(interp, (list, tuple)) and len(interp) == nt and not isinstance(interp[0], str):
+            W = [_numeric(w, 'interp[%d]' % t) for t, w in enumerate(interp)]
+        else:
+            raise ValueError("interp must be 'linear', ('taps', Lmax, nfft) or a list of nt matrices")
+        for t, w in enumerate(W):
+            if w.shape != (nsc, self.pilot_subcarriers[t].size):
+                raise ValueError('W[%d] must be [nsc, np_t] = [%d, %d], got %s' % (t, nsc, self.pilot_subcarriers[t].size, w.shape))
+            if not np.all(np.isfinite(w)):
+                raise ValueError('W[%d] holds a value that is not finite' % t)
+        self.nsc, self.nsym, self.nt, self.npil = nsc, nsym, nt, npil
+        self.pil_sym, self.pil_sc, self.pil_tx, self.pil_val, self.W = sym, sc, tx, val, W
+        is_data = np.ones(nsym * nsc, dtype=bool)
+        is_data[re] = False
+        data_re = np.flatnonzero(is_data)
+        self.ndata = int(data_re.size)
+        self.data_sym, self.data_sc = data_re // nsc, data_re % nsc
+        i32 = [np.ascontiguousarray(a, dtype=np.int32) for a in (sym, sc, tx)]
+        wflat = np.ascontiguousarray(np.concatenate([w.reshape(-1) for w in W]))
+
+        def create():
+            h = ctypes.c_void_p()
+            _lib.check(_lib.load().cpx_pilots_create(nsc, nsym, nt, npil, _lib.ptr(i32[0]), _lib.ptr(i32[1]), _lib.ptr(i32[2]),
+                                                          _lib.ptr(val), _lib.ptr(wflat), ctypes.byref(h)))
+            return h
+        self._handles = _lib.DeviceHandles(create, 'cpx_pilots_destroy')
+
+    def handle(self):
+        """Opaque cpx_ofdm_pilots* of the current device (created on first use, one per device)."""
+        return self._handles.get()
+
+    @classmethod
+    def comb(cls, nsc, nsym, nt, spacing, pilot_symbols, interp, values=None):
+        """Comb pilots: on each symbol of ``pilot_symbols`` antenna t takes subcarriers ``t, t + spacing, ...`` (``spacing >= nt``).
+        ``values``: one per pilot, pilot symbol after pilot symbol, antenna after antenna (default: PRBS QPSK points)."""
+        nsc, nt, spacing = _whole(nsc, 'nsc'), _whole(nt, 'nt'), _whole(spacing, 'spacing')
+        if nt < 1 or spacing < nt:
+            raise ValueError('comb pilots need spacing >= nt >= 1 (spacing = %d, nt = %d)' % (spacing, nt))
+        syms = _indices(pilot_symbols, 'pilot_symbols', len(pilot_symbols))
+        sym, sc, tx = [], [], []
+        for s in syms:
+            for t in range(nt):
+                k = np.arange(t, max(nsc, 0), spacing)
+                sym.append(np.full(k.size, s)), sc.append(k), tx.append(np.full(k.size, t))
+        sym, sc, tx = (np.concatenate(a).astype(np.int64) if a else np.zeros(0, np.int64) for a in (sym, sc, tx))
+        return cls(nsc, nsym, nt, sym, sc, tx, _default_pilot_values(sym.size) if values is None else values, interp)
+
+    @classmethod
+    def block(cls, nsc, nsym, nt, interp='linear', values=None):
+        """Block pilots: symbol t is antenna t's full-band pilot symbol (``nsym >= nt``)."""
+        nsc, nsym, nt = _whole(nsc, 'nsc'), _whole(nsym, 'nsym'), _whole(nt, 'nt')
+        if nt < 1 or nsym < nt:
+            raise ValueError('block pilots need nsym >= nt >= 1 (nsym = %d, nt = %d)' % (nsym, nt))
+        tx = np.repeat(np.arange(nt), max(nsc, 0))
+        sc = np.tile(np.arange(max(nsc, 0)), nt)
+        return cls(nsc, nsym, nt, tx.copy(), sc, tx, _default_pilot_values(tx.size) if values is None else values, interp)
+
+
+def _pilots_arg(pilots):
+    if not isinstance(pilots, OfdmPilots):
+        raise ValueError('pilots must be an OfdmPilots')
+    return pilots
+
+
+def ofdm_map_batch(data, pilots):
+    """Data symbols and pilots on the resource grid: ``data [B, ndata, nt]`` (vector-major, what the MIMO detectors return) ->
+    complex128 ``[B, nt, nsym, nsc]``, zeros where an antenna is silent.  ``grid.reshape(B * nt, nsym, nsc)`` is
+    ``ofdm_tx_batch``'s input."""
+    p = _pilots_arg(pilots)
+    x = _numeric(data, 'data')
+    if x.ndim != 3 or x.shape[1:] != (p.ndata, p.nt):
+        raise ValueError('data must be [B, ndata, nt] = [B, %d, %d], got %s' % (p.ndata, p.nt, x.shape))
+    B = x.shape[0]
+    grid = np.zeros((B, p.nt, p.nsym, p.nsc), dtype=np.complex128)
+    if B:
+        _lib.check(_lib.load().cpx_pilots_map(p.handle(), _lib.ptr(x), B, _lib.ptr(grid)))
+    return grid
+
+
+def ofdm_estimate_batch(Y, pilots, want=('y', 'h')):
+    """Pilot-aided channel estimation of ``Y [B, nr, nsym, nsc]`` (``ofdm_rx_batch`` of the B nr received streams, reshaped):
+    least squares at the pilots, then ``W[t]`` over the subcarriers.  Returns a tuple of the members of ``(y_data, h_data, h_sc)``
+    that ``want`` names ('y', 'h', 'h_sc'), in that order: ``y_data [B, ndata, nr]`` the received data elements, ``h_data
+    [B, ndata, nr, nt]`` the estimate at each of them -- reshaped to ``[B ndata, nr]`` and ``[B ndata, nr, nt]`` they are the
+    ``y`` and ``h`` of ``linear_batch``, ``kbest_batch``, ``mimo_ml_batch`` ... -- and ``h_sc [B, nsc, nr, nt]`` the estimate per
+    subcarrier."""
+    p = _pilots_arg(pilots)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ('y', 'h', 'h_sc') for w in want):
+        raise ValueError("want must name at least one of 'y', 'h', 'h_sc'")
+    y = _numeric(Y, 'Y')
+    if y.ndim != 4 or y.shape[1] < 1 or y.shape[2:] != (p.nsym, p.nsc):
+        raise ValueError('Y must be [B, nr, nsym, nsc] = [B, nr, %d, %d], got %s' % (p.nsym, p.nsc, y.shape))
+    B, nr = y.shape[:2]
+    if nr > OFDM_MAX_ANTENNAS:
+        raise ValueError('nr = %d is above the engine limit of %d' % (nr, OFDM_MAX_ANTENNAS))
+    shapes = {'y': (B, p.ndata, nr), 'h': (B, p.ndata, nr, p.nt), 'h_sc': (B, p.nsc, nr, p.nt)}
+    out = {k: np.zeros(shapes[k], dtype=np.complex128) for k in ('y', 'h', 'h_sc') if k in want}
+    if B:
+        ptrs = [_lib.ptr(out[k]) if k in out else None for k in ('h_sc', 'y', 'h')]
+        _lib.check(_lib.load().cpx_pilots_estimate(p.handle(), _lib.ptr(y), B, nr, *ptrs))
+    return tuple(out[k] for k in ('y', 'h', 'h_sc') if k in out)

@@ -357,6 +357,50 @@ int cpx_freq_offset(const double *x_re_im, int64_t B, int64_t n, const double *s
 int cpx_freq_offset_dev(const double *d_x_re_im, int64_t B, int64_t n, const double *d_step, int step_batched, double *d_out_re_im,
                         void *stream);
 
+/* ---- Multipath channel and pilot-aided OFDM channel estimation ----------------------------
+ * Not in the reference.  complex128 data, float64 arithmetic only (cpx_set_precision does not apply); B = 0 succeeds without a launch.
+ * cpx_multipath:  x [B][nt][n], g [B][nr][nt][L] (g_batched = 1) or [nr][nt][L] shared by all rows (g_batched = 0) ->
+ *   y [B][nr][n + L - 1], y[b][r] = sum_t convolve(x[b][t], g[b][r][t]): full length, which cpx_ofdm_rx takes as it is (it ignores
+ *   trailing samples).  Every sample is one chain of fused multiply-adds from +0 over t ascending, then tap index ascending:
+ *   bit-identical whatever the batch size, the row's place, the stream, and whether g is shared or replicated.  Taps are expected
+ *   to be finite.  CPX_EINVAL: nt, nr or L < 1, n < 1 with B > 0, null pointers; CPX_ELIMIT: L > 1024 or nr nt L > 2048 (one
+ *   row's taps are staged in 32 KB of LDS).  Noise: cpx_awgn_dev.
+ * The entry points of a pilot plan are named cpx_pilots_*: the cpx_ofdm_* family is the transform of DESIGN.md 4.9 alone.
+ * cpx_pilots_create: the pilot plan of a frame of nsym OFDM symbols x nsc used subcarriers (cpx_ofdm_tx's input order =
+ *   cpx_ofdm_rx's output order) of nt transmit antennas.  Pilot i puts pil_val[i] on resource element (pil_sym[i], pil_sc[i]) of
+ *   antenna pil_tx[i]; every other antenna is silent there; a resource element appears at most once.  All remaining resource
+ *   elements carry data and are numbered d = 0 .. ndata - 1 (ndata = nsym nsc - npil), symbol-major, then subcarrier ascending.
+ *   With k_0 < ... < k_{np_t - 1} the distinct pilot subcarriers of antenna t, `w_re_im` holds, antenna after antenna, the
+ *   interpolation matrix W_t [nsc][np_t], complex, row-major; the engine does not interpret it.  CPX_EINVAL: nsc odd or < 2;
+ *   nsym, nt or npil < 1; an index out of range; a repeated resource element; an antenna without a pilot; a pilot value that is
+ *   zero or not finite; a W entry that is not finite.  CPX_ELIMIT: nt > 1024, or nsym nsc >= 2^30.
+ * cpx_pilots_map:  data [B][ndata][nt] (vector-major, the layout of the MIMO detectors' symbols) -> grid [B][nt][nsym][nsc]: data at
+ *   the data elements, pilots at their antenna's pilot elements, exact zeros elsewhere.  grid viewed as [B nt][nsym][nsc] is
+ *   cpx_ofdm_tx's input, whose output is cpx_multipath's x.
+ * cpx_pilots_estimate:  Y [B][nr][nsym][nsc] (cpx_ofdm_rx's output for B nr rows; fading constant over the frame).
+ *   LS[b][r][t][j] = (sum_s Y[b][r][s][k_j] conj(p_s) / |p_s|^2) / count over antenna t's pilots on subcarrier k_j in ascending
+ *   symbol order; H^[b][k][r][t] = sum_j W_t[k][j] LS[b][r][t][j], an fma chain from +0 over ascending j.  Outputs, each nullable
+ *   (at least one must be given): h_sc [B][nsc][nr][nt] = H^; y_data [B][ndata][nr] = Y at the data elements; h_data
+ *   [B][ndata][nr][nt] = H^ of each data element's subcarrier -- (y_data, h_data) with V = B ndata vectors and h_batched = 1 are
+ *   what cpx_mimo_ml, cpx_kbest_*, cpx_best_first, cpx_mimo_linear and cpx_mimo_list_* take.  A non-finite sample of Y makes NaNs
+ *   in its own frame only; results are bit-identical whatever the batch size, the frame's place, the stream, the form (host or
+ *   device) and the outputs requested.  CPX_EINVAL: nr < 1, no output; CPX_ELIMIT: nr > 1024.
+ */
+typedef struct cpx_ofdm_pilots cpx_ofdm_pilots;
+int cpx_multipath(const double *x_re_im, const double *g_re_im, int g_batched, int64_t B, int nt, int nr, int64_t n, int L,
+                  double *y_re_im);
+int cpx_multipath_dev(const double *d_x_re_im, const double *d_g_re_im, int g_batched, int64_t B, int nt, int nr, int64_t n, int L,
+                      double *d_y_re_im, void *stream);
+int cpx_pilots_create(int nsc, int nsym, int nt, int64_t npil, const int32_t *pil_sym, const int32_t *pil_sc,
+                           const int32_t *pil_tx, const double *pil_val_re_im, const double *w_re_im, cpx_ofdm_pilots **out);
+int cpx_pilots_destroy(cpx_ofdm_pilots *plan);
+int cpx_pilots_map(const cpx_ofdm_pilots *plan, const double *data_re_im, int64_t B, double *grid_re_im);
+int cpx_pilots_map_dev(const cpx_ofdm_pilots *plan, const double *d_data_re_im, int64_t B, double *d_grid_re_im, void *stream);
+int cpx_pilots_estimate(const cpx_ofdm_pilots *plan, const double *Y_re_im, int64_t B, int nr, double *h_sc, double *y_data,
+                      double *h_data);
+int cpx_pilots_estimate_dev(const cpx_ofdm_pilots *plan, const double *d_Y_re_im, int64_t B, int nr, double *d_h_sc, double *d_y_data,
+                          double *d_h_data, void *stream);
+
 /* ---- MIMO detection ------------------------------------------------------------------------------
  * Replace mimo_ml / kbest of commpy/modulation.py:299-406 (with max_log_approx :599-646 for the soft output) for a batch of B
  * received vectors.  The constellation is the modem's (cpx_modem_create), float64 throughout.

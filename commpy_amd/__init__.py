@@ -2,8 +2,8 @@
 
 The modules of veeresht/CommPy 0.8.0, re-implemented as hand-written HIP kernels for gfx950 behind a ctypes C-ABI
 (include/commpy_amd.h) where they have a hot path -- Viterbi, BCJR/MAP + turbo, LDPC belief propagation, PSK/QAM modulation and
-hard/soft demodulation, MIMO detection, the fading channels and links, OFDM, and pulse shaping / matched filtering / frequency
-offset of sampled waveforms -- with the host-side descriptions either side of them (Trellis, interleavers, LDPC design files,
+hard/soft demodulation, MIMO detection, the fading channels and links, OFDM with timing / frequency-offset synchronisation, and
+pulse shaping / matched filtering / frequency offset of sampled waveforms -- with the host-side descriptions either side of them (Trellis, interleavers, LDPC design files,
 constellations, encoders, filter taps, PN and Zadoff-Chu sequences).  No PyTorch, no Triton, no CPU fallback: the device entry
 points raise if the HIP library or the GPU is missing.
 
@@ -12,6 +12,7 @@ points raise if the HIP library or the GPU is missing.
     from commpy_amd.filters import rrcosfilter, pulse_shape, matched_filter
     from commpy_amd.sequences import pnsequence, zcsequence
     from commpy_amd.impairments import add_frequency_offset
+    from commpy_amd.sync import schmidl_cox_preamble, sync_estimate_batch, frame_sync_batch
 """
 __version__ = "0.3.0"
 
@@ -51,4 +52,4 @@ class precision:
         return False
 
 
-__all__ = ["channelcoding", "modulation", "utilities", "parallel", "filters", "sequences", "impairments", "set_precision", "precision"]
+__all__ = ["channelcoding", "modulation", "utilities", "parallel", "filters", "sequences", "impairments", "sync", "set_precision", "precision"]

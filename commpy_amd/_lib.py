@@ -122,6 +122,13 @@ SYMBOLS = {
     "cpx_pilots_map_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "cpx_pilots_estimate": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "cpx_pilots_estimate_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpx_sync_metric": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cpx_sync_metric_dev": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpx_sync_estimate": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cpx_sync_estimate_dev": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    "cpx_sync_align": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "cpx_sync_align_dev": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "cpx_kbest_set_path": (c_int, [c_char_p]),
     "cpx_mimo_ml": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
     "cpx_mimo_ml_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),

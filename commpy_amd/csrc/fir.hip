@@ -28,6 +28,7 @@
 //   freq_offset_kernel      one sample per lane and step, sincos() of the float64 product (full-range argument reduction).
 // Offsets are 64-bit throughout.
 #include "cpx_internal.h"
+#include "cpx_rotate.h"
 
 #include <climits>
 
@@ -249,13 +250,7 @@ __global__ __launch_bounds__(FO_BLOCK) void freq_offset_kernel(const double2 *x,
 #pragma unroll
         for (int i = 0; i < FO_CHUNK / FO_BLOCK; i++) {
             const int64_t k = k0 + threadIdx.x + i * FO_BLOCK;
-            if (k < n) {
-                const double theta = st * (double)k;
-                double sn, cs;
-                sincos(theta, &sn, &cs);
-                const double2 v = x[b * n + k];
-                out[b * n + k] = make_double2(v.x * cs - v.y * sn, v.x * sn + v.y * cs);
-            }
+            if (k < n) out[b * n + k] = freq_rotate(x[b * n + k], st, k);
         }
     }
 }

@@ -15,7 +15,7 @@ from commpy_amd.channelcoding.ldpc import build_matrix
 
 __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu', 'mimo_channel_gpu', 'puncturing_gpu',
            'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder', 'gf2_generator',
-           'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev']
+           'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'sync_estimate_dev', 'sync_align_dev']
 
 
 class DeviceBuf:
@@ -388,3 +388,24 @@ def ofdm_estimate_dev(pilots, d_Y, B, nr, want=('y', 'h'), stream=None):
     ptrs = [out[k].ptr if k in out else None for k in ('h_sc', 'y', 'h')]
     _lib.check(_lib.load().cpx_pilots_estimate_dev(pilots.handle(), d_Y.ptr, B, nr, ptrs[0], ptrs[1], ptrs[2], stream))
     return tuple(out[k] for k in ('y', 'h', 'h_sc') if k in out)
+
+
+# ---- timing and frequency-offset synchronisation, device resident (csrc/sync.hip) -------------------------------------------------
+
+def sync_estimate_dev(d_y, B, nr, n, lag, window, search=None, stream=None):
+    """``cpx_sync_estimate_dev``: ``d_y [B][nr][n]`` -> new ``DeviceBuf``s ``(d_hat [B] int64, peak [B], step [B])``, queued on ``stream``;
+    ``search = (d_lo, d_hi)`` or None for the whole row."""
+    lo, hi = (0, (1 << 63) - 1) if search is None else search
+    d_hat, peak, step = DeviceBuf(B * 8), DeviceBuf(B * 8), DeviceBuf(B * 8)
+    _lib.check(d_hat.lib.cpx_sync_estimate_dev(d_y.ptr, B, nr, n, lag, window, lo, hi, d_hat.ptr, peak.ptr, step.ptr, stream))
+    return d_hat, peak, step
+
+
+def sync_align_dev(d_y, B, nr, n, d_start, d_step, nout, offset=0, stream=None):
+    """``cpx_sync_align_dev``: rows ``[B][nr][n]`` cut at ``d_start[b] + offset`` (device int64, e.g. ``sync_estimate_dev``'s d_hat with
+    ``offset = -cp_length``) and rotated by ``d_step[b]`` per sample (device float64; None: a pure copy) -> a new ``DeviceBuf``
+    ``[B][nr][nout]``."""
+    d_out = DeviceBuf(B * nr * nout * 16)
+    _lib.check(d_out.lib.cpx_sync_align_dev(d_y.ptr, B, nr, n, d_start.ptr, None if d_step is None else d_step.ptr, offset, nout,
+                                            d_out.ptr, stream))
+    return d_out

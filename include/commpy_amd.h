@@ -401,6 +401,44 @@ int cpx_pilots_estimate(const cpx_ofdm_pilots *plan, const double *Y_re_im, int6
 int cpx_pilots_estimate_dev(const cpx_ofdm_pilots *plan, const double *d_Y_re_im, int64_t B, int nr, double *d_h_sc, double *d_y_data,
                           double *d_h_data, void *stream);
 
+/* ---- OFDM timing and frequency-offset synchronisation ---------------------------------------
+ * Not in the reference.  complex128 data, float64 arithmetic only (cpx_set_precision does not apply, no path switch); B = 0 succeeds
+ * without a launch.  With y [B][nr][n], a lag D >= 1, a window W >= 1 and nd = n - D - W + 1:
+ *   q[b][i] = sum_r conj(y[b][r][i]) y[b][r][i+D],  e[b][i] = 1/2 sum_r (|y[b][r][i]|^2 + |y[b][r][i+D]|^2),
+ *   P[b][d] = sum_{i=d}^{d+W-1} q[b][i],  E[b][d] likewise from e,  M[b][d] = |P|^2 / E^2 where E > 0, +0 where E == 0, NaN where E
+ *   is NaN.  M <= 1 up to rounding; the antennas of a row are combined before the modulus.  D = W = nfft / 2 is the Schmidl-Cox
+ *   search on a two-halves preamble, D = nfft with W = cp_length the cyclic-prefix correlator.
+ * Sums: the q axis is cut into tiles of 1024 anchored at multiples of 1024 within the row; every P[d], E[d] is assembled from
+ *   in-tile prefix sums and whole-tile totals (csrc/sync.hip), so that the cost per output does not grow with W, no rounding involves
+ *   a product further than 1023 positions from the window, and |P - exact| <= 2 (W + 2048 + 8) 2^-53 sqrt(2) sum |y_i| |y_{i+D}| over
+ *   r and i in [d - 2048, d + W + 2048) within the row (E: the same with e under the sum).  Each value depends on the row's samples
+ *   and (n, D, W, d) alone: bit-identical whatever the batch size, the row's place, the stream, the form (host or device) and the
+ *   outputs requested.  A NaN or an infinity spoils windows of its own row only (those that share a tile sum with it).
+ * cpx_sync_metric:    P [B][nd] complex, E [B][nd], M [B][nd]; each nullable, at least one must be given.
+ * cpx_sync_estimate:  the fused search, nothing [B][nd] is written.  d_hat[b] = the smallest d in [d_lo, d_hi) n [0, nd) whose M is
+ *   the largest of the range's non-NaN values, peak[b] = M[b][d_hat], step[b] = -atan2(Im P, Re P) / D at d_hat in radians per
+ *   sample: what cpx_freq_offset and cpx_sync_align take to remove the offset.  A row without a non-NaN M: d_hat = -1, peak = step =
+ *   NaN.  d_lo = 0, d_hi = INT64_MAX searches the whole row.  M and P are bit for bit those of cpx_sync_metric.
+ * cpx_sync_align:     out[b][r][k] = s (cos t + i sin t), k < nout, with s = y[b][r][start[b] + offset + k], or exact +0 where that
+ *   index is outside [0, n), and t = step[b] k rounded once: the rotation of cpx_freq_offset, bit for bit (start = 0, offset = 0,
+ *   nout = n is cpx_freq_offset with step_batched = 1 on the B nr rows).  step == NULL: a pure gather, zeros are +0.  start [B] may
+ *   be negative; in the _dev form start and step are DEVICE arrays, so cpx_sync_estimate_dev's outputs feed it without a host stage
+ *   (offset = -cp_length turns the preamble's d_hat into the start of its cyclic prefix).  out must not alias y.
+ * CPX_EINVAL: nr, D or W < 1; nd < 1 with B > 0; nout < 1; null pointers; no output requested; an empty search range (d_lo >= d_hi,
+ *   or none of [0, nd) in it).  CPX_ELIMIT: nr > 1024; D or W > 2^20.
+ */
+int cpx_sync_metric(const double *y_re_im, int64_t B, int nr, int64_t n, int64_t D, int64_t W, double *P_re_im, double *E, double *M);
+int cpx_sync_metric_dev(const double *d_y_re_im, int64_t B, int nr, int64_t n, int64_t D, int64_t W, double *d_P_re_im, double *d_E,
+                        double *d_M, void *stream);
+int cpx_sync_estimate(const double *y_re_im, int64_t B, int nr, int64_t n, int64_t D, int64_t W, int64_t d_lo, int64_t d_hi,
+                      int64_t *d_hat, double *peak, double *step);
+int cpx_sync_estimate_dev(const double *d_y_re_im, int64_t B, int nr, int64_t n, int64_t D, int64_t W, int64_t d_lo, int64_t d_hi,
+                          int64_t *d_d_hat, double *d_peak, double *d_step, void *stream);
+int cpx_sync_align(const double *y_re_im, int64_t B, int nr, int64_t n, const int64_t *start, const double *step, int64_t offset,
+                   int64_t nout, double *out_re_im);
+int cpx_sync_align_dev(const double *d_y_re_im, int64_t B, int nr, int64_t n, const int64_t *d_start, const double *d_step, int64_t offset,
+                       int64_t nout, double *d_out_re_im, void *stream);
+
 /* ---- MIMO detection ------------------------------------------------------------------------------
  * Replace mimo_ml / kbest of commpy/modulation.py:299-406 (with max_log_approx :599-646 for the soft output) for a batch of B
  * received vectors.  The constellation is the modem's (cpx_modem_create), float64 throughout.

@@ -129,6 +129,19 @@ SYMBOLS = {
                                       c_void_p]),
     "cpx_sync_align": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "cpx_sync_align_dev": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "cpx_fading_params": (c_int, [c_int64, c_int, c_int, c_int, c_int, c_double, c_double, c_uint64, c_uint64, c_uint64, c_void_p]),
+    "cpx_fading_params_dev": (c_int, [c_int64, c_int, c_int, c_int, c_int, c_double, c_double, c_uint64, c_uint64, c_uint64, c_void_p,
+                                      c_void_p]),
+    "cpx_fading_gains": (c_int, [c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_int64, c_int64, c_int64,
+                                 c_uint64, c_uint64, c_uint64, c_void_p]),
+    "cpx_fading_gains_dev": (c_int, [c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_int64, c_int64, c_int64,
+                                     c_uint64, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "cpx_fading_convolve": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int64, c_int, c_int64, c_void_p]),
+    "cpx_fading_convolve_dev": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p]),
+    "cpx_fading_channel": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_int64,
+                                   c_int64, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "cpx_fading_channel_dev": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_double, c_double,
+                                       c_int64, c_int64, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "cpx_kbest_set_path": (c_int, [c_char_p]),
     "cpx_mimo_ml": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
     "cpx_mimo_ml_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),

@@ -17,7 +17,8 @@ from numpy import abs, absolute, asarray, isrealobj, sqrt, where, zeros
 from scipy.linalg import sqrtm
 from numpy.random import randn, random, standard_normal
 
-__all__ = ['SISOFlatChannel', 'MIMOFlatChannel', 'bec', 'bsc', 'awgn', 'multipath_batch']
+__all__ = ['SISOFlatChannel', 'MIMOFlatChannel', 'bec', 'bsc', 'awgn', 'multipath_batch', 'fading_params_batch', 'fading_gains_batch',
+           'fading_convolve_batch', 'fading_multipath_batch', 'tap_frequency_response', 'FADING_SCRATCH_BYTES', 'FADING_MAX_SINUSOIDS']
 
 
 class SISOFlatChannel:
@@ -282,3 +283,208 @@ def multipath_batch(x, g):
     if B:
         _lib.check(_lib.load().cpx_multipath(_lib.ptr(xa), _lib.ptr(ga), int(ga.ndim == 4), B, nt, nr, n, L, _lib.ptr(out)))
     return out[:, 0, :] if siso else out
+
+
+# ---- Doppler-fading multipath channel: time-varying taps (csrc/fading.hip; include/commpy_amd.h has the definitions) ---------------
+
+FADING_SCRATCH_BYTES = 64 << 20     # the most scratch cpx_fading_channel holds gains in (CPX_FADING_SCRATCH_BYTES)
+FADING_MAX_SINUSOIDS = 256
+_TWO52 = 1 << 52
+_UINT64_MAX = (1 << 64) - 1
+
+
+def _whole(value, name, lo=None, hi=None):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise ValueError('%s must be an integer, got %r' % (name, value))
+    value = int(value)
+    if (lo is not None and value < lo) or (hi is not None and value > hi):
+        raise ValueError('%s = %d is outside [%s, %s]' % (name, value, lo, '...' if hi is None else hi))
+    return value
+
+
+def _real(value, name, lo, hi):
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a real number, got %r' % (name, value)) from None
+    if isinstance(value, (bool, np.bool_)) or not lo <= v <= hi:            # NaN fails the comparison
+        raise ValueError('%s = %r is outside [%g, %g]' % (name, value, lo, hi))
+    return v
+
+
+class _FadingModel:
+    """The validated parameters of the fading model, as the C entry points take them."""
+
+    def __init__(self, B, nr, nt, pdp, fd, hold, t0, n_sin, k_factor, fd_los, seed, stream_id, first_row):
+        self.B = _whole(B, 'B', 0)
+        self.nr, self.nt = _whole(nr, 'nr', 1), _whole(nt, 'nt', 1)
+        pa = np.asarray(pdp)
+        if pa.dtype.kind not in 'biuf' or pa.ndim != 1 or pa.size < 1:
+            raise ValueError('pdp must be a 1-D array of at least one real tap power')
+        self.pdp = np.ascontiguousarray(pa, dtype=np.float64)
+        self.L = L = self.pdp.size
+        if not np.all(np.isfinite(self.pdp) & (self.pdp >= 0)):
+            raise ValueError('pdp must hold finite powers >= 0')
+        if L > MULTIPATH_MAX_L or self.nr * self.nt * L > MULTIPATH_MAX_TAPS:
+            raise ValueError('L = %d, nr nt L = %d: above the engine limits of %d and %d'
+                             % (L, self.nr * self.nt * L, MULTIPATH_MAX_L, MULTIPATH_MAX_TAPS))
+        self.kf = None
+        if k_factor is not None:
+            ka = np.asarray(k_factor)
+            if ka.dtype.kind not in 'biuf' or ka.ndim > 1:
+                raise ValueError('k_factor must be a real number or one per tap')
+            ka = np.ascontiguousarray(np.broadcast_to(ka, (L,)) if ka.ndim == 0 else ka, dtype=np.float64)
+            if ka.shape != (L,) or not np.all(np.isfinite(ka) & (ka >= 0)):
+                raise ValueError('k_factor must hold %d finite values >= 0' % L)
+            with np.errstate(over='ignore'):
+                if not np.all(np.isfinite(self.pdp * ka)):
+                    raise ValueError('pdp * k_factor overflows')
+            self.kf = ka
+        self.fd, self.fd_los = _real(fd, 'fd', 0.0, 0.5), _real(fd_los, 'fd_los', -0.5, 0.5)
+        self.n_sin = _whole(n_sin, 'n_sin', 1, FADING_MAX_SINUSOIDS)
+        self.hold, self.t0 = _whole(hold, 'hold', 1), _whole(t0, 't0', 0)
+        self.seed, self.stream_id = _whole(seed, 'seed', 0, _UINT64_MAX), _whole(stream_id, 'stream_id', 0, _UINT64_MAX)
+        self.first_row = _whole(first_row, 'first_row', 0, _UINT64_MAX)
+
+    def blocks(self, nblk):
+        nblk = _whole(nblk, 'nblk', 1)
+        if self.t0 + nblk * self.hold >= _TWO52:
+            raise ValueError('t0 + nblk * hold = %d reaches 2^52' % (self.t0 + nblk * self.hold))
+        return nblk
+
+    def draw_args(self):
+        return (self.n_sin, self.fd, self.fd_los)
+
+    def tap_args(self):
+        from commpy_amd import _lib
+        return (_lib.ptr(self.pdp), None if self.kf is None else _lib.ptr(self.kf))
+
+    def key_args(self):
+        return (self.seed, self.stream_id, self.first_row)
+
+
+def fading_params_batch(B, nr, nt, L, fd, n_sin=16, fd_los=0.0, seed=0, stream_id=0, first_row=0):
+    """``(nu, phi)`` of every sinusoid of the fading model, float64 ``[B, nr, nt, L, n_sin + 1, 2]``: Doppler ``nu`` in cycles per
+    sample and phase ``phi`` in cycles of sinusoid s < n_sin of each path, then of the path's line of sight (``nu = fd_los``).  With
+    these the channel is known analytically: ``G(tau) = a_l sum_s exp(2j pi (nu_s tau + phi_s))`` (+ the line of sight), see
+    ``fading_gains_batch``."""
+    from commpy_amd import _lib
+    md = _FadingModel(B, nr, nt, np.ones(_whole(L, 'L', 1)), fd, 1, 0, n_sin, None, fd_los, seed, stream_id, first_row)
+    out = np.zeros((md.B, md.nr, md.nt, md.L, md.n_sin + 1, 2), dtype=np.float64)
+    if md.B:
+        _lib.check(_lib.load().cpx_fading_params(md.B, md.nr, md.nt, md.L, *md.draw_args(), *md.key_args(), _lib.ptr(out)))
+    return out
+
+
+def fading_gains_batch(B, nr, nt, pdp, fd, nblk, hold=1, t0=0, n_sin=16, k_factor=None, fd_los=0.0, seed=0, stream_id=0, first_row=0):
+    """Tap gains of the Doppler-fading channel on the GPU (csrc/fading.hip), complex128 ``[B, nblk, nr, nt, L]``: block j holds the
+    gains at time ``t0 + j * hold`` (in samples).  Clarke's model: every path (row, antenna pair, tap) is a sum of ``n_sin`` sinusoids
+    with Dopplers ``fd cos(2 pi u)`` (``fd`` = maximum Doppler in cycles per sample, at most 0.5) and uniform phases, scaled to the
+    tap's power ``pdp[l]``; ``k_factor`` (a number or one per tap) adds a line of sight of Doppler ``fd_los`` with that Rician K.  The
+    draws come from the Philox stream ``(seed, stream_id)``: a gain is a pure function of (seed, stream id, first_row + b, r, t, l,
+    time), so rows and time spans may be generated in any number of calls."""
+    from commpy_amd import _lib
+    md = _FadingModel(B, nr, nt, pdp, fd, hold, t0, n_sin, k_factor, fd_los, seed, stream_id, first_row)
+    nblk = md.blocks(nblk)
+    out = np.zeros((md.B, nblk, md.nr, md.nt, md.L), dtype=np.complex128)
+    if md.B:
+        _lib.check(_lib.load().cpx_fading_gains(md.B, md.nr, md.nt, md.L, *md.tap_args(), *md.draw_args(), md.hold, md.t0, nblk,
+                                                *md.key_args(), _lib.ptr(out)))
+    return out
+
+
+def _fading_rows(x):
+    xa = np.asarray(x)
+    if xa.dtype.kind not in 'biufc':
+        raise ValueError('x must hold numbers, got dtype %s' % xa.dtype)
+    siso = xa.ndim == 2
+    if siso:
+        xa = xa[:, None, :]
+    elif xa.ndim != 3:
+        raise ValueError('x must be [B, nt, n] or [B, n], got shape %s' % (xa.shape,))
+    if xa.shape[1] < 1:
+        raise ValueError('x has no antenna (nt = 0)')
+    if xa.shape[0] and xa.shape[2] < 1:
+        raise ValueError('n = 0 (an empty row cannot be convolved)')
+    return np.ascontiguousarray(xa, dtype=np.complex128), siso
+
+
+def fading_convolve_batch(x, G, hold):
+    """Time-varying convolution on the GPU: ``y[b][r][m] = sum_t sum_l G[b][m // hold][r][t][l] x[b][t][m - l]``, full length.
+    ``x [B, nt, n]`` with ``G [B, nblk, nr, nt, L]`` or ``[nblk, nr, nt, L]`` (shared by all rows), ``nblk = ceil((n + L - 1) / hold)``
+    -> complex128 ``[B, nr, n + L - 1]``; the SISO short form ``x [B, n]`` with ``G [B, nblk, L]`` or ``[nblk, L]`` -> ``[B, n + L - 1]``.
+    With gains that do not change from block to block this is ``multipath_batch`` bit for bit."""
+    from commpy_amd import _lib
+    xa, siso = _fading_rows(x)
+    ga = np.asarray(G)
+    if ga.dtype.kind not in 'biufc':
+        raise ValueError('G must hold numbers, got dtype %s' % ga.dtype)
+    hold = _whole(hold, 'hold', 1)
+    if siso:
+        if ga.ndim not in (2, 3):
+            raise ValueError('x is [B, n]: G must be [nblk, L] or [B, nblk, L], got shape %s' % (ga.shape,))
+        ga = ga[..., None, None, :]
+    if ga.ndim not in (4, 5):
+        raise ValueError('x is [B, nt, n]: G must be [nblk, nr, nt, L] or [B, nblk, nr, nt, L], got shape %s' % (ga.shape,))
+    B, nt, n = xa.shape
+    nr, L = ga.shape[-3], ga.shape[-1]
+    if nr < 1 or L < 1:
+        raise ValueError('nr = %d, L = %d, need at least 1 of each' % (nr, L))
+    if L > MULTIPATH_MAX_L or nr * nt * L > MULTIPATH_MAX_TAPS:
+        raise ValueError('L = %d, nr nt L = %d: above the engine limits of %d and %d' % (L, nr * nt * L, MULTIPATH_MAX_L, MULTIPATH_MAX_TAPS))
+    nblk = -(-(n + L - 1) // hold)
+    if ga.shape[-2] != nt or (ga.ndim == 5 and ga.shape[0] != B) or (B and ga.shape[-4] != nblk):
+        raise ValueError('shape mismatch: x %s, G %s, hold %d (%d blocks)' % (xa.shape, ga.shape, hold, nblk))
+    ga = np.ascontiguousarray(ga, dtype=np.complex128)
+    out = np.zeros((B, nr, n + L - 1), dtype=np.complex128)
+    if B:
+        _lib.check(_lib.load().cpx_fading_convolve(_lib.ptr(xa), _lib.ptr(ga), int(ga.ndim == 5), B, nt, nr, n, L, hold, _lib.ptr(out)))
+    return out[:, 0, :] if siso else out
+
+
+def fading_multipath_batch(x, nr, pdp, fd, hold=1, t0=0, n_sin=16, k_factor=None, fd_los=0.0, seed=0, stream_id=0, first_row=0,
+                           want=('y',)):
+    """``x`` through the Doppler-fading multipath channel on the GPU: the gains of ``fading_gains_batch`` for ``ceil((n + L - 1) /
+    hold)`` blocks from ``t0``, then ``fading_convolve_batch``.  ``x [B, nt, n]`` -> ``y [B, nr, n + L - 1]``; the SISO short form
+    ``x [B, n]`` (with ``nr = 1``) -> ``[B, n + L - 1]``.  Returns ``y``, or ``(y, G)`` with 'g' in ``want`` (``G [B, nblk, nr, nt, L]``
+    always: with ``tap_frequency_response`` it is the perfect channel state per block).  Without 'g' the gains never leave the
+    device, where they take at most ``FADING_SCRATCH_BYTES``.  No noise: add it with ``awgn`` or ``cpx_awgn_dev``."""
+    from commpy_amd import _lib
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ('y', 'g') for w in want):
+        raise ValueError("want must name at least one of 'y', 'g'")
+    xa, siso = _fading_rows(x)
+    B, nt, n = xa.shape
+    md = _FadingModel(B, nr, nt, pdp, fd, hold, t0, n_sin, k_factor, fd_los, seed, stream_id, first_row)
+    if siso and md.nr != 1:
+        raise ValueError('x is [B, n]: nr must be 1, got %d' % md.nr)
+    lout = n + md.L - 1
+    nblk = md.blocks(-(-lout // md.hold)) if B else 1
+    y = np.zeros((B, md.nr, lout), dtype=np.complex128) if 'y' in want else None
+    G = np.zeros((B, nblk, md.nr, nt, md.L), dtype=np.complex128) if 'g' in want else None
+    if B:
+        _lib.check(_lib.load().cpx_fading_channel(_lib.ptr(xa) if y is not None else None, B, nt, md.nr, n, md.L, *md.tap_args(),
+                                                  *md.draw_args(), md.hold, md.t0, *md.key_args(),
+                                                  None if y is None else _lib.ptr(y), None if G is None else _lib.ptr(G)))
+    if y is not None and siso:
+        y = y[:, 0, :]
+    out = tuple(v for v in (y, G) if v is not None)
+    return out[0] if want == ('y',) else out
+
+
+def tap_frequency_response(G, nfft, nsc):
+    """Host-side helper (plain NumPy, no device): the frequency response of tap sets ``G [..., L]`` on the ``nsc`` used subcarriers of
+    an ``nfft``-point OFDM symbol, ``H[..., k] = sum_l G[..., l] exp(-2j pi f(k) l / nfft)`` with ``f = ofdm_subcarrier_frequencies(nsc)``
+    -> complex128 ``[..., nsc]``.  For ``G [B, nblk, nr, nt, L]`` of ``fading_multipath_batch`` with ``hold`` = one OFDM symbol it is
+    the perfect-CSI ``H`` per symbol (``L <= cp_length + 1``)."""
+    from commpy_amd.modulation import ofdm_subcarrier_frequencies
+    ga = np.asarray(G)
+    if ga.dtype.kind not in 'biufc' or ga.ndim < 1 or ga.shape[-1] < 1:
+        raise ValueError('G must be a numeric array [..., L] with L >= 1')
+    nfft, nsc = _whole(nfft, 'nfft', 1), _whole(nsc, 'nsc', 1)
+    if nsc < 2 or nsc % 2 or nsc // 2 > nfft - 1:
+        raise ValueError('nsc = %d must be even, at least 2, with nsc / 2 <= nfft - 1 = %d' % (nsc, nfft - 1))
+    f = ofdm_subcarrier_frequencies(nsc)
+    l = np.arange(ga.shape[-1])
+    E = np.exp(-2j * np.pi * ((f[None, :] * l[:, None]) % nfft) / nfft)       # [L, nsc]; the phase index is reduced exactly
+    return np.asarray(ga, dtype=np.complex128) @ E

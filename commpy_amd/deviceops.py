@@ -15,7 +15,8 @@ from commpy_amd.channelcoding.ldpc import build_matrix
 
 __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu', 'mimo_channel_gpu', 'puncturing_gpu',
            'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder', 'gf2_generator',
-           'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'sync_estimate_dev', 'sync_align_dev']
+           'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'sync_estimate_dev', 'sync_align_dev',
+           'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev']
 
 
 class DeviceBuf:
@@ -409,3 +410,62 @@ def sync_align_dev(d_y, B, nr, n, d_start, d_step, nout, offset=0, stream=None):
     _lib.check(d_out.lib.cpx_sync_align_dev(d_y.ptr, B, nr, n, d_start.ptr, None if d_step is None else d_step.ptr, offset, nout,
                                             d_out.ptr, stream))
     return d_out
+
+
+# ---- the Doppler-fading multipath channel, device resident (csrc/fading.hip) -------------------------------------------------------
+
+def _fading_model(B, nr, nt, pdp, fd, hold, t0, n_sin, k_factor, fd_los, seed, stream_id, first_row):
+    from commpy_amd.channels import _FadingModel
+    return _FadingModel(B, nr, nt, pdp, fd, hold, t0, n_sin, k_factor, fd_los, seed, stream_id, first_row)
+
+
+def fading_params_dev(B, nr, nt, L, fd, n_sin=16, fd_los=0.0, seed=0, stream_id=0, first_row=0, stream=None):
+    """``cpx_fading_params_dev``: a new ``DeviceBuf`` ``[B][nr][nt][L][n_sin + 1][2]`` float64 of every sinusoid's (nu, phi), queued on
+    ``stream`` (None: the library's).  The arguments are those of ``channels.fading_params_batch``."""
+    from commpy_amd.channels import _whole
+    md = _fading_model(B, nr, nt, np.ones(_whole(L, 'L', 1)), fd, 1, 0, n_sin, None, fd_los, seed, stream_id, first_row)
+    d_out = DeviceBuf(md.B * md.nr * md.nt * md.L * (md.n_sin + 1) * 16)
+    _lib.check(d_out.lib.cpx_fading_params_dev(md.B, md.nr, md.nt, md.L, *md.draw_args(), *md.key_args(), d_out.ptr, stream))
+    return d_out
+
+
+def fading_gains_dev(B, nr, nt, pdp, fd, nblk, hold=1, t0=0, n_sin=16, k_factor=None, fd_los=0.0, seed=0, stream_id=0, first_row=0,
+                     stream=None):
+    """``cpx_fading_gains_dev``: a new ``DeviceBuf`` ``G [B][nblk][nr][nt][L]`` (complex128), queued on ``stream``.  The arguments are
+    those of ``channels.fading_gains_batch``; ``pdp`` and ``k_factor`` are host arrays."""
+    md = _fading_model(B, nr, nt, pdp, fd, hold, t0, n_sin, k_factor, fd_los, seed, stream_id, first_row)
+    nblk = md.blocks(nblk)
+    d_G = DeviceBuf(md.B * nblk * md.nr * md.nt * md.L * 16)
+    _lib.check(d_G.lib.cpx_fading_gains_dev(md.B, md.nr, md.nt, md.L, *md.tap_args(), *md.draw_args(), md.hold, md.t0, nblk,
+                                            *md.key_args(), d_G.ptr, stream))
+    return d_G
+
+
+def fading_convolve_dev(d_x, d_G, g_batched, B, nt, nr, n, L, hold, stream=None):
+    """``cpx_fading_convolve_dev`` over ``DeviceBuf``s: ``d_x [B][nt][n]``, ``d_G [B][nblk][nr][nt][L]`` (``g_batched``) or
+    ``[nblk][nr][nt][L]`` with ``nblk = ceil((n + L - 1) / hold)`` -> a new ``DeviceBuf`` ``[B][nr][n + L - 1]``."""
+    d_y = DeviceBuf(B * nr * (n + L - 1) * 16)
+    _lib.check(d_y.lib.cpx_fading_convolve_dev(d_x.ptr, d_G.ptr, int(bool(g_batched)), B, nt, nr, n, L, hold, d_y.ptr, stream))
+    return d_y
+
+
+def fading_channel_dev(d_x, B, nt, nr, n, pdp, fd, hold=1, t0=0, n_sin=16, k_factor=None, fd_los=0.0, seed=0, stream_id=0, first_row=0,
+                       want=('y',), stream=None):
+    """``cpx_fading_channel_dev``: ``d_x [B][nt][n]`` through the fading channel -> new ``DeviceBuf``s, the members of ``(y [B][nr][n + L
+    - 1], G [B][nblk][nr][nt][L])`` that ``want`` names ('y', 'g'), in that order (a single ``DeviceBuf`` for ``want=('y',)``).  Without
+    'g' the gains stay in the engine's scratch arena, at most ``channels.FADING_SCRATCH_BYTES`` of it."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ('y', 'g') for w in want):
+        raise ValueError("want must name at least one of 'y', 'g'")
+    md = _fading_model(B, nr, nt, pdp, fd, hold, t0, n_sin, k_factor, fd_los, seed, stream_id, first_row)
+    if md.B and (isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1):
+        raise ValueError('n = %r, need an integer >= 1' % (n,))
+    lout = n + md.L - 1
+    nblk = md.blocks(-(-lout // md.hold)) if md.B else 1
+    d_y = DeviceBuf(md.B * md.nr * lout * 16) if 'y' in want else None
+    d_G = DeviceBuf(md.B * nblk * md.nr * md.nt * md.L * 16) if 'g' in want else None
+    _lib.check(_lib.load().cpx_fading_channel_dev(d_x.ptr if d_y is not None else None, md.B, md.nt, md.nr, n, md.L, *md.tap_args(),
+                                                  *md.draw_args(), md.hold, md.t0, *md.key_args(),
+                                                  None if d_y is None else d_y.ptr, None if d_G is None else d_G.ptr, stream))
+    out = tuple(v for v in (d_y, d_G) if v is not None)
+    return out[0] if want == ('y',) else out

@@ -643,6 +643,65 @@ int cpx_bec_dev(const uint8_t *d_bits, int64_t n, double p_e, uint64_t seed, uin
 int cpx_count_errors_dev(const uint8_t *d_msg, int64_t msg_stride, const uint8_t *d_dec, int64_t dec_stride,
                          int64_t B, int64_t nchunks, int64_t chunk, int32_t *d_errs, void *stream);
 
+/* ---- Doppler-fading multipath channel: time-varying taps (csrc/fading.hip; modelled by tests/fading_model.py) -------
+ * Not in the reference.  A tapped delay line whose tap gains follow Clarke's model (a sum of Ns sinusoids per path, Jakes Doppler
+ * spectrum), Rayleigh or Rician per tap, drawn from the random streams above.  complex128 data, float64 arithmetic only
+ * (cpx_set_precision does not apply, no path switch, no environment variable); B = 0 succeeds without a launch.
+ * Parameters.  fd: maximum Doppler in cycles per sample, 0 <= fd <= 0.5.  n_sin = Ns: sinusoids per path, 1 <= Ns <= 256.  pdp[L]:
+ *   linear tap powers, finite and >= 0.  kf[L]: Rician K factor per tap, finite and >= 0, or NULL for all zero.  fd_los: Doppler of
+ *   the line-of-sight component in cycles per sample, |fd_los| <= 0.5.  hold >= 1: samples per gain block.  t0 >= 0: the time of a
+ *   row's output sample 0.  first_row: the row number of b = 0 (as first_vector of cpx_mimo_channel_run_dev), so that rows [0, B) in
+ *   one call or in several give the same bytes.  pdp and kf are HOST arrays in both forms (they are read before the call returns).
+ * Counters.  Path p = (((first_row + b) nr + r) nt + t) L + l, modulo 2^64.  Sinusoid s < Ns of path p uses counter p (Ns + 1) + s,
+ *   counter p (Ns + 1) + Ns belongs to the path's line of sight (all modulo 2^64).  From a counter's words: u_a = u01(w0, w1),
+ *   u_b = u01(w2, w3).
+ * Sinusoid parameters.  nu_s = fd * cospi(2 u_a) (one cospi, one multiply), phi_s = u_b.  Line of sight: nu = fd_los, phi = u_b of
+ *   its counter; its u_a is unused.
+ * Gain of block j.  tau = t0 + j hold, exact in float64: t0 + nblk hold >= 2^52 is CPX_EINVAL.  Per sinusoid psi = fma(nu_s, tau,
+ *   phi_s), rho = psi - rint(psi) (exact), (sn, cs) = sincospi(2 rho).  S = the sum of (cs, sn) over s ascending, plain adds from +0.
+ *   G = a_l S with a_l = sqrt(pdp[l] / ((1 + kf[l]) Ns)) formed on the host (G.re = a_l S.re, G.im = a_l S.im).  Where kf[l] > 0, and
+ *   only there, the line of sight is added: G.re = fma(c_l, cs_los, G.re), G.im = fma(c_l, sn_los, G.im) with c_l = sqrt(pdp[l] kf[l]
+ *   / (1 + kf[l])).  pdp[l] == 0 gives exact +0.  The antenna pairs are independent (no spatial correlation).  No recurrence runs
+ *   along time: a gain does not depend on where a call starts, on the batch or on the stream.  cospi and sincospi are the device
+ *   library's: nu and the gains are within a few ulp of the model's.
+ * Layout.  G [B][nblk][nr][nt][L]: a cpx_multipath tap set per block; nblk = ceil((n + L - 1) / hold) where G belongs to a
+ *   convolution.
+ * Convolution.  y[b][r][m] = sum_t sum_l G[b][m div hold][r][t][l] x[b][t][m - l] for m < n + L - 1: cpx_multipath's chain (one
+ *   chain of fused multiply-adds from +0 over t ascending, then l ascending, the four fmas of a tap in the same order; terms outside
+ *   the row are skipped or meet zeros), so with gains that do not change from block to block it is cpx_multipath bit for bit, for
+ *   every hold.  Limits as cpx_multipath: L <= 1024, nr nt L <= 2048.
+ * cpx_fading_params:    (nu, phi) of every sinusoid and of the line of sight, [B][nr][nt][L][Ns + 1][2] float64.
+ * cpx_fading_gains:     G for nblk blocks from t0.
+ * cpx_fading_convolve:  the convolution with the caller's G [B][nblk][nr][nt][L] (g_batched = 1) or [nblk][nr][nt][L] shared by all
+ *   rows (g_batched = 0).
+ * cpx_fading_channel:   gains, then the convolution, in one call: y [B][nr][n + L - 1] and / or G (each nullable, at least one must
+ *   be given; x may be NULL where y is).  Without G the gains live in the scratch arena, in chunks of whole rows or, where one row's
+ *   gains are larger than the budget, of whole blocks of one row: never more than CPX_FADING_SCRATCH_BYTES (plus 16 KB for the tap
+ *   scales, which every gains call keeps there); the result is bit-identical to cpx_fading_gains followed by cpx_fading_convolve.
+ * CPX_EINVAL: the parameter ranges above, nr, nt or L < 1, n < 1 with B > 0, nblk < 1, null pointers, no output requested, sizes that
+ *   overflow.  CPX_ELIMIT: L > 1024, nr nt L > 2048, Ns > 256.  All are reported before a device is looked for.
+ */
+#define CPX_FADING_SCRATCH_BYTES 67108864   /* 64 MiB */
+int cpx_fading_params(int64_t B, int nr, int nt, int L, int n_sin, double fd, double fd_los, uint64_t seed, uint64_t stream_id,
+                      uint64_t first_row, double *params);
+int cpx_fading_params_dev(int64_t B, int nr, int nt, int L, int n_sin, double fd, double fd_los, uint64_t seed, uint64_t stream_id,
+                          uint64_t first_row, double *d_params, void *stream);
+int cpx_fading_gains(int64_t B, int nr, int nt, int L, const double *pdp, const double *kf, int n_sin, double fd, double fd_los,
+                     int64_t hold, int64_t t0, int64_t nblk, uint64_t seed, uint64_t stream_id, uint64_t first_row, double *G_re_im);
+int cpx_fading_gains_dev(int64_t B, int nr, int nt, int L, const double *pdp, const double *kf, int n_sin, double fd, double fd_los,
+                         int64_t hold, int64_t t0, int64_t nblk, uint64_t seed, uint64_t stream_id, uint64_t first_row,
+                         double *d_G_re_im, void *stream);
+int cpx_fading_convolve(const double *x_re_im, const double *G_re_im, int g_batched, int64_t B, int nt, int nr, int64_t n, int L,
+                        int64_t hold, double *y_re_im);
+int cpx_fading_convolve_dev(const double *d_x_re_im, const double *d_G_re_im, int g_batched, int64_t B, int nt, int nr, int64_t n, int L,
+                            int64_t hold, double *d_y_re_im, void *stream);
+int cpx_fading_channel(const double *x_re_im, int64_t B, int nt, int nr, int64_t n, int L, const double *pdp, const double *kf, int n_sin,
+                       double fd, double fd_los, int64_t hold, int64_t t0, uint64_t seed, uint64_t stream_id, uint64_t first_row,
+                       double *y_re_im, double *G_re_im);
+int cpx_fading_channel_dev(const double *d_x_re_im, int64_t B, int nt, int nr, int64_t n, int L, const double *pdp, const double *kf,
+                           int n_sin, double fd, double fd_los, int64_t hold, int64_t t0, uint64_t seed, uint64_t stream_id,
+                           uint64_t first_row, double *d_y_re_im, double *d_G_re_im, void *stream);
+
 /* ---- the stages of one Monte-Carlo point in front of the decoder as ONE kernel (round 6; same SURVEY 8f rows) ----------------------
  * random bits -> conv_encode ('cont') -> puncturing -> Modem.modulate -> AWGN -> Modem.demodulate('soft') -> depuncturing
  * (links.py:229-250, wifi80211.py:178-206, convcode.py:475-558, :752-804, modulation.py:79-141, channels.py:37-55) for T

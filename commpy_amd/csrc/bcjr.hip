@@ -1190,7 +1190,7 @@ int cpx_map_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const do
                              int64_t B, int64_t N, double noise_variance, int want_bits, double *d_L_ext,
                              uint8_t *d_bits, void *stream) {
     CPX_TRACE("cpx_map_decode_batch_dev");
-    cpx::IssueGuard issue_guard;
+    Scratch sc;
     MapParams p;
     int rc = fill_tables(t, p.tb);
     if (rc) return rc;
@@ -1199,7 +1199,7 @@ int cpx_map_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const do
     if (B == 0 || N == 0) return CPX_OK;
     hipStream_t st = pick_stream(stream);
     if (t->S > 16) {                                              // beyond the wave-pair kernels: the literal absolute-scale kernel alone
-        rc = bcjr_exact_map(t, d_sys, d_par, d_L_int, B, N, 2 * noise_variance, want_bits, d_L_ext, d_bits, nullptr, st);
+        rc = bcjr_exact_map(t, d_sys, d_par, d_L_int, B, N, 2 * noise_variance, want_bits, d_L_ext, d_bits, nullptr, sc, st);
         if (rc == CPX_OK) note_kernel("map_exact_kernel<true> (%d states, one codeword per lane)", t->S);
         return rc;
     }
@@ -1211,11 +1211,11 @@ int cpx_map_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const do
     p.sys = d_sys; p.par = d_par; p.Lin = d_L_int; p.Lout = d_L_ext; p.bits = d_bits;
     p.B = B; p.N = N; p.nv2 = 2 * noise_variance; p.want_bits = want_bits;
     CPX_REQUIRE(nblocks < (1ll << 31), CPX_ELIMIT, "map_decode: batch too large");
-    if ((rc = workspace(st, 0, sizeof(double) * (size_t)(nblocks * np * (K + 1) * 64), (void **)&p.scratch))) return rc;
-    // "detect and redo": one flag byte per codeword (scratch-arena slot 3), zeroed here, set by the kernel, consumed by the
+    if ((rc = sc.get(st, Slot::state, sizeof(double) * (size_t)(nblocks * np * (K + 1) * 64), &p.scratch))) return rc;
+    // "detect and redo": one flag byte per codeword (Slot::redo_flags), zeroed here, set by the kernel, consumed by the
     // absolute-scale redo launch below; blocks too long for that path's scratch are decoded by the fast kernel alone
     // (round 5: the redo launch is the wave-parallel literal kernel below, which needs no per-lane scratch: no block-length limit)
-    if ((rc = workspace(st, 3, (size_t)B, (void **)&p.flags))) return rc;
+    if ((rc = sc.get(st, Slot::redo_flags, (size_t)B, &p.flags))) return rc;
     CPX_HIP(hipMemsetAsync(p.flags, 0, (size_t)B, st));
     dim3 grid((unsigned)nblocks), block(128 * np);
     switch (p.tb.lgS) {
@@ -1230,7 +1230,7 @@ int cpx_map_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const do
     }
     CPX_HIP(hipGetLastError());
     // redo: pairs with a flagged codeword, literally (map_literal_kernel), same launch geometry
-    const RedoCounter redo = redo_counter(st);
+    const RedoCounter redo = redo_counter(sc, st);
     switch (p.tb.lgS) {
 #define CASE(LG) case LG: hipLaunchKernelGGL((map_literal_kernel<LG, false>), grid, block, sizeof(double) * 2 * np * wave_lds_doubles<LG>(GW), st, p, redo); break;
         case 2:
@@ -1251,7 +1251,7 @@ int cpx_turbo_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const 
                                const double *d_L_int_or_null, const int32_t *d_perm, int64_t B, int64_t N,
                                double noise_variance, int n_iter, uint8_t *d_bits, void *stream) {
     CPX_TRACE("cpx_turbo_decode_batch_dev");
-    cpx::IssueGuard issue_guard;
+    Scratch sc;
     TurboParams p;
     int rc = fill_tables(t, p.tb);
     if (rc) return rc;
@@ -1260,7 +1260,7 @@ int cpx_turbo_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const 
     if (B == 0 || N == 0) return CPX_OK;
     hipStream_t st = pick_stream(stream);
     if (t->S > 16) {                                              // see cpx_map_decode_batch_dev
-        rc = bcjr_exact_turbo(t, d_sys, d_p1, d_p2, d_L_int_or_null, d_perm, B, N, 2 * noise_variance, n_iter, d_bits, nullptr, st);
+        rc = bcjr_exact_turbo(t, d_sys, d_p1, d_p2, d_L_int_or_null, d_perm, B, N, 2 * noise_variance, n_iter, d_bits, nullptr, sc, st);
         if (rc == CPX_OK) note_kernel("turbo_exact_kernel<true> (%d states, one codeword per lane)", t->S);
         return rc;
     }
@@ -1272,7 +1272,7 @@ int cpx_turbo_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const 
     p.sys = d_sys; p.p1 = d_p1; p.p2 = d_p2; p.Lint = d_L_int_or_null; p.perm = d_perm; p.bits = d_bits;
     p.B = B; p.N = N; p.nv2 = 2 * noise_variance; p.n_iter = n_iter;
     CPX_REQUIRE(nblocks < (1ll << 31), CPX_ELIMIT, "turbo_decode: batch too large");
-    if ((rc = workspace(st, 0, sizeof(double) * (size_t)(nblocks * np * (K + 1) * 64), (void **)&p.ckpt))) return rc;
+    if ((rc = sc.get(st, Slot::state, sizeof(double) * (size_t)(nblocks * np * (K + 1) * 64), &p.ckpt))) return rc;
     // the time-major slab (TurboParams): five arrays of N rows of 16 slots per row group; sized in float64 whatever the precision
     // mode (the literal redo kernel reuses a pair's share as float64 scratch)
     const int RW = (int)TM_RW;
@@ -1282,15 +1282,15 @@ int cpx_turbo_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const 
     const int64_t ngroups = (npairs + (1 << p.lgG) - 1) >> p.lgG;
     p.NR = N | 1;
     CPX_REQUIRE(5 * p.NR * RW * 8 < (1ll << 31), CPX_ELIMIT, "turbo_decode: block too long for 31-bit lane offsets into a row group's slab");
-    if ((rc = workspace(st, 1, sizeof(double) * (size_t)(ngroups * 5 * p.NR * RW), (void **)&p.larr))) return rc;
+    if ((rc = sc.get(st, Slot::state2, sizeof(double) * (size_t)(ngroups * 5 * p.NR * RW), &p.larr))) return rc;
     // "detect and redo", as in cpx_map_decode_batch_dev (round 5: redone by turbo_literal_kernel, no block-length limit)
-    if ((rc = workspace(st, 3, (size_t)B, (void **)&p.flags))) return rc;
+    if ((rc = sc.get(st, Slot::redo_flags, (size_t)B, &p.flags))) return rc;
     CPX_HIP(hipMemsetAsync(p.flags, 0, (size_t)B, st));
     CPX_REQUIRE(npairs < (1ll << 31), CPX_ELIMIT, "turbo_decode: batch too large");
     // the two row index tables the library derives from the interleaver
     {
         int32_t *tabs = nullptr;
-        if ((rc = workspace(st, 11, 2 * sizeof(int32_t) * (size_t)N, (void **)&tabs))) return rc;
+        if ((rc = sc.get(st, Slot::turbo_tables, 2 * sizeof(int32_t) * (size_t)N, &tabs))) return rc;
         p.iperm = tabs; p.ident = tabs + N;
         hipLaunchKernelGGL(turbo_tables_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d_perm, tabs, tabs + N, N);
     }
@@ -1344,7 +1344,7 @@ int cpx_turbo_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const 
     note_kernel("turbo_pass_kernel<%d,%s%s> x %d (time-major slab, interleaver = row index) + turbo_init_kernel + turbo_final_kernel (%d wave pairs per workgroup, %d codewords per pair)", p.tb.lgS,
                 (p.tb.lgS == 2 && p.tb.sr4) ? "true" : "false", s32 ? ",f32 slab" : "", 2 * n_iter, np, GW);
     // redo: one launch; a pair with a flagged codeword decodes its codewords again, literally, all iterations (turbo_literal_kernel)
-    const RedoCounter redo = redo_counter(st);
+    const RedoCounter redo = redo_counter(sc, st);
     {
         const dim3 lgrid((unsigned)npairs), lblock(128);
         switch (p.tb.lgS) {

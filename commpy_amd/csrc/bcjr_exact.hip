@@ -263,15 +263,14 @@ bool bcjr_exact_supported(int S, int64_t N, int turbo) {
 }
 
 int bcjr_exact_map(const cpx_trellis *t, const double *sys, const double *par, const double *Lin, int64_t B, int64_t N, double nv2,
-                   int want_bits, double *Lout, uint8_t *bits, const uint8_t *flags, hipStream_t st) {
+                   int want_bits, double *Lout, uint8_t *bits, const uint8_t *flags, Scratch &sc, hipStream_t st) {
     ExMapParams p;
     p.cd = ex_code(t);
     const size_t per = lane_doubles(t->S, N, 0);
     p.C = pick_lanes(B, per, t->S > MAXS ? EXACT_BUDGET_BIG : EXACT_BUDGET);
     CPX_REQUIRE(p.C >= 64, CPX_ELIMIT, "map_decode: block too long for the absolute-scale path (%d states x %lld steps)", t->S, (long long)N);
-    void *sc = nullptr;
-    if (int rc = workspace(st, 5, per * (size_t)p.C * sizeof(double), &sc)) return rc;
-    p.sys = sys; p.par = par; p.Lin = Lin; p.Lout = Lout; p.bits = bits; p.flags = flags; p.scratch = static_cast<double *>(sc);
+    if (int rc = sc.get(st, Slot::exact_redo, per * (size_t)p.C * sizeof(double), &p.scratch)) return rc;
+    p.sys = sys; p.par = par; p.Lin = Lin; p.Lout = Lout; p.bits = bits; p.flags = flags;
     p.B = B; p.N = N; p.nv2 = nv2; p.want_bits = want_bits;
     if (t->S > MAXS) hipLaunchKernelGGL(map_exact_kernel<true>, dim3((unsigned)(p.C / 64)), dim3(64), 0, st, p);
     else hipLaunchKernelGGL(map_exact_kernel<false>, dim3((unsigned)(p.C / 64)), dim3(64), 0, st, p);
@@ -281,16 +280,14 @@ int bcjr_exact_map(const cpx_trellis *t, const double *sys, const double *par, c
 
 int bcjr_exact_turbo(const cpx_trellis *t, const double *sys, const double *p1, const double *p2, const double *Lint_or_null,
                      const int32_t *perm, int64_t B, int64_t N, double nv2, int n_iter, uint8_t *bits, const uint8_t *flags,
-                     hipStream_t st) {
+                     Scratch &sc, hipStream_t st) {
     ExTurboParams p;
     p.cd = ex_code(t);
     const size_t per = lane_doubles(t->S, N, 1);
     p.C = pick_lanes(B, per, t->S > MAXS ? EXACT_BUDGET_BIG : EXACT_BUDGET);
     CPX_REQUIRE(p.C >= 64, CPX_ELIMIT, "turbo_decode: block too long for the absolute-scale path (%d states x %lld steps)", t->S, (long long)N);
-    void *sc = nullptr;
-    if (int rc = workspace(st, 5, per * (size_t)p.C * sizeof(double), &sc)) return rc;
+    if (int rc = sc.get(st, Slot::exact_redo, per * (size_t)p.C * sizeof(double), &p.scratch)) return rc;
     p.sys = sys; p.p1 = p1; p.p2 = p2; p.Lint = Lint_or_null; p.perm = perm; p.bits = bits; p.flags = flags;
-    p.scratch = static_cast<double *>(sc);
     p.B = B; p.N = N; p.nv2 = nv2; p.n_iter = n_iter;
     if (t->S > MAXS) hipLaunchKernelGGL(turbo_exact_kernel<true>, dim3((unsigned)(p.C / 64)), dim3(64), 0, st, p);
     else hipLaunchKernelGGL(turbo_exact_kernel<false>, dim3((unsigned)(p.C / 64)), dim3(64), 0, st, p);

@@ -23,7 +23,8 @@ const char *last_kernel_name();
 // count to *host and zeroes the device words.  note_redo() AFTER the final note_kernel() makes cpx_last_kernel append
 // "redo: <host word> of <total> <what>" (pointers null: no counter available)
 struct RedoCounter { unsigned *dev, *host; };
-RedoCounter redo_counter(hipStream_t st);
+class Scratch;
+RedoCounter redo_counter(Scratch &sc, hipStream_t st);
 #ifdef __HIPCC__
 // collective over the workgroup (one __syncthreads); `mine` = this workgroup's contribution, added by thread 0
 __device__ __forceinline__ void redo_finish(RedoCounter rc, unsigned mine) {
@@ -49,12 +50,6 @@ int device_cus();           // compute units of the current device (256 on MI355
 // workgroups of `fn` (block size `threads`, no dynamic LDS) resident on the whole device at once -- the size of a
 // persistent grid; cached per kernel
 int resident_blocks(const void *fn, int threads);
-// Scratch arena keyed by (device, stream, slot): grown with hipMalloc on demand, reused by later calls and
-// released by cpx_release_workspace().  Kernels of one stream serialise, so one arena per stream is safe.
-// (Stream-ordered hipMallocAsync/hipFreeAsync was measured to hand out memory that is still in use on this
-//  stack -- 45/120 corrupted LDPC decodes -- so the engine never uses it.)
-int workspace(hipStream_t stream, int slot, size_t bytes, void **out, bool *fresh = nullptr);   // fresh: the block was (re)allocated by this call
-
 #define CPX_HIP(call)                                                                          \
     do {                                                                                       \
         hipError_t _e = (call);                                                                \
@@ -107,7 +102,7 @@ struct CwResult {
 // default depth, float64): the caller runs a remainder beside the round(s).
 // nanflags ('soft' only, else null): [B] bytes, set to 1 for every codeword that received a NaN (viterbi.hip re-decodes those)
 CwResult viterbi_codeword_path(const ::cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L, int64_t T, int tb,
-                               int type, uint8_t *d_bits, uint8_t *nanflags, hipStream_t st, bool any_batch_size, bool lean_ring);
+                               int type, uint8_t *d_bits, uint8_t *nanflags, Scratch &sc, hipStream_t st, bool any_batch_size, bool lean_ring);
 
 // LDS-resident LDPC path (ldpc_resident.hip): true when it handled the call (*rc = status)
 int ldpc_resident_tables(::cpx_ldpc *c, const int32_t *row_ptr, const int32_t *row_pad, const int32_t *col_ptr,
@@ -116,23 +111,78 @@ void ldpc_resident_free(::cpx_ldpc *c);
 // nanflags (min-sum only, else null): [B] bytes, written for every block: 1 = a NaN among its LLRs (ldpc.hip decodes it again)
 // block_major: d_dec / d_out are [B][n_v] (one block per row) instead of [n_v][B]
 bool ldpc_resident_path(const ::cpx_ldpc *c, double *d_llr, int64_t B, int alg, int n_iters, int8_t *d_dec, double *d_out,
-                        int block_major, int32_t *d_iters, int *d_clipped, uint8_t *nanflags, hipStream_t st, int *rc);
+                        int block_major, int32_t *d_iters, int *d_clipped, uint8_t *nanflags, Scratch &sc, hipStream_t st, int *rc);
 
 // absolute-scale BCJR / turbo redo path (bcjr_exact.hip): decodes the codewords whose flag byte is set, overwriting the outputs
 bool bcjr_exact_supported(int S, int64_t N, int turbo);
 int bcjr_exact_map(const ::cpx_trellis *t, const double *sys, const double *par, const double *Lin, int64_t B, int64_t N, double nv2,
-                   int want_bits, double *Lout, uint8_t *bits, const uint8_t *flags, hipStream_t st);
+                   int want_bits, double *Lout, uint8_t *bits, const uint8_t *flags, Scratch &sc, hipStream_t st);
 int bcjr_exact_turbo(const ::cpx_trellis *t, const double *sys, const double *p1, const double *p2, const double *Lint_or_null,
                      const int32_t *perm, int64_t B, int64_t N, double nv2, int n_iter, uint8_t *bits, const uint8_t *flags,
-                     hipStream_t st);
+                     Scratch &sc, hipStream_t st);
 
-// per-device issue lock for entry points that take scratch-arena memory (runtime.hip)
-struct IssueGuard {
-    IssueGuard();
-    ~IssueGuard();
-    IssueGuard(const IssueGuard &) = delete;
-    IssueGuard &operator=(const IssueGuard &) = delete;
-    int dev;
+// Scratch arena keyed by (device, stream, slot): grown with hipMalloc on demand, reused by later calls and released by
+// cpx_release_workspace / cpx_stream_destroy.  Kernels of one stream serialise, so one arena per stream is safe ACROSS calls; within
+// one call two live buffers must not share a slot (the second request returns the same block, or frees it when it grows).
+// (Stream-ordered hipMallocAsync/hipFreeAsync was measured to hand out memory that is still in use on this
+//  stack -- 45/120 corrupted LDPC decodes -- so the engine never uses it.)
+// One enumerator per slot: who takes it and what it holds; for a slot with several users, why no two of them are live in one call.
+enum class Slot : int {
+    // ldpc.hip tiled slab (R, Q, L, tables) | ldpc_resident.hip staging + queue + e0 | bcjr.hip map checkpoint rows | bcjr.hip turbo
+    // checkpoint rows | viterbi_cw.hip two-kernel decisions.  One per call: the three decoders are separate entry points; the LDPC slab is
+    // taken only once ldpc_resident_path has declined (returned false, before its own request); map and turbo are separate entry points
+    state,
+    // bcjr.hip turbo time-major slab (larr) | viterbi_cw.hip two-kernel best states: separate entry points
+    state2,
+    ldpc_pack,           // encoders.hip: packed message words of the LDPC encoder
+    // NaN / "detect and redo" flag bytes, one per codeword or work item: bcjr.hip map | bcjr.hip turbo | viterbi.hip 'soft'
+    // (viterbi_dispatch, read by the codeword path and launch_redo): separate entry points, each takes it once per call
+    redo_flags,
+    ldpc_nan_flags,      // ldpc.hip: min-sum NaN flag bytes, one per block (live together with exact_redo, hence a slot of its own)
+    // per-lane / per-workgroup float64 state of the literal kernels: ldpc.hip ldpc_exact_kernel (general path or min-sum redo: the general
+    // path returns before the redo exists) | bcjr_exact.hip map | bcjr_exact.hip turbo (trellises above 16 states; the entry point
+    // returns right behind it, before any other request): one launch per call
+    exact_redo,
+    vit_host_in,         // viterbi.hip cpx_viterbi_decode_batch_i64: device copy of the host input (library stream, see there)
+    vit_host_out,        // ... and of the decoded bits
+    vit_gen_ring,        // viterbi_generic.hip: decision ring, per workgroup
+    vit_gen_best,        // viterbi_generic.hip: best state per ring step, per workgroup
+    vit_gen_pm,          // viterbi_generic.hip: path metrics of trellises above 2048 states
+    turbo_tables,        // bcjr.hip turbo: inverse-permutation and identity row tables
+    redo_counter,        // runtime.hip redo_counter: the stream's two counter words, zeroed when the block is created
+    kbest_state,         // mimo.hip K-best: per-workgroup detector state that does not fit LDS
+    best_first_state,    // mimo.hip best-first: per-workgroup stacks that do not fit LDS
+    mimo_channel_state,  // mimo_channel.hip: per-wave scratch above 64 KB
+    ofdm_ls,             // ofdm_chan.hip: least-squares estimates at the pilots
+    ofdm_hsc,            // ofdm_chan.hip: the channel at every subcarrier, where the caller does not ask for it
+    sync_totals,         // sync.hip windows_setup: per-tile totals of the window sums
+    sync_parts,          // sync.hip cpx_sync_estimate_dev: per-tile partial results of the peak search
+    fading_taps,         // fading.hip launch_taps: the power-delay profile's taps
+    fading_gains,        // fading.hip cpx_fading_channel_dev: a chunk of tap gains, where the caller does not ask for them
+    count
+};
+
+// The device's issue lock for the lifetime of the object, and the only way to arena memory.  Host threads may call into the library
+// concurrently (ctypes drops the GIL).  Between get() handing out a block and the launches that use it, another thread growing the same
+// (device, stream, slot) would free it (the grow path synchronises the stream first -- which only protects work that has already been
+// issued).  An entry point therefore declares a Scratch before its first request and keeps it until its launches are queued; internal
+// functions that take arena memory receive the caller's by reference.  The lock is recursive per device (host-buffer entry points call
+// the device ones); the constructor touches no stream.
+class Scratch {
+public:
+    Scratch();
+    ~Scratch();
+    Scratch(const Scratch &) = delete;  Scratch &operator=(const Scratch &) = delete;
+    // *out = at least `bytes` bytes of `slot` on `st` (a zero-byte request still gets 8); fresh: the block was (re)allocated by this call
+    template <class T> int get(hipStream_t st, Slot slot, size_t bytes, T **out, bool *fresh = nullptr) {
+        void *p = nullptr;
+        const int rc = block(st, slot, bytes, &p, fresh);
+        *out = static_cast<T *>(p);
+        return rc;
+    }
+private:
+    static int block(hipStream_t st, Slot slot, size_t bytes, void **out, bool *fresh);   // runtime.hip
+    int dev_;
 };
 
 // blocking download into pageable host memory through pinned staging + host threads (runtime.hip)
@@ -170,7 +220,7 @@ inline bool ldpc_spa_exact() { return mode_of(Switch::ldpc_spa) == 1; }
 inline int viterbi_path_flags() { return mode_of(Switch::viterbi_path); }
 // the general Viterbi kernel (viterbi_generic.hip): any trellis cpx_trellis_create accepts, any traceback depth
 int viterbi_generic(const ::cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L, int64_t T, int tb, int type,
-                    uint8_t *d_bits, hipStream_t st);
+                    uint8_t *d_bits, Scratch &sc, hipStream_t st);
 
 inline hipStream_t pick_stream(void *s) { return s ? reinterpret_cast<hipStream_t>(s) : lib_stream(); }
 
@@ -236,12 +286,6 @@ int mimo_host_check(const double *y, const double *h, int64_t B, int nr, int nt,
 // y and H staged; an empty batch stages neither
 int mimo_in(HostStage &s, const double *y, const double *h, int h_batched, int64_t B, int nr, int nt, const double **dy,
             const double **dh);
-
-// a block of the scratch arena (not owned: released by cpx_release_workspace)
-struct ArenaBuf {
-    void *p = nullptr;
-    template <class T> T *as() { return static_cast<T *>(p); }
-};
 
 }  // namespace cpx
 

@@ -372,17 +372,15 @@ int cpx_ldpc_encoder_destroy(cpx_ldpc_encoder *e) {
 
 int cpx_ldpc_encode_batch_dev(const cpx_ldpc_encoder *e, const uint8_t *d_msg, int64_t B, uint8_t *d_code, void *stream) {
     CPX_TRACE("cpx_ldpc_encode_batch_dev");
-    cpx::IssueGuard issue_guard;
+    Scratch sc;
     CPX_REQUIRE(e, CPX_EINVAL, "ldpc_encode: null encoder");
     if (int rcd = check_handle_device(e->device, "ldpc_encode")) return rcd;
     CPX_REQUIRE(B >= 0, CPX_EINVAL, "ldpc_encode: negative batch");
     if (B == 0) return CPX_OK;
     hipStream_t st = pick_stream(stream);
     const int64_t n = e->k + e->m, groups = (B + 7) / 8;
-    void *ws = nullptr;
-    int rc = workspace(st, 2, (size_t)groups * e->kw32 * 8 * sizeof(uint32_t), &ws);
-    if (rc) return rc;
-    uint32_t *packed = static_cast<uint32_t *>(ws);
+    uint32_t *packed = nullptr;
+    if (int rc = sc.get(st, Slot::ldpc_pack, (size_t)groups * e->kw32 * 8 * sizeof(uint32_t), &packed)) return rc;
     int64_t pblocks = (B + 3) / 4;
     if (pblocks > 256 * 32) pblocks = 256 * 32;
     hipLaunchKernelGGL(ldpc_pack_kernel, dim3((unsigned)pblocks), dim3(EB), 0, st, d_msg, B, e->k, e->kw32, packed, d_code, n);

@@ -46,7 +46,6 @@ using namespace cpx;
 namespace {
 
 constexpr int64_t FD_TWO52 = (int64_t)1 << 52;
-constexpr int WS_TAPS = 20, WS_GAINS = 21;                  // scratch-arena slots
 
 // one tap of the chain (fir.hip's order)
 __device__ __forceinline__ void mac(double2 &acc, double2 h, double2 x) {
@@ -352,11 +351,10 @@ struct FdModel {
     }
 };
 
-// ---- launchers (the caller holds the IssueGuard where the scratch arena is used) ----------------------------------------------------
-int launch_taps(const std::vector<double2> &taps, hipStream_t st, const double2 **d_taps) {
-    void *p = nullptr;
-    if (int rc = workspace(st, WS_TAPS, 16 * (size_t)CPX_FD_MAX_L, &p)) return rc;
-    double2 *dst = static_cast<double2 *>(p);
+// ---- launchers -------------------------------------------------------------------------------------------------------------------
+int launch_taps(Scratch &sc, const std::vector<double2> &taps, hipStream_t st, const double2 **d_taps) {
+    double2 *dst = nullptr;
+    if (int rc = sc.get(st, Slot::fading_taps, 16 * (size_t)CPX_FD_MAX_L, &dst)) return rc;
     for (size_t off = 0; off < taps.size(); off += FT_CHUNK) {
         TapChunk c{};
         const int cnt = (int)(taps.size() - off < (size_t)FT_CHUNK ? taps.size() - off : (size_t)FT_CHUNK);
@@ -482,9 +480,9 @@ int cpx_fading_gains_dev(int64_t B, int nr, int nt, int L, const double *pdp, co
     if (int rc = tap_scales("fading_gains", pdp, kf, L, n_sin, taps)) return rc;
     const FdModel md{nr, nt, L, n_sin, fd, fd_los, hold, seed, stream_id, first_row};
     hipStream_t st = pick_stream(stream);
-    IssueGuard guard;
+    Scratch sc;
     const double2 *d_taps;
-    if (int rc = launch_taps(taps, st, &d_taps)) return rc;
+    if (int rc = launch_taps(sc, taps, st, &d_taps)) return rc;
     if (int rc = launch_gains(md, d_taps, 0, B, t0, 0, nblk, reinterpret_cast<double2 *>(d_G_re_im), st)) return rc;
     note_kernel("fading_gains_kernel");
     return CPX_OK;
@@ -571,9 +569,9 @@ int cpx_fading_channel_dev(const double *d_x_re_im, int64_t B, int nt, int nr, i
     double2 *y = reinterpret_cast<double2 *>(d_y_re_im);
     const int64_t lout = n + L - 1, ntaps = (int64_t)nr * nt * L;
     char name[64] = "";
-    IssueGuard guard;
+    Scratch sc;
     const double2 *d_taps;
-    if (int rc = launch_taps(taps, st, &d_taps)) return rc;
+    if (int rc = launch_taps(sc, taps, st, &d_taps)) return rc;
     if (d_G_re_im) {
         double2 *G = reinterpret_cast<double2 *>(d_G_re_im);
         if (int rc = launch_gains(md, d_taps, 0, B, t0, 0, nblk, G, st)) return rc;
@@ -589,13 +587,12 @@ int cpx_fading_channel_dev(const double *d_x_re_im, int64_t B, int nt, int nr, i
     // above the budget, of whole blocks of one row.  Gains and sums are pure functions of their indices: the chunks change nothing.
     const int64_t budget = CPX_FADING_SCRATCH_BYTES / 16;                   // complex values
     const int64_t row = nblk * ntaps;
-    void *ws = nullptr;
+    double2 *G = nullptr;
     int64_t chunks = 0;
     if (row <= budget) {
         int64_t rows = budget / row;
         if (rows > B) rows = B;
-        if (int rc = workspace(st, WS_GAINS, 16 * (size_t)(rows * row), &ws)) return rc;
-        double2 *G = static_cast<double2 *>(ws);
+        if (int rc = sc.get(st, Slot::fading_gains, 16 * (size_t)(rows * row), &G)) return rc;
         for (int64_t b0 = 0; b0 < B; b0 += rows, chunks++) {
             const int64_t bn = B - b0 < rows ? B - b0 : rows;
             if (int rc = launch_gains(md, d_taps, b0, bn, t0, 0, nblk, G, st)) return rc;
@@ -605,8 +602,7 @@ int cpx_fading_channel_dev(const double *d_x_re_im, int64_t B, int nt, int nr, i
         }
     } else {
         const int64_t per = budget / ntaps;                                  // blocks per chunk, at least 2048
-        if (int rc = workspace(st, WS_GAINS, 16 * (size_t)(per * ntaps), &ws)) return rc;
-        double2 *G = static_cast<double2 *>(ws);
+        if (int rc = sc.get(st, Slot::fading_gains, 16 * (size_t)(per * ntaps), &G)) return rc;
         for (int64_t b = 0; b < B; b++) {
             for (int64_t j0 = 0; j0 < nblk; j0 += per, chunks++) {
                 const int64_t jn = nblk - j0 < per ? nblk - j0 : per;

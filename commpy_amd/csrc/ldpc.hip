@@ -1020,7 +1020,7 @@ int cpx_ldpc_bp_decode_batch_bm_dev(const cpx_ldpc *c, double *d_llr, int64_t B,
 
 static int ldpc_decode_impl(const cpx_ldpc *c, double *d_llr, int64_t B, int alg, int n_iters, int8_t *d_dec, double *d_out,
                             int block_major, int32_t *d_iters, int *d_clipped, void *stream) {
-    cpx::IssueGuard issue_guard;
+    Scratch sc;
     CPX_REQUIRE(c, CPX_EINVAL, "ldpc: null code");
     if (int rcd = check_handle_device(c->device, "ldpc")) return rcd;
     CPX_REQUIRE(alg == CPX_LDPC_SPA || alg == CPX_LDPC_MSA, CPX_EINVAL,
@@ -1032,14 +1032,13 @@ static int ldpc_decode_impl(const cpx_ldpc *c, double *d_llr, int64_t B, int alg
     hipStream_t st = pick_stream(stream);
     const int64_t sv = block_major ? 1 : B, sb = block_major ? (int64_t)c->n_v : 1;    // strides of d_out / d_dec (variable, block)
     // min-sum: one flag byte per block, set by the kernels that load the LLRs when they meet a NaN; flagged blocks are
-    // decoded again by ldpc_exact_kernel<false> (scratch-arena slots 4 / 5)
+    // decoded again by ldpc_exact_kernel<false> (Slot::ldpc_nan_flags / exact_redo)
     uint8_t *nanflags = nullptr;
     // literal kernel: `flags` selects the blocks (null = all), `wgs` workgroups, each with (2 E + n_v) doubles of scratch
     auto exact = [&](const uint8_t *flags, unsigned wgs, int algo) -> int {
         ExactParams q;
-        void *sc = nullptr;
-        if (int rcs = workspace(st, 5, sizeof(double) * (size_t)wgs * (size_t)(2 * c->n_edges + c->n_v), &sc)) return rcs;
-        q.llr = d_llr; q.flags = flags; q.out = d_out; q.dec = d_dec; q.iters = d_iters; q.scratch = static_cast<double *>(sc);
+        if (int rcs = sc.get(st, Slot::exact_redo, sizeof(double) * (size_t)wgs * (size_t)(2 * c->n_edges + c->n_v), &q.scratch)) return rcs;
+        q.llr = d_llr; q.flags = flags; q.out = d_out; q.dec = d_dec; q.iters = d_iters;
         q.edge_var = c->d_edge_var; q.row_ptr = c->d_row_ptr; q.col_ptr = c->d_col_ptr; q.col_edge = c->d_col_edge;
         q.B = B; q.E = c->n_edges; q.n_v = c->n_v; q.n_c = c->n_c; q.n_iters = n_iters; q.sv = sv; q.sb = sb;
         if (algo == CPX_LDPC_SPA) hipLaunchKernelGGL(ldpc_exact_kernel<true>, dim3(wgs), dim3(256), 0, st, q);
@@ -1065,14 +1064,11 @@ static int ldpc_decode_impl(const cpx_ldpc *c, double *d_llr, int64_t B, int alg
         if (!nanflags) return CPX_OK;
         return exact(nanflags, (unsigned)std::min<int64_t>(B, 64), CPX_LDPC_MSA);
     };
-    if (alg == CPX_LDPC_MSA) {
-        void *w = nullptr;
-        if (int rcf = workspace(st, 4, (size_t)B, &w)) return rcf;
-        nanflags = static_cast<uint8_t *>(w);
-    }
+    if (alg == CPX_LDPC_MSA)
+        if (int rcf = sc.get(st, Slot::ldpc_nan_flags, (size_t)B, &nanflags)) return rcf;
     {   // the whole decoder state of a block in LDS, one persistent launch (ldpc_resident.hip) -- unless it does not fit
         int rcr = CPX_OK;
-        if (ldpc_resident_path(c, d_llr, B, alg, n_iters, d_dec, d_out, block_major, d_iters, d_clipped, nanflags, st, &rcr)) {
+        if (ldpc_resident_path(c, d_llr, B, alg, n_iters, d_dec, d_out, block_major, d_iters, d_clipped, nanflags, sc, st, &rcr)) {
             if (rcr == CPX_OK) {
                 char name[160];
                 snprintf(name, sizeof(name), "%s", last_kernel_name());
@@ -1094,7 +1090,7 @@ static int ldpc_decode_impl(const cpx_ldpc *c, double *d_llr, int64_t B, int alg
                  szI = al(sizeof(int32_t) * (size_t)S);
     char *slab = nullptr;
     int rcw;
-    if ((rcw = workspace(st, 0, 2 * szR + 4 * szV + 5 * szI + 256, (void **)&slab))) return rcw;
+    if ((rcw = sc.get(st, Slot::state, 2 * szR + 4 * szV + 5 * szI + 256, &slab))) return rcw;
     Bufs bf;
     char *p = slab;
     for (int i = 0; i < 2; i++) { bf.R[i] = (double *)p; p += szR; }

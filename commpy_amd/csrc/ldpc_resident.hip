@@ -847,7 +847,7 @@ void ldpc_resident_free(cpx_ldpc *c) {
 }
 
 bool ldpc_resident_path(const cpx_ldpc *c, double *d_llr, int64_t B, int alg, int n_iters, int8_t *d_dec, double *d_out,
-                        int block_major, int32_t *d_iters, int *d_clipped, uint8_t *nanflags, hipStream_t st, int *rc) {
+                        int block_major, int32_t *d_iters, int *d_clipped, uint8_t *nanflags, Scratch &sc, hipStream_t st, int *rc) {
     *rc = CPX_OK;
     const int mode = ldpc_forced_path();
     auto reject = [&](const char *why) {
@@ -874,7 +874,7 @@ bool ldpc_resident_path(const cpx_ldpc *c, double *d_llr, int64_t B, int alg, in
     char *slab = nullptr;
     const size_t sz_stage = block_major ? 0 : (sizeof(double) * (size_t)(B * c->n_v) + 255) & ~(size_t)255;
     const size_t sz_e0 = ratio ? sizeof(double) * (size_t)grid * (size_t)c->n_v : 0;
-    if ((*rc = workspace(st, 0, sz_stage + 256 + sz_e0, (void **)&slab))) return true;
+    if ((*rc = sc.get(st, Slot::state, sz_stage + 256 + sz_e0, &slab))) return true;
     ResParams p;
     p.llr = d_llr; p.iters = d_iters; p.queue = (int *)(slab + sz_stage); p.clipped = d_clipped; p.nanflags = nanflags;
     p.e0 = (double *)(slab + sz_stage + 256);

@@ -334,14 +334,14 @@ int kbest_run(const cpx_modem *md, const double *d_y, const double *d_h, int h_b
         note_kernel("kbest_kernel<lds> (K %d, m %d, %dx%d)", Ke, m, nr, nt);
         return CPX_OK;
     }
-    IssueGuard guard;
+    Scratch sc;
     int64_t grid = B < 2048 ? B : 2048;
     const int64_t budget = (int64_t(1) << 31) / int64_t(L.bytes);   // at most 2 GB of workspace
     if (grid > budget) grid = budget > 0 ? budget : 1;
-    void *ws = nullptr;
-    if (int rc = workspace(st, 13, size_t(grid) * L.bytes, &ws)) return rc;
+    char *ws = nullptr;
+    if (int rc = sc.get(st, Slot::kbest_state, size_t(grid) * L.bytes, &ws)) return rc;
     hipLaunchKernelGGL(kbest_kernel<true>, dim3(int(grid)), dim3(WAVE), 0, st, y, H, hs, B, nr, nt, c, m, md->nbits, Ke, L,
-                       static_cast<char *>(ws), mode, noise_var, d_idx, d_llr, d_count);
+                       ws, mode, noise_var, d_idx, d_llr, d_count);
     CPX_HIP(hipGetLastError());
     note_kernel("kbest_kernel<global> (K %d, m %d, %dx%d)", Ke, m, nr, nt);
     return CPX_OK;
@@ -653,14 +653,14 @@ int bf_run(const cpx_modem *md, const double *d_y, const double *d_h, int h_batc
         return CPX_OK;
     }
     CPX_REQUIRE(L.bytes <= (size_t(1) << 31), CPX_ELIMIT, "best_first: %zu bytes of state per vector above the 2 GB workspace", L.bytes);
-    IssueGuard guard;
+    Scratch sc;
     int64_t grid = B < 2048 ? B : 2048;
     const int64_t budget = (int64_t(1) << 31) / int64_t(L.bytes);   // at most 2 GB of workspace
     if (grid > budget) grid = budget > 0 ? budget : 1;
-    void *ws = nullptr;
-    if (int rc = workspace(st, 14, size_t(grid) * L.bytes, &ws)) return rc;
+    char *ws = nullptr;
+    if (int rc = sc.get(st, Slot::best_first_state, size_t(grid) * L.bytes, &ws)) return rc;
     hipLaunchKernelGGL(best_first_kernel<true>, dim3(int(grid)), dim3(WAVE), 0, st, y, H, hs, B, nr, nt, c, m, md->nbits, d_labels,
-                       llr_max, L, static_cast<char *>(ws), d_llr, d_iters);
+                       llr_max, L, ws, d_llr, d_iters);
     CPX_HIP(hipGetLastError());
     note_kernel("best_first_kernel<global> (m %d, %dx%d, %zu B per vector)", m, nr, nt, L.bytes);
     return CPX_OK;

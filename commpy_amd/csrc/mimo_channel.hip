@@ -201,15 +201,15 @@ int cpx_mimo_channel_run_dev(const cpx_mimo_channel *ch, const cpx_modem *md, co
     }
     // a wave's scratch above 64 KB: the same kernel on a global workspace of at most 1 GB (at least one wave's share: no shape is refused,
     // a share the device cannot hold fails as CPX_ENOMEM)
-    IssueGuard guard;
+    Scratch sc;
     const int64_t budget = (int64_t(1) << 30) / int64_t(wave_bytes);
     if (grid > budget) grid = budget > 0 ? budget : 1;
     if (grid > 8192) grid = 8192;
-    void *ws = nullptr;
-    if (int rc = workspace(st, 15, size_t(grid) * wave_bytes, &ws)) return rc;
+    double2 *ws = nullptr;
+    if (int rc = sc.get(st, Slot::mimo_channel_state, size_t(grid) * wave_bytes, &ws)) return rc;
     hipLaunchKernelGGL(mimo_channel_kernel<true>, dim3(unsigned(grid)), dim3(MC_WAVE), 0, st, d_bits, V, first_vector, md->nbits, cst, A, Bt,
                        mean, nr, nt, int(ch->a_identity), int(ch->b_identity), noise_scale, seed, stream_fading, stream_noise, y, H,
-                       static_cast<double2 *>(ws), per);
+                       ws, per);
     CPX_HIP(hipGetLastError());
     note_kernel("mimo_channel_kernel<global> (%dx%d%s%s)", nr, nt, ch->a_identity ? "" : ", A", ch->b_identity ? "" : ", Bt");
     return CPX_OK;

@@ -580,22 +580,21 @@ int cpx_pilots_estimate_dev(const cpx_ofdm_pilots *p, const double *d_Y_re_im, i
     OcArgs a = plan_args(p, B);
     a.nr = nr;
     const double2 *Y = reinterpret_cast<const double2 *>(d_Y_re_im);
-    IssueGuard guard;
+    Scratch sc;
     char names[160] = "";
     if (d_h_sc || (d_h_data && p->ndata)) {
-        void *ls = nullptr, *hsc = d_h_sc;
-        if (int rc = workspace(st, 16, 16 * (size_t)(B * p->nls * nr), &ls)) return rc;
+        double2 *ls = nullptr, *hsc = reinterpret_cast<double2 *>(d_h_sc);
+        if (int rc = sc.get(st, Slot::ofdm_ls, 16 * (size_t)(B * p->nls * nr), &ls)) return rc;
         if (!hsc)
-            if (int rc = workspace(st, 17, 16 * (size_t)(B * p->nsc * nr * p->nt), &hsc)) return rc;
+            if (int rc = sc.get(st, Slot::ofdm_hsc, 16 * (size_t)(B * p->nsc * nr * p->nt), &hsc)) return rc;
         hipLaunchKernelGGL(ofdm_ls_kernel, dim3(grid_of((B * p->nls * nr + OC_BLOCK - 1) / OC_BLOCK)), dim3(OC_BLOCK), 0, st, a, Y,
-                           static_cast<double2 *>(ls));
+                           ls);
         const int64_t itiles = ((B * nr + IK_CT - 1) / IK_CT) * p->nt * ((p->nsc + IK_KT - 1) / IK_KT);
-        hipLaunchKernelGGL(ofdm_interp_kernel, dim3(grid_of(itiles)), dim3(OC_BLOCK), 0, st, a, static_cast<const double2 *>(ls),
-                           static_cast<double2 *>(hsc));
+        hipLaunchKernelGGL(ofdm_interp_kernel, dim3(grid_of(itiles)), dim3(OC_BLOCK), 0, st, a, ls, hsc);
         strcat(names, "ofdm_ls_kernel+ofdm_interp_kernel");
         if (d_h_data && p->ndata) {
             hipLaunchKernelGGL(ofdm_hdemap_kernel, dim3(grid_of(B * ((p->ndata + HD_ROWS - 1) / HD_ROWS))), dim3(OC_BLOCK), 0, st, a,
-                               static_cast<const double2 *>(hsc), reinterpret_cast<double2 *>(d_h_data));
+                               hsc, reinterpret_cast<double2 *>(d_h_data));
             strcat(names, "+ofdm_hdemap_kernel");
         }
     }

@@ -55,11 +55,11 @@ void note_kernel(const char *fmt, ...) {
 // {device words [count, workgroups done] -- zero between launches: the kernel's last workgroup resets them --, pinned host word}.
 // No memset and no copy on the stream per decode: the redo kernel's LAST workgroup stores the count to the host word itself (round 5b;
 // a memset + a 4-byte D2H copy per decode cost ~8 us of a 0.33 ms map_decode).  Round 6 (advisor): the device words belong to the
-// (device, STREAM) the decode is issued on -- scratch slot 12 of that stream, zeroed once when the block is created, released with the
+// (device, STREAM) the decode is issued on -- Slot::redo_counter of that stream, zeroed once when the block is created, released with the
 // stream's other scratch blocks (cpx_stream_destroy / cpx_release_workspace) -- so two redo launches in flight on two streams never
 // share a counter, and launches on one stream are ordered.  The pinned host word stays per calling thread: it is what
 // cpx_last_kernel(), a per-thread string, reads.
-RedoCounter redo_counter(hipStream_t st) {
+RedoCounter redo_counter(Scratch &sc, hipStream_t st) {
     RedoCounter rc{nullptr, nullptr};
     if (!g_redo_word) {
         void *p = nullptr;
@@ -67,11 +67,11 @@ RedoCounter redo_counter(hipStream_t st) {
         g_redo_word = static_cast<unsigned *>(p);
         *g_redo_word = 0;
     }
-    void *w = nullptr;
+    unsigned *w = nullptr;
     bool fresh = false;
-    if (workspace(st, 12, 64, &w, &fresh) != CPX_OK) return rc;
+    if (sc.get(st, Slot::redo_counter, 64, &w, &fresh) != CPX_OK) return rc;
     if (fresh && hipMemsetAsync(w, 0, 64, st) != hipSuccess) { (void)hipGetLastError(); return rc; }
-    rc.dev = static_cast<unsigned *>(w);
+    rc.dev = w;
     rc.host = g_redo_word;
     return rc;
 }
@@ -92,11 +92,12 @@ int check_handle_device(int handle_device, const char *what) {
     return CPX_OK;
 }
 
-struct WsEntry { int dev; hipStream_t st; int slot; void *p; size_t cap; };
+struct WsEntry { int dev; hipStream_t st; Slot slot; void *p; size_t cap; };
 static std::vector<WsEntry> g_ws;
 static std::mutex g_ws_mu;
 
-int workspace(hipStream_t stream, int slot, size_t bytes, void **out, bool *fresh) {
+// the arena's lookup / grow / allocate: reached through Scratch::get only
+static int workspace(hipStream_t stream, Slot slot, size_t bytes, void **out, bool *fresh) {
     if (fresh) *fresh = false;
     int dev = 0;
     CPX_HIP(hipGetDevice(&dev));
@@ -216,17 +217,14 @@ struct Roctx {
 const Roctx &roctx() { static const Roctx r; return r; }
 }  // namespace
 
-// Host threads may call into the library concurrently (ctypes drops the GIL).  Kernels of one stream serialise, but the
-// scratch arena is shared per (device, stream, slot): between `workspace()` handing out a block and the launches that use it,
-// another thread growing the same slot would free it (the grow path synchronises the stream first -- which only protects work
-// that has already been issued).  Every entry point that takes arena memory therefore holds the device's issue lock from
-// before `workspace()` until its launches are queued; it is recursive (host-buffer entry points call the device ones).
+// the per-device issue locks (see Scratch, cpx_internal.h)
 namespace { std::recursive_mutex g_issue_mu[64]; }
-IssueGuard::IssueGuard() : dev(0) {
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    g_issue_mu[dev].lock();
+Scratch::Scratch() : dev_(0) {
+    if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) dev_ = 0;
+    g_issue_mu[dev_].lock();
 }
-IssueGuard::~IssueGuard() { g_issue_mu[dev].unlock(); }
+Scratch::~Scratch() { g_issue_mu[dev_].unlock(); }
+int Scratch::block(hipStream_t st, Slot slot, size_t bytes, void **out, bool *fresh) { return workspace(st, slot, bytes, out, fresh); }
 void issue_lock(int dev, bool lock) { if (lock) g_issue_mu[dev].lock(); else g_issue_mu[dev].unlock(); }
 
 // Download into PAGEABLE host memory, fast: the runtime's own pageable device-to-host path moved a fresh 0.57 GB NumPy result

@@ -368,8 +368,8 @@ int align_sizes(int64_t B, int nr, int64_t n, int64_t nout) {
 }
 
 // the launch geometry shared by metric and estimate; queues sync_totals_kernel where a window needs a total
-int windows_setup(SyArgs &a, const double *d_y, int64_t B, int nr, int64_t n, int64_t D, int64_t W, int64_t lo, int64_t hi, hipStream_t st,
-                  bool *totals) {
+int windows_setup(SyArgs &a, const double *d_y, int64_t B, int nr, int64_t n, int64_t D, int64_t W, int64_t lo, int64_t hi, Scratch &sc,
+                  hipStream_t st, bool *totals) {
     a.y = reinterpret_cast<const double2 *>(d_y);
     a.B = B; a.n = n; a.D = (int)D; a.W = (int)W; a.nr = nr;
     a.nq = n - D;
@@ -379,9 +379,7 @@ int windows_setup(SyArgs &a, const double *d_y, int64_t B, int nr, int64_t n, in
     *totals = wq >= 2 || (wq >= 1 && wr > 0);
     a.tot = nullptr;
     if (*totals) {
-        void *tot = nullptr;
-        if (int rc = workspace(st, 18, 24 * (size_t)(B * a.ntq), &tot)) return rc;
-        a.tot = static_cast<double *>(tot);
+        if (int rc = sc.get(st, Slot::sync_totals, 24 * (size_t)(B * a.ntq), &a.tot)) return rc;
         // the tiles between the ends of the windows of tiles k0 .. k1
         a.k0 = k0 + 1;
         const int64_t last = k1 + wq < a.ntq - 1 ? k1 + wq : a.ntq - 1;
@@ -407,10 +405,10 @@ int cpx_sync_metric_dev(const double *d_y_re_im, int64_t B, int nr, int64_t n, i
     if (B == 0) return CPX_OK;
     CPX_REQUIRE(d_y_re_im, CPX_EINVAL, "sync_metric: null pointer");
     hipStream_t st = pick_stream(stream);
-    IssueGuard guard;
+    Scratch sc;
     SyArgs a{};
     bool totals;
-    if (int rc = windows_setup(a, d_y_re_im, B, nr, n, D, W, 0, n - D - W + 1, st, &totals)) return rc;
+    if (int rc = windows_setup(a, d_y_re_im, B, nr, n, D, W, 0, n - D - W + 1, sc, st, &totals)) return rc;
     hipLaunchKernelGGL(sync_metric_kernel, tile_grid(B, a.nk), dim3(SY_BLOCK), 0, st, a, reinterpret_cast<double2 *>(d_P_re_im), d_E, d_M);
     CPX_HIP(hipGetLastError());
     note_kernel(totals ? "sync_totals_kernel+sync_metric_kernel" : "sync_metric_kernel");
@@ -447,14 +445,14 @@ int cpx_sync_estimate_dev(const double *d_y_re_im, int64_t B, int nr, int64_t n,
     if (B == 0) return CPX_OK;
     CPX_REQUIRE(d_y_re_im && d_d_hat && d_peak && d_step, CPX_EINVAL, "sync_estimate: null pointer");
     hipStream_t st = pick_stream(stream);
-    IssueGuard guard;
+    Scratch sc;
     SyArgs a{};
     bool totals;
-    if (int rc = windows_setup(a, d_y_re_im, B, nr, n, D, W, lo, hi, st, &totals)) return rc;
-    void *part = nullptr;
-    if (int rc = workspace(st, 19, sizeof(SyPart) * (size_t)(B * a.nk), &part)) return rc;
-    hipLaunchKernelGGL(sync_search_kernel, tile_grid(B, a.nk), dim3(SY_BLOCK), 0, st, a, lo, hi, static_cast<SyPart *>(part));
-    hipLaunchKernelGGL(sync_finish_kernel, dim3(grid_of(B)), dim3(SY_BLOCK), 0, st, static_cast<const SyPart *>(part), B, a.nk, (double)D,
+    if (int rc = windows_setup(a, d_y_re_im, B, nr, n, D, W, lo, hi, sc, st, &totals)) return rc;
+    SyPart *part = nullptr;
+    if (int rc = sc.get(st, Slot::sync_parts, sizeof(SyPart) * (size_t)(B * a.nk), &part)) return rc;
+    hipLaunchKernelGGL(sync_search_kernel, tile_grid(B, a.nk), dim3(SY_BLOCK), 0, st, a, lo, hi, part);
+    hipLaunchKernelGGL(sync_finish_kernel, dim3(grid_of(B)), dim3(SY_BLOCK), 0, st, part, B, a.nk, (double)D,
                        reinterpret_cast<long long *>(d_d_hat), d_peak, d_step);
     CPX_HIP(hipGetLastError());
     note_kernel(totals ? "sync_totals_kernel+sync_search_kernel+sync_finish_kernel" : "sync_search_kernel+sync_finish_kernel");

@@ -896,7 +896,8 @@ static VitPlan viterbi_plan(const cpx_trellis *t, int64_t B, int tb_depth, int d
 
 // any_batch_size: see viterbi_codeword_path (cpx_internal.h)
 static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const DemodSrc *dm, int64_t B, int64_t len, int64_t L,
-                            int64_t n_steps, int tb_depth, int decoding_type, uint8_t *d_bits, void *stream, bool any_batch_size = false) {
+                            int64_t n_steps, int tb_depth, int decoding_type, uint8_t *d_bits, Scratch &sc, void *stream,
+                            bool any_batch_size = false) {
     bool general = false;
     if (int rcv = viterbi_validate(t, dm, B, len, L, tb_depth, decoding_type, &general)) return rcv;
     if (B == 0 || L == 0) return CPX_OK;
@@ -906,14 +907,11 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
     note_kernel("");
     // (a forced 'general' path does not apply to the fused hard-demodulation entry point: it hands symbols in `dm`, d_coded is null)
     if (general || (!dm && (viterbi_path_flags() & 16)))
-        return viterbi_generic(t, d_coded, B, len, L, n_steps, tb_depth, decoding_type, d_bits, st);
-    // 'soft': one flag byte per work item of the launches below (see "NaN among 'soft' inputs"); scratch-arena slot 3
+        return viterbi_generic(t, d_coded, B, len, L, n_steps, tb_depth, decoding_type, d_bits, sc, st);
+    // 'soft': one flag byte per work item of the launches below (see "NaN among 'soft' inputs")
     uint8_t *nanflags = nullptr;
-    if (decoding_type == CPX_VIT_SOFT && !dm) {
-        void *w = nullptr;
-        if (int rcw = workspace(st, 3, (size_t)B + 64, &w)) return rcw;
-        nanflags = static_cast<uint8_t *>(w);
-    }
+    if (decoding_type == CPX_VIT_SOFT && !dm)
+        if (int rcw = sc.get(st, Slot::redo_flags, (size_t)B + 64, &nanflags)) return rcw;
     // parameters of the state-per-lane kernels for `nb` codewords starting at (`coded`, `bits`); `flags`: their flag bytes
     auto wave_params = [&](VitParams &p, const double *coded, uint8_t *bits, int64_t nb, uint8_t *flags) {
         p.coded = coded; p.bits = bits;
@@ -941,7 +939,7 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
         return e != hipSuccess ? CPX_EHIP : CPX_OK;
     };
     if (pl.Bcw > 0) {
-        const CwResult cw = viterbi_codeword_path(t, d_coded, pl.Bcw, len, L, n_steps, tb_depth, decoding_type, d_bits, nanflags, st,
+        const CwResult cw = viterbi_codeword_path(t, d_coded, pl.Bcw, len, L, n_steps, tb_depth, decoding_type, d_bits, nanflags, sc, st,
                                                   any_batch_size, pl.armed);
         if (cw.handled) {
             if (cw.rc != CPX_OK) return cw.rc;
@@ -1015,21 +1013,21 @@ static int viterbi_dispatch(const cpx_trellis *t, const double *d_coded, const D
 int cpx_viterbi_decode_batch_dev(const cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L,
                                  int64_t n_steps, int tb_depth, int decoding_type, uint8_t *d_bits, void *stream) {
     CPX_TRACE("cpx_viterbi_decode_batch_dev");
-    cpx::IssueGuard issue_guard;
-    return viterbi_dispatch(t, d_coded, nullptr, B, len, L, n_steps, tb_depth, decoding_type, d_bits, stream);
+    Scratch sc;
+    return viterbi_dispatch(t, d_coded, nullptr, B, len, L, n_steps, tb_depth, decoding_type, d_bits, sc, stream);
 }
 
 int cpx_demod_hard_viterbi_batch_dev(const cpx_modem *m, const cpx_trellis *t, const double *d_y_re_im, int64_t B,
                                      int64_t nsym, int64_t L, int64_t n_steps, int tb_depth, uint8_t *d_bits, void *stream) {
     CPX_TRACE("cpx_demod_hard_viterbi_batch_dev");
-    cpx::IssueGuard issue_guard;
+    Scratch sc;
     CPX_REQUIRE(m && t, CPX_EINVAL, "demod_hard_viterbi: null handle");
     if (int rcd = check_handle_device(m->device, "demod_hard_viterbi")) return rcd;
     CPX_REQUIRE(B >= 0 && nsym >= 0, CPX_EINVAL, "demod_hard_viterbi: negative size");
     CPX_REQUIRE(nsym * (int64_t)m->nbits < (1ll << 31), CPX_ELIMIT, "demod_hard_viterbi: codeword too long");
     DemodSrc dm{m, d_y_re_im, nsym};
     // len = the coded bits one codeword's symbols carry, exactly what demodulate(y, 'hard') would have returned
-    return viterbi_dispatch(t, nullptr, &dm, B, nsym * m->nbits, L, n_steps, tb_depth, CPX_VIT_HARD, d_bits, stream);
+    return viterbi_dispatch(t, nullptr, &dm, B, nsym * m->nbits, L, n_steps, tb_depth, CPX_VIT_HARD, d_bits, sc, stream);
 }
 
 int cpx_demod_hard_viterbi_batch(const cpx_modem *m, const cpx_trellis *t, const double *y_re_im, int64_t B, int64_t nsym,
@@ -1082,20 +1080,21 @@ int cpx_viterbi_decode_batch_i64(const cpx_trellis *t, const double *coded, int6
     // the arena blocks below are touched from this function's own three streams: hold the device's issue lock for the whole
     // call, so that cpx_release_workspace (which takes every issue lock, then synchronises the library stream only) cannot
     // free them while copies and kernels of the pipeline are still in flight
-    cpx::IssueGuard issue_guard;
+    Scratch sc;
     if (stage_cap < nout) {
         if (stage) (void)hipHostFree(stage);
         stage = nullptr; stage_cap = 0;
         CPX_HIP(hipHostMalloc((void **)&stage, nout, hipHostMallocDefault));
         stage_cap = nout;
     }
-    // device staging from the scratch arena -- slots 6 / 7 of the library stream, used by nothing else (this function is
+    // device staging from the scratch arena -- Slot::vit_host_in / vit_host_out of the library stream, used by nothing else (this function is
     // serialised by `mu`; the blocks are touched from the pipeline's own streams, so they must not be shared with entry points
     // that rely on the library stream's order): a
     // hipMalloc + hipFree of 1.08 GB per call is about a millisecond of a 23 ms call
-    ArenaBuf din, dout;
-    if ((rc = workspace(lib_stream(), 6, sizeof(double) * (size_t)(B * len), &din.p))) return rc;
-    if ((rc = workspace(lib_stream(), 7, nout, &dout.p))) return rc;
+    double *din;
+    uint8_t *dout;
+    if ((rc = sc.get(lib_stream(), Slot::vit_host_in, sizeof(double) * (size_t)(B * len), &din))) return rc;
+    if ((rc = sc.get(lib_stream(), Slot::vit_host_out, nout, &dout))) return rc;
     unsigned nt = std::thread::hardware_concurrency();
     if (nt > 16) nt = 16;
     if (nt < 1) nt = 1;
@@ -1162,7 +1161,7 @@ int cpx_viterbi_decode_batch_i64(const cpx_trellis *t, const double *coded, int6
             const int64_t lo = cw_lo(c), n = cw_lo(c + 1) - lo;
             {
                 CPX_TRACE("H2D chunk");
-                if (hipMemcpyAsync(din.as<double>() + lo * len, coded + lo * len, sizeof(double) * (size_t)(n * len),
+                if (hipMemcpyAsync(din + lo * len, coded + lo * len, sizeof(double) * (size_t)(n * len),
                                    hipMemcpyHostToDevice, s_up[dev]) != hipSuccess ||
                     hipEventRecord(ev_up[c].e, s_up[dev]) != hipSuccess) { set_error("viterbi: upload failed"); return fail(CPX_EHIP); }
             }
@@ -1170,12 +1169,12 @@ int cpx_viterbi_decode_batch_i64(const cpx_trellis *t, const double *coded, int6
             {
                 CPX_TRACE("cpx_viterbi_decode_batch_dev");
                 // the codeword path whatever the chunk's size: its round hides behind the next upload (viterbi_codeword_path)
-                rc = viterbi_dispatch(t, din.as<double>() + lo * len, nullptr, n, len, L, n_steps, tb_depth, decoding_type,
-                                      dout.as<uint8_t>() + lo * L, s_cmp[dev], true);
+                rc = viterbi_dispatch(t, din + lo * len, nullptr, n, len, L, n_steps, tb_depth, decoding_type, dout + lo * L, sc,
+                                      s_cmp[dev], true);
             }
             if (rc) return fail(rc);
             if (hipEventRecord(ev_cmp[c].e, s_cmp[dev]) != hipSuccess || hipStreamWaitEvent(s_dn[dev], ev_cmp[c].e, 0) != hipSuccess ||
-                hipMemcpyAsync(stage + lo * L, dout.as<uint8_t>() + lo * L, (size_t)(n * L), hipMemcpyDeviceToHost, s_dn[dev]) != hipSuccess ||
+                hipMemcpyAsync(stage + lo * L, dout + lo * L, (size_t)(n * L), hipMemcpyDeviceToHost, s_dn[dev]) != hipSuccess ||
                 hipEventRecord(ev_dn[c].e, s_dn[dev]) != hipSuccess) { set_error("viterbi: download failed"); return fail(CPX_EHIP); }
             { std::lock_guard<std::mutex> ql(qmu); issued = c + 1; }
             qcv.notify_all();
@@ -1188,15 +1187,14 @@ int cpx_viterbi_decode_batch_i64(const cpx_trellis *t, const double *coded, int6
     hipStream_t st = lib_stream();
     {
         CPX_TRACE("H2D coded");
-        CPX_HIP(hipMemcpyAsync(din.p, coded, sizeof(double) * (size_t)(B * len), hipMemcpyHostToDevice, st));
+        CPX_HIP(hipMemcpyAsync(din, coded, sizeof(double) * (size_t)(B * len), hipMemcpyHostToDevice, st));
         if (trace_enabled()) CPX_HIP(hipStreamSynchronize(st));   // ranges time the phases only if they do not overlap
     }
-    rc = cpx_viterbi_decode_batch_dev(t, din.as<double>(), B, len, L, n_steps, tb_depth, decoding_type,
-                                      dout.as<uint8_t>(), st);
+    rc = cpx_viterbi_decode_batch_dev(t, din, B, len, L, n_steps, tb_depth, decoding_type, dout, st);
     if (rc) return rc;
     {
         CPX_TRACE("D2H bits");
-        CPX_HIP(hipMemcpyAsync(stage, dout.p, nout, hipMemcpyDeviceToHost, st));
+        CPX_HIP(hipMemcpyAsync(stage, dout, nout, hipMemcpyDeviceToHost, st));
         CPX_HIP(hipStreamSynchronize(st));
     }
     CPX_TRACE("widen to int64 (host threads)");

@@ -1030,6 +1030,7 @@ const char *type_name(int type) { return type == CPX_VIT_HARD ? "hard" : type ==
 // what one call of viterbi_codeword_path works with
 struct CwCall {
     CwParams p;
+    Scratch *sc;
     hipStream_t st;
     size_t tb_lds;           // traceback window of the two-kernel form
     int64_t groups;
@@ -1065,12 +1066,9 @@ CwResult run_builtin(CwCall &c) {
                         deep ? ",runtime hops,64-slot ring" : tb == fused_tb<LG>() ? "" : ",runtime hops", (c.f32 && !deep) ? ",f32" : "");
             return r;
         }
-        void *w0 = nullptr, *w1 = nullptr;
         p.Tp = (p.T + LG - 1) / LG * LG;
-        if (int rc = workspace(c.st, 0, sizeof(unsigned long long) * (size_t)(c.groups * p.Tp * 64), &w0)) return {true, rc, CwFlavour::two_kernels};
-        if (int rc = workspace(c.st, 1, (size_t)(c.groups * p.Tp * 64), &w1)) return {true, rc, CwFlavour::two_kernels};
-        p.dec = static_cast<unsigned long long *>(w0);
-        p.best = static_cast<unsigned char *>(w1);
+        if (int rc = c.sc->get(c.st, Slot::state, sizeof(unsigned long long) * (size_t)(c.groups * p.Tp * 64), &p.dec)) return {true, rc, CwFlavour::two_kernels};
+        if (int rc = c.sc->get(c.st, Slot::state2, (size_t)(c.groups * p.Tp * 64), &p.best)) return {true, rc, CwFlavour::two_kernels};
         launch_two_kernels<LG, GA, GB>(p, c.tb_lds, c.st);
         const CwResult r = done(CwFlavour::two_kernels, "");
         note_kernel("viterbi_cw_acs_kernel<%d,0%o,0%o,%s> + viterbi_cw_tb_kernel<%d>", LG, GA, GB, type_name(type), LG);
@@ -1115,7 +1113,8 @@ CwResult run_table(int lg, CwCall &c) {
 namespace cpx {
 
 CwResult viterbi_codeword_path(const cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L, int64_t T,
-                               int tb, int type, uint8_t *d_bits, uint8_t *nanflags, hipStream_t st, bool any_batch_size, bool lean_ring) {
+                               int tb, int type, uint8_t *d_bits, uint8_t *nanflags, Scratch &sc, hipStream_t st, bool any_batch_size,
+                               bool lean_ring) {
     // path override (cpx_viterbi_set_path / CPX_VITERBI_PATH): "wave" = state-per-lane kernels; "cw" = this path whatever
     // the batch size; "cw!" = fail instead of falling back; "cw2", "cw2!" = the two-kernel form even where the fused
     // kernel applies
@@ -1132,6 +1131,7 @@ CwResult viterbi_codeword_path(const cpx_trellis *t, const double *d_coded, int6
     if (t->I != 2 || t->k != 1 || t->n != 2 || T < 1) return reject("needs a rate-1/2, k = 1 trellis");
     if ((len & 1) || ((uintptr_t)d_coded & 15)) return reject("rows must be 16-byte aligned");
     CwCall c;
+    c.sc = &sc;
     c.st = st;
     c.tb_lds = (size_t)(64 + tb - 2) * (TB_STRIDE * 8 + 64);
     if (c.tb_lds > 64 * 1024) return reject("traceback window exceeds 64 KiB of LDS");

@@ -199,7 +199,7 @@ int next_pow2_64(int64_t v) {
 namespace cpx {
 
 int viterbi_generic(const cpx_trellis *t, const double *d_coded, int64_t B, int64_t len, int64_t L, int64_t T, int tb, int type,
-                    uint8_t *d_bits, hipStream_t st) {
+                    uint8_t *d_bits, Scratch &sc, hipStream_t st) {
     CPX_REQUIRE(t->k <= 8, CPX_ELIMIT, "viterbi: k = %d > 8 not supported", t->k);
     CPX_REQUIRE(t->n <= 16, CPX_ELIMIT, "viterbi: n = %d > 16 not supported", t->n);
     GenParams p;
@@ -219,14 +219,10 @@ int viterbi_generic(const cpx_trellis *t, const double *d_coded, int64_t B, int6
     const size_t pm_bytes = lds_pm ? 0 : sizeof(double) * 2 * (size_t)t->S;
     int64_t grid = std::min<int64_t>(B, (int64_t)device_cus() * (NT == 64 ? 16 : 4));
     grid = std::min<int64_t>(grid, std::max<int64_t>(1, (int64_t)(((size_t)1 << 28) / (ring_bytes + pm_bytes))));
-    // scratch-arena slots 8 .. 10 (6 / 7 are the host-buffer pipeline's staging blocks, viterbi.hip)
-    void *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
-    if (int rc = workspace(st, 8, sizeof(unsigned long long) * (size_t)p.RS * p.k * p.W * (size_t)grid, &w0)) return rc;
-    if (int rc = workspace(st, 9, sizeof(int32_t) * (size_t)p.RS * (size_t)grid, &w1)) return rc;
-    if (!lds_pm) if (int rc = workspace(st, 10, pm_bytes * (size_t)grid, &w2)) return rc;
-    p.dring = static_cast<unsigned long long *>(w0);
-    p.bring = static_cast<int32_t *>(w1);
-    p.pm = static_cast<double *>(w2);
+    if (int rc = sc.get(st, Slot::vit_gen_ring, sizeof(unsigned long long) * (size_t)p.RS * p.k * p.W * (size_t)grid, &p.dring)) return rc;
+    if (int rc = sc.get(st, Slot::vit_gen_best, sizeof(int32_t) * (size_t)p.RS * (size_t)grid, &p.bring)) return rc;
+    p.pm = nullptr;
+    if (!lds_pm) if (int rc = sc.get(st, Slot::vit_gen_pm, pm_bytes * (size_t)grid, &p.pm)) return rc;
     if (NT == 64) hipLaunchKernelGGL((viterbi_generic_kernel<64>), dim3((unsigned)grid), dim3(64), lds, st, p);
     else hipLaunchKernelGGL((viterbi_generic_kernel<256>), dim3((unsigned)grid), dim3(256), lds, st, p);
     CPX_HIP(hipGetLastError());

@@ -247,7 +247,7 @@ def test_concurrent_host_threads_share_the_arena_safely(gpu):
     ldpc_in = [rs.randn(b * 1440) * 2 + 1.5 for b in sizes]
     vit_in = [rs.randn(b * 2, 2 * 70) * 2 for b in sizes]
     tur_in = [[rs.randn(b, 64) for _ in range(3)] for b in sizes]
-    with _lib.forced_path("viterbi", "cw2"):                        # two-kernel form: takes arena slots 0 and 1 as well
+    with _lib.forced_path("viterbi", "cw2"):                        # two-kernel form: takes arena slots `state` and `state2` as well
         want_l = [ldpc_bp_decode(x.copy(), p, "MSA", 8) for x in ldpc_in]
         want_v = [viterbi_decode(x, tr, 20, "soft") for x in vit_in]
         want_t = [turbo_decode(s, a, b, tr4, 0.8, 3, il) for s, a, b in tur_in]

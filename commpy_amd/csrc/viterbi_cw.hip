@@ -752,57 +752,73 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         // tile read before the next chunk overwrites it
     };
 
+    // One group of LGS steps starting at step t; `tile` = the lane's tile entry of step t.  Two bodies:
+    //  * FAST: every step of the group AND every step of the prefetch it issues for the next group carries received values and lies
+    //    inside [1, T] (t + 2 LGS - 1 <= tmax <= T).  Then `have` and `live` below hold for all LGS steps, the prefetch clamp is the
+    //    identity and step T is not among them: the pad selects, the clamp, the dummy-slot selects of the ring write(s) and the best_T
+    //    select are not compiled in.  With the selects gone the two stores of the mirrored ring sit a constant RING slots apart.
+    //  * general: any group (the body of every group before the split) -- the last groups of a codeword, all of them for T < 2 LGS.
+    // The values are the same either way: the fast body drops selects whose condition is known, never an operation on a metric.
+    auto group = [&](auto ftag, const int t, unsigned char *tile) __attribute__((always_inline)) {
+        constexpr bool FAST = decltype(ftag)::value;
+        // prefetch of the NEXT group, all of it at the top of this one: a whole group (~4700 instructions) lies between
+        // a load and the vmcnt(0) the compiler puts at the loop head.  (Reloading cur[R] inside step R saved 12
+        // registers but left the youngest load only one step of lead: rocprofv3 showed 14.5 % of the wave cycles
+        // parked in s_waitcnt.)
+        double2 nxt[LGS];
+        const double2 *xt = reinterpret_cast<const double2 *>(x) + (t - 1);   // FAST: one address per group, the steps are immediate offsets
+#pragma unroll
+        for (int u = 0; u < LGS; u++) nxt[u] = FAST ? xt[LGS + u] : load(t + LGS + u);
+        auto one = [&](auto rtag) {
+            constexpr int R = decltype(rtag)::value;
+            const int tt = t + R;
+            const bool have = FAST || tt <= tmax;
+            const double r0 = have ? cur[R].x : pad, r1 = have ? cur[R].y : pad;
+            unsigned long long word;
+            int bst;
+            if constexpr (TYPE == CPX_VIT_SOFT) nan_or(nanmask, cur[R].x, cur[R].y);   // (steps > tmax re-read step tmax)
+            cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, walk, nullptr, gidx);   // + hops 0 .. 3/4 H of the walk of step tt - 1
+            walk.finish();
+            tile[R] = (unsigned char)((walk.st >> (LGS - 1)) & 1u);           // input bit of the branch into the state at step tt - 1 - H
+            // ring slot of step tt and (mirrored ring) its copy RING slots above; the (at most LGS - 1) steps > T of the last group
+            // write to two dummy slots instead: the ring must keep the words of steps T-H+1 .. T for the final walk
+            const bool live = FAST || tt <= T;
+            const int q = tt & (RING - 1);
+            unsigned long long *wb = mycol + q * 64;
+            if constexpr (MIR) {
+                unsigned long long *w0 = live ? wb : mycol + (2 * RING) * 64;
+                unsigned long long *w1 = live ? wb + RING * 64 : mycol + (2 * RING + 1) * 64;
+                *w0 = word;
+                *w1 = word;
+                walk.pw = wb;                                                 // next: the walk of this step
+            } else {
+                unsigned long long *w0 = live ? wb : mycol + RING * 64;
+                *w0 = word;
+                walk.q = q;
+            }
+            if constexpr (!FAST) best_T = (tt == T) ? bst : best_T;
+            walk.st = (unsigned)bst;
+        };
+        if constexpr (LGS >= 1) one(std::integral_constant<int, 0>{});
+        if constexpr (LGS >= 2) one(std::integral_constant<int, 1 % LGS>{});
+        if constexpr (LGS >= 3) one(std::integral_constant<int, 2 % LGS>{});
+        if constexpr (LGS >= 4) one(std::integral_constant<int, 3 % LGS>{});
+        if constexpr (LGS >= 5) one(std::integral_constant<int, 4 % LGS>{});
+        if constexpr (LGS >= 6) one(std::integral_constant<int, 5 % LGS>{});
+#pragma unroll
+        for (int u = 0; u < LGS; u++) cur[u] = nxt[u];
+    };
+
     for (int tc0 = 1; tc0 <= T; tc0 += CHUNK) {
         const int left = (T - tc0) / LGS + 1;                                      // groups that start at a step <= T
         const int ngroups = left < FR_GROUPS ? left : FR_GROUPS;
-        for (int g = 0; g < ngroups; g++) {
-            const int t = tc0 + g * LGS;
-            // prefetch of the NEXT group, all of it at the top of this one: a whole group (~4700 instructions) lies between
-            // a load and the vmcnt(0) the compiler puts at the loop head.  (Reloading cur[R] inside step R saved 12
-            // registers but left the youngest load only one step of lead: rocprofv3 showed 14.5 % of the wave cycles
-            // parked in s_waitcnt.)
-            double2 nxt[LGS];
-#pragma unroll
-            for (int u = 0; u < LGS; u++) nxt[u] = load(t + LGS + u);
-            auto one = [&](auto rtag) {
-                constexpr int R = decltype(rtag)::value;
-                const int tt = t + R;
-                const bool have = tt <= tmax;
-                const double r0 = have ? cur[R].x : pad, r1 = have ? cur[R].y : pad;
-                unsigned long long word;
-                int bst;
-                if constexpr (TYPE == CPX_VIT_SOFT) nan_or(nanmask, cur[R].x, cur[R].y);   // (steps > tmax re-read step tmax)
-                cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, walk, nullptr, gidx);   // + hops 0 .. 3/4 H of the walk of step tt - 1
-                walk.finish();
-                myrow[g * LGS + R] = (unsigned char)((walk.st >> (LGS - 1)) & 1u);   // input bit of the branch into the state at step tt - 1 - H
-                // ring slot of step tt and (mirrored ring) its copy RING slots above; the (at most LGS - 1) steps > T of the last group
-                // write to two dummy slots instead: the ring must keep the words of steps T-H+1 .. T for the final walk
-                const bool live = tt <= T;
-                const int q = tt & (RING - 1);
-                unsigned long long *wb = mycol + q * 64;
-                if constexpr (MIR) {
-                    unsigned long long *w0 = live ? wb : mycol + (2 * RING) * 64;
-                    unsigned long long *w1 = live ? wb + RING * 64 : mycol + (2 * RING + 1) * 64;
-                    *w0 = word;
-                    *w1 = word;
-                    walk.pw = wb;                                                 // next: the walk of this step
-                } else {
-                    unsigned long long *w0 = live ? wb : mycol + RING * 64;
-                    *w0 = word;
-                    walk.q = q;
-                }
-                best_T = (tt == T) ? bst : best_T;
-                walk.st = (unsigned)bst;
-            };
-            if constexpr (LGS >= 1) one(std::integral_constant<int, 0>{});
-            if constexpr (LGS >= 2) one(std::integral_constant<int, 1 % LGS>{});
-            if constexpr (LGS >= 3) one(std::integral_constant<int, 2 % LGS>{});
-            if constexpr (LGS >= 4) one(std::integral_constant<int, 3 % LGS>{});
-            if constexpr (LGS >= 5) one(std::integral_constant<int, 4 % LGS>{});
-            if constexpr (LGS >= 6) one(std::integral_constant<int, 5 % LGS>{});
-#pragma unroll
-            for (int u = 0; u < LGS; u++) cur[u] = nxt[u];
-        }
+        // the chunk's fast groups are its first nfast ones (the condition only gets harder as t grows): wave-uniform, scalar unit
+        const int room = tmax - tc0 - (2 * LGS - 1);                               // >= 0: the chunk's first group is fast
+        const int nfast = room < 0 ? 0 : (room / LGS + 1 < ngroups ? room / LGS + 1 : ngroups);
+        int t = tc0;
+        unsigned char *tile = myrow;                                               // advanced by LGS entries per group: the step's offset R is an immediate
+        for (int g = 0; g < nfast; g++, t += LGS, tile += LGS) group(std::true_type{}, t, tile);
+        for (int g = nfast; g < ngroups; g++, t += LGS, tile += LGS) group(std::false_type{}, t, tile);
         int n = ngroups * LGS;
         if (tc0 + CHUNK > T) {                                                     // last chunk: finish the pending walk (of its last step)
             unsigned st = walk.st;

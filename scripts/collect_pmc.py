@@ -67,9 +67,12 @@ def main():
     # ---- pass 0: kernel trace + stats ----
     d = os.path.join(out, a.name + "_trace")
     shutil.rmtree(d, ignore_errors=True)
-    subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] + cmd,
-                   cwd="/tmp", env=env, timeout=a.timeout, stdout=open(os.path.join(out, a.name + "_trace.log"), "w"),
-                   stderr=subprocess.STDOUT)
+    # a pass that fails (or runs into its time limit: TimeoutExpired) ends the collection -- nothing more is started on that GPU
+    rc = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] + cmd,
+                        cwd="/tmp", env=env, timeout=a.timeout, stdout=open(os.path.join(out, a.name + "_trace.log"), "w"),
+                        stderr=subprocess.STDOUT).returncode
+    if rc != 0:
+        sys.exit("kernel-trace pass: exit %d (see %s_trace.log)" % (rc, a.name))
     # bench.py's own line from INSIDE the profiled run (round 5): its shader-clock probe and per-launch event times under rocprofv3
     profiled_line = None
     try:
@@ -94,9 +97,11 @@ def main():
         tag = "_".join(grp)[:40]
         d = os.path.join(out, a.name + "_pmc_" + tag)
         shutil.rmtree(d, ignore_errors=True)
-        subprocess.run(["rocprofv3", "--pmc"] + grp + ["--kernel-trace", "--output-format", "csv", "-d", d, "--"] + cmd,
-                       cwd="/tmp", env=env, timeout=a.timeout,
-                       stdout=open(os.path.join(out, a.name + "_pmc_" + tag + ".log"), "w"), stderr=subprocess.STDOUT)
+        rc = subprocess.run(["rocprofv3", "--pmc"] + grp + ["--kernel-trace", "--output-format", "csv", "-d", d, "--"] + cmd,
+                            cwd="/tmp", env=env, timeout=a.timeout,
+                            stdout=open(os.path.join(out, a.name + "_pmc_" + tag + ".log"), "w"), stderr=subprocess.STDOUT).returncode
+        if rc != 0:
+            sys.exit("counter pass %s: exit %d (see %s_pmc_%s.log)" % (tag, rc, a.name, tag))
         acc = collections.defaultdict(lambda: [0.0, 0])
         for path in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
             for r in csv.DictReader(open(path)):

@@ -127,8 +127,10 @@ def position_table(loop, steps):
     return out
 
 
-def chunk_table(body, addr, hot):
-    """Static counts of the per-chunk code around the hot loop `hot` = (first, last) and of the flush rounds inside it."""
+def chunk_table(body, addr, hot, general=None):
+    """Static counts of the per-chunk code around the hot loop `hot` = (first, last) and of the flush rounds inside it.
+    `general`: the second group loop of a kernel that splits its groups into fast and general ones (main()); the compiler may
+    then lay the chunk loop out so that no backward branch spans the hot loop -- the whole kernel stands in for it."""
     def branches():
         for i, (ad, op, args) in enumerate(body):
             if op.startswith("s_cbranch") or op == "s_branch":
@@ -141,25 +143,31 @@ def chunk_table(body, addr, hot):
         return ((j, i) for j, i in branches() if j < i)
     outer = min(((j, i) for j, i in loops() if j < hot[0] and i > hot[1]), key=lambda ji: ji[1] - ji[0], default=None)
     out = ["", "per 96-step chunk, outside the hot loop (static counts; the hot loop runs 16 trips per chunk):", ""]
-    if outer is None:
-        return out + ["(no loop around the hot loop found)"]
+    whole = outer is None
+    if whole:
+        if general is None:
+            return out + ["(no loop around the hot loop found)"]
+        outer = (0, len(body) - 1)
+        out += ["(no backward branch spans the hot loop: counted over the whole kernel, its prologue and epilogue included)", ""]
     rounds = [(j, i) for j, i in loops() if outer[0] <= j and i <= outer[1] and (i < hot[0] or j > hot[1]) and
+              not (general and general[0] <= j and i <= general[1]) and not (general and j <= general[0] and i >= general[1]) and
               any(o.startswith("global_store") for _, o, _ in body[j:i + 1])]
     rnd = min(rounds, key=lambda ji: ji[1] - ji[0], default=None)
     # the float64 fallback of the 32-bit first-argmin: blocks behind the hot loop that a forward branch out of the loop enters and
     # that end with a branch back into it, each holding a first-equal scan (64 v_cmp_eq_f64).  A step runs one only when a lane of
     # its wave has a high-dword tie; they are not part of what a chunk executes besides its steps.
     cold = []
-    for t, i in branches():
-        if hot[0] <= i <= hot[1] and outer[1] >= t > hot[1]:
-            e = next((k for j, k in branches() if k >= t and hot[0] <= j <= hot[1]), None)
-            if e is not None and sum(1 for _, o, _ in body[t:e + 1] if o == "v_cmp_eq_f64") >= 64 and (t, e) not in cold:
-                cold.append((t, e))
+    for lp in [hot] + ([general] if general else []):
+        for t, i in branches():
+            if lp[0] <= i <= lp[1] and outer[1] >= t > lp[1]:
+                e = next((k for j, k in branches() if k >= t and lp[0] <= j <= lp[1]), None)
+                if e is not None and sum(1 for _, o, _ in body[t:e + 1] if o == "v_cmp_eq_f64") >= 64 and (t, e) not in cold:
+                    cold.append((t, e))
     n_cold = sum(e - t + 1 for t, e in cold)
-    n_outer = outer[1] - outer[0] + 1 - (hot[1] - hot[0] + 1) - n_cold
+    n_outer = outer[1] - outer[0] + 1 - (hot[1] - hot[0] + 1) - n_cold - (general[1] - general[0] + 1 if general else 0)
     out += ["| block | instructions |", "|---|---|"]
     if cold:
-        out.append("| float64 fallback of the first-argmin, %d blocks out of line behind the loop (one per unrolled step; a step runs its block "
+        out.append("| float64 fallback of the first-argmin, %d blocks out of line behind the loop(s) (one per unrolled step; a step runs its block "
                    "only when a lane of the wave has a high-dword tie): NOT part of the rows below | %d |" % (len(cold), n_cold))
     if rnd:
         seg = body[rnd[0]:rnd[1] + 1]
@@ -167,9 +175,13 @@ def chunk_table(body, addr, hot):
         out.append("| flush, one round of eight codewords (x 8 per chunk): %d LDS reads, %d stores, %d branches | %d |" %
                    (sum(o.startswith("ds_read") for _, o, _ in seg), sum(o.startswith("global_store") for _, o, _ in seg),
                     sum(o.startswith(("s_cbranch", "s_branch")) for _, o, _ in seg), n_rnd))
-        out.append("| chunk set-up, flush set-up, the last chunk's pending walk | %d |" % (n_outer - n_rnd))
-        out.append("| **per chunk, every flush instruction executed** | **%d** = %.1f per trellis step |" %
-                   (n_outer - n_rnd + 8 * n_rnd, (n_outer - n_rnd + 8 * n_rnd) / 96.0))
+        if whole:
+            out.append("| everything else outside the two group loops: kernel prologue, chunk set-up, flush set-up, the pending and the "
+                       "final walk (not a per-chunk figure) | %d |" % (n_outer - n_rnd))
+        else:
+            out.append("| chunk set-up, flush set-up, the last chunk's pending walk | %d |" % (n_outer - n_rnd))
+            out.append("| **per chunk, every flush instruction executed** | **%d** = %.1f per trellis step |" %
+                       (n_outer - n_rnd + 8 * n_rnd, (n_outer - n_rnd + 8 * n_rnd) / 96.0))
     else:
         out.append("| all of it (no flush round loop found) | %d |" % n_outer)
     return out
@@ -213,15 +225,21 @@ def main():
         sys.exit("no loop found")
     loop = body[best[0]:best[1] + 1]
     steps = eq_compares(loop) // 64
+    # a kernel that splits its groups into fast and general ones has a second loop of as many steps beside the hot one: the general
+    # body, run by the groups that touch padding or step T (the last ones of a codeword)
+    others = [c for c in cands if -c[0] == steps and (c[3] < best[0] or c[2] > best[1])]
+    general = min(others)[2:] if others else None
     cnt = collections.Counter(classify(op, args, loop[k - 1][1] if k else None) for k, (_, op, args) in enumerate(loop))
     valu = sum(v for k, v in cnt.items() if not k.startswith(("LDS", "memory", "s_", "scalar")))
     lines = ["kernel: %s" % a.kernel,
-             "hot loop: %d instructions per trip, %d trellis steps per trip (kernel: %d instructions)" % (len(loop), steps, len(body)), "",
+             "hot loop: %d instructions per trip, %d trellis steps per trip (kernel: %d instructions)" % (len(loop), steps, len(body))] + \
+            (["general group loop (behind the hot loop; groups that touch padding or step T): %d instructions per trip = %.1f per step"
+              % (general[1] - general[0] + 1, (general[1] - general[0] + 1) / steps)] if general else []) + ["",
              "| phase of cw_step | instructions per trellis step |", "|---|---|"]
     for k, v in sorted(cnt.items(), key=lambda kv: -kv[1]):
         lines.append("| %s | %.1f |" % (k, v / steps))
     lines += ["| **all** | **%.1f** (vector ALU: %.1f) |" % (len(loop) / steps, valu / steps)]
-    lines += position_table(loop, steps) + chunk_table(body, addr, best)
+    lines += position_table(loop, steps) + chunk_table(body, addr, best, general)
     text = "\n".join(lines)
     print(text)
     if a.md:

@@ -10,6 +10,7 @@ points raise if the HIP library or the GPU is missing.
 
     from commpy_amd.channelcoding import Trellis, viterbi_decode, map_decode, turbo_decode, ldpc_bp_decode
     from commpy_amd.modulation import PSKModem, QAMModem, ofdm_tx, ofdm_rx
+    from commpy_amd.modulation import OfdmPilots, ofdm_map_batch, ofdm_estimate_batch, ofdm_estimate_tv_batch
     from commpy_amd.filters import rrcosfilter, pulse_shape, matched_filter
     from commpy_amd.sequences import pnsequence, zcsequence
     from commpy_amd.impairments import add_frequency_offset

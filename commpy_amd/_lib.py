@@ -122,6 +122,10 @@ SYMBOLS = {
     "cpx_pilots_map_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "cpx_pilots_estimate": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "cpx_pilots_estimate_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpx_pilots_create_tv": (c_int, [c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     POINTER(c_void_p)]),
+    "cpx_pilots_estimate_tv": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "cpx_pilots_estimate_tv_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cpx_sync_metric": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "cpx_sync_metric_dev": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cpx_sync_estimate": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -155,6 +155,8 @@ enum class Slot : int {
     mimo_channel_state,  // mimo_channel.hip: per-wave scratch above 64 KB
     ofdm_ls,             // ofdm_chan.hip: least-squares estimates at the pilots
     ofdm_hsc,            // ofdm_chan.hip: the channel at every subcarrier, where the caller does not ask for it
+    ofdm_lsp,            // ofdm_chan.hip cpx_pilots_estimate_tv_dev: least-squares estimates per pilot (no averaging over symbols)
+    ofdm_hp,             // ofdm_chan.hip cpx_pilots_estimate_tv_dev: the channel at every subcarrier of every pilot symbol
     sync_totals,         // sync.hip windows_setup: per-tile totals of the window sums
     sync_parts,          // sync.hip cpx_sync_estimate_dev: per-tile partial results of the peak search
     fading_taps,         // fading.hip launch_taps: the power-delay profile's taps

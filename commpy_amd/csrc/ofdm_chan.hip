@@ -30,6 +30,18 @@
 //   ofdm_ydemap_kernel   y_data[b][d][r] = Y[b][r][re(d)]: the transposition goes through the LDS (odd row stride), so that loads
 //                        run along the subcarriers and stores are one contiguous run per workgroup.
 //   ofdm_map_kernel      the inverse for the transmitter: a contiguous run of data vectors -> LDS -> one row of the grid per antenna.
+// Time tracking (cpx_pilots_create_tv / cpx_pilots_estimate_tv): the estimator is separable, frequency first, then time.
+// Antenna t's pilots form a rectangle, its pilot symbols s_0 < ... < s_{ns_t - 1} times its pilot subcarriers; a second caller-supplied
+// matrix V_t [nsym][ns_t] spreads the estimates at the pilot symbols over all symbols (linear, hold, Wiener: all "a matrix").
+//   ofdm_ls_kernel          on tables with ONE pilot per item (t, i, j): LSp = Y[s_i][k_j] c, one mac from +0 (its division by 1 is exact)
+//   ofdm_interp_kernel<1>   Hp[b][i][k][r][t] = sum_j W_t[k][j] LSp[b][r][t][i][j]: the same tile and chain with columns (b, r, i)
+//   ofdm_tv_kernel          H^[b][s][k][r][t] = sum_i V_t[s][i] Hp[b][i][k][r][t], a chain of mac from +0 over ascending i, fused with the
+//                           demap.  A workgroup owns 256 consecutive values of one frame's [nsc][nr][nt] plane: a thread loads its
+//                           element of Hp for the first 4 pilot symbols once into registers (further ones are read again per symbol,
+//                           from the L1 / L2), then loops over the symbols; per symbol it stores the value to h_sym (if requested) and,
+//                           where the resource element carries data, to h_data -- consecutive lanes, consecutive addresses, since the
+//                           data elements of a symbol are numbered by ascending subcarrier.  H^ per symbol is never read back.  V
+//                           (all antennas) is staged in the LDS once per workgroup where it fits 16 KB.
 // Every output element goes through the same operations wherever its frame sits in the batch: bit-identical across batch sizes,
 // positions, streams and whichever outputs are requested; a frame's samples meet no other frame's (NaN isolation).  Offsets 64-bit.
 #include "cpx_internal.h"
@@ -59,6 +71,14 @@ struct cpx_ofdm_pilots {
     double2 *d_ls_coef = nullptr;   // [npil] conj(p) / |p|^2
     int64_t *d_ant = nullptr;       // [nt][3] np_t, first item, offset of W_t in d_w (complex values)
     double2 *d_w = nullptr;         // W_0 [nsc][np_0], W_1 ...
+    // time tracking (cpx_pilots_create_tv), absent (ns_max = 0) in a plan of cpx_pilots_create
+    int ns_max = 0;                 // the most pilot symbols of an antenna
+    int64_t nlsp = 0, nv = 0;       // nlsp = sum_t ns_t np_t items (t, i, j) of a (b, r); nv = sum_t nsym ns_t entries of V
+    int32_t *d_tv_ptr = nullptr;    // [nlsp + 1] 0, 1, 2 ...: ofdm_ls_kernel's tables with one pilot per item, ordered (t, i, j)
+    int32_t *d_tv_re = nullptr;     // [nlsp] resource element s_i nsc + k_j
+    double2 *d_tv_coef = nullptr;   // [nlsp] conj(p) / |p|^2
+    int64_t *d_tv_ant = nullptr;    // [nt][3] ns_t, first item, offset of V_t in d_v (complex values)
+    double2 *d_v = nullptr;         // V_0 [nsym][ns_0], V_1 ...
 };
 
 namespace {
@@ -206,9 +226,10 @@ int oc_rows(int width) { const int v = OC_TILE / (width | 1); return v > 256 ? 2
 struct OcArgs {
     const int32_t *code, *dcount, *data_re, *data_sc, *pil_tx, *ls_ptr, *ls_re;
     const double2 *pil_val, *ls_coef, *w;
-    const int64_t *ant;
+    const int64_t *ant, *tv_ant;
     int64_t B, F, ndata, nls;       // F = nsym nsc
     int nsc, nt, nr, rows;          // rows: oc_rows of the kernel's width
+    int ns_max;                     // ofdm_interp_kernel<true>
 };
 
 __global__ __launch_bounds__(OC_BLOCK) void ofdm_map_kernel(OcArgs a, const double2 *data, double2 *grid) {
@@ -254,10 +275,13 @@ __global__ __launch_bounds__(OC_BLOCK) void ofdm_ls_kernel(OcArgs a, const doubl
 
 constexpr int IK_KT = 64, IK_CT = 32, IK_JC = 16, IK_CPT = IK_CT / (OC_BLOCK / 64);
 
+// TV: the columns are (b, r, i) with i < ns_max a pilot symbol (skipped where antenna t has fewer), ls holds one item per (t, i, j) and
+// the output is Hp [B][ns_max][nsc][nr][nt]; tile, staging and chain are the same
+template <bool TV>
 __global__ __launch_bounds__(OC_BLOCK) void ofdm_interp_kernel(OcArgs a, const double2 *ls, double2 *hsc) {
     __shared__ double2 wt[IK_JC][IK_KT + 1];               // W_t tile, transposed; the odd stride spreads the staging stores
     __shared__ double2 lt[IK_JC][IK_CT];
-    const int64_t C = a.B * a.nr;                           // columns (b, r)
+    const int64_t C = TV ? a.B * a.nr * a.ns_max : a.B * a.nr;   // columns (b, r) or (b, r, i)
     const int64_t ktiles = (a.nsc + IK_KT - 1) / IK_KT, ctiles = (C + IK_CT - 1) / IK_CT;
     const int64_t ntiles = ctiles * a.nt * ktiles;
     const int kl = threadIdx.x & 63, cg = threadIdx.x >> 6;
@@ -267,7 +291,8 @@ __global__ __launch_bounds__(OC_BLOCK) void ofdm_interp_kernel(OcArgs a, const d
         const int k0 = (int)(rem - t * ktiles) * IK_KT;
         const int64_t c0 = ct * IK_CT;
         const int np = (int)a.ant[3 * t];
-        const int64_t item0 = a.ant[3 * t + 1];
+        const int64_t item0 = TV ? a.tv_ant[3 * t + 1] : a.ant[3 * t + 1];
+        const int ns = TV ? (int)a.tv_ant[3 * t] : 1;
         const double2 *w = a.w + a.ant[3 * t + 2];
         double2 acc[IK_CPT];
 #pragma unroll
@@ -281,8 +306,16 @@ __global__ __launch_bounds__(OC_BLOCK) void ofdm_interp_kernel(OcArgs a, const d
             for (int e = threadIdx.x; e < IK_JC * IK_CT; e += OC_BLOCK) {
                 const int jj = e / IK_CT, cc = e - jj * IK_CT;
                 if (jj < JCn) {
-                    const int64_t c = c0 + cc, b = c / a.nr;
-                    lt[jj][cc] = c < C ? ls[(b * a.nls + item0 + j0 + jj) * a.nr + (c - b * a.nr)] : make_double2(0.0, 0.0);
+                    const int64_t c = c0 + cc;
+                    if constexpr (TV) {
+                        const int64_t q = c / a.ns_max, b = q / a.nr;
+                        const int i = (int)(c - q * a.ns_max);
+                        lt[jj][cc] = c < C && i < ns ? ls[(b * a.nls + item0 + (int64_t)i * np + j0 + jj) * a.nr + (q - b * a.nr)]
+                                                     : make_double2(0.0, 0.0);
+                    } else {
+                        const int64_t b = c / a.nr;
+                        lt[jj][cc] = c < C ? ls[(b * a.nls + item0 + j0 + jj) * a.nr + (c - b * a.nr)] : make_double2(0.0, 0.0);
+                    }
                 }
             }
             __syncthreads();
@@ -297,7 +330,11 @@ __global__ __launch_bounds__(OC_BLOCK) void ofdm_interp_kernel(OcArgs a, const d
 #pragma unroll
             for (int i = 0; i < IK_CPT; i++) {
                 const int64_t c = c0 + cg * IK_CPT + i;
-                if (c < C) {
+                if constexpr (TV) {
+                    const int64_t q = c / a.ns_max, b = q / a.nr;
+                    const int ip = (int)(c - q * a.ns_max);
+                    if (c < C && ip < ns) hsc[(((b * a.ns_max + ip) * a.nsc + k0 + kl) * a.nr + (q - b * a.nr)) * a.nt + t] = acc[i];
+                } else if (c < C) {
                     const int64_t b = c / a.nr;
                     hsc[((b * a.nsc + k0 + kl) * a.nr + (c - b * a.nr)) * a.nt + t] = acc[i];
                 }
@@ -346,12 +383,67 @@ __global__ __launch_bounds__(OC_BLOCK) void ofdm_ydemap_kernel(OcArgs a, const d
     }
 }
 
+constexpr int TV_NS = 4;          // pilot symbols of an element kept in registers
+constexpr int TV_VMAX = 1024;     // entries of V staged in the LDS (16 KB)
+
+struct TvArgs {
+    const int32_t *code;
+    const int64_t *tv_ant;
+    const double2 *v, *hp;          // hp [B][ns_max][nsc][nr][nt]
+    double2 *hsym, *hdata;          // either may be null
+    int64_t B, ndata, FE, nv;       // FE = nsc nr nt, one symbol's plane
+    int nsc, nsym, nt, E, ns_max;   // E = nr nt
+};
+
+// time interpolation fused with the demap: one element (k, r, t) per thread, its pilot symbols loaded once, all symbols written
+template <bool VLDS>
+__global__ __launch_bounds__(OC_BLOCK) void ofdm_tv_kernel(TvArgs a) {
+    __shared__ double2 vs[VLDS ? TV_VMAX : 1];
+    if constexpr (VLDS) {
+        for (int i = threadIdx.x; i < (int)a.nv; i += OC_BLOCK) vs[i] = a.v[i];
+        __syncthreads();
+    }
+    auto v_at = [&](int64_t i) -> double2 {
+        if constexpr (VLDS) return vs[i];
+        else return a.v[i];
+    };
+    const int32_t *__restrict__ code = a.code;
+    const int64_t ftiles = (a.FE + OC_BLOCK - 1) / OC_BLOCK, ntiles = a.B * ftiles;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t b = tile / ftiles;
+        const int64_t f = (tile - b * ftiles) * OC_BLOCK + threadIdx.x;
+        if (f >= a.FE) continue;
+        const int64_t k = f / a.E;
+        const int e = (int)(f - k * a.E), t = e % a.nt;
+        const int ns = (int)a.tv_ant[3 * t];
+        const int64_t voff = a.tv_ant[3 * t + 2];
+        const double2 *h = a.hp + b * a.ns_max * a.FE + f;  // pilot symbol i at h[i FE]
+        double2 hr[TV_NS];
+#pragma unroll
+        for (int i = 0; i < TV_NS; i++) hr[i] = i < ns ? h[i * a.FE] : make_double2(0.0, 0.0);
+        for (int s = 0; s < a.nsym; s++) {
+            const int64_t vrow = voff + (int64_t)s * ns;
+            double2 acc = make_double2(0.0, 0.0);
+#pragma unroll
+            for (int i = 0; i < TV_NS; i++)
+                if (i < ns) mac(acc, v_at(vrow + i), hr[i]);
+            for (int i = TV_NS; i < ns; i++) mac(acc, v_at(vrow + i), h[i * a.FE]);
+            if (a.hsym) a.hsym[(b * a.nsym + s) * a.FE + f] = acc;
+            if (a.hdata) {
+                const int d = code[(int64_t)s * a.nsc + k];
+                if (d >= 0) a.hdata[(b * a.ndata + d) * a.E + e] = acc;
+            }
+        }
+    }
+}
+
 OcArgs plan_args(const cpx_ofdm_pilots *p, int64_t B) {
     OcArgs a{};
     a.code = p->d_code; a.dcount = p->d_dcount; a.data_re = p->d_data_re; a.data_sc = p->d_data_sc; a.pil_tx = p->d_pil_tx;
     a.ls_ptr = p->d_ls_ptr; a.ls_re = p->d_ls_re; a.pil_val = p->d_pil_val; a.ls_coef = p->d_ls_coef; a.w = p->d_w; a.ant = p->d_ant;
     a.B = B; a.F = (int64_t)p->nsym * p->nsc; a.ndata = p->ndata; a.nls = p->nls;
     a.nsc = p->nsc; a.nt = p->nt;
+    a.tv_ant = p->d_tv_ant; a.ns_max = p->ns_max;
     return a;
 }
 
@@ -362,14 +454,22 @@ int map_sizes(const cpx_ofdm_pilots *p, int64_t B) {
     return CPX_OK;
 }
 
-int estimate_sizes(const cpx_ofdm_pilots *p, int64_t B, int nr, const void *h_sc, const void *y_data, const void *h_data) {
-    CPX_REQUIRE(p, CPX_EINVAL, "ofdm_estimate: null plan");
-    CPX_REQUIRE(B >= 0, CPX_EINVAL, "ofdm_estimate: negative batch size");
-    CPX_REQUIRE(nr >= 1, CPX_EINVAL, "ofdm_estimate: nr = %d, need at least 1", nr);
-    CPX_REQUIRE(nr <= CPX_OC_MAX_ANT, CPX_ELIMIT, "ofdm_estimate: nr = %d is above the engine's limit of %d", nr, CPX_OC_MAX_ANT);
-    CPX_REQUIRE(h_sc || y_data || h_data, CPX_EINVAL, "ofdm_estimate: no output requested");
-    CPX_REQUIRE(B == 0 || B <= INT64_MAX / 64 / ((int64_t)p->nsym * p->nsc * p->nt * nr), CPX_EINVAL, "ofdm_estimate: %lld frames overflow",
+// nsym nsc nt nr values per frame: the size of Y times nt, and of cpx_pilots_estimate_tv's h_sym, its largest array
+int estimate_sizes(const cpx_ofdm_pilots *p, int64_t B, int nr, const void *h_sc, const void *y_data, const void *h_data,
+                   const char *what = "ofdm_estimate") {
+    CPX_REQUIRE(p, CPX_EINVAL, "%s: null plan", what);
+    CPX_REQUIRE(B >= 0, CPX_EINVAL, "%s: negative batch size", what);
+    CPX_REQUIRE(nr >= 1, CPX_EINVAL, "%s: nr = %d, need at least 1", what, nr);
+    CPX_REQUIRE(nr <= CPX_OC_MAX_ANT, CPX_ELIMIT, "%s: nr = %d is above the engine's limit of %d", what, nr, CPX_OC_MAX_ANT);
+    CPX_REQUIRE(h_sc || y_data || h_data, CPX_EINVAL, "%s: no output requested", what);
+    CPX_REQUIRE(B == 0 || B <= INT64_MAX / 64 / ((int64_t)p->nsym * p->nsc * p->nt * nr), CPX_EINVAL, "%s: %lld frames overflow", what,
                 (long long)B);
+    return CPX_OK;
+}
+
+int estimate_tv_sizes(const cpx_ofdm_pilots *p, int64_t B, int nr, const void *h_sym, const void *y_data, const void *h_data) {
+    if (int rc = estimate_sizes(p, B, nr, h_sym, y_data, h_data, "ofdm_estimate_tv")) return rc;
+    CPX_REQUIRE(p->ns_max > 0, CPX_EINVAL, "ofdm_estimate_tv: the plan has no time matrices (it was made by cpx_pilots_create, not cpx_pilots_create_tv)");
     return CPX_OK;
 }
 
@@ -430,15 +530,16 @@ int cpx_multipath(const double *x_re_im, const double *g_re_im, int g_batched, i
     return s.get(y_re_im, dy, y_bytes);
 }
 
-int cpx_pilots_create(int nsc, int nsym, int nt, int64_t npil, const int32_t *pil_sym, const int32_t *pil_sc, const int32_t *pil_tx,
-                           const double *pil_val_re_im, const double *w_re_im, cpx_ofdm_pilots **out) {
-    CPX_TRACE("cpx_pilots_create");
+// both forms of the plan: tv = with the time matrices v_re_im
+static int pilots_create(int nsc, int nsym, int nt, int64_t npil, const int32_t *pil_sym, const int32_t *pil_sc, const int32_t *pil_tx,
+                         const double *pil_val_re_im, const double *w_re_im, bool tv, const double *v_re_im, cpx_ofdm_pilots **out) {
     CPX_REQUIRE(out, CPX_EINVAL, "ofdm_pilots: null pointer");
     *out = nullptr;
     CPX_REQUIRE(nsc >= 2 && nsc % 2 == 0, CPX_EINVAL, "ofdm_pilots: nsc = %d, need an even number >= 2", nsc);
     CPX_REQUIRE(nsym >= 1 && nt >= 1 && npil >= 1, CPX_EINVAL, "ofdm_pilots: nsym = %d, nt = %d, npil = %lld, need at least 1 of each", nsym, nt,
                 (long long)npil);
     CPX_REQUIRE(pil_sym && pil_sc && pil_tx && pil_val_re_im && w_re_im, CPX_EINVAL, "ofdm_pilots: null pointer");
+    CPX_REQUIRE(!tv || v_re_im, CPX_EINVAL, "ofdm_pilots: null time matrices (v_re_im)");
     CPX_REQUIRE(nt <= CPX_OC_MAX_ANT, CPX_ELIMIT, "ofdm_pilots: nt = %d is above the engine's limit of %d", nt, CPX_OC_MAX_ANT);
     const int64_t F = (int64_t)nsym * nsc;
     CPX_REQUIRE(F <= INT32_MAX / 2, CPX_ELIMIT, "ofdm_pilots: a frame of %lld resource elements is above the engine's limit", (long long)F);
@@ -491,6 +592,50 @@ int cpx_pilots_create(int nsc, int nsym, int nt, int64_t npil, const int32_t *pi
     }
     for (int64_t i = 0; i < 2 * w_total; i++)
         CPX_REQUIRE(std::isfinite(w_re_im[i]), CPX_EINVAL, "ofdm_pilots: the interpolation matrices hold a value that is not finite");
+    // time tracking: per antenna the rectangle (pilot symbols) x (pilot subcarriers), one least-squares item per pilot in (t, i, j) order
+    std::vector<int32_t> tv_ptr, tv_re;
+    std::vector<double> tv_coef;
+    std::vector<int64_t> tv_ant(3 * (size_t)nt, 0);
+    int64_t nv = 0;
+    int ns_max = 0;
+    if (tv) {
+        tv_re.reserve(npil);
+        tv_coef.reserve(2 * (size_t)npil);
+        std::vector<int32_t> syms, on_sym(nsym);
+        for (int t = 0; t < nt; t++) {
+            const int64_t i0 = ls_ptr[ant[3 * t + 1]], i1 = ls_ptr[ant[3 * t + 1] + ant[3 * t]];   // antenna t's sorted pilots
+            std::fill(on_sym.begin(), on_sym.end(), 0);
+            for (int64_t s = i0; s < i1; s++) on_sym[pil[s].sym]++;
+            syms.clear();
+            for (int s = 0; s < nsym; s++) {
+                if (!on_sym[s]) continue;
+                CPX_REQUIRE(on_sym[s] == ant[3 * t], CPX_EINVAL,
+                            "ofdm_pilots: antenna %d has pilots on %d of its %lld pilot subcarriers in symbol %d (time tracking needs the "
+                            "same subcarriers on every pilot symbol)", t, on_sym[s], (long long)ant[3 * t], s);
+                syms.push_back(s);
+            }
+            const int ns = (int)syms.size();
+            tv_ant[3 * t] = ns;
+            tv_ant[3 * t + 1] = (int64_t)tv_re.size();
+            tv_ant[3 * t + 2] = nv;
+            nv += (int64_t)nsym * ns;
+            CPX_REQUIRE(nv <= INT32_MAX / 2, CPX_ELIMIT, "ofdm_pilots: time matrices of %lld values are above the engine's limit", (long long)nv);
+            ns_max = ns > ns_max ? ns : ns_max;
+            for (int i = 0; i < ns; i++) {
+                for (int64_t j = 0; j < ant[3 * t]; j++) {
+                    // the pilots of subcarrier k_j are sorted by symbol, and every pilot symbol is among them: the i-th is s_i's
+                    const int64_t s = ls_ptr[ant[3 * t + 1] + j] + i;
+                    tv_re.push_back(ls_re[s]);
+                    tv_coef.push_back(ls_coef[2 * s]);
+                    tv_coef.push_back(ls_coef[2 * s + 1]);
+                }
+            }
+        }
+        for (int64_t i = 0; i < 2 * nv; i++)
+            CPX_REQUIRE(std::isfinite(v_re_im[i]), CPX_EINVAL, "ofdm_pilots: the time matrices hold a value that is not finite");
+        tv_ptr.resize(tv_re.size() + 1);
+        for (size_t i = 0; i < tv_ptr.size(); i++) tv_ptr[i] = (int32_t)i;
+    }
     std::vector<int32_t> dcount(F + 1), data_re, data_sc, ptx(npil);
     data_re.reserve(F - npil);
     data_sc.reserve(F - npil);
@@ -521,18 +666,41 @@ int cpx_pilots_create(int nsc, int nsym, int nt, int64_t npil, const int32_t *pi
         (rc = upload((void **)&p->d_ls_re, ls_re.data(), 4 * ls_re.size(), what)) ||
         (rc = upload((void **)&p->d_ls_coef, ls_coef.data(), 8 * ls_coef.size(), what)) ||
         (rc = upload((void **)&p->d_ant, ant.data(), 8 * ant.size(), what)) ||
-        (rc = upload((void **)&p->d_w, w_re_im, 16 * (size_t)w_total, what))) {
+        (rc = upload((void **)&p->d_w, w_re_im, 16 * (size_t)w_total, what)) ||
+        (tv && ((rc = upload((void **)&p->d_tv_ptr, tv_ptr.data(), 4 * tv_ptr.size(), what)) ||
+                (rc = upload((void **)&p->d_tv_re, tv_re.data(), 4 * tv_re.size(), what)) ||
+                (rc = upload((void **)&p->d_tv_coef, tv_coef.data(), 8 * tv_coef.size(), what)) ||
+                (rc = upload((void **)&p->d_tv_ant, tv_ant.data(), 8 * tv_ant.size(), what)) ||
+                (rc = upload((void **)&p->d_v, v_re_im, 16 * (size_t)nv, what))))) {
         cpx_pilots_destroy(p);
         return rc;
+    }
+    if (tv) {
+        p->ns_max = ns_max;
+        p->nlsp = (int64_t)tv_re.size();
+        p->nv = nv;
     }
     *out = p;
     return CPX_OK;
 }
 
+int cpx_pilots_create(int nsc, int nsym, int nt, int64_t npil, const int32_t *pil_sym, const int32_t *pil_sc, const int32_t *pil_tx,
+                           const double *pil_val_re_im, const double *w_re_im, cpx_ofdm_pilots **out) {
+    CPX_TRACE("cpx_pilots_create");
+    return pilots_create(nsc, nsym, nt, npil, pil_sym, pil_sc, pil_tx, pil_val_re_im, w_re_im, false, nullptr, out);
+}
+
+int cpx_pilots_create_tv(int nsc, int nsym, int nt, int64_t npil, const int32_t *pil_sym, const int32_t *pil_sc, const int32_t *pil_tx,
+                         const double *pil_val_re_im, const double *w_re_im, const double *v_re_im, cpx_ofdm_pilots **out) {
+    CPX_TRACE("cpx_pilots_create_tv");
+    return pilots_create(nsc, nsym, nt, npil, pil_sym, pil_sc, pil_tx, pil_val_re_im, w_re_im, true, v_re_im, out);
+}
+
 int cpx_pilots_destroy(cpx_ofdm_pilots *p) {
     if (!p) return CPX_OK;
     for (void *d : {(void *)p->d_code, (void *)p->d_dcount, (void *)p->d_data_re, (void *)p->d_data_sc, (void *)p->d_pil_tx,
-                    (void *)p->d_pil_val, (void *)p->d_ls_ptr, (void *)p->d_ls_re, (void *)p->d_ls_coef, (void *)p->d_ant, (void *)p->d_w})
+                    (void *)p->d_pil_val, (void *)p->d_ls_ptr, (void *)p->d_ls_re, (void *)p->d_ls_coef, (void *)p->d_ant, (void *)p->d_w,
+                    (void *)p->d_tv_ptr, (void *)p->d_tv_re, (void *)p->d_tv_coef, (void *)p->d_tv_ant, (void *)p->d_v})
         (void)hipFree(d);
     delete p;
     return CPX_OK;
@@ -590,7 +758,7 @@ int cpx_pilots_estimate_dev(const cpx_ofdm_pilots *p, const double *d_Y_re_im, i
         hipLaunchKernelGGL(ofdm_ls_kernel, dim3(grid_of((B * p->nls * nr + OC_BLOCK - 1) / OC_BLOCK)), dim3(OC_BLOCK), 0, st, a, Y,
                            ls);
         const int64_t itiles = ((B * nr + IK_CT - 1) / IK_CT) * p->nt * ((p->nsc + IK_KT - 1) / IK_KT);
-        hipLaunchKernelGGL(ofdm_interp_kernel, dim3(grid_of(itiles)), dim3(OC_BLOCK), 0, st, a, ls, hsc);
+        hipLaunchKernelGGL(ofdm_interp_kernel<false>, dim3(grid_of(itiles)), dim3(OC_BLOCK), 0, st, a, ls, hsc);
         strcat(names, "ofdm_ls_kernel+ofdm_interp_kernel");
         if (d_h_data && p->ndata) {
             hipLaunchKernelGGL(ofdm_hdemap_kernel, dim3(grid_of(B * ((p->ndata + HD_ROWS - 1) / HD_ROWS))), dim3(OC_BLOCK), 0, st, a,
@@ -628,6 +796,73 @@ int cpx_pilots_estimate(const cpx_ofdm_pilots *p, const double *Y_re_im, int64_t
     if (h_data && (rc = s.out(hd_bytes, &dhd))) return rc;
     if ((rc = cpx_pilots_estimate_dev(p, din, B, nr, dhsc, dy, dhd, s.st))) return rc;
     if ((rc = s.get(h_sc, dhsc, hsc_bytes)) || (rc = s.get(y_data, dy, y_bytes))) return rc;
+    return s.get(h_data, dhd, hd_bytes);
+}
+
+int cpx_pilots_estimate_tv_dev(const cpx_ofdm_pilots *p, const double *d_Y_re_im, int64_t B, int nr, double *d_h_sym, double *d_y_data,
+                               double *d_h_data, void *stream) {
+    CPX_TRACE("cpx_pilots_estimate_tv_dev");
+    if (int rc = estimate_tv_sizes(p, B, nr, d_h_sym, d_y_data, d_h_data)) return rc;
+    if (B == 0) return CPX_OK;
+    if (int rcd = check_handle_device(p->device, "ofdm_estimate_tv")) return rcd;
+    CPX_REQUIRE(d_Y_re_im, CPX_EINVAL, "ofdm_estimate_tv: null pointer");
+    hipStream_t st = pick_stream(stream);
+    OcArgs a = plan_args(p, B);
+    a.nr = nr;
+    const double2 *Y = reinterpret_cast<const double2 *>(d_Y_re_im);
+    Scratch sc;
+    char names[160] = "";
+    if (d_h_sym || (d_h_data && p->ndata)) {
+        double2 *lsp = nullptr, *hp = nullptr;
+        if (int rc = sc.get(st, Slot::ofdm_lsp, 16 * (size_t)(B * p->nlsp * nr), &lsp)) return rc;
+        if (int rc = sc.get(st, Slot::ofdm_hp, 16 * (size_t)(B * p->ns_max * p->nsc * nr * p->nt), &hp)) return rc;
+        OcArgs l = a;                                       // the least-squares kernel with one pilot per item
+        l.ls_ptr = p->d_tv_ptr; l.ls_re = p->d_tv_re; l.ls_coef = p->d_tv_coef; l.nls = p->nlsp;
+        hipLaunchKernelGGL(ofdm_ls_kernel, dim3(grid_of((B * p->nlsp * nr + OC_BLOCK - 1) / OC_BLOCK)), dim3(OC_BLOCK), 0, st, l, Y, lsp);
+        const int64_t itiles = ((B * nr * p->ns_max + IK_CT - 1) / IK_CT) * p->nt * ((p->nsc + IK_KT - 1) / IK_KT);
+        hipLaunchKernelGGL(ofdm_interp_kernel<true>, dim3(grid_of(itiles)), dim3(OC_BLOCK), 0, st, l, lsp, hp);
+        TvArgs v{};
+        v.code = p->d_code; v.tv_ant = p->d_tv_ant; v.v = p->d_v; v.hp = hp;
+        v.hsym = reinterpret_cast<double2 *>(d_h_sym);
+        v.hdata = p->ndata ? reinterpret_cast<double2 *>(d_h_data) : nullptr;
+        v.B = B; v.ndata = p->ndata; v.FE = (int64_t)p->nsc * nr * p->nt; v.nv = p->nv;
+        v.nsc = p->nsc; v.nsym = p->nsym; v.nt = p->nt; v.E = nr * p->nt; v.ns_max = p->ns_max;
+        const dim3 grid(grid_of(B * ((v.FE + OC_BLOCK - 1) / OC_BLOCK)));
+        if (p->nv <= TV_VMAX) hipLaunchKernelGGL(ofdm_tv_kernel<true>, grid, dim3(OC_BLOCK), 0, st, v);
+        else hipLaunchKernelGGL(ofdm_tv_kernel<false>, grid, dim3(OC_BLOCK), 0, st, v);
+        snprintf(names, sizeof names, "ofdm_ls_kernel+ofdm_interp_kernel<tv>+ofdm_tv_kernel<%s>", p->nv <= TV_VMAX ? "lds" : "global");
+    }
+    if (d_y_data && p->ndata) {
+        a.rows = oc_rows(nr);
+        hipLaunchKernelGGL(ofdm_ydemap_kernel, dim3(grid_of(B * ((p->ndata + a.rows - 1) / a.rows))), dim3(OC_BLOCK), 0, st, a, Y,
+                           reinterpret_cast<double2 *>(d_y_data));
+        strcat(names, names[0] ? "+ofdm_ydemap_kernel" : "ofdm_ydemap_kernel");
+    }
+    CPX_HIP(hipGetLastError());
+    note_kernel("%s", names);
+    return CPX_OK;
+}
+
+int cpx_pilots_estimate_tv(const cpx_ofdm_pilots *p, const double *Y_re_im, int64_t B, int nr, double *h_sym, double *y_data,
+                           double *h_data) {
+    CPX_TRACE("cpx_pilots_estimate_tv");
+    if (int rc = estimate_tv_sizes(p, B, nr, h_sym, y_data, h_data)) return rc;
+    if (B == 0) return CPX_OK;
+    CPX_REQUIRE(Y_re_im, CPX_EINVAL, "ofdm_estimate_tv: null pointer");
+    int rc = ensure_device();
+    if (rc) return rc;
+    const size_t in_bytes = 16 * (size_t)(B * nr * p->nsym * p->nsc);
+    const size_t hsym_bytes = h_sym ? in_bytes * p->nt : 0, y_bytes = y_data ? 16 * (size_t)(B * p->ndata * nr) : 0,
+                 hd_bytes = h_data ? 16 * (size_t)(B * p->ndata * nr * p->nt) : 0;
+    HostStage s;
+    const double *din;
+    double *dhsym = nullptr, *dy = nullptr, *dhd = nullptr;
+    if ((rc = s.in(Y_re_im, in_bytes, &din))) return rc;
+    if (h_sym && (rc = s.out(hsym_bytes, &dhsym))) return rc;
+    if (y_data && (rc = s.out(y_bytes, &dy))) return rc;
+    if (h_data && (rc = s.out(hd_bytes, &dhd))) return rc;
+    if ((rc = cpx_pilots_estimate_tv_dev(p, din, B, nr, dhsym, dy, dhd, s.st))) return rc;
+    if ((rc = s.get(h_sym, dhsym, hsym_bytes)) || (rc = s.get(y_data, dy, y_bytes))) return rc;
     return s.get(h_data, dhd, hd_bytes);
 }
 

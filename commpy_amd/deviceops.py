@@ -15,7 +15,7 @@ from commpy_amd.channelcoding.ldpc import build_matrix
 
 __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu', 'mimo_channel_gpu', 'puncturing_gpu',
            'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder', 'gf2_generator',
-           'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'sync_estimate_dev', 'sync_align_dev',
+           'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
            'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev']
 
 
@@ -389,6 +389,20 @@ def ofdm_estimate_dev(pilots, d_Y, B, nr, want=('y', 'h'), stream=None):
     ptrs = [out[k].ptr if k in out else None for k in ('h_sc', 'y', 'h')]
     _lib.check(_lib.load().cpx_pilots_estimate_dev(pilots.handle(), d_Y.ptr, B, nr, ptrs[0], ptrs[1], ptrs[2], stream))
     return tuple(out[k] for k in ('y', 'h', 'h_sc') if k in out)
+
+
+def ofdm_estimate_tv_dev(pilots, d_Y, B, nr, want=('y', 'h'), stream=None):
+    """``cpx_pilots_estimate_tv_dev`` (``pilots`` made with ``time_interp``): ``d_Y [B][nr][nsym][nsc]`` -> a tuple of new
+    ``DeviceBuf``s, the members of ``(y_data [B][ndata][nr], h_data [B][ndata][nr][nt], h_sym [B][nsym][nsc][nr][nt])`` that ``want``
+    names ('y', 'h', 'h_sym'), in that order; the first two feed the detectors as ``ofdm_estimate_dev``'s do."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ('y', 'h', 'h_sym') for w in want):
+        raise ValueError("want must name at least one of 'y', 'h', 'h_sym'")
+    sizes = {'y': pilots.ndata * nr, 'h': pilots.ndata * nr * pilots.nt, 'h_sym': pilots.nsym * pilots.nsc * nr * pilots.nt}
+    out = {k: DeviceBuf(B * sizes[k] * 16) for k in ('y', 'h', 'h_sym') if k in want}
+    ptrs = [out[k].ptr if k in out else None for k in ('h_sym', 'y', 'h')]
+    _lib.check(_lib.load().cpx_pilots_estimate_tv_dev(pilots.handle(), d_Y.ptr, B, nr, ptrs[0], ptrs[1], ptrs[2], stream))
+    return tuple(out[k] for k in ('y', 'h', 'h_sym') if k in out)
 
 
 # ---- timing and frequency-offset synchronisation, device resident (csrc/sync.hip) -------------------------------------------------

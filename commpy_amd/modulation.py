@@ -12,7 +12,8 @@ for ``links.idd_decoder``.  The linear detectors -- zero forcing and MMSE, hard 
 ``max_log_approx`` and ``bit_lvl_repr`` are small host functions.  ``ofdm_tx`` / ``ofdm_rx`` (modulation.py:265-296) run on the
 GPU too (csrc/ofdm.hip), float64 only, with the symbol-major batched forms ``ofdm_tx_batch`` / ``ofdm_rx_batch``.
 ``OfdmPilots`` describes the pilots of an OFDM frame; ``ofdm_map_batch`` puts data and pilots on the resource grid and
-``ofdm_estimate_batch`` estimates the channel from the received grid and hands ``(y, H)`` to the MIMO detectors in their own layout
+``ofdm_estimate_batch`` (``ofdm_estimate_tv_batch`` for a channel that moves inside the frame) estimates the channel from the received
+grid and hands ``(y, H)`` to the MIMO detectors in their own layout
 (csrc/ofdm_chan.hip; not in the reference).
 """
 import ctypes
@@ -27,7 +28,7 @@ from commpy_amd.utilities import signal_power
 __all__ = ['PSKModem', 'QAMModem', 'Modem', 'mimo_ml', 'kbest', 'max_log_approx', 'bit_lvl_repr', 'mimo_ml_batch',
            'kbest_batch', 'best_first_detector', 'best_first_batch', 'list_apriori_batch', 'apriori_detector', 'zf_detector', 'mmse_detector',
            'linear_batch', 'linear_equalize_batch', 'ofdm_tx', 'ofdm_rx', 'ofdm_tx_batch', 'ofdm_rx_batch', 'OfdmPilots', 'ofdm_map_batch',
-           'ofdm_estimate_batch', 'ofdm_subcarrier_frequencies']
+           'ofdm_estimate_batch', 'ofdm_estimate_tv_batch', 'ofdm_subcarrier_frequencies']
 
 
 def _gray_rank(m):
@@ -732,6 +733,44 @@ def _interp_taps(nsc, pk, Lmax, nfft):
     return np.ascontiguousarray(F.dot(np.linalg.pinv(F[pk])))
 
 
+def _time_linear(nsym, ps):
+    """V [nsym, len(ps)]: linear interpolation in the symbol index between the neighbouring pilot symbols ``ps`` (ascending), the
+    nearest one held outside their range -- the time twin of ``_interp_linear``."""
+    f, fp = np.arange(nsym, dtype=np.float64), np.asarray(ps, dtype=np.float64)
+    V = np.zeros((nsym, len(ps)), dtype=np.complex128)
+    if len(ps) == 1:
+        V[:, 0] = 1.0
+        return V
+    i = np.clip(np.searchsorted(fp, f, side='right') - 1, 0, len(ps) - 2)
+    rows = np.arange(nsym)
+    a = np.clip((f - fp[i]) / (fp[i + 1] - fp[i]), 0.0, 1.0)
+    V[rows, i] = 1.0 - a
+    V[rows, i + 1] += a
+    return V
+
+
+def _time_hold(nsym, ps):
+    """V [nsym, len(ps)]: every symbol takes the estimate of the nearest pilot symbol, the lower one on a tie."""
+    ps = np.asarray(ps, dtype=np.int64)
+    V = np.zeros((nsym, len(ps)), dtype=np.complex128)
+    V[np.arange(nsym), np.argmin(np.abs(np.arange(nsym)[:, None] - ps[None, :]), axis=1)] = 1.0     # argmin: the first = the lower
+    return V
+
+
+def _time_doppler(nsym, ps, fd_sym, nvar):
+    """V [nsym, len(ps)] = R_sp (R_pp + nvar I)^-1 with Clarke's autocorrelation R[a][b] = J0(2 pi fd_sym |a - b|): the Wiener filter
+    in time for a maximum Doppler shift of ``fd_sym`` cycles per OFDM symbol and a noise variance ``nvar`` of the pilot estimates."""
+    from scipy.special import j0
+    ps = np.asarray(ps, dtype=np.float64)
+    r_sp = j0(2.0 * np.pi * fd_sym * np.abs(np.arange(nsym, dtype=np.float64)[:, None] - ps[None, :]))
+    r_pp = j0(2.0 * np.pi * fd_sym * np.abs(ps[:, None] - ps[None, :])) + nvar * np.eye(len(ps))
+    try:
+        V = np.linalg.solve(r_pp.T, r_sp.T).T
+    except np.linalg.LinAlgError:
+        raise ValueError("time_interp ('doppler', %g, %g): the pilot symbols' autocorrelation matrix is singular" % (fd_sym, nvar))
+    return np.ascontiguousarray(V, dtype=np.complex128)
+
+
 def _default_pilot_values(n):
     """``n`` unit-modulus QPSK points from the PRBS x^15 + x^14 + 1 (``pnsequence``), two bits per point."""
     from commpy_amd.sequences import pnsequence
@@ -748,9 +787,17 @@ class OfdmPilots:
     ``interp`` gives, per antenna t, the matrix ``W[t] [nsc, np_t]`` that spreads the least-squares estimates at its ``np_t`` distinct
     pilot subcarriers ``pilot_subcarriers[t]`` (ascending) over all subcarriers: 'linear' (in frequency, the nearest pilot held
     outside their range), ``('taps', Lmax, nfft)`` (least-squares fit of Lmax time-domain taps, ``F_all pinv(F_p)``) or a list of
-    nt arrays.  Everything is validated here (ValueError) before a device is touched."""
+    nt arrays.
 
-    def __init__(self, nsc, nsym, nt, pil_sym, pil_sc, pil_tx, pil_val, interp='linear'):
+    ``time_interp`` (None: the fading is taken as constant over the frame) makes the plan track a channel that moves inside the
+    frame: per antenna t a matrix ``V[t] [nsym, ns_t]`` spreads the estimates at its ``ns_t`` distinct pilot symbols
+    ``pilot_symbols[t]`` (ascending) over all symbols, for ``ofdm_estimate_tv_batch``.  'linear' (in the symbol index, the nearest
+    pilot symbol held outside their range), 'hold' (the nearest pilot symbol, the lower one on a tie), ``('doppler', fd_sym,
+    nvar)`` (the Wiener filter ``R_sp (R_pp + nvar I)^-1`` on Clarke's ``J0(2 pi fd_sym |a - b|)``, ``fd_sym`` in cycles per OFDM
+    symbol) or a list of nt arrays.  The pattern must then be a rectangle per antenna: the same pilot subcarriers on each of its
+    pilot symbols (``comb`` and ``block`` are).  Everything is validated here (ValueError) before a device is touched."""
+
+    def __init__(self, nsc, nsym, nt, pil_sym, pil_sc, pil_tx, pil_val, interp='linear', time_interp=None):
         nsc, nsym, nt = _whole(nsc, 'nsc'), _whole(nsym, 'nsym'), _whole(nt, 'nt')
         if nsc < 2 or nsc % 2:
             raise ValueError('nsc = %d, need an even number >= 2' % nsc)
@@ -796,8 +843,38 @@ class OfdmPilots:
                 raise ValueError('W[%d] must be [nsc, np_t] = [%d, %d], got %s' % (t, nsc, self.pilot_subcarriers[t].size, w.shape))
             if not np.all(np.isfinite(w)):
                 raise ValueError('W[%d] holds a value that is not finite' % t)
+        self.pilot_symbols = [np.unique(sym[tx == t]) for t in range(nt)]
+        V = None
+        if time_interp is not None:
+            for t in range(nt):
+                on = np.bincount(sym[tx == t], minlength=nsym)
+                bad = np.flatnonzero((on != 0) & (on != self.pilot_subcarriers[t].size))
+                if bad.size:
+                    raise ValueError('time_interp needs the same pilot subcarriers on every pilot symbol of an antenna: antenna %d has '
+                                     '%d of its %d in symbol %d' % (t, on[bad[0]], self.pilot_subcarriers[t].size, bad[0]))
+            if isinstance(time_interp, str) and time_interp == 'linear':
+                V = [_time_linear(nsym, ps) for ps in self.pilot_symbols]
+            elif isinstance(time_interp, str) and time_interp == 'hold':
+                V = [_time_hold(nsym, ps) for ps in self.pilot_symbols]
+            elif isinstance(time_interp, tuple) and len(time_interp) == 3 and time_interp[0] == 'doppler':
+                try:
+                    fd_sym, nvar = float(time_interp[1]), float(time_interp[2])
+                except (TypeError, ValueError):
+                    raise ValueError("time_interp ('doppler', fd_sym, nvar) needs two numbers")
+                if not (np.isfinite(fd_sym) and np.isfinite(nvar) and fd_sym >= 0 and nvar >= 0):
+                    raise ValueError("time_interp ('doppler', fd_sym, nvar) needs finite fd_sym >= 0 and nvar >= 0")
+                V = [_time_doppler(nsym, ps, fd_sym, nvar) for ps in self.pilot_symbols]
+            elif isinstance(time_interp, (list, tuple)) and len(time_interp) == nt and not isinstance(time_interp[0], str):
+                V = [_numeric(v, 'time_interp[%d]' % t) for t, v in enumerate(time_interp)]
+            else:
+                raise ValueError("time_interp must be None, 'linear', 'hold', ('doppler', fd_sym, nvar) or a list of nt matrices")
+            for t, v in enumerate(V):
+                if v.shape != (nsym, self.pilot_symbols[t].size):
+                    raise ValueError('V[%d] must be [nsym, ns_t] = [%d, %d], got %s' % (t, nsym, self.pilot_symbols[t].size, v.shape))
+                if not np.all(np.isfinite(v)):
+                    raise ValueError('V[%d] holds a value that is not finite' % t)
         self.nsc, self.nsym, self.nt, self.npil = nsc, nsym, nt, npil
-        self.pil_sym, self.pil_sc, self.pil_tx, self.pil_val, self.W = sym, sc, tx, val, W
+        self.pil_sym, self.pil_sc, self.pil_tx, self.pil_val, self.W, self.V = sym, sc, tx, val, W, V
         is_data = np.ones(nsym * nsc, dtype=bool)
         is_data[re] = False
         data_re = np.flatnonzero(is_data)
@@ -806,10 +883,16 @@ class OfdmPilots:
         i32 = [np.ascontiguousarray(a, dtype=np.int32) for a in (sym, sc, tx)]
         wflat = np.ascontiguousarray(np.concatenate([w.reshape(-1) for w in W]))
 
+        vflat = None if V is None else np.ascontiguousarray(np.concatenate([v.reshape(-1) for v in V]))
+
         def create():
             h = ctypes.c_void_p()
-            _lib.check(_lib.load().cpx_pilots_create(nsc, nsym, nt, npil, _lib.ptr(i32[0]), _lib.ptr(i32[1]), _lib.ptr(i32[2]),
-                                                          _lib.ptr(val), _lib.ptr(wflat), ctypes.byref(h)))
+            if vflat is None:
+                _lib.check(_lib.load().cpx_pilots_create(nsc, nsym, nt, npil, _lib.ptr(i32[0]), _lib.ptr(i32[1]), _lib.ptr(i32[2]),
+                                                              _lib.ptr(val), _lib.ptr(wflat), ctypes.byref(h)))
+            else:
+                _lib.check(_lib.load().cpx_pilots_create_tv(nsc, nsym, nt, npil, _lib.ptr(i32[0]), _lib.ptr(i32[1]), _lib.ptr(i32[2]),
+                                                            _lib.ptr(val), _lib.ptr(wflat), _lib.ptr(vflat), ctypes.byref(h)))
             return h
         self._handles = _lib.DeviceHandles(create, 'cpx_pilots_destroy')
 
@@ -818,7 +901,7 @@ class OfdmPilots:
         return self._handles.get()
 
     @classmethod
-    def comb(cls, nsc, nsym, nt, spacing, pilot_symbols, interp, values=None):
+    def comb(cls, nsc, nsym, nt, spacing, pilot_symbols, interp, values=None, time_interp=None):
         """Comb pilots: on each symbol of ``pilot_symbols`` antenna t takes subcarriers ``t, t + spacing, ...`` (``spacing >= nt``).
         ``values``: one per pilot, pilot symbol after pilot symbol, antenna after antenna (default: PRBS QPSK points)."""
         nsc, nt, spacing = _whole(nsc, 'nsc'), _whole(nt, 'nt'), _whole(spacing, 'spacing')
@@ -831,17 +914,17 @@ class OfdmPilots:
                 k = np.arange(t, max(nsc, 0), spacing)
                 sym.append(np.full(k.size, s)), sc.append(k), tx.append(np.full(k.size, t))
         sym, sc, tx = (np.concatenate(a).astype(np.int64) if a else np.zeros(0, np.int64) for a in (sym, sc, tx))
-        return cls(nsc, nsym, nt, sym, sc, tx, _default_pilot_values(sym.size) if values is None else values, interp)
+        return cls(nsc, nsym, nt, sym, sc, tx, _default_pilot_values(sym.size) if values is None else values, interp, time_interp)
 
     @classmethod
-    def block(cls, nsc, nsym, nt, interp='linear', values=None):
+    def block(cls, nsc, nsym, nt, interp='linear', values=None, time_interp=None):
         """Block pilots: symbol t is antenna t's full-band pilot symbol (``nsym >= nt``)."""
         nsc, nsym, nt = _whole(nsc, 'nsc'), _whole(nsym, 'nsym'), _whole(nt, 'nt')
         if nt < 1 or nsym < nt:
             raise ValueError('block pilots need nsym >= nt >= 1 (nsym = %d, nt = %d)' % (nsym, nt))
         tx = np.repeat(np.arange(nt), max(nsc, 0))
         sc = np.tile(np.arange(max(nsc, 0)), nt)
-        return cls(nsc, nsym, nt, tx.copy(), sc, tx, _default_pilot_values(tx.size) if values is None else values, interp)
+        return cls(nsc, nsym, nt, tx.copy(), sc, tx, _default_pilot_values(tx.size) if values is None else values, interp, time_interp)
 
 
 def _pilots_arg(pilots):
@@ -888,3 +971,30 @@ def ofdm_estimate_batch(Y, pilots, want=('y', 'h')):
         ptrs = [_lib.ptr(out[k]) if k in out else None for k in ('h_sc', 'y', 'h')]
         _lib.check(_lib.load().cpx_pilots_estimate(p.handle(), _lib.ptr(y), B, nr, *ptrs))
     return tuple(out[k] for k in ('y', 'h', 'h_sc') if k in out)
+
+
+def ofdm_estimate_tv_batch(Y, pilots, want=('y', 'h')):
+    """Pilot-aided estimation of a channel that moves inside the frame: ``Y [B, nr, nsym, nsc]`` as for ``ofdm_estimate_batch``,
+    ``pilots`` made with ``time_interp``.  Least squares at every pilot, ``W[t]`` over the subcarriers of each pilot symbol, then
+    ``V[t]`` over the symbols.  Returns a tuple of the members of ``(y_data, h_data, h_sym)`` that ``want`` names ('y', 'h',
+    'h_sym'), in that order: ``y_data [B, ndata, nr]`` and ``h_data [B, ndata, nr, nt]``, the estimate at each data element's own
+    symbol and subcarrier, feed the MIMO detectors as ``ofdm_estimate_batch``'s do; ``h_sym [B, nsym, nsc, nr, nt]`` is the estimate
+    on the whole grid."""
+    p = _pilots_arg(pilots)
+    if p.V is None:
+        raise ValueError('pilots were made without time_interp')
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ('y', 'h', 'h_sym') for w in want):
+        raise ValueError("want must name at least one of 'y', 'h', 'h_sym'")
+    y = _numeric(Y, 'Y')
+    if y.ndim != 4 or y.shape[1] < 1 or y.shape[2:] != (p.nsym, p.nsc):
+        raise ValueError('Y must be [B, nr, nsym, nsc] = [B, nr, %d, %d], got %s' % (p.nsym, p.nsc, y.shape))
+    B, nr = y.shape[:2]
+    if nr > OFDM_MAX_ANTENNAS:
+        raise ValueError('nr = %d is above the engine limit of %d' % (nr, OFDM_MAX_ANTENNAS))
+    shapes = {'y': (B, p.ndata, nr), 'h': (B, p.ndata, nr, p.nt), 'h_sym': (B, p.nsym, p.nsc, nr, p.nt)}
+    out = {k: np.zeros(shapes[k], dtype=np.complex128) for k in ('y', 'h', 'h_sym') if k in want}
+    if B:
+        ptrs = [_lib.ptr(out[k]) if k in out else None for k in ('h_sym', 'y', 'h')]
+        _lib.check(_lib.load().cpx_pilots_estimate_tv(p.handle(), _lib.ptr(y), B, nr, *ptrs))
+    return tuple(out[k] for k in ('y', 'h', 'h_sym') if k in out)

@@ -377,7 +377,8 @@ int cpx_freq_offset_dev(const double *d_x_re_im, int64_t B, int64_t n, const dou
  * cpx_pilots_map:  data [B][ndata][nt] (vector-major, the layout of the MIMO detectors' symbols) -> grid [B][nt][nsym][nsc]: data at
  *   the data elements, pilots at their antenna's pilot elements, exact zeros elsewhere.  grid viewed as [B nt][nsym][nsc] is
  *   cpx_ofdm_tx's input, whose output is cpx_multipath's x.
- * cpx_pilots_estimate:  Y [B][nr][nsym][nsc] (cpx_ofdm_rx's output for B nr rows; fading constant over the frame).
+ * cpx_pilots_estimate:  Y [B][nr][nsym][nsc] (cpx_ofdm_rx's output for B nr rows; fading constant over the frame -- a channel that
+ *   moves inside the frame is followed by cpx_pilots_create_tv + cpx_pilots_estimate_tv below).
  *   LS[b][r][t][j] = (sum_s Y[b][r][s][k_j] conj(p_s) / |p_s|^2) / count over antenna t's pilots on subcarrier k_j in ascending
  *   symbol order; H^[b][k][r][t] = sum_j W_t[k][j] LS[b][r][t][j], an fma chain from +0 over ascending j.  Outputs, each nullable
  *   (at least one must be given): h_sc [B][nsc][nr][nt] = H^; y_data [B][ndata][nr] = Y at the data elements; h_data
@@ -385,6 +386,25 @@ int cpx_freq_offset_dev(const double *d_x_re_im, int64_t B, int64_t n, const dou
  *   what cpx_mimo_ml, cpx_kbest_*, cpx_best_first, cpx_mimo_linear and cpx_mimo_list_* take.  A non-finite sample of Y makes NaNs
  *   in its own frame only; results are bit-identical whatever the batch size, the frame's place, the stream, the form (host or
  *   device) and the outputs requested.  CPX_EINVAL: nr < 1, no output; CPX_ELIMIT: nr > 1024.
+ * Time-varying channels: a separable estimator, frequency first (W_t, as above), then time.
+ * cpx_pilots_create_tv: cpx_pilots_create's arguments and checks, the same handle type, plus the time matrices.  With s_0 < ... <
+ *   s_{ns_t - 1} the distinct pilot symbols of antenna t, the pattern must be a rectangle per antenna: on every one of those symbols
+ *   antenna t has pilots on exactly its pilot subcarriers k_0 < ... < k_{np_t - 1} (comb and block patterns are; a staggered one is
+ *   CPX_EINVAL, the message names the antenna and the symbol).  `v_re_im` holds, antenna after antenna, V_t [nsym][ns_t], complex,
+ *   row-major: it spreads the estimates at the antenna's pilot symbols over all symbols, and the engine does not interpret it (linear,
+ *   hold, Wiener and polynomial tracking are all "a matrix").  CPX_EINVAL also: v_re_im null, a V entry that is not finite.  The
+ *   handle serves cpx_pilots_map and cpx_pilots_estimate as one of cpx_pilots_create does, bit for bit.
+ * cpx_pilots_estimate_tv:  Y [B][nr][nsym][nsc] as above.
+ *   LSp[b][r][t][i][j] = Y[b][r][s_i][k_j] c, c = conj(p) / |p|^2 of that pilot formed on the host: one complex multiply-add from +0,
+ *     no averaging;
+ *   Hp[b][i][k][r][t] = sum_j W_t[k][j] LSp[b][r][t][i][j], an fma chain from +0 over ascending j (cpx_pilots_estimate's, per pilot symbol);
+ *   H^[b][s][k][r][t] = sum_i V_t[s][i] Hp[b][i][k][r][t], a chain of complex multiply-adds (re += vr hr, re -= vi hi, im += vr hi,
+ *     im += vi hr, four fma) from +0 over ascending i.
+ *   Outputs, each nullable (at least one must be given): h_sym [B][nsym][nsc][nr][nt] = H^; y_data [B][ndata][nr], exactly
+ *   cpx_pilots_estimate's; h_data [B][ndata][nr][nt] = H^ at each data element's (symbol, subcarrier).  (y_data, h_data) feed the
+ *   detectors with V = B ndata and h_batched = 1 as above.  A non-finite sample of Y stays in its own frame; results are bit-identical
+ *   whatever the batch size, the frame's place, the stream, the form (host or device) and the outputs requested; B = 0 succeeds
+ *   without a launch.  CPX_EINVAL: a plan made by cpx_pilots_create (no time matrices), nr < 1, no output; CPX_ELIMIT: nr > 1024.
  */
 typedef struct cpx_ofdm_pilots cpx_ofdm_pilots;
 int cpx_multipath(const double *x_re_im, const double *g_re_im, int g_batched, int64_t B, int nt, int nr, int64_t n, int L,
@@ -400,6 +420,13 @@ int cpx_pilots_estimate(const cpx_ofdm_pilots *plan, const double *Y_re_im, int6
                       double *h_data);
 int cpx_pilots_estimate_dev(const cpx_ofdm_pilots *plan, const double *d_Y_re_im, int64_t B, int nr, double *d_h_sc, double *d_y_data,
                           double *d_h_data, void *stream);
+int cpx_pilots_create_tv(int nsc, int nsym, int nt, int64_t npil, const int32_t *pil_sym, const int32_t *pil_sc,
+                         const int32_t *pil_tx, const double *pil_val_re_im, const double *w_re_im, const double *v_re_im,
+                         cpx_ofdm_pilots **out);
+int cpx_pilots_estimate_tv(const cpx_ofdm_pilots *plan, const double *Y_re_im, int64_t B, int nr, double *h_sym, double *y_data,
+                           double *h_data);
+int cpx_pilots_estimate_tv_dev(const cpx_ofdm_pilots *plan, const double *d_Y_re_im, int64_t B, int nr, double *d_h_sym,
+                               double *d_y_data, double *d_h_data, void *stream);
 
 /* ---- OFDM timing and frequency-offset synchronisation ---------------------------------------
  * Not in the reference.  complex128 data, float64 arithmetic only (cpx_set_precision does not apply, no path switch); B = 0 succeeds

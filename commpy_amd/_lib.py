@@ -271,6 +271,14 @@ def ptr(arr):
     return arr.ctypes.data_as(c_void_p)
 
 
+def wanted(want, names):
+    """The ``want`` argument of the calls with optional outputs, as a tuple: one name or several of ``names`` (host only)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in names for w in want):
+        raise ValueError("want must name at least one of %s" % ", ".join("'%s'" % n for n in names))
+    return want
+
+
 def as_f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 

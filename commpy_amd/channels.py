@@ -450,9 +450,7 @@ def fading_multipath_batch(x, nr, pdp, fd, hold=1, t0=0, n_sin=16, k_factor=None
     always: with ``tap_frequency_response`` it is the perfect channel state per block).  Without 'g' the gains never leave the
     device, where they take at most ``FADING_SCRATCH_BYTES``.  No noise: add it with ``awgn`` or ``cpx_awgn_dev``."""
     from commpy_amd import _lib
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ('y', 'g') for w in want):
-        raise ValueError("want must name at least one of 'y', 'g'")
+    want = _lib.wanted(want, ('y', 'g'))
     xa, siso = _fading_rows(x)
     B, nt, n = xa.shape
     md = _FadingModel(B, nr, nt, pdp, fd, hold, t0, n_sin, k_factor, fd_los, seed, stream_id, first_row)

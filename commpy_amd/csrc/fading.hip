@@ -33,6 +33,7 @@
 // and cpx_multipath where the gains do not change, agree bit for bit.  Offsets are 64-bit, grids are capped at 65 535 workgroups.
 #include "cpx_internal.h"
 #include "cpx_rng.h"
+#include "cpx_wave.h"             // mac: the chain step shared with fir.hip and ofdm_chan.hip; grid_of
 
 #include <climits>
 #include <cmath>
@@ -46,19 +47,6 @@ using namespace cpx;
 namespace {
 
 constexpr int64_t FD_TWO52 = (int64_t)1 << 52;
-
-// one tap of the chain (fir.hip's order)
-__device__ __forceinline__ void mac(double2 &acc, double2 h, double2 x) {
-    acc.x = fma(h.x, x.x, acc.x);
-    acc.x = fma(-h.y, x.y, acc.x);
-    acc.y = fma(h.x, x.y, acc.y);
-    acc.y = fma(h.y, x.x, acc.y);
-}
-
-unsigned grid_of(int64_t items) {
-    const int64_t cap = 65535;
-    return (unsigned)(items < 1 ? 1 : items > cap ? cap : items);
-}
 
 // ---- the model -------------------------------------------------------------------------------------------------------------------
 struct FdDraw {

@@ -29,6 +29,7 @@
 // Offsets are 64-bit throughout.
 #include "cpx_internal.h"
 #include "cpx_rotate.h"
+#include "cpx_wave.h"
 
 #include <climits>
 
@@ -50,16 +51,11 @@ template <> struct TapOf<true> { using T = double2; };
 __device__ __forceinline__ double tap_zero(double) { return 0.0; }
 __device__ __forceinline__ double2 tap_zero(double2) { return make_double2(0.0, 0.0); }
 
-// one tap of the chain
+// one tap of the chain: a real tap here, a complex one in cpx_wave.h (named so that both overloads are found from this namespace)
+using cpx::mac;
 __device__ __forceinline__ void mac(double2 &acc, double h, double2 x) {
     acc.x = fma(h, x.x, acc.x);
     acc.y = fma(h, x.y, acc.y);
-}
-__device__ __forceinline__ void mac(double2 &acc, double2 h, double2 x) {
-    acc.x = fma(h.x, x.x, acc.x);
-    acc.x = fma(-h.y, x.y, acc.x);
-    acc.y = fma(h.x, x.y, acc.y);
-    acc.y = fma(h.y, x.x, acc.y);
 }
 
 struct FirArgs {
@@ -74,10 +70,7 @@ struct FirArgs {
     int pad_shift;          // decimator: a (31 = no padding)
 };
 
-unsigned grid_of(int64_t items) {
-    const int64_t cap = 1 << 20;
-    return (unsigned)(items < 1 ? 1 : items > cap ? cap : items);
-}
+unsigned fir_grid(int64_t items) { return grid_of(items, 1 << 20); }
 
 // ---- interpolator ----------------------------------------------------------------------------------------------------------
 constexpr int FI_BLOCK = 256, FI_R = 4, FI_KT = 512, FI_MAX_SPS = 64;
@@ -264,12 +257,12 @@ int launch_interp(FirArgs a, int64_t B, hipStream_t st) {
     if (TQ && 2 * nq >= TQ) {
         a.tiles_per_row = (nq + TQ - 1) / TQ;
         a.ntiles = B * a.tiles_per_row;
-        hipLaunchKernelGGL((fir_interp_kernel<C>), dim3(grid_of(a.ntiles)), dim3(FI_BLOCK), 0, st, a);
+        hipLaunchKernelGGL((fir_interp_kernel<C>), dim3(fir_grid(a.ntiles)), dim3(FI_BLOCK), 0, st, a);
         CPX_HIP(hipGetLastError());
         note_kernel("fir_interp_kernel<%s>", C ? "complex" : "real");
         return CPX_OK;
     }
-    hipLaunchKernelGGL((fir_interp_direct<C>), dim3(grid_of((a.total + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((fir_interp_direct<C>), dim3(fir_grid((a.total + 255) / 256)), dim3(256), 0, st, a);
     CPX_HIP(hipGetLastError());
     note_kernel("fir_interp_direct<%s>", C ? "complex" : "real");
     return CPX_OK;
@@ -290,7 +283,7 @@ bool try_decim(FirArgs a, int64_t B, hipStream_t st) {
     a.pad_shift = sh;
     a.tiles_per_row = tiles;
     a.ntiles = B * tiles;
-    hipLaunchKernelGGL((fir_decim_kernel<C, R>), dim3(grid_of(a.ntiles)), dim3(FD_BLOCK), (size_t)Wp * 16 + tap_bytes, st, a);
+    hipLaunchKernelGGL((fir_decim_kernel<C, R>), dim3(fir_grid(a.ntiles)), dim3(FD_BLOCK), (size_t)Wp * 16 + tap_bytes, st, a);
     note_kernel("fir_decim_kernel<%s,%d>", C ? "complex" : "real", R);
     return true;
 }
@@ -298,7 +291,7 @@ bool try_decim(FirArgs a, int64_t B, hipStream_t st) {
 template <bool C>
 int launch_decim(const FirArgs &a, int64_t B, hipStream_t st) {
     if (!try_decim<C, 4>(a, B, st) && !try_decim<C, 2>(a, B, st) && !try_decim<C, 1>(a, B, st)) {
-        hipLaunchKernelGGL((fir_decim_direct<C>), dim3(grid_of((a.total + 255) / 256)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((fir_decim_direct<C>), dim3(fir_grid((a.total + 255) / 256)), dim3(256), 0, st, a);
         note_kernel("fir_decim_direct<%s>", C ? "complex" : "real");
     }
     CPX_HIP(hipGetLastError());
@@ -419,7 +412,7 @@ int cpx_freq_offset_dev(const double *d_x_re_im, int64_t B, int64_t n, const dou
     if (B * n == 0) return CPX_OK;
     CPX_REQUIRE(d_x_re_im && d_out_re_im && d_step, CPX_EINVAL, "freq_offset: null pointer");
     const int64_t cpr = (n + FO_CHUNK - 1) / FO_CHUNK, nchunks = B * cpr;
-    hipLaunchKernelGGL(freq_offset_kernel, dim3(grid_of(nchunks)), dim3(FO_BLOCK), 0, pick_stream(stream),
+    hipLaunchKernelGGL(freq_offset_kernel, dim3(fir_grid(nchunks)), dim3(FO_BLOCK), 0, pick_stream(stream),
                        reinterpret_cast<const double2 *>(d_x_re_im), reinterpret_cast<double2 *>(d_out_re_im), d_step, step_batched, n,
                        cpr, nchunks);
     CPX_HIP(hipGetLastError());

@@ -21,6 +21,7 @@
 // Every symbol goes through the same operations wherever it sits in the batch: outputs are bit-identical across batch sizes,
 // positions and streams.  Offsets are 64-bit.
 #include "cpx_internal.h"
+#include "cpx_wave.h"             // grid_of
 
 #include <climits>
 #include <cmath>
@@ -295,11 +296,6 @@ __global__ __launch_bounds__(OD_BLOCK) void ofdm_dft_kernel(OfdmArgs a, int N) {
             }
         }
     }
-}
-
-unsigned grid_of(int64_t items) {
-    const int64_t cap = 65535;
-    return (unsigned)(items < 1 ? 1 : items > cap ? cap : items);
 }
 
 template <bool TX>

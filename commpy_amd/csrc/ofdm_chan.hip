@@ -7,8 +7,8 @@
 //               detectors' layout: y_data [B][ndata][nr], h_data [B][ndata][nr][nt]
 //
 // Multipath: every output sample is ONE chain of fused multiply-adds from +0 over t ascending, then tap index ascending (per
-// complex tap re += gr xr, re -= gi xi, im += gr xi, im += gi xr, fir.hip's order).  Terms under a row's edges are skipped (direct
-// kernel) or meet zero inputs (tiled kernel), which leaves the chain's value unchanged for finite data: the result depends on
+// complex tap re += gr xr, re -= gi xi, im += gr xi, im += gi xr: cpx_wave.h's mac, fir.hip's too).  Terms under a row's edges are
+// skipped (direct kernel) or meet zero inputs (tiled kernel), which leaves the chain's value unchanged for finite data: the result depends on
 // (nt, L, n, index in the row) alone, never on B, the row's place, the stream or whether g is shared.  The row's shape picks the
 // kernel (no process-wide switch):
 //   multipath_kernel<NRG>   n + L - 1 >= 512.  A workgroup of 256 threads owns 1024 consecutive output positions of one b, for ALL
@@ -42,9 +42,12 @@
 //                           where the resource element carries data, to h_data -- consecutive lanes, consecutive addresses, since the
 //                           data elements of a symbol are numbered by ascending subcarrier.  H^ per symbol is never read back.  V
 //                           (all antennas) is staged in the LDS once per workgroup where it fits 16 KB.
+// On the host both estimators are sequences of the same steps (est_begin, est_ls_interp on the estimator's tables and Interp,
+// est_ydemap_end); each adds only its own launch between them, ofdm_hdemap_kernel or ofdm_tv_kernel.
 // Every output element goes through the same operations wherever its frame sits in the batch: bit-identical across batch sizes,
 // positions, streams and whichever outputs are requested; a frame's samples meet no other frame's (NaN isolation).  Offsets 64-bit.
 #include "cpx_internal.h"
+#include "cpx_wave.h"             // mac: the chain step shared with fir.hip and fading.hip; grid_of
 
 #include <algorithm>
 #include <climits>
@@ -82,19 +85,6 @@ struct cpx_ofdm_pilots {
 };
 
 namespace {
-
-// one tap of the chain (fir.hip's order)
-__device__ __forceinline__ void mac(double2 &acc, double2 h, double2 x) {
-    acc.x = fma(h.x, x.x, acc.x);
-    acc.x = fma(-h.y, x.y, acc.x);
-    acc.y = fma(h.x, x.y, acc.y);
-    acc.y = fma(h.y, x.x, acc.y);
-}
-
-unsigned grid_of(int64_t items) {
-    const int64_t cap = 65535;
-    return (unsigned)(items < 1 ? 1 : items > cap ? cap : items);
-}
 
 // ---- multipath -------------------------------------------------------------------------------------------------------------
 constexpr int MP_BLOCK = 256, MP_R = 4, MP_TQ = MP_BLOCK * MP_R, MP_KC = 512;
@@ -437,11 +427,16 @@ __global__ __launch_bounds__(OC_BLOCK) void ofdm_tv_kernel(TvArgs a) {
     }
 }
 
-OcArgs plan_args(const cpx_ofdm_pilots *p, int64_t B) {
+// the tables ofdm_ls_kernel walks: a frame's (an item = the pilots of one (antenna, subcarrier)) or time tracking's (one pilot per item)
+struct LsTables { const int32_t *ptr, *re; const double2 *coef; int64_t n; };
+LsTables frame_tables(const cpx_ofdm_pilots *p) { return {p->d_ls_ptr, p->d_ls_re, p->d_ls_coef, p->nls}; }
+LsTables tv_tables(const cpx_ofdm_pilots *p) { return {p->d_tv_ptr, p->d_tv_re, p->d_tv_coef, p->nlsp}; }
+
+OcArgs plan_args(const cpx_ofdm_pilots *p, int64_t B, const LsTables &ls) {
     OcArgs a{};
     a.code = p->d_code; a.dcount = p->d_dcount; a.data_re = p->d_data_re; a.data_sc = p->d_data_sc; a.pil_tx = p->d_pil_tx;
-    a.ls_ptr = p->d_ls_ptr; a.ls_re = p->d_ls_re; a.pil_val = p->d_pil_val; a.ls_coef = p->d_ls_coef; a.w = p->d_w; a.ant = p->d_ant;
-    a.B = B; a.F = (int64_t)p->nsym * p->nsc; a.ndata = p->ndata; a.nls = p->nls;
+    a.ls_ptr = ls.ptr; a.ls_re = ls.re; a.pil_val = p->d_pil_val; a.ls_coef = ls.coef; a.w = p->d_w; a.ant = p->d_ant;
+    a.B = B; a.F = (int64_t)p->nsym * p->nsc; a.ndata = p->ndata; a.nls = ls.n;
     a.nsc = p->nsc; a.nt = p->nt;
     a.tv_ant = p->d_tv_ant; a.ns_max = p->ns_max;
     return a;
@@ -471,6 +466,88 @@ int estimate_tv_sizes(const cpx_ofdm_pilots *p, int64_t B, int nr, const void *h
     if (int rc = estimate_sizes(p, B, nr, h_sym, y_data, h_data, "ofdm_estimate_tv")) return rc;
     CPX_REQUIRE(p->ns_max > 0, CPX_EINVAL, "ofdm_estimate_tv: the plan has no time matrices (it was made by cpx_pilots_create, not cpx_pilots_create_tv)");
     return CPX_OK;
+}
+
+// ---- the steps of an estimate call, shared by cpx_pilots_estimate_dev and cpx_pilots_estimate_tv_dev -------------------------------
+struct Est {
+    hipStream_t st;
+    OcArgs a;
+    const double2 *Y;
+    char names[160] = "";           // the launches so far, joined with '+': cpx_last_kernel's text
+    void launched(const char *kernel) {
+        if (names[0]) strcat(names, "+");
+        strcat(names, kernel);
+    }
+};
+
+// after the size checks of a call with B > 0: the plan's device, the input, the stream and the kernels' arguments
+int est_begin(Est &e, const cpx_ofdm_pilots *p, const char *what, const LsTables &ls, const double *d_Y_re_im, int64_t B, int nr,
+              void *stream) {
+    if (int rcd = check_handle_device(p->device, what)) return rcd;
+    CPX_REQUIRE(d_Y_re_im, CPX_EINVAL, "%s: null pointer", what);
+    e.st = pick_stream(stream);
+    e.a = plan_args(p, B, ls);
+    e.a.nr = nr;
+    e.Y = reinterpret_cast<const double2 *>(d_Y_re_im);
+    return CPX_OK;
+}
+
+// the interpolation in frequency of one estimator: its kernel, and the arena slots of the least-squares values and of its output
+struct Interp {
+    void (*kernel)(OcArgs, const double2 *, double2 *);
+    const char *name;
+    Slot ls, out;
+};
+
+// least squares on the tables of e.a, then k over B nr per columns into *out [B][per][nsc][nr][nt] (null: taken from k's slot)
+int est_ls_interp(Est &e, Scratch &sc, const Interp &k, int per, double2 **out) {
+    const OcArgs &a = e.a;
+    double2 *ls = nullptr;
+    if (int rc = sc.get(e.st, k.ls, 16 * (size_t)(a.B * a.nls * a.nr), &ls)) return rc;
+    if (!*out)
+        if (int rc = sc.get(e.st, k.out, 16 * (size_t)(a.B * per * a.nsc * a.nr * a.nt), out)) return rc;
+    hipLaunchKernelGGL(ofdm_ls_kernel, dim3(grid_of((a.B * a.nls * a.nr + OC_BLOCK - 1) / OC_BLOCK)), dim3(OC_BLOCK), 0, e.st, a, e.Y,
+                       ls);
+    const int64_t itiles = ((a.B * a.nr * per + IK_CT - 1) / IK_CT) * a.nt * ((a.nsc + IK_KT - 1) / IK_KT);
+    hipLaunchKernelGGL(k.kernel, dim3(grid_of(itiles)), dim3(OC_BLOCK), 0, e.st, a, ls, *out);
+    e.launched("ofdm_ls_kernel");
+    e.launched(k.name);
+    return CPX_OK;
+}
+
+// y_data where it is asked for and the frame has data elements, then the call's end
+int est_ydemap_end(Est &e, double *d_y_data) {
+    if (d_y_data && e.a.ndata) {
+        e.a.rows = oc_rows(e.a.nr);
+        hipLaunchKernelGGL(ofdm_ydemap_kernel, dim3(grid_of(e.a.B * ((e.a.ndata + e.a.rows - 1) / e.a.rows))), dim3(OC_BLOCK), 0, e.st,
+                           e.a, e.Y, reinterpret_cast<double2 *>(d_y_data));
+        e.launched("ofdm_ydemap_kernel");
+    }
+    CPX_HIP(hipGetLastError());
+    note_kernel("%s", e.names);
+    return CPX_OK;
+}
+
+// a host-buffer estimator: dev = the device one, first = the first output (h_sc or h_sym) of first_bytes bytes
+using EstimateDev = int (*)(const cpx_ofdm_pilots *, const double *, int64_t, int, double *, double *, double *, void *);
+int estimate_host(EstimateDev dev, const char *what, const cpx_ofdm_pilots *p, const double *Y_re_im, int64_t B, int nr, double *first,
+                  size_t first_bytes, double *y_data, double *h_data) {
+    CPX_REQUIRE(Y_re_im, CPX_EINVAL, "%s: null pointer", what);
+    int rc = ensure_device();
+    if (rc) return rc;
+    const size_t in_bytes = 16 * (size_t)(B * nr * p->nsym * p->nsc);
+    const size_t y_bytes = y_data ? 16 * (size_t)(B * p->ndata * nr) : 0, hd_bytes = h_data ? 16 * (size_t)(B * p->ndata * nr * p->nt) : 0;
+    if (!first) first_bytes = 0;
+    HostStage s;
+    const double *din;
+    double *dfirst = nullptr, *dy = nullptr, *dhd = nullptr;
+    if ((rc = s.in(Y_re_im, in_bytes, &din))) return rc;
+    if (first && (rc = s.out(first_bytes, &dfirst))) return rc;
+    if (y_data && (rc = s.out(y_bytes, &dy))) return rc;
+    if (h_data && (rc = s.out(hd_bytes, &dhd))) return rc;
+    if ((rc = dev(p, din, B, nr, dfirst, dy, dhd, s.st))) return rc;
+    if ((rc = s.get(first, dfirst, first_bytes)) || (rc = s.get(y_data, dy, y_bytes))) return rc;
+    return s.get(h_data, dhd, hd_bytes);
 }
 
 }  // namespace
@@ -712,7 +789,7 @@ int cpx_pilots_map_dev(const cpx_ofdm_pilots *p, const double *d_data_re_im, int
     if (B == 0) return CPX_OK;
     if (int rcd = check_handle_device(p->device, "ofdm_map")) return rcd;
     CPX_REQUIRE((d_data_re_im || p->ndata == 0) && d_grid_re_im, CPX_EINVAL, "ofdm_map: null pointer");
-    OcArgs a = plan_args(p, B);
+    OcArgs a = plan_args(p, B, frame_tables(p));
     a.rows = oc_rows(p->nt);
     const int64_t ntiles = B * ((a.F + a.rows - 1) / a.rows);
     hipLaunchKernelGGL(ofdm_map_kernel, dim3(grid_of(ntiles)), dim3(OC_BLOCK), 0, pick_stream(stream), a,
@@ -742,61 +819,28 @@ int cpx_pilots_estimate_dev(const cpx_ofdm_pilots *p, const double *d_Y_re_im, i
     CPX_TRACE("cpx_pilots_estimate_dev");
     if (int rc = estimate_sizes(p, B, nr, d_h_sc, d_y_data, d_h_data)) return rc;
     if (B == 0) return CPX_OK;
-    if (int rcd = check_handle_device(p->device, "ofdm_estimate")) return rcd;
-    CPX_REQUIRE(d_Y_re_im, CPX_EINVAL, "ofdm_estimate: null pointer");
-    hipStream_t st = pick_stream(stream);
-    OcArgs a = plan_args(p, B);
-    a.nr = nr;
-    const double2 *Y = reinterpret_cast<const double2 *>(d_Y_re_im);
+    Est e;
+    if (int rc = est_begin(e, p, "ofdm_estimate", frame_tables(p), d_Y_re_im, B, nr, stream)) return rc;
     Scratch sc;
-    char names[160] = "";
     if (d_h_sc || (d_h_data && p->ndata)) {
-        double2 *ls = nullptr, *hsc = reinterpret_cast<double2 *>(d_h_sc);
-        if (int rc = sc.get(st, Slot::ofdm_ls, 16 * (size_t)(B * p->nls * nr), &ls)) return rc;
-        if (!hsc)
-            if (int rc = sc.get(st, Slot::ofdm_hsc, 16 * (size_t)(B * p->nsc * nr * p->nt), &hsc)) return rc;
-        hipLaunchKernelGGL(ofdm_ls_kernel, dim3(grid_of((B * p->nls * nr + OC_BLOCK - 1) / OC_BLOCK)), dim3(OC_BLOCK), 0, st, a, Y,
-                           ls);
-        const int64_t itiles = ((B * nr + IK_CT - 1) / IK_CT) * p->nt * ((p->nsc + IK_KT - 1) / IK_KT);
-        hipLaunchKernelGGL(ofdm_interp_kernel<false>, dim3(grid_of(itiles)), dim3(OC_BLOCK), 0, st, a, ls, hsc);
-        strcat(names, "ofdm_ls_kernel+ofdm_interp_kernel");
+        double2 *hsc = reinterpret_cast<double2 *>(d_h_sc);
+        const Interp k = {ofdm_interp_kernel<false>, "ofdm_interp_kernel", Slot::ofdm_ls, Slot::ofdm_hsc};
+        if (int rc = est_ls_interp(e, sc, k, 1, &hsc)) return rc;
         if (d_h_data && p->ndata) {
-            hipLaunchKernelGGL(ofdm_hdemap_kernel, dim3(grid_of(B * ((p->ndata + HD_ROWS - 1) / HD_ROWS))), dim3(OC_BLOCK), 0, st, a,
+            hipLaunchKernelGGL(ofdm_hdemap_kernel, dim3(grid_of(B * ((p->ndata + HD_ROWS - 1) / HD_ROWS))), dim3(OC_BLOCK), 0, e.st, e.a,
                                hsc, reinterpret_cast<double2 *>(d_h_data));
-            strcat(names, "+ofdm_hdemap_kernel");
+            e.launched("ofdm_hdemap_kernel");
         }
     }
-    if (d_y_data && p->ndata) {
-        a.rows = oc_rows(nr);
-        hipLaunchKernelGGL(ofdm_ydemap_kernel, dim3(grid_of(B * ((p->ndata + a.rows - 1) / a.rows))), dim3(OC_BLOCK), 0, st, a, Y,
-                           reinterpret_cast<double2 *>(d_y_data));
-        strcat(names, names[0] ? "+ofdm_ydemap_kernel" : "ofdm_ydemap_kernel");
-    }
-    CPX_HIP(hipGetLastError());
-    note_kernel("%s", names);
-    return CPX_OK;
+    return est_ydemap_end(e, d_y_data);
 }
 
 int cpx_pilots_estimate(const cpx_ofdm_pilots *p, const double *Y_re_im, int64_t B, int nr, double *h_sc, double *y_data, double *h_data) {
     CPX_TRACE("cpx_pilots_estimate");
     if (int rc = estimate_sizes(p, B, nr, h_sc, y_data, h_data)) return rc;
     if (B == 0) return CPX_OK;
-    CPX_REQUIRE(Y_re_im, CPX_EINVAL, "ofdm_estimate: null pointer");
-    int rc = ensure_device();
-    if (rc) return rc;
-    const size_t in_bytes = 16 * (size_t)(B * nr * p->nsym * p->nsc);
-    const size_t hsc_bytes = h_sc ? 16 * (size_t)(B * p->nsc * nr * p->nt) : 0, y_bytes = y_data ? 16 * (size_t)(B * p->ndata * nr) : 0,
-                 hd_bytes = h_data ? 16 * (size_t)(B * p->ndata * nr * p->nt) : 0;
-    HostStage s;
-    const double *din;
-    double *dhsc = nullptr, *dy = nullptr, *dhd = nullptr;
-    if ((rc = s.in(Y_re_im, in_bytes, &din))) return rc;
-    if (h_sc && (rc = s.out(hsc_bytes, &dhsc))) return rc;
-    if (y_data && (rc = s.out(y_bytes, &dy))) return rc;
-    if (h_data && (rc = s.out(hd_bytes, &dhd))) return rc;
-    if ((rc = cpx_pilots_estimate_dev(p, din, B, nr, dhsc, dy, dhd, s.st))) return rc;
-    if ((rc = s.get(h_sc, dhsc, hsc_bytes)) || (rc = s.get(y_data, dy, y_bytes))) return rc;
-    return s.get(h_data, dhd, hd_bytes);
+    return estimate_host(cpx_pilots_estimate_dev, "ofdm_estimate", p, Y_re_im, B, nr, h_sc, 16 * (size_t)(B * p->nsc * nr * p->nt), y_data,
+                         h_data);
 }
 
 int cpx_pilots_estimate_tv_dev(const cpx_ofdm_pilots *p, const double *d_Y_re_im, int64_t B, int nr, double *d_h_sym, double *d_y_data,
@@ -804,23 +848,13 @@ int cpx_pilots_estimate_tv_dev(const cpx_ofdm_pilots *p, const double *d_Y_re_im
     CPX_TRACE("cpx_pilots_estimate_tv_dev");
     if (int rc = estimate_tv_sizes(p, B, nr, d_h_sym, d_y_data, d_h_data)) return rc;
     if (B == 0) return CPX_OK;
-    if (int rcd = check_handle_device(p->device, "ofdm_estimate_tv")) return rcd;
-    CPX_REQUIRE(d_Y_re_im, CPX_EINVAL, "ofdm_estimate_tv: null pointer");
-    hipStream_t st = pick_stream(stream);
-    OcArgs a = plan_args(p, B);
-    a.nr = nr;
-    const double2 *Y = reinterpret_cast<const double2 *>(d_Y_re_im);
+    Est e;
+    if (int rc = est_begin(e, p, "ofdm_estimate_tv", tv_tables(p), d_Y_re_im, B, nr, stream)) return rc;
     Scratch sc;
-    char names[160] = "";
     if (d_h_sym || (d_h_data && p->ndata)) {
-        double2 *lsp = nullptr, *hp = nullptr;
-        if (int rc = sc.get(st, Slot::ofdm_lsp, 16 * (size_t)(B * p->nlsp * nr), &lsp)) return rc;
-        if (int rc = sc.get(st, Slot::ofdm_hp, 16 * (size_t)(B * p->ns_max * p->nsc * nr * p->nt), &hp)) return rc;
-        OcArgs l = a;                                       // the least-squares kernel with one pilot per item
-        l.ls_ptr = p->d_tv_ptr; l.ls_re = p->d_tv_re; l.ls_coef = p->d_tv_coef; l.nls = p->nlsp;
-        hipLaunchKernelGGL(ofdm_ls_kernel, dim3(grid_of((B * p->nlsp * nr + OC_BLOCK - 1) / OC_BLOCK)), dim3(OC_BLOCK), 0, st, l, Y, lsp);
-        const int64_t itiles = ((B * nr * p->ns_max + IK_CT - 1) / IK_CT) * p->nt * ((p->nsc + IK_KT - 1) / IK_KT);
-        hipLaunchKernelGGL(ofdm_interp_kernel<true>, dim3(grid_of(itiles)), dim3(OC_BLOCK), 0, st, l, lsp, hp);
+        double2 *hp = nullptr;
+        const Interp k = {ofdm_interp_kernel<true>, "ofdm_interp_kernel<tv>", Slot::ofdm_lsp, Slot::ofdm_hp};
+        if (int rc = est_ls_interp(e, sc, k, p->ns_max, &hp)) return rc;
         TvArgs v{};
         v.code = p->d_code; v.tv_ant = p->d_tv_ant; v.v = p->d_v; v.hp = hp;
         v.hsym = reinterpret_cast<double2 *>(d_h_sym);
@@ -828,19 +862,11 @@ int cpx_pilots_estimate_tv_dev(const cpx_ofdm_pilots *p, const double *d_Y_re_im
         v.B = B; v.ndata = p->ndata; v.FE = (int64_t)p->nsc * nr * p->nt; v.nv = p->nv;
         v.nsc = p->nsc; v.nsym = p->nsym; v.nt = p->nt; v.E = nr * p->nt; v.ns_max = p->ns_max;
         const dim3 grid(grid_of(B * ((v.FE + OC_BLOCK - 1) / OC_BLOCK)));
-        if (p->nv <= TV_VMAX) hipLaunchKernelGGL(ofdm_tv_kernel<true>, grid, dim3(OC_BLOCK), 0, st, v);
-        else hipLaunchKernelGGL(ofdm_tv_kernel<false>, grid, dim3(OC_BLOCK), 0, st, v);
-        snprintf(names, sizeof names, "ofdm_ls_kernel+ofdm_interp_kernel<tv>+ofdm_tv_kernel<%s>", p->nv <= TV_VMAX ? "lds" : "global");
+        if (p->nv <= TV_VMAX) hipLaunchKernelGGL(ofdm_tv_kernel<true>, grid, dim3(OC_BLOCK), 0, e.st, v);
+        else hipLaunchKernelGGL(ofdm_tv_kernel<false>, grid, dim3(OC_BLOCK), 0, e.st, v);
+        e.launched(p->nv <= TV_VMAX ? "ofdm_tv_kernel<lds>" : "ofdm_tv_kernel<global>");
     }
-    if (d_y_data && p->ndata) {
-        a.rows = oc_rows(nr);
-        hipLaunchKernelGGL(ofdm_ydemap_kernel, dim3(grid_of(B * ((p->ndata + a.rows - 1) / a.rows))), dim3(OC_BLOCK), 0, st, a, Y,
-                           reinterpret_cast<double2 *>(d_y_data));
-        strcat(names, names[0] ? "+ofdm_ydemap_kernel" : "ofdm_ydemap_kernel");
-    }
-    CPX_HIP(hipGetLastError());
-    note_kernel("%s", names);
-    return CPX_OK;
+    return est_ydemap_end(e, d_y_data);
 }
 
 int cpx_pilots_estimate_tv(const cpx_ofdm_pilots *p, const double *Y_re_im, int64_t B, int nr, double *h_sym, double *y_data,
@@ -848,22 +874,8 @@ int cpx_pilots_estimate_tv(const cpx_ofdm_pilots *p, const double *Y_re_im, int6
     CPX_TRACE("cpx_pilots_estimate_tv");
     if (int rc = estimate_tv_sizes(p, B, nr, h_sym, y_data, h_data)) return rc;
     if (B == 0) return CPX_OK;
-    CPX_REQUIRE(Y_re_im, CPX_EINVAL, "ofdm_estimate_tv: null pointer");
-    int rc = ensure_device();
-    if (rc) return rc;
-    const size_t in_bytes = 16 * (size_t)(B * nr * p->nsym * p->nsc);
-    const size_t hsym_bytes = h_sym ? in_bytes * p->nt : 0, y_bytes = y_data ? 16 * (size_t)(B * p->ndata * nr) : 0,
-                 hd_bytes = h_data ? 16 * (size_t)(B * p->ndata * nr * p->nt) : 0;
-    HostStage s;
-    const double *din;
-    double *dhsym = nullptr, *dy = nullptr, *dhd = nullptr;
-    if ((rc = s.in(Y_re_im, in_bytes, &din))) return rc;
-    if (h_sym && (rc = s.out(hsym_bytes, &dhsym))) return rc;
-    if (y_data && (rc = s.out(y_bytes, &dy))) return rc;
-    if (h_data && (rc = s.out(hd_bytes, &dhd))) return rc;
-    if ((rc = cpx_pilots_estimate_tv_dev(p, din, B, nr, dhsym, dy, dhd, s.st))) return rc;
-    if ((rc = s.get(h_sym, dhsym, hsym_bytes)) || (rc = s.get(y_data, dy, y_bytes))) return rc;
-    return s.get(h_data, dhd, hd_bytes);
+    return estimate_host(cpx_pilots_estimate_tv_dev, "ofdm_estimate_tv", p, Y_re_im, B, nr, h_sym,
+                         16 * (size_t)(B * nr * p->nsym * p->nsc) * p->nt, y_data, h_data);
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@
 // workgroups that stride over their tiles.
 #include "cpx_internal.h"
 #include "cpx_rotate.h"
+#include "cpx_wave.h"             // grid_of
 
 #include <climits>
 #include <cmath>
@@ -40,11 +41,6 @@ using namespace cpx;
 namespace {
 
 constexpr int SY_BLOCK = 256, SY_R = 4, SY_T = SY_BLOCK * SY_R, SY_WAVES = SY_BLOCK / 64;
-
-unsigned grid_of(int64_t items) {
-    const int64_t cap = 65535;
-    return (unsigned)(items < 1 ? 1 : items > cap ? cap : items);
-}
 
 struct Sum3 { double x, y, e; };     // (Re q, Im q, e)
 __device__ __forceinline__ Sum3 zero3() { return Sum3{0.0, 0.0, 0.0}; }

@@ -377,32 +377,29 @@ def ofdm_map_dev(pilots, d_data, B, stream=None):
     return d_grid
 
 
+def _ofdm_estimate(entry, third, rows, pilots, d_Y, B, nr, want, stream):
+    """Both estimators: ``entry`` writes y_data, h_data and its own third output, ``third`` ``[B][rows][nr][nt]``."""
+    names = ('y', 'h', third)
+    want = _lib.wanted(want, names)
+    sizes = {'y': pilots.ndata * nr, 'h': pilots.ndata * nr * pilots.nt, third: rows * nr * pilots.nt}
+    out = {k: DeviceBuf(B * sizes[k] * 16) for k in names if k in want}
+    ptrs = [out[k].ptr if k in out else None for k in (third, 'y', 'h')]
+    _lib.check(getattr(_lib.load(), entry)(pilots.handle(), d_Y.ptr, B, nr, ptrs[0], ptrs[1], ptrs[2], stream))
+    return tuple(out[k] for k in names if k in out)
+
+
 def ofdm_estimate_dev(pilots, d_Y, B, nr, want=('y', 'h'), stream=None):
     """``cpx_pilots_estimate_dev``: ``d_Y [B][nr][nsym][nsc]`` -> a tuple of new ``DeviceBuf``s, the members of ``(y_data
     [B][ndata][nr], h_data [B][ndata][nr][nt], h_sc [B][nsc][nr][nt])`` that ``want`` names ('y', 'h', 'h_sc'), in that order:
     the first two are the ``y`` and ``H`` of the ``cpx_mimo_*_dev`` / ``cpx_kbest_*_dev`` detectors for ``V = B ndata`` vectors."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ('y', 'h', 'h_sc') for w in want):
-        raise ValueError("want must name at least one of 'y', 'h', 'h_sc'")
-    sizes = {'y': pilots.ndata * nr, 'h': pilots.ndata * nr * pilots.nt, 'h_sc': pilots.nsc * nr * pilots.nt}
-    out = {k: DeviceBuf(B * sizes[k] * 16) for k in ('y', 'h', 'h_sc') if k in want}
-    ptrs = [out[k].ptr if k in out else None for k in ('h_sc', 'y', 'h')]
-    _lib.check(_lib.load().cpx_pilots_estimate_dev(pilots.handle(), d_Y.ptr, B, nr, ptrs[0], ptrs[1], ptrs[2], stream))
-    return tuple(out[k] for k in ('y', 'h', 'h_sc') if k in out)
+    return _ofdm_estimate('cpx_pilots_estimate_dev', 'h_sc', pilots.nsc, pilots, d_Y, B, nr, want, stream)
 
 
 def ofdm_estimate_tv_dev(pilots, d_Y, B, nr, want=('y', 'h'), stream=None):
     """``cpx_pilots_estimate_tv_dev`` (``pilots`` made with ``time_interp``): ``d_Y [B][nr][nsym][nsc]`` -> a tuple of new
     ``DeviceBuf``s, the members of ``(y_data [B][ndata][nr], h_data [B][ndata][nr][nt], h_sym [B][nsym][nsc][nr][nt])`` that ``want``
     names ('y', 'h', 'h_sym'), in that order; the first two feed the detectors as ``ofdm_estimate_dev``'s do."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ('y', 'h', 'h_sym') for w in want):
-        raise ValueError("want must name at least one of 'y', 'h', 'h_sym'")
-    sizes = {'y': pilots.ndata * nr, 'h': pilots.ndata * nr * pilots.nt, 'h_sym': pilots.nsym * pilots.nsc * nr * pilots.nt}
-    out = {k: DeviceBuf(B * sizes[k] * 16) for k in ('y', 'h', 'h_sym') if k in want}
-    ptrs = [out[k].ptr if k in out else None for k in ('h_sym', 'y', 'h')]
-    _lib.check(_lib.load().cpx_pilots_estimate_tv_dev(pilots.handle(), d_Y.ptr, B, nr, ptrs[0], ptrs[1], ptrs[2], stream))
-    return tuple(out[k] for k in ('y', 'h', 'h_sym') if k in out)
+    return _ofdm_estimate('cpx_pilots_estimate_tv_dev', 'h_sym', pilots.nsym * pilots.nsc, pilots, d_Y, B, nr, want, stream)
 
 
 # ---- timing and frequency-offset synchronisation, device resident (csrc/sync.hip) -------------------------------------------------
@@ -468,9 +465,7 @@ def fading_channel_dev(d_x, B, nt, nr, n, pdp, fd, hold=1, t0=0, n_sin=16, k_fac
     """``cpx_fading_channel_dev``: ``d_x [B][nt][n]`` through the fading channel -> new ``DeviceBuf``s, the members of ``(y [B][nr][n + L
     - 1], G [B][nblk][nr][nt][L])`` that ``want`` names ('y', 'g'), in that order (a single ``DeviceBuf`` for ``want=('y',)``).  Without
     'g' the gains stay in the engine's scratch arena, at most ``channels.FADING_SCRATCH_BYTES`` of it."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ('y', 'g') for w in want):
-        raise ValueError("want must name at least one of 'y', 'g'")
+    want = _lib.wanted(want, ('y', 'g'))
     md = _fading_model(B, nr, nt, pdp, fd, hold, t0, n_sin, k_factor, fd_los, seed, stream_id, first_row)
     if md.B and (isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1):
         raise ValueError('n = %r, need an integer >= 1' % (n,))

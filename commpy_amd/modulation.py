@@ -778,6 +778,21 @@ def _default_pilot_values(n):
     return ((1.0 - 2.0 * bits[0::2]) + 1j * (1.0 - 2.0 * bits[1::2])) * np.sqrt(0.5)
 
 
+def _antenna_matrices(named, spec, arg, schemes, letter, dims, rows, cols):
+    """The interpolation matrices of the len(cols) antennas, each [rows, cols[t]] and finite: ``named``, what the caller made of a
+    named scheme, or else argument ``arg`` = ``spec`` itself, a list of that many arrays (``schemes``: the names, for the message)."""
+    if named is None:
+        if not (isinstance(spec, (list, tuple)) and len(spec) == len(cols) and not isinstance(spec[0], str)):
+            raise ValueError("%s must be %s or a list of nt matrices" % (arg, schemes))
+        named = [_numeric(m, '%s[%d]' % (arg, t)) for t, m in enumerate(spec)]
+    for t, m in enumerate(named):
+        if m.shape != (rows, cols[t]):
+            raise ValueError('%s[%d] must be [%s] = [%d, %d], got %s' % (letter, t, dims, rows, cols[t], m.shape))
+        if not np.all(np.isfinite(m)):
+            raise ValueError('%s[%d] holds a value that is not finite' % (letter, t))
+    return named
+
+
 class OfdmPilots:
     """The pilots of a frame of ``nsym`` OFDM symbols x ``nsc`` used subcarriers (``ofdm_tx``'s input order) of ``nt`` transmit
     antennas.  Pilot i puts ``pil_val[i]`` on resource element ``(pil_sym[i], pil_sc[i])`` of antenna ``pil_tx[i]``; the other
@@ -827,6 +842,7 @@ class OfdmPilots:
         for t, pk in enumerate(self.pilot_subcarriers):
             if pk.size == 0:
                 raise ValueError('antenna %d has no pilot' % t)
+        W = None
         if isinstance(interp, str) and interp == 'linear':
             W = [_interp_linear(nsc, pk) for pk in self.pilot_subcarriers]
         elif isinstance(interp, tuple) and len(interp) == 3 and interp[0] == 'taps':
@@ -834,15 +850,8 @@ class OfdmPilots:
             if Lmax < 1 or nfft < 2:
                 raise ValueError("interp ('taps', Lmax, nfft) needs Lmax >= 1 and nfft >= 2")
             W = [_interp_taps(nsc, pk, Lmax, nfft) for pk in self.pilot_subcarriers]
-        elif isinstance(interp, (list, tuple)) and len(interp) == nt and not isinstance(interp[0], str):
-            W = [_numeric(w, 'interp[%d]' % t) for t, w in enumerate(interp)]
-        else:
-            raise ValueError("interp must be 'linear', ('taps', Lmax, nfft) or a list of nt matrices")
-        for t, w in enumerate(W):
-            if w.shape != (nsc, self.pilot_subcarriers[t].size):
-                raise ValueError('W[%d] must be [nsc, np_t] = [%d, %d], got %s' % (t, nsc, self.pilot_subcarriers[t].size, w.shape))
-            if not np.all(np.isfinite(w)):
-                raise ValueError('W[%d] holds a value that is not finite' % t)
+        W = _antenna_matrices(W, interp, 'interp', "'linear', ('taps', Lmax, nfft)", 'W', 'nsc, np_t', nsc,
+                              [pk.size for pk in self.pilot_subcarriers])
         self.pilot_symbols = [np.unique(sym[tx == t]) for t in range(nt)]
         V = None
         if time_interp is not None:
@@ -864,15 +873,8 @@ class OfdmPilots:
                 if not (np.isfinite(fd_sym) and np.isfinite(nvar) and fd_sym >= 0 and nvar >= 0):
                     raise ValueError("time_interp ('doppler', fd_sym, nvar) needs finite fd_sym >= 0 and nvar >= 0")
                 V = [_time_doppler(nsym, ps, fd_sym, nvar) for ps in self.pilot_symbols]
-            elif isinstance(time_interp, (list, tuple)) and len(time_interp) == nt and not isinstance(time_interp[0], str):
-                V = [_numeric(v, 'time_interp[%d]' % t) for t, v in enumerate(time_interp)]
-            else:
-                raise ValueError("time_interp must be None, 'linear', 'hold', ('doppler', fd_sym, nvar) or a list of nt matrices")
-            for t, v in enumerate(V):
-                if v.shape != (nsym, self.pilot_symbols[t].size):
-                    raise ValueError('V[%d] must be [nsym, ns_t] = [%d, %d], got %s' % (t, nsym, self.pilot_symbols[t].size, v.shape))
-                if not np.all(np.isfinite(v)):
-                    raise ValueError('V[%d] holds a value that is not finite' % t)
+            V = _antenna_matrices(V, time_interp, 'time_interp', "None, 'linear', 'hold', ('doppler', fd_sym, nvar)", 'V',
+                                  'nsym, ns_t', nsym, [ps.size for ps in self.pilot_symbols])
         self.nsc, self.nsym, self.nt, self.npil = nsc, nsym, nt, npil
         self.pil_sym, self.pil_sc, self.pil_tx, self.pil_val, self.W, self.V = sym, sc, tx, val, W, V
         is_data = np.ones(nsym * nsc, dtype=bool)
@@ -948,6 +950,24 @@ def ofdm_map_batch(data, pilots):
     return grid
 
 
+def _ofdm_estimate(entry, third, dims, Y, p, want):
+    """Both estimators: ``entry`` writes y_data, h_data and its own third output, ``third`` ``[B, *dims, nr, nt]``."""
+    names = ('y', 'h', third)
+    want = _lib.wanted(want, names)
+    y = _numeric(Y, 'Y')
+    if y.ndim != 4 or y.shape[1] < 1 or y.shape[2:] != (p.nsym, p.nsc):
+        raise ValueError('Y must be [B, nr, nsym, nsc] = [B, nr, %d, %d], got %s' % (p.nsym, p.nsc, y.shape))
+    B, nr = y.shape[:2]
+    if nr > OFDM_MAX_ANTENNAS:
+        raise ValueError('nr = %d is above the engine limit of %d' % (nr, OFDM_MAX_ANTENNAS))
+    shapes = {'y': (B, p.ndata, nr), 'h': (B, p.ndata, nr, p.nt), third: (B,) + dims + (nr, p.nt)}
+    out = {k: np.zeros(shapes[k], dtype=np.complex128) for k in names if k in want}
+    if B:
+        ptrs = [_lib.ptr(out[k]) if k in out else None for k in (third, 'y', 'h')]
+        _lib.check(getattr(_lib.load(), entry)(p.handle(), _lib.ptr(y), B, nr, *ptrs))
+    return tuple(out[k] for k in names if k in out)
+
+
 def ofdm_estimate_batch(Y, pilots, want=('y', 'h')):
     """Pilot-aided channel estimation of ``Y [B, nr, nsym, nsc]`` (``ofdm_rx_batch`` of the B nr received streams, reshaped):
     least squares at the pilots, then ``W[t]`` over the subcarriers.  Returns a tuple of the members of ``(y_data, h_data, h_sc)``
@@ -956,21 +976,7 @@ def ofdm_estimate_batch(Y, pilots, want=('y', 'h')):
     ``y`` and ``h`` of ``linear_batch``, ``kbest_batch``, ``mimo_ml_batch`` ... -- and ``h_sc [B, nsc, nr, nt]`` the estimate per
     subcarrier."""
     p = _pilots_arg(pilots)
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ('y', 'h', 'h_sc') for w in want):
-        raise ValueError("want must name at least one of 'y', 'h', 'h_sc'")
-    y = _numeric(Y, 'Y')
-    if y.ndim != 4 or y.shape[1] < 1 or y.shape[2:] != (p.nsym, p.nsc):
-        raise ValueError('Y must be [B, nr, nsym, nsc] = [B, nr, %d, %d], got %s' % (p.nsym, p.nsc, y.shape))
-    B, nr = y.shape[:2]
-    if nr > OFDM_MAX_ANTENNAS:
-        raise ValueError('nr = %d is above the engine limit of %d' % (nr, OFDM_MAX_ANTENNAS))
-    shapes = {'y': (B, p.ndata, nr), 'h': (B, p.ndata, nr, p.nt), 'h_sc': (B, p.nsc, nr, p.nt)}
-    out = {k: np.zeros(shapes[k], dtype=np.complex128) for k in ('y', 'h', 'h_sc') if k in want}
-    if B:
-        ptrs = [_lib.ptr(out[k]) if k in out else None for k in ('h_sc', 'y', 'h')]
-        _lib.check(_lib.load().cpx_pilots_estimate(p.handle(), _lib.ptr(y), B, nr, *ptrs))
-    return tuple(out[k] for k in ('y', 'h', 'h_sc') if k in out)
+    return _ofdm_estimate('cpx_pilots_estimate', 'h_sc', (p.nsc,), Y, p, want)
 
 
 def ofdm_estimate_tv_batch(Y, pilots, want=('y', 'h')):
@@ -983,18 +989,4 @@ def ofdm_estimate_tv_batch(Y, pilots, want=('y', 'h')):
     p = _pilots_arg(pilots)
     if p.V is None:
         raise ValueError('pilots were made without time_interp')
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ('y', 'h', 'h_sym') for w in want):
-        raise ValueError("want must name at least one of 'y', 'h', 'h_sym'")
-    y = _numeric(Y, 'Y')
-    if y.ndim != 4 or y.shape[1] < 1 or y.shape[2:] != (p.nsym, p.nsc):
-        raise ValueError('Y must be [B, nr, nsym, nsc] = [B, nr, %d, %d], got %s' % (p.nsym, p.nsc, y.shape))
-    B, nr = y.shape[:2]
-    if nr > OFDM_MAX_ANTENNAS:
-        raise ValueError('nr = %d is above the engine limit of %d' % (nr, OFDM_MAX_ANTENNAS))
-    shapes = {'y': (B, p.ndata, nr), 'h': (B, p.ndata, nr, p.nt), 'h_sym': (B, p.nsym, p.nsc, nr, p.nt)}
-    out = {k: np.zeros(shapes[k], dtype=np.complex128) for k in ('y', 'h', 'h_sym') if k in want}
-    if B:
-        ptrs = [_lib.ptr(out[k]) if k in out else None for k in ('h_sym', 'y', 'h')]
-        _lib.check(_lib.load().cpx_pilots_estimate_tv(p.handle(), _lib.ptr(y), B, nr, *ptrs))
-    return tuple(out[k] for k in ('y', 'h', 'h_sym') if k in out)
+    return _ofdm_estimate('cpx_pilots_estimate_tv', 'h_sym', (p.nsym, p.nsc), Y, p, want)

@@ -64,9 +64,7 @@ def sync_metric_batch(y, lag, window, want=('m',)):
     """The timing metric of every position: a tuple of the members of ``(M, E, P)`` that ``want`` names ('m', 'e', 'p'), in that
     order, each ``[B, n - lag - window + 1]`` (M and E float64, P complex128).  A diagnostic: the search itself
     (``sync_estimate_batch``) writes no such array."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ('m', 'e', 'p') for w in want):
-        raise ValueError("want must name at least one of 'm', 'e', 'p'")
+    want = _lib.wanted(want, ('m', 'e', 'p'))
     ya, _ = _rows(y)
     B, nr, n = ya.shape
     D, W, nd = _window_sizes(B, n, lag, window)

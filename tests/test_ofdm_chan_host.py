@@ -180,6 +180,34 @@ def test_builders_and_calls_refused(no_device):
     assert multipath_batch(np.zeros((0, 4)), np.ones(5)).shape == (0, 8)
 
 
+def test_want_names_outputs_alike_in_every_call(no_device):
+    """One name may come as a bare string, the members come back in the documented order whatever the order asked in, and every call
+    refuses an empty or unknown ``want`` before anything else, in its own fixed words."""
+    from commpy_amd import deviceops
+    from commpy_amd.channels import fading_multipath_batch
+    from commpy_amd.sync import sync_metric_batch
+    p = OfdmPilots(**GOOD)
+    Y0 = np.zeros((0, 3, 2, 8))
+    assert [a.shape for a in ofdm_estimate_batch(Y0, p, want='h_sc')] == [(0, 8, 3, 2)]
+    assert [a.shape for a in ofdm_estimate_batch(Y0, p, want=['h_sc', 'h', 'y'])] == [(0, 13, 3), (0, 13, 3, 2), (0, 8, 3, 2)]
+    assert [a.dtype for a in sync_metric_batch(np.zeros((0, 8)), 2, 2, want=('p', 'e', 'm'))] == [np.float64, np.float64, np.complex128]
+    assert [a.dtype for a in sync_metric_batch(np.zeros((0, 8)), 2, 2, want='p')] == [np.complex128]
+    x0 = np.zeros((0, 2, 4))
+    assert [a.shape for a in fading_multipath_batch(x0, 3, np.ones(5), 0.01, want=('g', 'y'))] == [(0, 3, 8), (0, 1, 3, 2, 5)]
+    assert [a.shape for a in fading_multipath_batch(x0, 3, np.ones(5), 0.01, want='g')] == [(0, 1, 3, 2, 5)]
+    assert fading_multipath_batch(x0, 3, np.ones(5), 0.01, want='y').shape == (0, 3, 8)
+    calls = [(lambda w: ofdm_estimate_batch(Y0, p, want=w), "'y', 'h', 'h_sc'"),
+             (lambda w: deviceops.ofdm_estimate_dev(p, None, 1, 3, want=w), "'y', 'h', 'h_sc'"),
+             (lambda w: sync_metric_batch(np.zeros((0, 8)), 2, 2, want=w), "'m', 'e', 'p'"),
+             (lambda w: fading_multipath_batch(x0, 3, np.ones(5), 0.01, want=w), "'y', 'g'"),
+             (lambda w: deviceops.fading_channel_dev(None, 1, 2, 3, 4, np.ones(5), 0.01, want=w), "'y', 'g'")]
+    for call, names in calls:
+        for bad in ((), [], '', 'x', ('y', 'x'), (None,), 'h_sym'):
+            with pytest.raises(ValueError) as e:
+                call(bad)
+            assert str(e.value) == "want must name at least one of " + names
+
+
 def test_engine_checks_without_device():
     """The C entry points: argument errors are reported before the device is looked for; a valid call fails loudly without one."""
     lib = _lib.load()

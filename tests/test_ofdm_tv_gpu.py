@@ -204,6 +204,42 @@ def test_grid_cap(gpu):
     assert same_bits(hs[:, :, 0], hs[:, :, 1])
 
 
+# ---- 4b. frames without a data element -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("time_interp", [None, 'hold'])
+@pytest.mark.parametrize("shape", [(2, 1, 1, 1), (4, 2, 2, 3)])
+def test_frames_of_pilots_only(gpu, shape, time_interp):
+    """Every resource element is a pilot (ndata = 0): y_data and h_data are empty and no demap kernel is launched, by either estimator
+    (the time-tracking one needs a plan made with time_interp); the estimates on the grid are the models'."""
+    nsc, nsym, nt, nr = shape
+    B = 2
+    p = OfdmPilots.block(nsc, nsym, nt, time_interp=time_interp)
+    assert p.ndata == 0
+    Y = cplx(np.random.RandomState(8 + nsc), B, nr, nsym, nsc)
+    fr0 = M.Frame(p.nsc, p.nsym, p.nt, p.pil_sym, p.pil_sc, p.pil_tx, p.pil_val, p.W)
+    y_m, h_m, hsc_m, ls = M.estimate(fr0, Y)
+    assert y_m.shape == (B, 0, nr) and h_m.shape == (B, 0, nr, nt)
+    y, h, hsc = ofdm_estimate_batch(Y, p, want=('y', 'h', 'h_sc'))
+    assert _lib.last_kernel() == "ofdm_ls_kernel+ofdm_interp_kernel"
+    assert same_bits(y, y_m) and same_bits(h, h_m)
+    err, bound = np.abs(hsc - hsc_m), M.h_bound(fr0, ls)
+    print("pilots only", shape, time_interp, "per frame: largest share of the bound %.3f" % np.max(err / bound))
+    assert hsc.shape == (B, nsc, nr, nt) and np.all(err <= bound)
+    assert [a.shape for a in ofdm_estimate_batch(Y, p, want=('y', 'h'))] == [(B, 0, nr), (B, 0, nr, nt)]
+    if time_interp is None:
+        return
+    fr = frame_of(p)
+    y_m, h_m, hs_m, lsp, hp = T.estimate_tv(fr, Y)
+    assert y_m.shape == (B, 0, nr) and h_m.shape == (B, 0, nr, nt)
+    y, h, hs = ofdm_estimate_tv_batch(Y, p, want=ALL)
+    assert _lib.last_kernel() == TV_KERNELS % "lds"
+    assert same_bits(y, y_m) and same_bits(h, h_m)
+    err, bound = np.abs(hs - hs_m), T.h_tv_bound(fr, lsp, hp)
+    pos = bound > 0
+    print("pilots only", shape, time_interp, "time tracking: largest share of the bound %.3f" % np.max(err[pos] / bound[pos]))
+    assert hs.shape == (B, nsym, nsc, nr, nt) and np.all(err <= bound)
+    assert [a.shape for a in ofdm_estimate_tv_batch(Y, p, want=('y', 'h'))] == [(B, 0, nr), (B, 0, nr, nt)]
+
+
 # ---- 5. errors on the device path -----------------------------------------------------------------------------------------------------
 def test_device_path_errors(gpu):
     lib = _lib.load()

@@ -138,6 +138,21 @@ def test_calls_refused(no_device):
     assert [a.shape for a in ofdm_estimate_tv_batch(np.zeros((0, 3, 3, 8)), p, want=('h_sym', 'y', 'h'))] == [(0, 19, 3), (0, 19, 3, 2), (0, 3, 8, 3, 2)]
 
 
+def test_want_names_outputs(no_device):
+    """As for the per-frame estimator: a bare string is one name, the order asked in does not matter, and an empty or unknown ``want``
+    is refused in fixed words, by the host-buffer call and by the device-resident one."""
+    from commpy_amd import deviceops
+    p = OfdmPilots(**GOOD)
+    Y0 = np.zeros((0, 3, 3, 8))
+    assert [a.shape for a in ofdm_estimate_tv_batch(Y0, p, want='h_sym')] == [(0, 3, 8, 3, 2)]
+    assert [a.shape for a in ofdm_estimate_tv_batch(Y0, p, want=['h', 'y'])] == [(0, 19, 3), (0, 19, 3, 2)]
+    for call in (lambda w: ofdm_estimate_tv_batch(Y0, p, want=w), lambda w: deviceops.ofdm_estimate_tv_dev(p, None, 1, 3, want=w)):
+        for bad in ((), [], '', 'x', ('y', 'x'), (None,), 'h_sc'):
+            with pytest.raises(ValueError) as e:
+                call(bad)
+            assert str(e.value) == "want must name at least one of 'y', 'h', 'h_sym'"
+
+
 def test_engine_checks_without_device():
     """cpx_pilots_create_tv and cpx_pilots_estimate_tv report argument errors before the device is looked for."""
     lib = _lib.load()

@@ -323,30 +323,40 @@ __device__ __forceinline__ void cw_step(double (&pm)[1 << LGS], double r0, doubl
     // doubles the numeric order IS the unsigned order of the 64-bit patterns, equal values have equal patterns, and +inf (0x7ff00000
     // 00000000) is simply the largest pattern in the domain.  Hence the minimum's high dword is the unsigned minimum of the 64 high dwords,
     // and the first-argmin state is one of the states whose high dword equals it (the "hits"): with exactly one hit that state IS the
-    // first-argmin, whatever the low dwords hold.  With two or more hits in any lane (an exact tie, or metrics that differ only in the low
+    // first-argmin, whatever the low dwords hold.  The step needs that state's index and whether a lane has more than one hit, not a hit
+    // bit per state, so it reads both off an 8 x 8 GRID of the high dwords, logical state s = 8 j + i in row j and column i: the eight row
+    // minima, the eight column minima, m = the minimum of the column minima, and one 16-bit word of "row / column minimum == m" bits
+    // (v_cmp_eq_u32 -> v_addc_co_u32, as the decision words are shifted in; columns in bits 15:8, rows in bits 7:0).  Every lane has at
+    // least one hit row and one hit column.  Two different hit states differ in row or in column, so two row bits or two column bits are
+    // set; and two set row (column) bits come from two different hit states: exactly two bits set <=> exactly one hit, the state
+    // 8 j* + i* (tests/test_viterbi_argmin_rowcol_gpu.py asserts the identity on its metrics).  106 instructions (16 x 4 minima, 4 for m,
+    // 16 x 2 hit bits, 6 for index and tie mask) where a hit bit per state took 166.  Column part first, then hook 3, then the rows three
+    // at a time, each compared as soon as it exists: ten temporaries at most.
+    // With two or more hits in any lane (an exact tie, or metrics that differ only in the low
     // dword) the whole wave runs the float64 tree and first-equal scan below and takes their result -- on the benchmark's input 0.54 % of
     // the wave-steps, 0.48 % of them the five all-tie steps of the zero tail (profiles/viterbi_argmin32_tie_rate.txt).  The branch is
     // wave-uniform (an SGPR pair written by one compare) and marked unlikely: the float64 block sits out of line, the step's hot path has
     // no taken branch, and the hook calls stay unconditional and in order.  (Measured issue costs: profiles/viterbi_argmin32_issue_cost.txt.)
     constexpr bool ARGMIN32 = LEAN && S == 64 && TYPE == CPX_VIT_SOFT && !GEN;   // the fused kernel, compiled-in generators
-    unsigned long long tie = ~0ull;                                // lanes with more than one hit
+    unsigned long long tie = ~0ull;                                // lanes with more than one hit (hit word: not exactly two bits)
     if constexpr (ARGMIN32) {
-        unsigned h0, h1, h2, h3;
-#define CPX_H4(a) "v"(__double2hiint(pm[a])), "v"(__double2hiint(pm[(a) + 1])), "v"(__double2hiint(pm[(a) + 2])), "v"(__double2hiint(pm[(a) + 3]))
-        asm(CPX_HMIN_BLOCK0 : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3) : CPX_H4(0), CPX_H4(4), CPX_H4(8), CPX_H4(12), CPX_H4(16));
-        asm(CPX_HMIN_BLOCK1 : "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3) : CPX_H4(20), CPX_H4(24), CPX_H4(28), CPX_H4(32), CPX_H4(36), CPX_H4(40));
-        asm(CPX_HMIN_BLOCK2 : "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3) : CPX_H4(44), CPX_H4(48), CPX_H4(52), CPX_H4(56), CPX_H4(60));
-#undef CPX_H4
+        // (state s sits in register rotl(s, R + 1): only a question of which operand is named)
+#define CPX_HI(s) "v"(__double2hiint(pm[rotl<LGS>((s), R + 1)]))
+#define CPX_COL(i) CPX_HI(i), CPX_HI((i) + 8), CPX_HI((i) + 16), CPX_HI((i) + 24), CPX_HI((i) + 32), CPX_HI((i) + 40), CPX_HI((i) + 48), CPX_HI((i) + 56)
+#define CPX_ROW(j) CPX_HI(8 * (j)), CPX_HI(8 * (j) + 1), CPX_HI(8 * (j) + 2), CPX_HI(8 * (j) + 3), CPX_HI(8 * (j) + 4), CPX_HI(8 * (j) + 5), CPX_HI(8 * (j) + 6), CPX_HI(8 * (j) + 7)
+        unsigned q0, q1, q2, q3, q4, q5, q6, q7, m, w;                 // column minima, the minimum, the hit word
+        asm(CPX_COL_BLOCK3 : "=&v"(q0), "=&v"(q1), "=&v"(q2) : CPX_COL(0), CPX_COL(1), CPX_COL(2));
+        asm(CPX_COL_BLOCK3 : "=&v"(q3), "=&v"(q4), "=&v"(q5) : CPX_COL(3), CPX_COL(4), CPX_COL(5));
+        asm(CPX_COL_BLOCK_LAST : "=&v"(q6), "=&v"(q7), "=&v"(m), "=&v"(w) : "v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(q4), "v"(q5), CPX_COL(6), CPX_COL(7)
+            : "vcc");
         hook.template at<3>();
-        // hit words in logical state order (state s sits in register rotl(s, R + 1)): ha = states 0 .. 31, hb = states 32 .. 63
-        unsigned ha, hb, tmp;
-#define CPX_P1(a) "v"(__double2hiint(pm[rotl<LGS>((a), R + 1)])), "v"(__double2hiint(pm[rotl<LGS>((a) + 32, R + 1)]))
-#define CPX_P4(a) CPX_P1(a), CPX_P1((a) + 1), CPX_P1((a) + 2), CPX_P1((a) + 3)
-        asm(CPX_HIT_BLOCK0 : "=&v"(ha), "=&v"(hb) : "v"(h0), CPX_P4(0), CPX_P4(4), CPX_P4(8) : "vcc");
-        asm(CPX_HIT_BLOCK1 : "+v"(ha), "+v"(hb) : "v"(h0), CPX_P4(12), CPX_P4(16), CPX_P4(20) : "vcc");
-        asm(CPX_HIT_BLOCK2 : "+v"(ha), "+v"(hb), "=&v"(bst), "=&v"(tmp), "=&s"(tie) : "v"(h0), CPX_P4(24), CPX_P4(28) : "vcc");
-#undef CPX_P4
-#undef CPX_P1
+        unsigned r0_, r1_, r2_;                                        // row minima: dead once compared
+        asm(CPX_ROW_BLOCK3 : "+v"(w), "=&v"(r0_), "=&v"(r1_), "=&v"(r2_) : "v"(m), CPX_ROW(7), CPX_ROW(6), CPX_ROW(5) : "vcc");
+        asm(CPX_ROW_BLOCK3 : "+v"(w), "=&v"(r0_), "=&v"(r1_), "=&v"(r2_) : "v"(m), CPX_ROW(4), CPX_ROW(3), CPX_ROW(2) : "vcc");
+        asm(CPX_ROW_BLOCK_LAST : "+v"(w), "=&v"(r0_), "=&v"(r1_), "=&v"(bst), "=&s"(tie) : "v"(m), CPX_ROW(1), CPX_ROW(0) : "vcc");
+#undef CPX_ROW
+#undef CPX_COL
+#undef CPX_HI
     }
     if (__builtin_expect(tie != 0, !ARGMIN32)) {
         // first-argmin state (:645): the minimum (v_min_f64 tree, as viterbi.hip's cross-lane tree) and the first state equal to it

@@ -9,10 +9,12 @@ steps).  Inside ONE statement the order is ours: four independent chains are int
 the number of statement boundaries drops from ~80 to 6 per step.  An asm statement takes at most 30 operands, hence blocks of 24
 registers; state numbers are literals in the text (they are inline constants of v_cndmask_b32).
 
-'soft' runs a 32-bit form of the same block first (cw_step: "first-argmin on the high dwords"): the unsigned minimum of the 64 high
-dwords as a v_min3_u32 tree (CPX_HMIN_BLOCK*), then one hit bit per state -- v_cmp_eq_u32 against that minimum, shifted into two
-32-bit words by v_addc_co_u32 exactly as the decision words are -- and the index of the first hit and the hit count from the two
-words (CPX_HIT_BLOCK*).  The float64 blocks above then run only for a wave in which some lane has more than one hit.
+'soft' runs a 32-bit block first (cw_step: "first-argmin on the high dwords"): the 64 high dwords as an 8 x 8 grid over the logical
+state, the unsigned minimum of every column and of every row as a chain of three v_min3_u32 and one v_min_u32 (CPX_COL_BLOCK*,
+CPX_ROW_BLOCK*; three chains interleaved per statement), the overall minimum from the column minima, and one hit bit per column and per row
+-- v_cmp_eq_u32 against that minimum, shifted into ONE 16-bit word by v_addc_co_u32 exactly as the decision words are.  The index of the
+single hit and the mask of lanes with more than one come from that word.  The float64 blocks above then run only for a wave in which some
+lane has more than one hit.  Which register holds which state is the caller's business: the blocks only fix the operand order.
 
     python scripts/gen_viterbi_cw_asm.py > commpy_amd/csrc/viterbi_cw_asm.h
 """
@@ -36,43 +38,54 @@ def scan_block(states):
     return "\\n\\t".join(out)
 
 
-def hmin_block(n_in, first=False, last=False):
-    """4 accumulators %0..%3 (=&v if first, else +v), n_in high dwords %4..: acc[c] = min3(acc[c], in, in), chains interleaved.
-    first: the accumulators start as the minimum of three inputs each.  last: the final four inputs and the four accumulators fold
-    into %0."""
-    out, i = [], 0
-    if first:
-        out += ["v_min3_u32 %%%d, %%%d, %%%d, %%%d" % (c, 4 + c, 8 + c, 12 + c) for c in range(4)]
-        i = 12
-    body = n_in - (4 if last else 0)
-    while i < body:
-        out += ["v_min3_u32 %%%d, %%%d, %%%d, %%%d" % (c, c, 4 + i + c, 8 + i + c) for c in range(4)]
-        i += 8
-    assert i == body
-    if last:
-        out += ["v_min3_u32 %%0, %%0, %%%d, %%%d" % (4 + i, 5 + i), "v_min3_u32 %%1, %%1, %%%d, %%%d" % (6 + i, 7 + i),
-                "v_min3_u32 %0, %0, %2, %3", "v_min_u32 %0, %0, %1"]
+def min8(dst, ins):
+    """The four instructions that leave the unsigned minimum of the eight operands `ins` in `dst`."""
+    return ["v_min3_u32 %%%d, %%%d, %%%d, %%%d" % (dst, ins[0], ins[1], ins[2]), "v_min3_u32 %%%d, %%%d, %%%d, %%%d" % (dst, dst, ins[3], ins[4]),
+            "v_min3_u32 %%%d, %%%d, %%%d, %%%d" % (dst, dst, ins[5], ins[6]), "v_min_u32 %%%d, %%%d, %%%d" % (dst, dst, ins[7])]
+
+
+def interleave(chains):
+    return [ins for rank in zip(*chains) for ins in rank]
+
+
+def hit(word, m, x, first=False):
+    """word = 2 word + (x == m): the compare -> v_addc pattern of the decision words (first: the word starts as the bit itself)."""
+    return ["v_cmp_eq_u32 vcc, %%%d, %%%d" % (m, x),
+            "v_cndmask_b32 %%%d, 0, 1, vcc" % word if first else "v_addc_co_u32 %%%d, vcc, %%%d, %%%d, vcc" % (word, word, word)]
+
+
+def col_block(n):
+    """%0..%(n-1) (=&v) the minima of n columns, %n.. the eight high dwords of each column in turn; the n chains interleaved."""
+    return "\\n\\t".join(interleave([min8(c, [n + 8 * c + k for k in range(8)]) for c in range(n)]))
+
+
+def col_last_block():
+    """%0 %1 (=&v) the minima of columns 6 and 7, %2 (=&v) m = the minimum of the eight column minima, %3 (=&v) the hit word, %4..%9 the
+    minima of columns 0..5, %10.. the high dwords of columns 6 and 7.  Two of m's four instructions need columns 0..5 only and run
+    between the two chains.  Then the column hits, column 7 first: column i ends at bit i of the word (at bit 8 + i once the eight
+    row hits have been shifted in behind them)."""
+    c6, c7 = min8(0, list(range(10, 18))), min8(1, list(range(18, 26)))
+    fold = ["v_min3_u32 %2, %4, %5, %6", "v_min3_u32 %3, %7, %8, %9"]
+    out = c6[:1] + c7[:1] + fold[:1] + c6[1:2] + c7[1:2] + fold[1:] + c6[2:3] + c7[2:3] + c6[3:] + c7[3:]
+    out += ["v_min3_u32 %2, %2, %3, %0", "v_min_u32 %2, %2, %1"]
+    for i in range(7, -1, -1):
+        out += hit(3, 2, (4 + i) if i < 6 else (i - 6), first=(i == 7))
     return "\\n\\t".join(out)
 
 
-def hit_block(n_pairs, first=False, last=False):
-    """%0 / %1 the hit words of states 0..31 / 32..63 (=&v if first, else +v), %m the minimum high dword, %(m+1).. the high dwords of
-    n_pairs pairs of states (s, s + 32), s ascending: word = 2 word + (high dword == minimum), the two words alternating so that a
-    v_addc never waits for the previous one of its own chain.  State s of a half ends at bit 31 - s of its word: the first hit is the
-    leading one.  first: the words start as the hit bit itself (v_cndmask_b32 0, 1), no zeroing.  m = 2, but for last, which has three
-    more outputs in front (m = 5): %2 = index of the first hit (v_ffbh_u32 returns -1 for an empty word: the unsigned minimum then takes
-    the other word's), %3 a temporary, %4 an SGPR pair = lanes with more than one hit."""
-    out, m = [], 5 if last else 2
-    for j in range(n_pairs):
-        for w in range(2):
-            out.append("v_cmp_eq_u32 vcc, %%%d, %%%d" % (m, m + 1 + 2 * j + w))
-            if first and j == 0:
-                out.append("v_cndmask_b32 %%%d, 0, 1, vcc" % w)
-            else:
-                out.append("v_addc_co_u32 %%%d, vcc, %%%d, %%%d, vcc" % (w, w, w))
+def row_block(n, last=False):
+    """%0 the hit word (+v), %1..%n row minima (=&v, temporaries), then m and the eight high dwords of each of n rows, the highest row
+    first: the n chains interleaved, each row compared with m and shifted into the word as the columns were -- row j ends at bit j.
+    last: two more outputs between the temporaries and m: the index 8 j + i of the hit (=&v; j = the lowest set bit of the word, i =
+    the lowest set bit above bit 7; the temporaries serve as scratch) and an SGPR pair = lanes whose word has not exactly two bits
+    set -- more than one hit row or more than one hit column, i.e. more than one hit state."""
+    m = n + 1 + (2 if last else 0)
+    out = interleave([min8(1 + r, [m + 1 + 8 * r + k for k in range(8)]) for r in range(n)])
+    for r in range(n):
+        out += hit(0, m, 1 + r)
     if last:
-        out += ["v_ffbh_u32 %2, %0", "v_ffbh_u32 %3, %1", "v_bcnt_u32_b32 %0, %0, 0", "v_add_u32 %3, 32, %3",
-                "v_bcnt_u32_b32 %0, %1, %0", "v_min_u32 %2, %2, %3", "v_cmp_lt_u32 %4, 1, %0"]
+        out += ["v_ffbl_b32 %3, %0", "v_lshrrev_b32 %1, 8, %0", "v_bcnt_u32_b32 %2, %0, 0", "v_ffbl_b32 %1, %1", "v_cmp_ne_u32 %4, 2, %2",
+                "v_lshl_or_b32 %3, %3, 3, %1"]
     return "\\n\\t".join(out)
 
 
@@ -83,9 +96,7 @@ print('#define CPX_MIN_BLOCK12 "%s"' % min_block(12))
 blocks = [list(range(63, 39, -1)), list(range(39, 15, -1)), list(range(15, -1, -1))]
 for i, b in enumerate(blocks):
     print('#define CPX_SCAN_BLOCK%d "%s"   // states %d .. %d' % (i, scan_block(b), b[0], b[-1]))
-print('#define CPX_HMIN_BLOCK0 "%s"   // 20 high dwords in' % hmin_block(20, first=True))
-print('#define CPX_HMIN_BLOCK1 "%s"   // 24 more' % hmin_block(24))
-print('#define CPX_HMIN_BLOCK2 "%s"   // the last 20; %%0 = the minimum' % hmin_block(20, last=True))
-print('#define CPX_HIT_BLOCK0 "%s"   // states 0 .. 11 | 32 .. 43' % hit_block(12, first=True))
-print('#define CPX_HIT_BLOCK1 "%s"   // states 12 .. 23 | 44 .. 55' % hit_block(12))
-print('#define CPX_HIT_BLOCK2 "%s"   // states 24 .. 31 | 56 .. 63, first hit, tie mask' % hit_block(8, last=True))
+print('#define CPX_COL_BLOCK3 "%s"   // three column minima' % col_block(3))
+print('#define CPX_COL_BLOCK_LAST "%s"   // columns 6 and 7, the minimum, the column hits' % col_last_block())
+print('#define CPX_ROW_BLOCK3 "%s"   // three rows: minima and hits' % row_block(3))
+print('#define CPX_ROW_BLOCK_LAST "%s"   // rows 1 and 0, the index, the tie mask' % row_block(2, last=True))

@@ -3,7 +3,10 @@
 
 The fused Viterbi kernel ('soft', 64 states, float64) finds the first-argmin state of a step on the upper 32 bits of the metrics and
 falls back to the float64 minimum tree + first-equal scan for a whole wave of 64 codewords when any of its lanes has two or more
-states whose high dword equals the minimum high dword (csrc/viterbi_cw.hip, cw_step).  This script measures that rate on the CPU, on
+states whose high dword equals the minimum high dword (csrc/viterbi_cw.hip, cw_step).  The kernel reads that condition off the minima
+of an 8 x 8 grid of the high dwords (state s = 8 j + i: more than one row minimum or more than one column minimum equals the overall
+minimum); the script counts the lanes where that flag and the hit count disagree, and where the grid's index is not the single hit
+(both 0 by construction).  This script measures that rate on the CPU, on
 the input of `bench.py --synth host`: the same messages, noise seeds, QPSK mapping and Eb/N0 (bench.synth_inputs' arithmetic), the
 reference's soft-demodulator formula and a NumPy float64 add-compare-select written after oracle/np_viterbi.py.
 
@@ -68,7 +71,7 @@ def main():
     T = L + 6 - 1
     pm = np.full((B, S), np.inf)
     pm[:, 0] = 0.0
-    cw_steps = cw_hi_tie = cw_f64_tie = cw_wrong = wave_steps = wave_fb = 0
+    cw_steps = cw_hi_tie = cw_f64_tie = cw_wrong = wave_steps = wave_fb = grid_flag_differs = grid_index_differs = 0
     per_wave_lanes = []
     for t in range(1, T + 1):
         r = x[:, 2 * (t - 1):2 * t] if t <= L else np.zeros((B, 2))
@@ -81,6 +84,10 @@ def main():
         hit = hi == hi.min(axis=1, keepdims=True)
         n_hit = hit.sum(axis=1)
         tie = n_hit >= 2
+        grid = (hi == hi.min(axis=1, keepdims=True)).reshape(B, 8, 8)      # row / column minimum == minimum <=> a hit in that row / column
+        rows, cols = grid.any(axis=2), grid.any(axis=1)
+        grid_flag_differs += int(((rows.sum(axis=1) + cols.sum(axis=1) != 2) != tie).sum())
+        grid_index_differs += int(((8 * rows.argmax(axis=1) + cols.argmax(axis=1) != hit.argmax(axis=1)) & ~tie).sum())
         cw_steps += B
         cw_hi_tie += int(tie.sum())
         cw_f64_tie += int(((pm == pm.min(axis=1, keepdims=True)).sum(axis=1) >= 2).sum())
@@ -95,6 +102,8 @@ def main():
     print("  >= 2 states share the minimum high dword                  %d  (%.3e)" % (cw_hi_tie, cw_hi_tie / cw_steps))
     print("  exact float64 tie of the minimum                          %d  (%.3e)" % (cw_f64_tie, cw_f64_tie / cw_steps))
     print("  first high-dword hit is NOT the first-argmin              %d  (%.3e)" % (cw_wrong, cw_wrong / cw_steps))
+    print("  row/column flag differs from (hits >= 2)                  %d" % grid_flag_differs)
+    print("  one hit, and 8 j* + i* is not that state                  %d" % grid_index_differs)
     print("wave-steps (64 consecutive codewords)                       %d" % wave_steps)
     print("  any lane ties on the high dword = the fallback runs       %d  (%.3e)" % (wave_fb, wave_fb / wave_steps))
     print("  tying lanes per falling-back wave-step: mean %.2f, max %d" % (lanes[lanes > 0].mean() if wave_fb else 0.0, lanes.max()))

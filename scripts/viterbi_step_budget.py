@@ -4,8 +4,8 @@
     python scripts/viterbi_step_budget.py [--kernel "viterbi_cw_fused_kernel<6, 109u, 79u, 1, 28, false, double, 32, true>"] [--md out.md]
 
 Disassembles commpy_amd/csrc/build/viterbi_cw.o (device part, gfx950), finds the kernel's step loop (the smallest backward branch that spans
-a whole trellis step), counts the steps of one trip of it by the 64 equality compares per step it contains (v_cmp_eq_u32 of the
-hit words; v_cmp_eq_f64 of the first-equal scan where the 32-bit first-argmin is not compiled in) and sorts every instruction of the
+a whole trellis step), counts the steps of one trip of it by the equality compares per step it contains (16 v_cmp_eq_u32, the row and
+column hits of the 32-bit first-argmin; 64 v_cmp_eq_f64 of the first-equal scan where that is not compiled in) and sorts every instruction of the
 loop body into the phases of cw_step (csrc/viterbi_cw.hip) by opcode -- the table of DESIGN.md 4.1.  The float64 minimum tree and
 first-equal scan that 'soft' keeps as the fallback of the 32-bit first-argmin are compiled out of line, behind the loop (the branch
 to them is marked unlikely): the loop body counted here is what a step executes when no lane of the wave ties.
@@ -55,14 +55,15 @@ def kernel_body(dis, name):
     return out
 
 
-ARGMIN32 = "first-argmin on the high dwords: v_min3_u32 tree, v_cmp_eq_u32 + v_addc_co_u32 hit words, index, tie test"
+ARGMIN32 = "first-argmin on the high dwords: v_min3_u32 row and column minima, v_cmp_eq_u32 + v_addc_co_u32 hit word, index, tie test"
 
 
 def classify(op, args, prev=None):
     # (only in a kernel that has the 32-bit first-argmin compiled in, main(): elsewhere these opcodes belong to the traceback)
     if EQ[0] == "v_cmp_eq_u32" and (
-            op in ("v_min3_u32", "v_min_u32", "v_cmp_eq_u32", "v_ffbh_u32", "v_bcnt_u32_b32", "v_cmp_lt_u32") or
-            (prev == "v_cmp_eq_u32" and (op.startswith("v_addc_co") or op == "v_cndmask_b32"))):
+            op in ("v_min3_u32", "v_min_u32", "v_cmp_eq_u32", "v_ffbl_b32", "v_bcnt_u32_b32", "v_cmp_ne_u32") or
+            (prev == "v_cmp_eq_u32" and (op.startswith("v_addc_co") or op == "v_cndmask_b32")) or
+            (prev == "v_ffbl_b32" and op == "v_lshrrev_b32") or (prev == "v_cmp_ne_u32" and op == "v_lshl_or_b32")):
         return ARGMIN32
     if op in ("v_add_f64",):
         return "add-compare-select: v_add_f64 (path metric + branch metric)"
@@ -187,12 +188,12 @@ def chunk_table(body, addr, hot, general=None):
     return out
 
 
-EQ = ["v_cmp_eq_f64"]          # main(): "v_cmp_eq_u32" for a kernel that has the 32-bit first-argmin (its float64 scan is the cold fallback)
+EQ = ["v_cmp_eq_f64", 64]      # main(): "v_cmp_eq_u32", 16 per step, for a kernel that has the 32-bit first-argmin (its float64 scan is the cold fallback)
 
 
 def eq_compares(seg):
-    """Equality compares of the step's first-argmin in a stretch of code: 64 per trellis step."""
-    return sum(1 for _, o, _ in seg if o == EQ[0])
+    """Equality compares of the step's first-argmin in a stretch of code, in units of 64: EQ[1] of them per trellis step."""
+    return sum(1 for _, o, _ in seg if o == EQ[0]) * (64 // EQ[1])
 
 
 def main():
@@ -205,8 +206,8 @@ def main():
     if not body:
         sys.exit("kernel not found: " + a.kernel)
     addr = {ad: i for i, (ad, _, _) in enumerate(body)}
-    if sum(1 for _, o, _ in body if o == "v_cmp_eq_u32") >= 64:
-        EQ[0] = "v_cmp_eq_u32"
+    if sum(1 for _, o, _ in body if o == "v_cmp_eq_u32") >= 16 and any(o == "v_min3_u32" for _, o, _ in body):
+        EQ[:] = ["v_cmp_eq_u32", 16]
     # the step loop: of the backward branches whose span holds the most trellis steps (64 equality compares each), the SMALLEST span.
     # (The loop around it, which flushes the output tile every 96 steps, holds the same steps in a larger span; the out-of-line
     # fallback blocks of the 32-bit first-argmin sit behind the loop and branch back into it: their spans hold fewer steps.)
@@ -220,6 +221,11 @@ def main():
             j = addr.get(body[0][0] + int(m.group(1), 16))
             if j is not None and j < i and eq_compares(body[j:i + 1]) >= 64:
                 cands.append((-(eq_compares(body[j:i + 1]) // 64), i - j, j, i))
+    # (where the compiler lays the chunk loop out around both group loops, that span holds twice the steps: a trip of the step loop is
+    # one group of LGS steps, the kernel's first template argument)
+    lgs = re.search(r"<(\d+),", a.kernel)
+    group = [c for c in cands if lgs and -c[0] == int(lgs.group(1))]
+    cands = group or cands
     best = min(cands)[2:] if cands else None
     if best is None:
         sys.exit("no loop found")

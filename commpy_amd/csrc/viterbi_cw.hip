@@ -79,6 +79,13 @@ __device__ __forceinline__ double acs_min(unsigned &acc, double x, double y) {
         : "=&v"(r), "+v"(acc) : "v"(x), "v"(y) : "vcc");
     return r;
 }
+// the first decision of a word: acc = d, written outright (v_cndmask_b32 0, 1, vcc) -- no accumulator to clear every step
+__device__ __forceinline__ double acs_min_first(unsigned &acc, double x, double y) {
+    double r;
+    asm("v_cmp_lt_f64 vcc, %3, %2\n\tv_cndmask_b32 %1, 0, 1, vcc\n\tv_min_f64 %0, %2, %3"
+        : "=&v"(r), "=&v"(acc) : "v"(x), "v"(y) : "vcc");
+    return r;
+}
 
 __device__ __forceinline__ double acs_select(unsigned &acc, double x, double y) {
     int rlo, rhi;
@@ -172,7 +179,7 @@ struct NoHook {
 };
 
 // `hook.at<P>()` is called at four fixed points of the step (after the branch metrics, after each half of the butterflies,
-// after the minimum tree): the fused kernel slots the traceback of the previous step in there.
+// after the minimum tree): the fused kernel issues the traceback reads of the previous step there.
 // G0 = G1 = 0: TABLE-DRIVEN codes -- any shift-register code whose two generators both tap the input bit and the oldest register bit
 // (every rate-1/2 code of full constraint length).  The four branches of butterfly j then carry the codes c_j, c_j ^ 3, c_j ^ 3, c_j,
 // so one 2-bit number per butterfly describes the code; it arrives packed in scalar registers (goff) and selects the branch metric by
@@ -222,6 +229,9 @@ __device__ __forceinline__ void cw_step(double (&pm)[1 << LGS], double r0, doubl
         if (TYPE == CPX_VIT_UNQUANTIZED) {
             pm[x] = acs_select(da, a0, a1);                        // state j     now lives in register rotl(j, R+1) = x
             pm[y] = acs_select(db, b0, b1);                        // state j+S/2 now lives in register y
+        } else if (j == 0) {                                       // (j is a constant once the loop is unrolled)
+            pm[x] = acs_min_first(da, a0, a1);
+            pm[y] = acs_min_first(db, b0, b1);
         } else {
             pm[x] = acs_min(da, a0, a1);
             pm[y] = acs_min(db, b0, b1);
@@ -591,7 +601,7 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_acs_kernel(CwParams
 // leave the CU: every wave keeps the last 32 words of its 64 codewords in an LDS ring [slot][lane] (conflict-free, each
 // lane reads only its own column) and, right after the add-compare-select of step t, walks the H hops back from the
 // step's first-argmin state -- 2 VALU instructions per hop (tb_hop), LDS addresses that do not depend on the states, the
-// whole walk straight-line code that the scheduler interleaves with the next step's arithmetic.  The ring is stored
+// whole walk straight-line code whose LDS reads are spread over the next step's arithmetic (WalkHook).  The ring is stored
 // twice, 32 slots apart, so that the H + 1 words of a walk sit at constant offsets below one base address.  The decoded
 // bit of step t - H goes to a staging tile in LDS and the tile is written out every 96 steps, one coalesced 64-byte
 // store per codeword and half-tile.  HBM traffic is the algorithmic one again (the two-kernel path moves 9 B per
@@ -611,53 +621,79 @@ constexpr size_t fused_wave_lds() {
     return (size_t)fused_slots<RING, MIR>() * 64 * 8 + (size_t)64 * FR_OBPAD;   // (GEN: rounds 3 / 4 kept an LDS table of 4 KB here)
 }
 
-// The traceback walk of one step, cut into four batches of hops that cw_step's hook runs between the phases of the NEXT
-// step: the LDS reads of a batch are issued one phase before their hops, so their latency hides behind the
-// add-compare-select arithmetic (left to itself the compiler emits the walk as 14 read -> wait -> 2-hop rounds at the end
-// of the step: +0.5 ms).  sched_barrier pins the batches where they are put.
-// RT: the number of hops is a run-time value hr <= H (traceback depths below the default): hops h >= hr leave the state alone
-// (one v_cndmask each, +4 % per step); their LDS reads still go to valid, older ring slots.
-template <int LGS, int H, bool RT = false, int RING = FR_RING, bool MIR = true>
+// The traceback walk of one step.  Its LDS reads are cut into four batches that cw_step's hook ISSUES between the phases of the NEXT
+// step, so their latency hides behind the add-compare-select arithmetic (left to itself the compiler emits the walk as 14 read ->
+// wait -> 2-hop rounds at the end of the step: +0.5 ms); sched_barrier pins the batches where they are put.  In the LATE form (below) the
+// hops all run in finish(), behind ONE wait for the LDS counter: the youngest read was issued before the row part of the first-argmin, the
+// others hundreds of instructions earlier, and with one wave per SIMD every counted wait in front of a pair of hops is an issue slot of
+// its own even when it never waits (the compiler counted the reads down one by one: 13 waits per step).  The wait is the builtin, not an
+// asm statement, so that the compiler's own wait insertion knows the counter is zero behind it and adds nothing; it names the LDS
+// counter only (vmcnt and expcnt at their maxima): the next group's LLR prefetch stays in flight.
+//
+// WHICH HOPS A WALK NEEDS.  The state of a walk is never masked (tb_hop): after n hops its bit k is the bit shifted in at hop n - k
+// (k < n) or bit k - n of the start state.  The output of a walk of H hops, bit LGS - 1 of its final state, is therefore bit sh of the
+// state after he hops, he = max(H - (LGS - 1), 0), sh = LGS - 1 - min(H, LGS - 1) (tests/test_viterbi_walk_stop.py): the last LGS - 1
+// hops and the ring words they read cannot change it.
+//  * compile-time hop count (!RT): all H hops stand in the source and the compiler's dead-code elimination removes the last LGS - 1
+//    and their reads by itself (23 of the 28 hops of the K = 7 default depth are in the code object) -- nothing to "add back".
+//  * RT: the number of hops is a run-time value (traceback depths below the flavour's own), every compiled hop slot runs and slots
+//    h >= he leave the state alone (one v_cndmask each; their LDS reads still go to valid, older ring slots).  The select hides the
+//    identity from the compiler, so it is spelled out: only NH = H - (LGS - 1) slots are compiled and loaded, he and sh come from the
+//    caller as wave-uniform values.
+constexpr int WAIT_LGKM0 = 0xC07F;          // s_waitcnt simm16 (gfx9): vmcnt 63 (bits 15:14, 3:0), expcnt 7 (6:4), lgkmcnt 0 (11:8)
+//
+// LATE selects the single-wait form.  It is on exactly where the step has the tie branch of the 32-bit first-argmin ('soft', 64 states,
+// float64, compiled-in generators): there the compiler sinks the hops behind the branch's join whatever the source says, so all NH words
+// are live until finish() anyway and the single wait costs no register.  Every other flavour has no such branch; its hops really run
+// between the phases, batch P - 1 at hook P and the last batch in finish(), with PER words live at a time -- holding all NH words to the
+// end of the step there cost up to 32 AGPRs and the first VGPR spills (experiments/README.md), so those flavours keep the batched hops.
+template <int LGS, int H, bool RT = false, int RING = FR_RING, bool MIR = true, bool LATE = false>
 struct WalkHook {
-    static constexpr int NB = 4, PER = (H + NB - 1) / NB;
+    static constexpr int NH = RT ? (H > LGS - 1 ? H - (LGS - 1) : 0) : H;   // compiled hop slots
+    static constexpr int NB = 4, PER = (NH + NB - 1) / NB;
     // MIR: ring pointer of the walked step t': word of step t' - h at pw[(RING - h) * 64].  Not mirrored: pw = this lane's
     // column, q = ring slot of step t' (wave-uniform), word of step t' - h at pw[((q - h) mod RING) * 64].
     const unsigned long long *pw;
     int q;
     mutable unsigned st;                    // state of the walk
-    int hr;                                 // hops to execute (RT only)
-    mutable unsigned long long buf[PER];
+    int he, sh;                             // RT: hops to execute, bit of the state to take after them (!RT: H, LGS - 1)
+    mutable unsigned long long buf[LATE ? (NH > 0 ? NH : 1) : (PER > 0 ? PER : 1)];   // LATE: word h in buf[h]; else batch B, word i in buf[i]
     __device__ __forceinline__ unsigned long long word(int h) const {
         return MIR ? pw[(RING - h) * 64] : pw[((q - h) & (RING - 1)) * 64];
     }
-    template <int B> __device__ __forceinline__ void issue() const {
+    template <int B> __device__ __forceinline__ void issue() const {       // the reads of batch B
 #pragma unroll
         for (int i = 0; i < PER; i++)
-            if (B * PER + i < H) buf[i] = word(B * PER + i);
+            if (B * PER + i < NH) buf[LATE ? B * PER + i : i] = word(B * PER + i);
     }
-    template <int B> __device__ __forceinline__ void hops() const {
+    template <int B> __device__ __forceinline__ void hops() const {        // the hops of batch B
 #pragma unroll
         for (int i = 0; i < PER; i++)
-            if (B * PER + i < H) {
-                const unsigned nx = tb_hop<LGS>(buf[i], st);
-                st = (!RT || B * PER + i < hr) ? nx : st;
+            if (B * PER + i < NH) {
+                const unsigned nx = tb_hop<LGS>(buf[LATE ? B * PER + i : i], st);
+                st = (!RT || B * PER + i < he) ? nx : st;
             }
     }
     template <int P> __device__ __forceinline__ void at() const {
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (P == 0) {
-            issue<0>();
-        } else {
-            hops<P - 1>();
-            issue<P>();
-        }
+        if constexpr (!LATE && P > 0) hops<P - 1>();
+        issue<P>();
         __builtin_amdgcn_sched_barrier(0);
     }
     __device__ __forceinline__ void finish() const {
         __builtin_amdgcn_sched_barrier(0);
-        hops<NB - 1>();
+        if constexpr (LATE) {
+            if constexpr (NH > 0) {
+                __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
+                asm volatile("" : "+v"(st));    // every hop reads st: none of them is moved above the wait (the hops are pure arithmetic)
+            }
+            hops<0>(); hops<1>(); hops<2>(); hops<3>();
+        } else {
+            hops<NB - 1>();
+        }
         __builtin_amdgcn_sched_barrier(0);
     }
+    __device__ __forceinline__ unsigned bit() const { return (st >> (RT ? sh : LGS - 1)) & 1u; }   // the walk's output
 };
 
 template <int LGS, unsigned G0, unsigned G1, int TYPE, int HT, bool RT = false, class F = double, int RING = FR_RING, bool MIR = true>
@@ -705,11 +741,13 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
     for (int u = 0; u < LGS; u++) cur[u] = load(1 + u);
     int best_T = 0;                                                               // first-argmin state of step T
     unsigned long long nanmask = 0;                                               // 'soft': lanes that received a NaN
-    WalkHook<LGS, HT, RT, RING, MIR> walk;                                             // walk of the previous step (step 0: a dummy)
+    constexpr bool LATE = LGS == 6 && TYPE == CPX_VIT_SOFT && !GEN && std::is_same<F, double>::value;   // cw_step's ARGMIN32 (WalkHook)
+    WalkHook<LGS, HT, RT, RING, MIR, LATE> walk;                                             // walk of the previous step (step 0: a dummy)
     walk.pw = mycol;
     walk.q = 0;
     walk.st = 0;
-    walk.hr = H;
+    walk.he = H > LGS - 1 ? H - (LGS - 1) : 0;                                     // (WalkHook: the hops the output bit can see)
+    walk.sh = H > LGS - 1 ? 0 : LGS - 1 - H;
 
     // writes the decoded bits staged in tile entries 0 .. n-1: entry li holds the result of the walk of step tc0 + li - 1,
     // i.e. output step so = tc0 + li - 1 - H, and is written when 1 <= so <= min(T - H, L).  Those bounds are wave-uniform, so the
@@ -787,9 +825,9 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
             unsigned long long word;
             int bst;
             if constexpr (TYPE == CPX_VIT_SOFT) nan_or(nanmask, cur[R].x, cur[R].y);   // (steps > tmax re-read step tmax)
-            cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, walk, nullptr, gidx);   // + hops 0 .. 3/4 H of the walk of step tt - 1
-            walk.finish();
-            tile[R] = (unsigned char)((walk.st >> (LGS - 1)) & 1u);           // input bit of the branch into the state at step tt - 1 - H
+            cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, walk, nullptr, gidx);   // + the four read batches of the walk of step tt - 1
+            walk.finish();                                                    // one wait, then all of its hops
+            tile[R] = (unsigned char)walk.bit();                              // input bit of the branch into the state at step tt - 1 - H
             // ring slot of step tt and (mirrored ring) its copy RING slots above; the (at most LGS - 1) steps > T of the last group
             // write to two dummy slots instead: the ring must keep the words of steps T-H+1 .. T for the final walk
             const bool live = FAST || tt <= T;

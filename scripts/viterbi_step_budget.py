@@ -67,7 +67,8 @@ def classify(op, args, prev=None):
         return ARGMIN32
     if op in ("v_add_f64",):
         return "add-compare-select: v_add_f64 (path metric + branch metric)"
-    if op == "v_cmp_lt_f64" or op.startswith("v_addc_co"):
+    # (the first decision of a word is written outright, v_cmp_lt_f64 -> v_cndmask_b32 0, 1, vcc: acs_min_first)
+    if op == "v_cmp_lt_f64" or op.startswith("v_addc_co") or (prev == "v_cmp_lt_f64" and op == "v_cndmask_b32"):
         return "add-compare-select: v_cmp_lt_f64 + v_addc_co_u32 (decision bit)"
     if op == "v_min_f64":
         return "v_min_f64 (64 survivor selects + 63 of the minimum tree)"

@@ -696,6 +696,55 @@ struct WalkHook {
     __device__ __forceinline__ unsigned bit() const { return (st >> (RT ? sh : LGS - 1)) & 1u; }   // the walk's output
 };
 
+// THE BURST FORM: the LGS walks of a group in one go (LATE flavours with a compile-time hop count on the mirrored ring).  The walk of
+// step s reads the words of steps s .. s - NHE + 1, the walk of step s + 1 all but one of them again: walked one per step, every ring word
+// is fetched NHE times.  Here steps R = 0 .. LGS - 2 of a group starting at step t run with no walk at all (NoHook: no ring read, no wait,
+// no hop, no tile byte) and step R = LGS - 1 carries the walks of steps t - 1 .. t + LGS - 2 -- the walk left pending by the previous
+// group and this group's first LGS - 1; the walk of step t + LGS - 1 stays pending, as one walk is pending in the other form.  Together
+// they name NW = NHE + LGS - 1 distinct words (28 for the K = 7 default depth, not 6 x 23), the word of step t + LGS - 2 - d at
+// pb[(RING - d) * 64], pb = the ring slot of step t + LGS - 2: adjacent slots, fetched in pairs, each word once per group, issued in four
+// batches at the hook points of that one step (newest words first: the hops need them first) and used by up to LGS walks from registers.
+// All hops run in finish() behind one wait, the LGS chains interleaved (they are independent).
+// Only the hops the output can see are written (NHE = H - (LGS - 1), output = bit 0 of the state: see above).
+// RING SAFETY.  When the burst reads, the newest slot written is that of step t + LGS - 2 (every LDS access of a wave is executed in
+// order) and the oldest word it needs is d = NW - 1, hop NHE - 1 of the pending walk.  The ring holds d = 0 .. RING - 1; the write of step
+// t + LGS - 1 comes after finish() and replaces d = RING - 1.  Hence NHE + LGS <= RING (asserted in the kernel; one slot to spare).
+// tests/test_viterbi_walk_burst.py models the schedule slot by slot, across the ring wrap and the chunk boundary.
+// RT (a traceback depth below the flavour's own): all NHE hop slots run and slots h >= he leave the state alone, as in WalkHook; their
+// reads go to the same NW slots.
+template <int LGS, int NHE, int RING, bool RT>
+struct WalkBurst {
+    static constexpr int NW = NHE + LGS - 1;                      // distinct words of the LGS walks
+    static constexpr int NB = 4, PER = 2 * ((NW + 2 * NB - 1) / (2 * NB));   // words per batch: even, so that a batch is whole pairs of slots
+    const unsigned long long *pb;           // ring slot (lower copy) of step t + LGS - 2
+    int he, sh;                             // RT: hops to execute, bit of the state to take after them (!RT: NHE, 0)
+    mutable unsigned st[LGS];               // st[k]: state of the walk of step t - 1 + k (before finish(): the step's first-argmin state)
+    mutable unsigned long long w[NW];       // w[d]: word of step t + LGS - 2 - d
+    template <int P> __device__ __forceinline__ void at() const {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < PER; i++)
+            if (P * PER + i < NW) w[P * PER + i] = pb[(RING - (P * PER + i)) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ void finish() const {
+        static_assert(LGS == 6, "the walk states are named one by one below");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
+        asm volatile("" : "+v"(st[0]), "+v"(st[1]), "+v"(st[2]), "+v"(st[3]), "+v"(st[4]), "+v"(st[5]));   // no hop moves above the wait (WalkHook)
+#pragma unroll
+        for (int h = 0; h < NHE; h++) {
+#pragma unroll
+            for (int k = 0; k < LGS; k++) {
+                const unsigned nx = tb_hop<LGS>(w[LGS - 1 - k + h], st[k]);
+                st[k] = (!RT || h < he) ? nx : st[k];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ unsigned bit(int k) const { return (st[k] >> (RT ? sh : 0)) & 1u; }   // the output of walk k (!RT: sh = 0 after NHE hops)
+};
+
 template <int LGS, unsigned G0, unsigned G1, int TYPE, int HT, bool RT = false, class F = double, int RING = FR_RING, bool MIR = true>
 __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwParams p) {
     constexpr int S = 1 << LGS, FR_GROUPS = FR_CHUNK / LGS, CHUNK = FR_GROUPS * LGS;
@@ -748,6 +797,17 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
     walk.st = 0;
     walk.he = H > LGS - 1 ? H - (LGS - 1) : 0;                                     // (WalkHook: the hops the output bit can see)
     walk.sh = H > LGS - 1 ? 0 : LGS - 1 - H;
+    // the burst form (WalkBurst): `walk` then only carries the pending walk (pw, st) to the end of the last chunk.  Deep64 and Lean32
+    // (rings stored once) and every flavour that is not LATE keep the walk per step.
+    constexpr bool BURST = LATE && MIR && HT > LGS - 1;
+    constexpr int NHE = BURST ? HT - (LGS - 1) : 1;                                 // hop slots: the hops the output can see
+    static_assert(!BURST || NHE + LGS <= RING, "ring too small for the words of LGS walks at once");
+    WalkBurst<LGS, NHE, RING, RT> burst;
+    burst.pb = mycol;
+    burst.he = walk.he;
+    burst.sh = walk.sh;
+#pragma unroll
+    for (int k = 0; k < LGS; k++) burst.st[k] = 0;                                 // st[0]: the pending walk (step 0: a dummy)
 
     // writes the decoded bits staged in tile entries 0 .. n-1: entry li holds the result of the walk of step tc0 + li - 1,
     // i.e. output step so = tc0 + li - 1 - H, and is written when 1 <= so <= min(T - H, L).  Those bounds are wave-uniform, so the
@@ -825,9 +885,19 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
             unsigned long long word;
             int bst;
             if constexpr (TYPE == CPX_VIT_SOFT) nan_or(nanmask, cur[R].x, cur[R].y);   // (steps > tmax re-read step tmax)
+            if constexpr (BURST && R == LGS - 1) {
+                burst.pb = mycol + ((tt - 1) & (RING - 1)) * 64;              // the slot of step t + LGS - 2, written by the step before
+                cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, burst, nullptr, gidx);   // + the read batches of the group's walks
+                burst.finish();                                               // one wait, then the hops of the walks of steps t - 1 .. t + LGS - 2
+#pragma unroll
+                for (int k = 0; k < LGS; k++) tile[k] = (unsigned char)burst.bit(k);   // entry k: the walk of step t - 1 + k
+            } else if constexpr (BURST) {
+                cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, NoHook(), nullptr, gidx);   // no walk in this step
+            } else {
             cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, walk, nullptr, gidx);   // + the four read batches of the walk of step tt - 1
             walk.finish();                                                    // one wait, then all of its hops
             tile[R] = (unsigned char)walk.bit();                              // input bit of the branch into the state at step tt - 1 - H
+            }
             // ring slot of step tt and (mirrored ring) its copy RING slots above; the (at most LGS - 1) steps > T of the last group
             // write to two dummy slots instead: the ring must keep the words of steps T-H+1 .. T for the final walk
             const bool live = FAST || tt <= T;
@@ -846,6 +916,7 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
             }
             if constexpr (!FAST) best_T = (tt == T) ? bst : best_T;
             walk.st = (unsigned)bst;
+            if constexpr (BURST) burst.st[(R + 1) % LGS] = (unsigned)bst;     // start state of this step's walk (R = LGS - 1: the pending one)
         };
         if constexpr (LGS >= 1) one(std::integral_constant<int, 0>{});
         if constexpr (LGS >= 2) one(std::integral_constant<int, 1 % LGS>{});

@@ -15,7 +15,8 @@ Two more tables:
   cw_step (WalkHook::at, sched_barrier), and a step ends with the byte it stores into the output tile, so the read batches cut a step
   into: LLR -> branch metrics | butterflies, first half | second half | minimum tree | first-equal scan and the step's tail.  The
   traceback's own instructions (hops, LDS, waits for LDS) are listed apart wherever they sit.  An opcode table cannot tell the
-  v_add_f64 of exp / log from those of the add-compare-select; this one can.
+  v_add_f64 of exp / log from those of the add-compare-select; this one can.  A kernel with the 32-bit first-argmin is cut at the
+  compares every step has instead (position_table): where a group's walks run in one burst, five steps of six have no reads.
 * the code of a 96-step chunk OUTSIDE the hot loop: the loop around it (chunk set-up, the pending walk of the last chunk) and, inside
   that, the rounds of the output flush (eight codewords each, eight rounds per flush), as static instruction counts."""
 import argparse
@@ -107,8 +108,19 @@ def position_table(loop, steps):
     (ds_read* more than 20 instructions after the previous one) starts the next phase."""
     cnt, tb = collections.Counter(), collections.Counter()
     phase, since, nsteps = 0, 10 ** 6, 0
+    # A kernel with the 32-bit first-argmin may walk a whole group's tracebacks in ONE of its steps (WalkBurst): five steps of six then
+    # have no read batch and no tile store to cut at.  Its steps are cut by what every step has, in the fixed order of cw_step's asm
+    # statements: the first v_cmp_lt_f64 opens the butterflies, the 33rd their second half, the 64th closes them; the 8th v_cmp_eq_u32
+    # (column hits) ends the minimum part and the 16th (row hits) the step -- the few instructions behind it (index, tie test, decision
+    # word, ring write) are counted with the next step's first phase, as the ring and tile addresses always were.
+    landmarks = EQ[0] == "v_cmp_eq_u32"
+    lt = eq = 0
     for _, op, args in loop:
-        if op.startswith("ds_read"):
+        if landmarks:
+            if op == "v_cmp_lt_f64":
+                lt += 1
+                phase = 1 if lt <= 32 else 2
+        elif op.startswith("ds_read"):
             if since > 20:
                 phase = min(phase + 1, len(PHASES) - 1)
             since = 0
@@ -118,9 +130,19 @@ def position_table(loop, steps):
             tb["traceback + tile: " + ("LDS" if op.startswith("ds_") else "s_waitcnt" if op.startswith("s_waitcnt") else "hops")] += 1
         else:
             cnt[phase] += 1
-        if op == "ds_write_b8":
+        if landmarks:
+            if op == "v_cmp_lt_f64" and lt == 64:
+                phase = 3
+            elif op == "v_cmp_eq_u32":
+                eq += 1
+                if eq == 8:
+                    phase = 4
+                elif eq == 16:
+                    phase, nsteps, lt, eq = 0, nsteps + 1, 0, 0
+        elif op == "ds_write_b8":
             phase, nsteps = 0, nsteps + 1
-    out = ["", "by position in the step (%d tile stores = steps found per trip):" % nsteps, "",
+    out = ["", "by position in the step (%d steps found per trip, cut at %s):" %
+           (nsteps, "the compares every step has" if landmarks else "the tile stores"), "",
            "| phase of cw_step, by position | instructions per trellis step |", "|---|---|"]
     for ph in range(len(PHASES)):
         out.append("| %s | %.1f |" % (PHASES[ph], cnt[ph] / steps))

@@ -75,7 +75,8 @@ constexpr unsigned TM_RW = 16; // codeword slots per row of turbo_decode's time-
 // (turbo.py:62-76, :110-111, :155-158).  Wherever every term of the reference stays a normal float64 the two agree to
 // rounding; where its terms underflow (symbol amplitudes of 5 - 20 at sigma^2 <= 0.1, priors of e^-200 meeting a contradicting
 // channel) the reference returns NaN / +-inf LLRs and these kernels would not.  So the fast kernels DETECT, conservatively,
-// every codeword for which that can happen and a literal absolute-scale kernel (bcjr_exact.hip) decodes those again:
+// every codeword for which that can happen and a literal absolute-scale kernel on the same wave-pair mapping (map_literal_kernel,
+// turbo_literal_kernel below) decodes those again:
 //   (A) a received pair whose worst branch probability is below e^-345:  (|r0| + 1)^2 + (|r1| + 1)^2 > 345 * 2 sigma^2
 //       (also true for NaN / inf);
 //   (C) a normalisation sum of alpha or beta below 1e-150 (or NaN): up to KNORM steps lost 150 decades;
@@ -845,14 +846,18 @@ struct MapParams {
     int want_bits, GW;
 };
 
+// The wave pair a wavefront belongs to: wave-uniform by construction; readfirstlane tells the compiler, so that everything derived
+// from it (the pair's base pointers, codeword counts) lives in SGPRs and the loads take the `saddr + 32-bit voffset` form
+__device__ __forceinline__ int64_t pair_index() {
+    return (int64_t)blockIdx.x * (blockDim.x >> 7) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 7));
+}
+
 template <int LGS, bool SR>
 __global__ __launch_bounds__(128 * NPAIR) void map_decode_kernel(MapParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     Ctx<LGS> c;
     init_ctx<LGS>(c, p.tb, smem, p.GW);
-    // wave-uniform by construction; readfirstlane tells the compiler, so that everything derived from it (the pair's base
-    // pointers, codeword counts) lives in SGPRs and the loads take the `saddr + 32-bit voffset` form
-    const int64_t pair = (int64_t)blockIdx.x * (blockDim.x >> 7) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 7));
+    const int64_t pair = pair_index();
     const int64_t K = (p.N + CH - 1) / CH;
     const int64_t cw0 = pair * p.GW, o0 = cw0 * p.N;
     const int64_t left = p.B - cw0;
@@ -872,8 +877,8 @@ __global__ __launch_bounds__(128 * NPAIR) void map_decode_kernel(MapParams p) {
 }
 
 // ---- the LITERAL wave-parallel kernel: the redo path behind map_decode_kernel (round 5) ------------------------------------------
-// Round 3's redo path (bcjr_exact.hip, one codeword per LANE, state vectors in HBM scratch) is literal but serial: 7 ms per flagged
-// codeword, 28 ms when flag (A) sends a whole batch there -- which it does above Es/N0 ~ 14 dB (sigma^2 = 0.01: 0.35 -> 28 ms, a silent
+// Round 3's redo path (bcjr_exact.hip, one codeword per LANE, today only for > 16 states) was literal but serial: 7 ms per flagged
+// codeword, 28 ms when flag (A) sent a whole batch there -- which it does above Es/N0 ~ 14 dB (sigma^2 = 0.01: 0.35 -> 28 ms, a silent
 // 80 x cliff).  This is the same reference arithmetic -- absolute gamma, priors 1 / (1 + e^L) and 1 - p0, (metric * gamma) * prior
 // summed over the two branches, every column divided by its NumPy-ordered sum at every step, app sums in state order, L_int +
 // log(app1 / app0) -- on the wave-pair mapping of map_decode_kernel: one state per lane, forward and reverse wave, checkpoints, the
@@ -886,7 +891,7 @@ __global__ __launch_bounds__(128 * NPAIR) void map_decode_kernel(MapParams p) {
 template <int LGS, bool SR>
 __global__ __launch_bounds__(128 * NPAIR) void map_literal_kernel(MapParams p, RedoCounter redo) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int64_t pair = (int64_t)blockIdx.x * (blockDim.x >> 7) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 7));
+    const int64_t pair = pair_index();
     const int64_t cw0 = pair * p.GW, left = p.B - cw0;
     const int ncw = (int)(left < p.GW ? left : p.GW);
     const int lane = threadIdx.x & 63;
@@ -964,7 +969,7 @@ __global__ __launch_bounds__(128 * NPAIR) void turbo_pass_kernel(TurboParams p, 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     Ctx<LGS> c;
     init_ctx<LGS>(c, p.tb, smem, p.GW);
-    const int64_t pair = (int64_t)blockIdx.x * (blockDim.x >> 7) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 7));
+    const int64_t pair = pair_index();
     const int64_t N = p.N, K = (N + CH - 1) / CH, cw0 = pair * p.GW;
     const int64_t left = p.B - cw0;
     PassIO io;
@@ -1070,7 +1075,7 @@ __global__ __launch_bounds__(FT) void turbo_final_kernel(TurboParams p, int ntil
 }
 
 // ---- turbo_decode, the LITERAL redo (round 5): flagged pairs decode their codewords again, all iterations, in ONE launch -----------
-// Round 3's redo (bcjr_exact.hip turbo_exact_kernel, one codeword per lane) costs 2 x iterations x 7 ms for ANY number of flagged
+// Round 3's redo (bcjr_exact.hip turbo_exact_kernel, one codeword per lane) cost 2 x iterations x 7 ms for ANY number of flagged
 // codewords.  A pair's codewords are independent of every other pair's, so here a flagged pair runs the reference's whole loop
 // (turbo.py:300-331) by itself: map_pass<LIT> for MAP 1 and MAP 2 -- the literal wave-parallel pass of map_literal_kernel -- and
 // between them, elementwise in the pair's own rows of the slab (the fast sequence is done with them), what the reference writes:
@@ -1182,6 +1187,70 @@ int fill_tables(const cpx_trellis *t, MapTables &tb) {
     return CPX_OK;
 }
 
+// The kernel variants, one row each: (LGS, SR) = (log2 of the state count, 4-state shift-register fast path).  Calls f with the row
+// of `tb` as compile-time constants and returns true; false, and no call, for a state count that has no row.
+template <int LGS> using lgs_c = std::integral_constant<int, LGS>;
+template <class F>
+bool with_variant(const MapTables &tb, F &&f) {
+    switch (tb.lgS) {
+        case 1: f(lgs_c<1>{}, std::false_type{}); return true;
+        case 2: tb.sr4 ? f(lgs_c<2>{}, std::true_type{}) : f(lgs_c<2>{}, std::false_type{}); return true;
+        case 3: f(lgs_c<3>{}, std::false_type{}); return true;
+        case 4: f(lgs_c<4>{}, std::false_type{}); return true;
+        default: return false;
+    }
+}
+// ... and a run-time flag as a std::bool_constant ("fp32-fast": the float32 slab of the turbo kernels)
+template <class F>
+void with_bool(bool b, F &&f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// dynamic LDS of a workgroup of np wave pairs
+template <int LGS>
+size_t pass_lds(int np, int GW) { return sizeof(double) * 2 * np * wave_lds_doubles<LGS>(GW); }
+
+// The launch geometry and the per-call buffers of the wave-pair kernels, the same for map_decode and turbo_decode
+struct PassSetup {
+    bool done;                     // nothing left to launch: an empty batch, or a trellis above 16 states that bcjr_exact.hip has served
+    MapTables tb;
+    hipStream_t st;
+    int GW, np;                    // codewords per wave pair, wave pairs per workgroup
+    int64_t npairs, nblocks, K;    // K: chunks per block
+    dim3 grid, block;
+    double *ckpt;                  // Slot::state: checkpoint rows [nblocks * np][K + 1][64]
+    uint8_t *flags;                // Slot::redo_flags: "detect and redo", one byte per codeword, zeroed on the stream
+};
+
+// The checks both entry points make, in the order a caller sees them, then the geometry and the buffers.  what: "map" / "turbo";
+// blocks of 2^lgN steps or more are refused (31-bit lane offsets `offsets`); exact(stream): the entry point's own call of
+// bcjr_exact.hip, the only path for trellises above 16 states (the literal absolute-scale kernel alone).
+template <class Exact>
+int pass_setup(PassSetup &ps, const char *what, int lgN, const char *offsets, const cpx_trellis *t, int64_t B, int64_t N, int n_iter,
+               Scratch &sc, void *stream, Exact &&exact) {
+    ps.done = true;
+    int rc = fill_tables(t, ps.tb);
+    if (rc) return rc;
+    CPX_REQUIRE(B >= 0 && N >= 0 && n_iter >= 0, CPX_EINVAL, "%s_decode: negative size", what);
+    CPX_REQUIRE(N < (1ll << lgN), CPX_ELIMIT, "%s_decode: blocks of 2^%d steps or more are not supported (31-bit lane offsets %s)", what, lgN, offsets);
+    if (B == 0 || N == 0) return CPX_OK;
+    ps.st = pick_stream(stream);
+    if (t->S > 16) {
+        rc = exact(ps.st);
+        if (rc == CPX_OK) note_kernel("%s_exact_kernel (%d states, one codeword per lane)", what, t->S);
+        return rc;
+    }
+    CPX_REQUIRE(with_variant(ps.tb, [](auto, auto) {}), CPX_ELIMIT, "%s_decode: unsupported state count", what);
+    ps.GW = pick_gw(t->S, B); ps.npairs = (B + ps.GW - 1) / ps.GW;
+    ps.np = pick_npair(ps.npairs); ps.nblocks = (ps.npairs + ps.np - 1) / ps.np;
+    ps.K = (N + CH - 1) / CH; ps.grid = dim3((unsigned)ps.nblocks); ps.block = dim3(128 * ps.np);
+    CPX_REQUIRE(ps.nblocks < (1ll << 31), CPX_ELIMIT, "%s_decode: batch too large", what);
+    if ((rc = sc.get(ps.st, Slot::state, sizeof(double) * (size_t)(ps.nblocks * ps.np * (ps.K + 1) * 64), &ps.ckpt))) return rc;
+    // set by the fast kernels, consumed by the entry point's literal redo launch
+    if ((rc = sc.get(ps.st, Slot::redo_flags, (size_t)B, &ps.flags))) return rc;
+    CPX_HIP(hipMemsetAsync(ps.flags, 0, (size_t)B, ps.st));
+    ps.done = false;
+    return CPX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1191,58 +1260,28 @@ int cpx_map_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const do
                              uint8_t *d_bits, void *stream) {
     CPX_TRACE("cpx_map_decode_batch_dev");
     Scratch sc;
+    PassSetup ps;
+    int rc = pass_setup(ps, "map", 24, "over 16 codewords", t, B, N, 0, sc, stream, [&](hipStream_t st) {
+        return bcjr_exact_map(t, d_sys, d_par, d_L_int, B, N, 2 * noise_variance, want_bits, d_L_ext, d_bits, sc, st);
+    });
+    if (rc || ps.done) return rc;
     MapParams p;
-    int rc = fill_tables(t, p.tb);
-    if (rc) return rc;
-    CPX_REQUIRE(B >= 0 && N >= 0, CPX_EINVAL, "map_decode: negative size");
-    CPX_REQUIRE(N < (1ll << 24), CPX_ELIMIT, "map_decode: blocks of 2^24 steps or more are not supported (31-bit lane offsets over 16 codewords)");
-    if (B == 0 || N == 0) return CPX_OK;
-    hipStream_t st = pick_stream(stream);
-    if (t->S > 16) {                                              // beyond the wave-pair kernels: the literal absolute-scale kernel alone
-        rc = bcjr_exact_map(t, d_sys, d_par, d_L_int, B, N, 2 * noise_variance, want_bits, d_L_ext, d_bits, nullptr, sc, st);
-        if (rc == CPX_OK) note_kernel("map_exact_kernel<true> (%d states, one codeword per lane)", t->S);
-        return rc;
-    }
-    const int GW = pick_gw(t->S, B);
-    const int64_t npairs = (B + GW - 1) / GW;
-    const int np = pick_npair(npairs);
-    const int64_t nblocks = (npairs + np - 1) / np, K = (N + CH - 1) / CH;
-    p.GW = GW;
+    p.tb = ps.tb; p.GW = ps.GW; p.scratch = ps.ckpt; p.flags = ps.flags;
     p.sys = d_sys; p.par = d_par; p.Lin = d_L_int; p.Lout = d_L_ext; p.bits = d_bits;
     p.B = B; p.N = N; p.nv2 = 2 * noise_variance; p.want_bits = want_bits;
-    CPX_REQUIRE(nblocks < (1ll << 31), CPX_ELIMIT, "map_decode: batch too large");
-    if ((rc = sc.get(st, Slot::state, sizeof(double) * (size_t)(nblocks * np * (K + 1) * 64), &p.scratch))) return rc;
-    // "detect and redo": one flag byte per codeword (Slot::redo_flags), zeroed here, set by the kernel, consumed by the
-    // absolute-scale redo launch below; blocks too long for that path's scratch are decoded by the fast kernel alone
-    // (round 5: the redo launch is the wave-parallel literal kernel below, which needs no per-lane scratch: no block-length limit)
-    if ((rc = sc.get(st, Slot::redo_flags, (size_t)B, &p.flags))) return rc;
-    CPX_HIP(hipMemsetAsync(p.flags, 0, (size_t)B, st));
-    dim3 grid((unsigned)nblocks), block(128 * np);
-    switch (p.tb.lgS) {
-#define CASE(LG) case LG: hipLaunchKernelGGL((map_decode_kernel<LG, false>), grid, block, sizeof(double) * 2 * np * wave_lds_doubles<LG>(GW), st, p); break;
-        case 2:                                                   // 4 states: the shift-register fast path where it applies
-            if (p.tb.sr4) hipLaunchKernelGGL((map_decode_kernel<2, true>), grid, block, sizeof(double) * 2 * np * wave_lds_doubles<2>(GW), st, p);
-            else hipLaunchKernelGGL((map_decode_kernel<2, false>), grid, block, sizeof(double) * 2 * np * wave_lds_doubles<2>(GW), st, p);
-            break;
-        CASE(1) CASE(3) CASE(4)
-#undef CASE
-        default: set_error("map_decode: unsupported state count"); return CPX_ELIMIT;
-    }
+    with_variant(p.tb, [&](auto lg, auto sr) {
+        constexpr int LG = decltype(lg)::value;
+        hipLaunchKernelGGL((map_decode_kernel<LG, decltype(sr)::value>), ps.grid, ps.block, pass_lds<LG>(ps.np, ps.GW), ps.st, p);
+    });
     CPX_HIP(hipGetLastError());
     // redo: pairs with a flagged codeword, literally (map_literal_kernel), same launch geometry
-    const RedoCounter redo = redo_counter(sc, st);
-    switch (p.tb.lgS) {
-#define CASE(LG) case LG: hipLaunchKernelGGL((map_literal_kernel<LG, false>), grid, block, sizeof(double) * 2 * np * wave_lds_doubles<LG>(GW), st, p, redo); break;
-        case 2:
-            if (p.tb.sr4) hipLaunchKernelGGL((map_literal_kernel<2, true>), grid, block, sizeof(double) * 2 * np * wave_lds_doubles<2>(GW), st, p, redo);
-            else hipLaunchKernelGGL((map_literal_kernel<2, false>), grid, block, sizeof(double) * 2 * np * wave_lds_doubles<2>(GW), st, p, redo);
-            break;
-        CASE(1) CASE(3) CASE(4)
-#undef CASE
-        default: break;
-    }
+    const RedoCounter redo = redo_counter(sc, ps.st);
+    with_variant(p.tb, [&](auto lg, auto sr) {
+        constexpr int LG = decltype(lg)::value;
+        hipLaunchKernelGGL((map_literal_kernel<LG, decltype(sr)::value>), ps.grid, ps.block, pass_lds<LG>(ps.np, ps.GW), ps.st, p, redo);
+    });
     CPX_HIP(hipGetLastError());
-    note_kernel("map_decode_kernel<%d,%s> (%d wave pairs per workgroup, %d codewords per pair) + map_literal_kernel", p.tb.lgS, (p.tb.lgS == 2 && p.tb.sr4) ? "true" : "false", np, GW);
+    note_kernel("map_decode_kernel<%d,%s> (%d wave pairs per workgroup, %d codewords per pair) + map_literal_kernel", p.tb.lgS, (p.tb.lgS == 2 && p.tb.sr4) ? "true" : "false", ps.np, ps.GW);
     note_redo((long long)B, "codewords flagged (their pairs decoded literally)");
     return CPX_OK;
 }
@@ -1252,113 +1291,73 @@ int cpx_turbo_decode_batch_dev(const cpx_trellis *t, const double *d_sys, const 
                                double noise_variance, int n_iter, uint8_t *d_bits, void *stream) {
     CPX_TRACE("cpx_turbo_decode_batch_dev");
     Scratch sc;
+    PassSetup ps;
+    int rc = pass_setup(ps, "turbo", 21, "into a 16-codeword slab", t, B, N, n_iter, sc, stream, [&](hipStream_t st) {
+        return bcjr_exact_turbo(t, d_sys, d_p1, d_p2, d_L_int_or_null, d_perm, B, N, 2 * noise_variance, n_iter, d_bits, sc, st);
+    });
+    if (rc || ps.done) return rc;
+    const hipStream_t st = ps.st;
     TurboParams p;
-    int rc = fill_tables(t, p.tb);
-    if (rc) return rc;
-    CPX_REQUIRE(B >= 0 && N >= 0 && n_iter >= 0, CPX_EINVAL, "turbo_decode: negative size");
-    CPX_REQUIRE(N < (1ll << 21), CPX_ELIMIT, "turbo_decode: blocks of 2^21 steps or more are not supported (31-bit lane offsets into a 16-codeword slab)");
-    if (B == 0 || N == 0) return CPX_OK;
-    hipStream_t st = pick_stream(stream);
-    if (t->S > 16) {                                              // see cpx_map_decode_batch_dev
-        rc = bcjr_exact_turbo(t, d_sys, d_p1, d_p2, d_L_int_or_null, d_perm, B, N, 2 * noise_variance, n_iter, d_bits, nullptr, sc, st);
-        if (rc == CPX_OK) note_kernel("turbo_exact_kernel<true> (%d states, one codeword per lane)", t->S);
-        return rc;
-    }
-    const int GW = pick_gw(t->S, B);
-    const int64_t npairs = (B + GW - 1) / GW;
-    const int np = pick_npair(npairs);
-    const int64_t nblocks = (npairs + np - 1) / np, K = (N + CH - 1) / CH;
-    p.GW = GW;
+    p.tb = ps.tb; p.GW = ps.GW; p.ckpt = ps.ckpt; p.flags = ps.flags;
     p.sys = d_sys; p.p1 = d_p1; p.p2 = d_p2; p.Lint = d_L_int_or_null; p.perm = d_perm; p.bits = d_bits;
     p.B = B; p.N = N; p.nv2 = 2 * noise_variance; p.n_iter = n_iter;
-    CPX_REQUIRE(nblocks < (1ll << 31), CPX_ELIMIT, "turbo_decode: batch too large");
-    if ((rc = sc.get(st, Slot::state, sizeof(double) * (size_t)(nblocks * np * (K + 1) * 64), &p.ckpt))) return rc;
     // the time-major slab (TurboParams): five arrays of N rows of 16 slots per row group; sized in float64 whatever the precision
     // mode (the literal redo kernel reuses a pair's share as float64 scratch)
     const int RW = (int)TM_RW;
-    p.RW = RW;
-    p.lgG = 0;
-    while ((GW << p.lgG) < RW) p.lgG++;
-    const int64_t ngroups = (npairs + (1 << p.lgG) - 1) >> p.lgG;
+    p.RW = RW; p.lgG = 0;
+    while ((p.GW << p.lgG) < RW) p.lgG++;
+    const int64_t ngroups = (ps.npairs + (1 << p.lgG) - 1) >> p.lgG;
     p.NR = N | 1;
     CPX_REQUIRE(5 * p.NR * RW * 8 < (1ll << 31), CPX_ELIMIT, "turbo_decode: block too long for 31-bit lane offsets into a row group's slab");
     if ((rc = sc.get(st, Slot::state2, sizeof(double) * (size_t)(ngroups * 5 * p.NR * RW), &p.larr))) return rc;
-    // "detect and redo", as in cpx_map_decode_batch_dev (round 5: redone by turbo_literal_kernel, no block-length limit)
-    if ((rc = sc.get(st, Slot::redo_flags, (size_t)B, &p.flags))) return rc;
-    CPX_HIP(hipMemsetAsync(p.flags, 0, (size_t)B, st));
-    CPX_REQUIRE(npairs < (1ll << 31), CPX_ELIMIT, "turbo_decode: batch too large");
+    CPX_REQUIRE(ps.npairs < (1ll << 31), CPX_ELIMIT, "turbo_decode: batch too large");
     // the two row index tables the library derives from the interleaver
-    {
-        int32_t *tabs = nullptr;
-        if ((rc = sc.get(st, Slot::turbo_tables, 2 * sizeof(int32_t) * (size_t)N, &tabs))) return rc;
-        p.iperm = tabs; p.ident = tabs + N;
-        hipLaunchKernelGGL(turbo_tables_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d_perm, tabs, tabs + N, N);
-    }
+    int32_t *tabs;
+    if ((rc = sc.get(st, Slot::turbo_tables, 2 * sizeof(int32_t) * (size_t)N, &tabs))) return rc;
+    p.iperm = tabs; p.ident = tabs + N;
+    hipLaunchKernelGGL(turbo_tables_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d_perm, tabs, tabs + N, N);
+    CPX_HIP(hipGetLastError());
     if (n_iter == 0) {                                            // the reference's loop never runs: no decision is ever taken
         CPX_HIP(hipMemsetAsync(d_bits, 0, (size_t)(B * N), st));
         note_kernel("turbo_decode: 0 iterations");
         return CPX_OK;
     }
-    dim3 grid((unsigned)nblocks), block(128 * np);
-    // "fp32-fast" (cpx_set_precision; not the parity mode): the slab between the passes in float32 (slab_ld), arithmetic unchanged
-    const bool s32 = precision_fast();
     const int itiles = (int)((N + IT - 1) / IT), ftiles = (int)((N + FT - 1) / FT);
     CPX_REQUIRE(ngroups * itiles < (1ll << 31) && ngroups * ftiles < (1ll << 31), CPX_ELIMIT, "turbo_decode: batch too large");
-    {
-        const dim3 igrid((unsigned)(ngroups * itiles));
-        const size_t ilds = sizeof(double) * 4 * (size_t)RW * IT_ROW;
-        if (s32) hipLaunchKernelGGL(turbo_init_kernel<true>, igrid, dim3(256), ilds, st, p, itiles);
-        else hipLaunchKernelGGL(turbo_init_kernel<false>, igrid, dim3(256), ilds, st, p, itiles);
-    }
-    auto pass = [&](const int32_t *idx, int second, int pout, int llr_in, int last) -> int {
-        switch (p.tb.lgS) {
-#define LAUNCH(LG, SRV) do { if (s32) hipLaunchKernelGGL((turbo_pass_kernel<LG, SRV, true>), grid, block, sizeof(double) * 2 * np * wave_lds_doubles<LG>(GW), st, p, idx, second, pout, llr_in, last); \
-                             else hipLaunchKernelGGL((turbo_pass_kernel<LG, SRV, false>), grid, block, sizeof(double) * 2 * np * wave_lds_doubles<LG>(GW), st, p, idx, second, pout, llr_in, last); } while (0)
-#define CASE(LG) case LG: LAUNCH(LG, false); break;
-            case 2:
-                if (p.tb.sr4) LAUNCH(2, true);
-                else LAUNCH(2, false);
-                break;
-            CASE(1) CASE(3) CASE(4)
-#undef CASE
-#undef LAUNCH
-            default: set_error("turbo_decode: unsupported state count"); return CPX_ELIMIT;
-        }
-        return CPX_OK;
-    };
+    // "fp32-fast" (cpx_set_precision; not the parity mode): the slab between the passes in float32 (slab_ld), arithmetic unchanged
+    const bool s32 = precision_fast();
+    with_bool(s32, [&](auto f32) {
+        hipLaunchKernelGGL(turbo_init_kernel<decltype(f32)::value>, dim3((unsigned)(ngroups * itiles)), dim3(256), sizeof(double) * 4 * (size_t)RW * IT_ROW, st, p, itiles);
+    });
     int prev_pout = 1;                                            // (turbo_init_kernel wrote a prior)
     for (int h = 0; h < 2 * n_iter; h++) {
         // every pass but the last two hands prior0(E) to the next one directly (epilogue): the last MAP 2 needs L_int_2 and E_2 as
         // LLRs for the decision L_2 = L_int_2 + E_2 > 0 (:148-152, :326-331), so the last MAP 1 writes E_1 itself
-        const int pout = h <= 2 * n_iter - 3 ? 1 : 0;
-        const int last = h == 2 * n_iter - 1;
+        const int pout = h <= 2 * n_iter - 3 ? 1 : 0, last = h == 2 * n_iter - 1;
+        const int second = h & 1, llr_in = (h > 0 && !prev_pout) ? 1 : 0;
         // the prior of MAP 2 is interlv(E_1) (:319): row perm[t]; of MAP 1 deinterlv(E_2) (:329): row inverse_perm[t]; of the very
         // first pass L_int_1 as turbo_init_kernel laid it out: row t
-        const int32_t *idx = (h & 1) ? d_perm : (h == 0 ? p.ident : p.iperm);
-        if ((rc = pass(idx, h & 1, pout, (h > 0 && !prev_pout) ? 1 : 0, last))) return rc;
+        const int32_t *idx = second ? d_perm : (h == 0 ? p.ident : p.iperm);
+        with_variant(p.tb, [&](auto lg, auto sr) {
+            constexpr int LG = decltype(lg)::value; constexpr bool SR = decltype(sr)::value;
+            with_bool(s32, [&](auto f32) {
+                hipLaunchKernelGGL((turbo_pass_kernel<LG, SR, decltype(f32)::value>), ps.grid, ps.block, pass_lds<LG>(ps.np, ps.GW), st, p, idx, second, pout, llr_in, last);
+            });
+        });
         prev_pout = pout;
     }
-    if (s32) hipLaunchKernelGGL(turbo_final_kernel<true>, dim3((unsigned)(ngroups * ftiles)), dim3(FT), 0, st, p, ftiles);
-    else hipLaunchKernelGGL(turbo_final_kernel<false>, dim3((unsigned)(ngroups * ftiles)), dim3(FT), 0, st, p, ftiles);
-    CPX_HIP(hipGetLastError());
+    with_bool(s32, [&](auto f32) {
+        hipLaunchKernelGGL(turbo_final_kernel<decltype(f32)::value>, dim3((unsigned)(ngroups * ftiles)), dim3(FT), 0, st, p, ftiles);
+    });
     note_kernel("turbo_pass_kernel<%d,%s%s> x %d (time-major slab, interleaver = row index) + turbo_init_kernel + turbo_final_kernel (%d wave pairs per workgroup, %d codewords per pair)", p.tb.lgS,
-                (p.tb.lgS == 2 && p.tb.sr4) ? "true" : "false", s32 ? ",f32 slab" : "", 2 * n_iter, np, GW);
-    // redo: one launch; a pair with a flagged codeword decodes its codewords again, literally, all iterations (turbo_literal_kernel)
+                (p.tb.lgS == 2 && p.tb.sr4) ? "true" : "false", s32 ? ",f32 slab" : "", 2 * n_iter, ps.np, ps.GW);
+    // redo: one launch, ONE pair per workgroup; a pair with a flagged codeword decodes its codewords again, literally, all iterations
     const RedoCounter redo = redo_counter(sc, st);
-    {
-        const dim3 lgrid((unsigned)npairs), lblock(128);
-        switch (p.tb.lgS) {
-#define CASE(LG) case LG: hipLaunchKernelGGL((turbo_literal_kernel<LG, false>), lgrid, lblock, sizeof(double) * 2 * wave_lds_doubles<LG>(GW), st, p, redo); break;
-            case 2:
-                if (p.tb.sr4) hipLaunchKernelGGL((turbo_literal_kernel<2, true>), lgrid, lblock, sizeof(double) * 2 * wave_lds_doubles<2>(GW), st, p, redo);
-                else hipLaunchKernelGGL((turbo_literal_kernel<2, false>), lgrid, lblock, sizeof(double) * 2 * wave_lds_doubles<2>(GW), st, p, redo);
-                break;
-            CASE(1) CASE(3) CASE(4)
-#undef CASE
-            default: break;
-        }
-        CPX_HIP(hipGetLastError());
-    }
+    with_variant(p.tb, [&](auto lg, auto sr) {
+        constexpr int LG = decltype(lg)::value;
+        hipLaunchKernelGGL((turbo_literal_kernel<LG, decltype(sr)::value>), dim3((unsigned)ps.npairs), dim3(128), pass_lds<LG>(1, ps.GW), st, p, redo);
+    });
+    CPX_HIP(hipGetLastError());
     note_redo((long long)B, "codewords flagged (their pairs decoded literally)");
     return CPX_OK;
 }

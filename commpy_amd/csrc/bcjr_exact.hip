@@ -1,5 +1,6 @@
-// Absolute-scale BCJR / turbo decoder: the redo path behind bcjr.hip's "detect and redo", and the ONLY path for trellises of
-// more than 16 states (the reference's map_decode takes any number of states; flags == null decodes every codeword).
+// Absolute-scale BCJR / turbo decoder for trellises of MORE THAN 16 STATES: bcjr.hip's wave-pair kernels hold one state per lane of
+// a 16-lane row at the most, the reference's map_decode takes any number of states, and this file serves the rest.  Every codeword
+// of the batch is decoded here, once.
 //
 // A literal restatement, one codeword per lane, of
 //   map_decode    (/root/reference/commpy/channelcoding/turbo.py:163-251)
@@ -7,11 +8,12 @@
 //   turbo_decode  (turbo.py:254-333) with interlv / deinterlv (interleavers.py:13-47)
 // in the reference's own scale and evaluation order: absolute gamma = exp(-(x^2 + y^2) / (2 sigma^2)), priors
 // p0 = 1 / (1 + e^L), p1 = 1 - p0, every beta / alpha column divided by its NumPy-ordered sum at every step.  Where the
-// terms of that recursion underflow, the reference returns NaN or +-inf LLRs (a column sum of 0, app0 = 0); bcjr.hip's fast,
-// scale-free kernels would return finite values there, so they flag every codeword for which any term of the reference can
-// leave the normal float64 range and the kernels below decode exactly those codewords again, overwriting the outputs.
-// Speed is not a goal: lane = codeword, the backward metrics of a lane live in an HBM scratch laid out [t][state][lane]
-// (coalesced over the lanes).  With no flag raised a launch is C / 64 wavefronts that read B / C flag bytes per lane and exit.
+// terms of that recursion underflow, the reference returns NaN or +-inf LLRs (a column sum of 0, app0 = 0) and so do these kernels:
+// nothing is detected and nothing decoded twice.  (Up to 16 states the same arithmetic runs wave-parallel as bcjr.hip's
+// map_literal_kernel / turbo_literal_kernel, behind its fast kernels' "detect and redo"; until those existed the kernels below
+// were that redo path as well.)
+// Speed is not a goal: lane = codeword, the backward metrics and the three state vectors of a lane live in an HBM scratch laid
+// out [row][lane] (coalesced over the lanes).
 #include "cpx_internal.h"
 
 #include <algorithm>
@@ -20,8 +22,7 @@ using namespace cpx;
 
 namespace {
 
-constexpr int MAXS = 16;        // bcjr.hip's fast kernels support 2..16 states: their state vectors fit a lane's registers here.
-                                // Larger trellises (the reference takes any, turbo.py:163-251) keep them in the HBM scratch (MemVec)
+constexpr int MAXS = 16;        // precondition of the two entry functions: S > MAXS (bcjr.hip's own kernels serve 2..16 states)
 
 struct ExCode {
     const int32_t *next_state, *output;   // [S][2]
@@ -88,14 +89,8 @@ __device__ double np_sum(const A &a, int n) {
     return ret;
 }
 
-// the three state vectors of a pass (sums of a column before normalisation, alpha, next alpha): a lane's registers up to
-// MAXS states, else three rows [S] of the lane's HBM scratch (lane stride C)
-struct RegVec {
-    double acc_[MAXS], f_[MAXS], fn_[MAXS];
-    __device__ __forceinline__ double &acc(int s) { return acc_[s]; }
-    __device__ __forceinline__ double &f(int s) { return f_[s]; }
-    __device__ __forceinline__ double &fn(int s) { return fn_[s]; }
-};
+// the three state vectors of a pass (sums of a column before normalisation, alpha, next alpha): three rows [S] of the lane's HBM
+// scratch (lane stride C), behind the rows a kernel uses otherwise
 struct MemVec {
     double *base;              // [3][S] with lane stride C
     int64_t C;
@@ -107,10 +102,9 @@ struct MemVec {
 
 // One MAP pass of one codeword (turbo.py:163-251).  beta: scratch [(N + 1)][S] with lane stride C; Lout: stride lst;
 // bits (may be null): stride 1, written at position (bperm ? bperm[t] : t) -- deinterlv of turbo_decode's last pass (:331).
-template <class Vec>
 __device__ void exact_map(const ExCode &cd, int64_t N, double nv2, const View &sys, const View &par, const View &lin,
                           double *beta, int64_t C, double *Lout, int64_t lst, uint8_t *bits, const int32_t *bperm, int want_bits,
-                          Vec &v) {
+                          MemVec &v) {
     const int S = cd.S, sh = cd.n - 2;
     auto B_ = [&](int64_t t, int s) -> double & { return beta[(t * S + s) * C]; };
     auto gammas = [&](int64_t t, double (&g)[4]) {                // _compute_branch_prob for the four (msg_bit, parity_bit) pairs
@@ -166,34 +160,20 @@ struct ExMapParams {
     const double *sys, *par, *Lin;   // [B][N]
     double *Lout;                    // [B][N]
     uint8_t *bits;                   // [B][N]
-    const uint8_t *flags;            // [B], or null: every codeword (trellises the fast kernels do not serve)
-    double *scratch;                 // beta: [(N + 1) * S][C] (+ [3 S][C] state vectors when S > MAXS)
+    double *scratch;                 // [(N + 1) * S + 3 S][C]: beta, the state vectors
     int64_t B, N, C;
     double nv2;
     int want_bits;
 };
 
-// the state vectors of lane j: registers, or three rows behind the `used` doubles of its scratch column
-template <bool BIG> struct VecOf;
-template <> struct VecOf<false> {
-    RegVec v;
-    __device__ VecOf(double *, int64_t, int64_t, int) {}
-};
-template <> struct VecOf<true> {
-    MemVec v;
-    __device__ VecOf(double *col, int64_t used, int64_t C, int S) : v{col + used * C, C, S} {}
-};
-
-template <bool BIG>
 __global__ __launch_bounds__(64) void map_exact_kernel(ExMapParams p) {
-    const int64_t j = (int64_t)blockIdx.x * 64 + threadIdx.x;    // lane = scratch column; decodes the flagged codewords = j (mod C)
-    VecOf<BIG> vec(p.scratch + j, (p.N + 1) * p.cd.S, p.C, p.cd.S);
+    const int64_t j = (int64_t)blockIdx.x * 64 + threadIdx.x;    // lane = scratch column; decodes the codewords = j (mod C)
+    MemVec vec{p.scratch + j + (p.N + 1) * p.cd.S * p.C, p.C, p.cd.S};
     for (int64_t cw = j; cw < p.B; cw += p.C) {
-        if (p.flags && !p.flags[cw]) continue;
         const int64_t o = cw * p.N;
         const View sys{p.sys + o, 1, nullptr}, par{p.par + o, 1, nullptr}, lin{p.Lin + o, 1, nullptr};
         exact_map(p.cd, p.N, p.nv2, sys, par, lin, p.scratch + j, p.C, p.Lout + o, 1, p.bits ? p.bits + o : nullptr, nullptr,
-                  p.want_bits, vec.v);
+                  p.want_bits, vec);
     }
 }
 
@@ -202,22 +182,19 @@ struct ExTurboParams {
     const double *sys, *p1, *p2, *Lint;   // [B][N], Lint may be null
     const int32_t *perm;                  // [N]
     uint8_t *bits;                        // [B][N]
-    const uint8_t *flags;                 // [B], or null: every codeword
-    double *scratch;                      // [(N + 1) * S + 4 N][C]: beta, L_int_1, L_ext, L_int_2, L_2 (+ [3 S][C] when S > MAXS)
+    double *scratch;                      // [(N + 1) * S + 4 N + 3 S][C]: beta, L_int_1, L_ext, L_int_2, L_2, the state vectors
     int64_t B, N, C;
     double nv2;
     int n_iter;
 };
 
-template <bool BIG>
 __global__ __launch_bounds__(64) void turbo_exact_kernel(ExTurboParams p) {
     const int64_t j = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const int64_t N = p.N, C = p.C;
     double *beta = p.scratch + j;
     double *L1 = beta + (N + 1) * p.cd.S * C, *Le = L1 + N * C, *L2in = Le + N * C, *L2 = L2in + N * C;
-    VecOf<BIG> vec(p.scratch + j, (N + 1) * p.cd.S + 4 * N, C, p.cd.S);
+    MemVec vec{beta + ((N + 1) * p.cd.S + 4 * N) * C, C, p.cd.S};
     for (int64_t cw = j; cw < p.B; cw += C) {
-        if (p.flags && !p.flags[cw]) continue;
         const int64_t o = cw * N;
         uint8_t *bits = p.bits + o;
         for (int64_t i = 0; i < N; i++) {
@@ -227,17 +204,17 @@ __global__ __launch_bounds__(64) void turbo_exact_kernel(ExTurboParams p) {
         const View sys{p.sys + o, 1, nullptr}, sysi{p.sys + o, 1, p.perm};          // interlv(sys_symbols) (:310)
         const View y1{p.p1 + o, 1, nullptr}, y2{p.p2 + o, 1, nullptr};
         for (int it = 0; it < p.n_iter; it++) {
-            exact_map(p.cd, N, p.nv2, sys, y1, View{L1, C, nullptr}, beta, C, Le, C, nullptr, nullptr, 0, vec.v);   // 'compute' (:315)
+            exact_map(p.cd, N, p.nv2, sys, y1, View{L1, C, nullptr}, beta, C, Le, C, nullptr, nullptr, 0, vec);   // 'compute' (:315)
             for (int64_t i = 0; i < N; i++) Le[i * C] = Le[i * C] - L1[i * C];                           // (:318)
             for (int64_t i = 0; i < N; i++) L2in[i * C] = Le[(int64_t)p.perm[i] * C];                    // interlv (:319)
             const bool last = it == p.n_iter - 1;                 // mode 'decode' in the last iteration only (:320-323)
-            exact_map(p.cd, N, p.nv2, sysi, y2, View{L2in, C, nullptr}, beta, C, L2, C, last ? bits : nullptr, p.perm, 1, vec.v);   // (:326, :331)
+            exact_map(p.cd, N, p.nv2, sysi, y2, View{L2in, C, nullptr}, beta, C, L2, C, last ? bits : nullptr, p.perm, 1, vec);   // (:326, :331)
             for (int64_t i = 0; i < N; i++) L1[(int64_t)p.perm[i] * C] = L2[i * C] - L2in[i * C];       // deinterlv (:328-329)
         }
     }
 }
 
-// lanes of the redo launch: a multiple of 64, at most one per codeword, at most `budget` bytes of scratch
+// lanes of a launch: a multiple of 64, at most one per codeword, at most `budget` bytes of scratch
 int64_t pick_lanes(int64_t B, size_t doubles_per_lane, size_t budget) {
     int64_t c = (int64_t)(budget / (doubles_per_lane * sizeof(double)));
     c = std::min<int64_t>(c, 4096);
@@ -247,50 +224,42 @@ int64_t pick_lanes(int64_t B, size_t doubles_per_lane, size_t budget) {
 
 ExCode ex_code(const cpx_trellis *t) { return ExCode{t->d_next, t->d_out, t->S, t->n}; }
 
-constexpr size_t EXACT_BUDGET = (size_t)1 << 28;     // 256 MB: 4096 lanes for N = 1024, four states
-constexpr size_t EXACT_BUDGET_BIG = (size_t)1 << 32; // trellises only this path serves: 4 GB (64 lanes of 1024 steps x 8192 states)
+constexpr size_t SCRATCH_BUDGET = (size_t)1 << 32;   // 4 GB: 64 lanes of 1024 steps x 8192 states
+
+size_t lane_doubles(int S, int64_t N, int turbo) { return (size_t)((N + 1) * S + (turbo ? 4 * N : 0) + 3 * S); }
 
 }  // namespace
 
 namespace cpx {
 
-static size_t lane_doubles(int S, int64_t N, int turbo) {
-    return (size_t)((N + 1) * S + (turbo ? 4 * N : 0) + (S > MAXS ? 3 * S : 0));
-}
-
-bool bcjr_exact_supported(int S, int64_t N, int turbo) {
-    return pick_lanes(64, lane_doubles(S, N, turbo), S > MAXS ? EXACT_BUDGET_BIG : EXACT_BUDGET) >= 64;
-}
-
 int bcjr_exact_map(const cpx_trellis *t, const double *sys, const double *par, const double *Lin, int64_t B, int64_t N, double nv2,
-                   int want_bits, double *Lout, uint8_t *bits, const uint8_t *flags, Scratch &sc, hipStream_t st) {
+                   int want_bits, double *Lout, uint8_t *bits, Scratch &sc, hipStream_t st) {
+    CPX_REQUIRE(t->S > MAXS, CPX_EINVAL, "map_decode: the absolute-scale path serves trellises above %d states (got %d)", MAXS, t->S);
     ExMapParams p;
     p.cd = ex_code(t);
     const size_t per = lane_doubles(t->S, N, 0);
-    p.C = pick_lanes(B, per, t->S > MAXS ? EXACT_BUDGET_BIG : EXACT_BUDGET);
+    p.C = pick_lanes(B, per, SCRATCH_BUDGET);
     CPX_REQUIRE(p.C >= 64, CPX_ELIMIT, "map_decode: block too long for the absolute-scale path (%d states x %lld steps)", t->S, (long long)N);
     if (int rc = sc.get(st, Slot::exact_redo, per * (size_t)p.C * sizeof(double), &p.scratch)) return rc;
-    p.sys = sys; p.par = par; p.Lin = Lin; p.Lout = Lout; p.bits = bits; p.flags = flags;
+    p.sys = sys; p.par = par; p.Lin = Lin; p.Lout = Lout; p.bits = bits;
     p.B = B; p.N = N; p.nv2 = nv2; p.want_bits = want_bits;
-    if (t->S > MAXS) hipLaunchKernelGGL(map_exact_kernel<true>, dim3((unsigned)(p.C / 64)), dim3(64), 0, st, p);
-    else hipLaunchKernelGGL(map_exact_kernel<false>, dim3((unsigned)(p.C / 64)), dim3(64), 0, st, p);
+    hipLaunchKernelGGL(map_exact_kernel, dim3((unsigned)(p.C / 64)), dim3(64), 0, st, p);
     CPX_HIP(hipGetLastError());
     return CPX_OK;
 }
 
 int bcjr_exact_turbo(const cpx_trellis *t, const double *sys, const double *p1, const double *p2, const double *Lint_or_null,
-                     const int32_t *perm, int64_t B, int64_t N, double nv2, int n_iter, uint8_t *bits, const uint8_t *flags,
-                     Scratch &sc, hipStream_t st) {
+                     const int32_t *perm, int64_t B, int64_t N, double nv2, int n_iter, uint8_t *bits, Scratch &sc, hipStream_t st) {
+    CPX_REQUIRE(t->S > MAXS, CPX_EINVAL, "turbo_decode: the absolute-scale path serves trellises above %d states (got %d)", MAXS, t->S);
     ExTurboParams p;
     p.cd = ex_code(t);
     const size_t per = lane_doubles(t->S, N, 1);
-    p.C = pick_lanes(B, per, t->S > MAXS ? EXACT_BUDGET_BIG : EXACT_BUDGET);
+    p.C = pick_lanes(B, per, SCRATCH_BUDGET);
     CPX_REQUIRE(p.C >= 64, CPX_ELIMIT, "turbo_decode: block too long for the absolute-scale path (%d states x %lld steps)", t->S, (long long)N);
     if (int rc = sc.get(st, Slot::exact_redo, per * (size_t)p.C * sizeof(double), &p.scratch)) return rc;
-    p.sys = sys; p.p1 = p1; p.p2 = p2; p.Lint = Lint_or_null; p.perm = perm; p.bits = bits; p.flags = flags;
+    p.sys = sys; p.p1 = p1; p.p2 = p2; p.Lint = Lint_or_null; p.perm = perm; p.bits = bits;
     p.B = B; p.N = N; p.nv2 = nv2; p.n_iter = n_iter;
-    if (t->S > MAXS) hipLaunchKernelGGL(turbo_exact_kernel<true>, dim3((unsigned)(p.C / 64)), dim3(64), 0, st, p);
-    else hipLaunchKernelGGL(turbo_exact_kernel<false>, dim3((unsigned)(p.C / 64)), dim3(64), 0, st, p);
+    hipLaunchKernelGGL(turbo_exact_kernel, dim3((unsigned)(p.C / 64)), dim3(64), 0, st, p);
     CPX_HIP(hipGetLastError());
     return CPX_OK;
 }

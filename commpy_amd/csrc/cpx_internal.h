@@ -113,13 +113,12 @@ void ldpc_resident_free(::cpx_ldpc *c);
 bool ldpc_resident_path(const ::cpx_ldpc *c, double *d_llr, int64_t B, int alg, int n_iters, int8_t *d_dec, double *d_out,
                         int block_major, int32_t *d_iters, int *d_clipped, uint8_t *nanflags, Scratch &sc, hipStream_t st, int *rc);
 
-// absolute-scale BCJR / turbo redo path (bcjr_exact.hip): decodes the codewords whose flag byte is set, overwriting the outputs
-bool bcjr_exact_supported(int S, int64_t N, int turbo);
+// absolute-scale BCJR / turbo decoder for trellises above 16 states (bcjr_exact.hip; CPX_EINVAL for any other): every codeword of the
+// batch, one per lane
 int bcjr_exact_map(const ::cpx_trellis *t, const double *sys, const double *par, const double *Lin, int64_t B, int64_t N, double nv2,
-                   int want_bits, double *Lout, uint8_t *bits, const uint8_t *flags, Scratch &sc, hipStream_t st);
+                   int want_bits, double *Lout, uint8_t *bits, Scratch &sc, hipStream_t st);
 int bcjr_exact_turbo(const ::cpx_trellis *t, const double *sys, const double *p1, const double *p2, const double *Lint_or_null,
-                     const int32_t *perm, int64_t B, int64_t N, double nv2, int n_iter, uint8_t *bits, const uint8_t *flags,
-                     Scratch &sc, hipStream_t st);
+                     const int32_t *perm, int64_t B, int64_t N, double nv2, int n_iter, uint8_t *bits, Scratch &sc, hipStream_t st);
 
 // Scratch arena keyed by (device, stream, slot): grown with hipMalloc on demand, reused by later calls and released by
 // cpx_release_workspace / cpx_stream_destroy.  Kernels of one stream serialise, so one arena per stream is safe ACROSS calls; within
@@ -140,8 +139,8 @@ enum class Slot : int {
     redo_flags,
     ldpc_nan_flags,      // ldpc.hip: min-sum NaN flag bytes, one per block (live together with exact_redo, hence a slot of its own)
     // per-lane / per-workgroup float64 state of the literal kernels: ldpc.hip ldpc_exact_kernel (general path or min-sum redo: the general
-    // path returns before the redo exists) | bcjr_exact.hip map | bcjr_exact.hip turbo (trellises above 16 states; the entry point
-    // returns right behind it, before any other request): one launch per call
+    // path returns before the redo exists) | bcjr_exact.hip map | bcjr_exact.hip turbo (the only decoder of trellises above 16
+    // states, not a redo: the entry point returns right behind it, before any other request): one launch per call
     exact_redo,
     vit_host_in,         // viterbi.hip cpx_viterbi_decode_batch_i64: device copy of the host input (library stream, see there)
     vit_host_out,        // ... and of the decoded bits

@@ -199,6 +199,14 @@ SYMBOLS = {
     "cpx_ldpc_encoder_create": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_void_p)]),
     "cpx_ldpc_encoder_destroy": (c_int, [c_void_p]),
     "cpx_ldpc_encode_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cpx_polar_create": (c_int, [c_int, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
+    "cpx_polar_destroy": (c_int, [c_void_p]),
+    "cpx_polar_encode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "cpx_polar_encode_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cpx_polar_decode": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
+    "cpx_polar_decode_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
     "cpx_comm_unique_id": (c_int, [c_void_p]),
     "cpx_comm_init_rank": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
     "cpx_comm_init_all": (c_int, [POINTER(c_int), c_int, POINTER(c_void_p)]),

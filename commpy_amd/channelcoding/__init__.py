@@ -6,7 +6,10 @@ from commpy_amd.channelcoding.interleavers import RandInterlv
 from commpy_amd.channelcoding.turbo import turbo_encode, map_decode, turbo_decode
 from commpy_amd.channelcoding.ldpc import (build_matrix, get_ldpc_code_params, ldpc_bp_decode, write_ldpc_params,
                                            triang_ldpc_systematic_encode)
+from commpy_amd.channelcoding.polar import (polar_reliability_order, PolarCode, crc_append, crc_check, polar_encode,
+                                            polar_decode)
 
 __all__ = ['Trellis', 'conv_encode', 'conv_encode_batch', 'viterbi_decode', 'puncturing', 'depuncturing',
            'RandInterlv', 'turbo_encode', 'map_decode', 'turbo_decode', 'build_matrix', 'get_ldpc_code_params',
-           'ldpc_bp_decode', 'write_ldpc_params', 'triang_ldpc_systematic_encode']
+           'ldpc_bp_decode', 'write_ldpc_params', 'triang_ldpc_systematic_encode',
+           'polar_reliability_order', 'PolarCode', 'crc_append', 'crc_check', 'polar_encode', 'polar_decode']

@@ -16,7 +16,7 @@ from commpy_amd.channelcoding.ldpc import build_matrix
 __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu', 'mimo_channel_gpu', 'puncturing_gpu',
            'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder', 'gf2_generator',
            'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
-           'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev']
+           'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev']
 
 
 class DeviceBuf:
@@ -478,3 +478,38 @@ def fading_channel_dev(d_x, B, nt, nr, n, pdp, fd, hold=1, t0=0, n_sin=16, k_fac
                                                   None if d_y is None else d_y.ptr, None if d_G is None else d_G.ptr, stream))
     out = tuple(v for v in (d_y, d_G) if v is not None)
     return out[0] if want == ('y',) else out
+
+
+# ---- polar codes, device resident (csrc/polar.hip) ----------------------------------------------------------------------------------
+
+def polar_encode_dev(code, d_msg, B, stream=None):
+    """``cpx_polar_encode_dev``: ``d_msg [B][A]`` uint8 -> a new ``DeviceBuf`` ``[B][N]`` uint8 of code words, queued on ``stream``
+    (None: the library's); ``code`` is a ``channelcoding.PolarCode``."""
+    from commpy_amd.channelcoding.polar import _code, _whole
+    code, B = _code(code), _whole(B, 'B', 0)
+    d_x = DeviceBuf(B * code.N)
+    if B:
+        _lib.check(d_x.lib.cpx_polar_encode_dev(code._device_handle(), d_msg.ptr, B, d_x.ptr, stream))
+    return d_x
+
+
+def polar_decode_dev(code, d_llr, B, list_size=1, want=('bits',), stream=None):
+    """``cpx_polar_decode_dev``: ``d_llr [B][N]`` float64 -> new ``DeviceBuf``s, the results of ``channelcoding.polar_decode`` that
+    ``want`` names, in its order: 'bits' ``[B][A]`` uint8, 'crc' ``[B]`` uint8, 'metric' ``[B]`` float64, 'u_llr' ``[B][N]`` float64
+    (``list_size = 1``), 'list' a tuple ``(bits [B][L][K] uint8, metrics [B][L] float64, live [B] int32)``; a single result for one
+    name."""
+    from commpy_amd.channelcoding.polar import WANT, _code, _whole, check_want
+    code, B = _code(code), _whole(B, 'B', 0)
+    L = code.check_list_size(list_size)
+    want = check_want(want, L)
+    sizes = {'bits': B * code.A, 'crc': B, 'metric': B * 8, 'u_llr': B * code.N * 8}
+    out = {k: DeviceBuf(sizes[k]) for k in sizes if k in want}
+    lst = (DeviceBuf(B * L * code.K), DeviceBuf(B * L * 8), DeviceBuf(B * 4)) if 'list' in want else (None,) * 3
+    if B:
+        p = lambda v: None if v is None else v.ptr
+        _lib.check(_lib.load().cpx_polar_decode_dev(code._device_handle(), d_llr.ptr, B, L, p(out.get('bits')), p(out.get('crc')),
+                                                    p(out.get('metric')), p(out.get('u_llr')), p(lst[0]), p(lst[1]), p(lst[2]), stream))
+    if 'list' in want:
+        out['list'] = lst
+    res = tuple(out[k] for k in WANT if k in want)
+    return res[0] if len(res) == 1 else res

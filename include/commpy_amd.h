@@ -775,6 +775,33 @@ int cpx_ldpc_encoder_destroy(cpx_ldpc_encoder *e);
 int cpx_ldpc_encode_batch_dev(const cpx_ldpc_encoder *e, const uint8_t *d_msg, int64_t B, uint8_t *d_code,
                               void *stream);
 
+/* ---- polar codes: encoder, successive cancellation and CRC-aided list decoding (csrc/polar.hip) --------
+ * x = u F^{(x)n} over GF(2), F = [[1,0],[1,1]], natural order (no bit reversal), N = 2^n <= 8192.  The K positions with frozen[i] = 0
+ * carry the information bits, in increasing position; with a CRC of crc_bits = c bits (1 <= c <= 32, c < K) these are A = K - c message
+ * bits followed by the CRC bits, most significant first, else A = K.  crc_table [K] uint32: entry k = x^(K-1-k) mod g (NULL and
+ * crc_bits = 0: no CRC); a word passes iff the XOR of the entries of its one bits is 0.
+ *   cpx_polar_create      validates the mask and the table (CPX_EINVAL, before a device is looked for) and uploads them.
+ *   cpx_polar_encode      msg [B][A] uint8 -> x [B][N] uint8 (CRC appended on the device).
+ *   cpx_polar_decode      llr [B][N] float64, positive = bit 0.  L = 1: successive cancellation; L in {2, 4, 8, 16, 32}: list decoding,
+ *                         min-sum f and exact g in float64, the list sorted stably by path metric at every information bit; the chosen
+ *                         path is the lowest rank that passes the CRC (rank 0 and crc_ok = 0 if none does; rank 0 and crc_ok = 1 without
+ *                         a CRC).  L * N <= 8192, else CPX_ELIMIT.  Every output may be NULL (not all of them): bits [B][A] uint8,
+ *                         crc_ok [B] uint8, metric [B] float64 (of the chosen path), u_llr [B][N] float64 (the decision LLR of every
+ *                         position; L = 1 only, else CPX_EINVAL), list_bits [B][L][K] uint8 (information bits by rank), list_metric
+ *                         [B][L] float64, list_live [B] int32 (paths alive at the end = min(L, 2^K)); rows past the live count hold
+ *                         zeros and metrics of +inf.  Bit-identical to tests/polar_model.py; the precision mode has no effect.
+ * The _dev forms take device pointers and a stream and are asynchronous; the others take host pointers and return synchronised.
+ * B = 0 returns CPX_OK without a launch. */
+typedef struct cpx_polar cpx_polar;
+int cpx_polar_create(int N, const uint8_t *frozen, int crc_bits, const uint32_t *crc_table, cpx_polar **out);
+int cpx_polar_destroy(cpx_polar *p);
+int cpx_polar_encode(const cpx_polar *p, const uint8_t *msg, int64_t B, uint8_t *x);
+int cpx_polar_encode_dev(const cpx_polar *p, const uint8_t *d_msg, int64_t B, uint8_t *d_x, void *stream);
+int cpx_polar_decode(const cpx_polar *p, const double *llr, int64_t B, int L, uint8_t *bits, uint8_t *crc_ok, double *metric,
+                     double *u_llr, uint8_t *list_bits, double *list_metric, int32_t *list_live);
+int cpx_polar_decode_dev(const cpx_polar *p, const double *d_llr, int64_t B, int L, uint8_t *d_bits, uint8_t *d_crc_ok, double *d_metric,
+                         double *d_u_llr, uint8_t *d_list_bits, double *d_list_metric, int32_t *d_list_live, void *stream);
+
 /* ---- multi-GPU: RCCL collectives of the sharded decode ------------------------------------
  * The path shards by codeword (contiguous blocks of B/G codewords per GPU, tables replicated) and has no exchange
  * step inside a decoder.  Two collectives exist around it:

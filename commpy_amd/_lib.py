@@ -6,7 +6,7 @@ import contextlib
 import ctypes
 import os
 from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_int8, c_int32, c_int64, c_size_t,
-                    c_uint8, c_uint64, c_void_p)
+                    c_uint8, c_uint32, c_uint64, c_void_p)
 
 import numpy as np
 
@@ -207,6 +207,12 @@ SYMBOLS = {
                                  c_void_p]),
     "cpx_polar_decode_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
+    "cpx_bch_create": (c_int, [c_int, c_uint32, c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),
+    "cpx_bch_destroy": (c_int, [c_void_p]),
+    "cpx_bch_encode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "cpx_bch_encode_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cpx_bch_decode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cpx_bch_decode_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cpx_comm_unique_id": (c_int, [c_void_p]),
     "cpx_comm_init_rank": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
     "cpx_comm_init_all": (c_int, [POINTER(c_int), c_int, POINTER(c_void_p)]),

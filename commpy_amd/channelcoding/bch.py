@@ -1,0 +1,117 @@
+"""Binary BCH codes on MI355X: systematic encoder and bounded-distance decoder (syndromes, Berlekamp-Massey, Chien search).
+
+A word is ``n`` bits; bit ``i`` is the coefficient of ``x^(n-1-i)``: the ``k`` message bits first, then the ``n - k`` bits of
+``x^(n-k) m(x) mod g(x)``.  The generator (``algcode.bch_genpoly``) and the field are host work; the kernels of csrc/bch.hip receive
+the generator and the field tables as data and equal the NumPy model tests/bch_model.py byte for byte.
+"""
+import ctypes
+
+import numpy as np
+
+from commpy_amd import _lib
+from commpy_amd.channelcoding.algcode import bch_genpoly
+from commpy_amd.channelcoding.gfields import field, whole
+
+__all__ = ['BCHCode', 'bch_encode', 'bch_decode']
+
+BCH_MIN_M, BCH_MAX_M, BCH_MAX_T = 3, 14, 32      # csrc/bch.hip
+WANT = ('bits', 'codeword', 'errors')
+
+
+class BCHCode:
+    """The narrow-sense binary BCH code of length ``n`` that corrects ``t`` errors over GF(2^m): primitive for ``n = 2^m - 1``,
+    shortened below.  ``m`` defaults to the smallest degree with ``2^m - 1 >= n`` (at least 3), ``prim_poly`` to the default
+    primitive polynomial of that degree (DVB-S2's GF(2^14) uses 16427).  Limits: 3 <= m <= 14, 1 <= t <= 32,
+    deg g < n <= 2^m - 1.  Attributes: ``n, k, t, m, prim_poly, genpoly`` (a Python int, bit i = coefficient of x^i)."""
+
+    def __init__(self, n, t, m=None, prim_poly=None):
+        self.n = n = whole(n, 'n', 2)
+        self.t = t = whole(t, 't', 1, BCH_MAX_T)
+        if m is None:
+            if n > (1 << BCH_MAX_M) - 1:
+                raise ValueError('n = %d is above the engine limit of 2^%d - 1' % (n, BCH_MAX_M))
+            m = max(BCH_MIN_M, n.bit_length())
+        self.m = m = whole(m, 'm', BCH_MIN_M, BCH_MAX_M)
+        if n > (1 << m) - 1:
+            raise ValueError('n = %d is above 2^m - 1 = %d' % (n, (1 << m) - 1))
+        self.prim_poly = field(m, prim_poly).prim_poly
+        self.genpoly = bch_genpoly(m, t, self.prim_poly)
+        deg = self.genpoly.bit_length() - 1
+        if deg >= n:
+            raise ValueError('the generator of t = %d over GF(2^%d) has degree %d, need less than n = %d' % (t, m, deg, n))
+        self.k = n - deg
+
+        def create():
+            h = ctypes.c_void_p()
+            bits = np.array([(self.genpoly >> i) & 1 for i in range(deg + 1)], dtype=np.uint8)
+            _lib.check(_lib.load().cpx_bch_create(m, self.prim_poly, n, t, _lib.ptr(bits), deg, ctypes.byref(h)))
+            return h
+        self._handles = _lib.DeviceHandles(create, 'cpx_bch_destroy')
+
+    def _device_handle(self):
+        return self._handles.get()
+
+
+def _code(code):
+    if not isinstance(code, BCHCode):
+        raise ValueError('code must be a BCHCode')
+    return code
+
+
+def check_want(want):
+    """``want`` as a tuple of names out of 'bits', 'codeword', 'errors'."""
+    return _lib.wanted(want, WANT)
+
+
+def _bit_rows(bits, name, width):
+    a = np.asarray(bits)
+    if a.ndim not in (1, 2):
+        raise ValueError('%s must be 1-D or 2-D, got %d dimensions' % (name, a.ndim))
+    if a.dtype.kind not in 'biu':
+        raise ValueError('%s must hold integers 0 / 1, got dtype %s' % (name, a.dtype))
+    if a.shape[-1] != width:
+        raise ValueError('%s has %d bits per row, need %d' % (name, a.shape[-1], width))
+    if a.size and (a.min() < 0 or a.max() > 1):
+        raise ValueError('%s must hold 0 / 1' % name)
+    return np.ascontiguousarray(np.atleast_2d(a), dtype=np.uint8), a.ndim == 1
+
+
+def bch_encode(message_bits, code):
+    """``message_bits [B, k]`` (or 1-D ``[k]``) in 0 / 1 -> code words ``[B, n]`` (``[n]``) uint8, systematic: the message, then
+    the parity bits."""
+    code = _code(code)
+    msg, one = _bit_rows(message_bits, 'message_bits', code.k)
+    out = np.zeros((msg.shape[0], code.n), dtype=np.uint8)
+    if msg.shape[0]:
+        _lib.check(_lib.load().cpx_bch_encode(code._device_handle(), _lib.ptr(msg), msg.shape[0], _lib.ptr(out)))
+    return out[0] if one else out
+
+
+def bch_decode(bits, code, want=('bits',)):
+    """Bounded-distance decoding of the hard decisions ``bits [B, n]`` (or 1-D ``[n]``) in 0 / 1.  ``want`` names the results; they
+    are returned in the order listed here (a single result for one name):
+
+    ``'bits'`` message bits ``[B, k]`` uint8; ``'codeword'`` ``[B, n]`` uint8; ``'errors'`` ``[B]`` int32, the number of corrected
+    bits, -1 after a decoding failure.
+
+    The syndromes ``S_1 .. S_2t`` all zero: accepted with 0 errors.  Otherwise Berlekamp-Massey gives the locator ``sigma`` of length
+    ``L``; it is a failure if ``L > t``, if the coefficient of ``x^L`` is zero, or if ``sigma`` has not exactly ``L`` roots among the
+    inverse locators of the positions ``0 .. n - 1`` (for a shortened code a root in the shortened-away positions).  After a failure
+    ``'bits'`` and ``'codeword'`` hold the received word unchanged."""
+    code = _code(code)
+    want = check_want(want)
+    rows, one = _bit_rows(bits, 'bits', code.n)
+    B = rows.shape[0]
+    res = {}
+    if 'bits' in want:
+        res['bits'] = np.zeros((B, code.k), dtype=np.uint8)
+    if 'codeword' in want:
+        res['codeword'] = np.zeros((B, code.n), dtype=np.uint8)
+    if 'errors' in want:
+        res['errors'] = np.zeros(B, dtype=np.int32)
+    if B:
+        p = lambda v: None if v is None else _lib.ptr(v)
+        _lib.check(_lib.load().cpx_bch_decode(code._device_handle(), _lib.ptr(rows), B, p(res.get('bits')), p(res.get('codeword')),
+                                              p(res.get('errors'))))
+    out = [res[name][0] if one else res[name] for name in WANT if name in want]
+    return out[0] if len(out) == 1 else tuple(out)

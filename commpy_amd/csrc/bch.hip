@@ -1,0 +1,488 @@
+// Binary BCH codes: systematic encoder and bounded-distance decoder (syndromes, Berlekamp-Massey, Chien search) over GF(2^m), 3 <= m <= 14.
+//
+// A word is n bits, bit i the coefficient of x^(n-1-i): the k message bits first, then the n - k bits of x^(n-k) m(x) mod g(x).  A code
+// shortened from 2^m - 1 to n drops the highest degrees.  Field elements are integers (bit j = coefficient of alpha^j); the handle holds
+// exp[e] = alpha^e and log[v] as uint16 tables of 2^m entries each.
+//
+// bch_decode_kernel: one received word per wave, up to 16 waves per workgroup, workgroups stride over the batch.  The two tables are staged
+//   into LDS once per workgroup (2^(m+2) bytes: 64 KiB at m = 14); after that barrier the waves never meet again.  Per word:
+//   1. the bytes are read once, 64 positions per load and eight loads in flight, and kept as ballot words in LDS (rw);
+//   2. S_j for odd j, four indices at a time: a lane whose bit is set adds alpha^(j d) of its degree d (the exponent moves by -64 j mod N
+//      from one 64-position chunk to the next); XOR across the wave; S_2j = S_j^2 by repeated squaring on the lane of the odd j.  All
+//      zero: no error, skip to 5;
+//   3. Berlekamp-Massey over the 2t syndromes, lane i holding the coefficients C_i and B_i (degrees stay <= t <= 32: the first length
+//      above t is a failure at once), the discrepancy an XOR across the wave;
+//   4. Chien search, four chunks at a time: the lane of degree d evaluates sigma(alpha^-d); the ballot of the roots is the chunk's flip
+//      mask (fm), its popcount adds to the root count.  The word is corrected iff sigma's leading coefficient is non-zero and the count
+//      equals its degree;
+//   5. bytes out: (rw ^ fm) bit by bit, fm taken as zero after a failure.
+//   The table gathers are 2-byte reads at data-dependent addresses, two entries per bank word: they conflict at random (not measured).
+// bch_encode_kernel: one word per lane, 64 words per wave.  The wave reads 64 message bytes of each of its words at a time (a coalesced
+//   row segment, copied to the output on the way) and ballots them into one 64-bit word per lane; every lane then runs 64 steps of the long
+//   division on its own remainder of RW 64-bit words, the generator being kernel-argument data.  Nothing in it is specific to BCH codes.
+#include "cpx_internal.h"
+#include "cpx_wave.h"
+
+#include <mutex>
+
+using namespace cpx;
+
+#define CPX_BCH_MIN_M 3
+#define CPX_BCH_MAX_M 14
+#define CPX_BCH_MAX_T 32
+#define CPX_BCH_MAX_GEN_WORDS 7            // 64-bit words of a remainder: deg g <= 14 * 32 = 448
+#define CPX_BCH_LDS_MAX (160 * 1024)
+#define BCH_MAX_WAVES 16
+#define BCH_ENC_THREADS 256
+
+struct cpx_bch {
+    __attribute__((visibility("hidden"))) ~cpx_bch() = default;
+    int m, N, n, k, t, deg, device;
+    uint64_t gen[CPX_BCH_MAX_GEN_WORDS];   // g without its leading term, bit j of word w = coefficient of x^(64 w + j)
+    uint16_t *d_tab = nullptr;             // [2][2^m]: exp then log
+};
+
+namespace {
+
+struct BchDecArgs {
+    const uint8_t *in;                     // [B][n], non-zero = 1
+    const uint16_t *tab;
+    int64_t B;
+    int m, N, n, k, t, nw;                 // nw = ceil(n / 64)
+    uint8_t *bits, *word;                  // [B][k], [B][n]
+    int32_t *errors;                       // [B]
+};
+
+// bytes of LDS per wave: rw and fm (nw 64-bit words each), then the 2t syndromes and the logarithms of sigma's coefficients
+__host__ __device__ inline unsigned bch_wave_lds(int nw) { return 16u * (unsigned)nw + 2u * 64u + 2u * 64u; }
+__host__ __device__ inline unsigned bch_tab_lds(int m) { return 4u << m; }
+
+// waves per workgroup and workgroups of the grid: small tables leave room for several workgroups per compute unit
+inline int bch_waves(int m) { return m <= 8 ? 4 : m <= 11 ? 8 : BCH_MAX_WAVES; }
+
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ unsigned wave_xor(unsigned v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v ^= (unsigned)__shfl_xor((int)v, d);
+    return v;
+}
+
+struct Gf {
+    const uint16_t *ex, *lg;
+    int N;
+    __device__ __forceinline__ unsigned mul(unsigned a, unsigned b) const {
+        if (a == 0u || b == 0u) return 0u;
+        int e = (int)lg[a] + (int)lg[b];
+        if (e >= N) e -= N;
+        return ex[e];
+    }
+};
+
+// S_j for the G odd indices j0, j0 + 2, ...: synd[j - 1] = XOR over the set bits of alpha^(j d), d the degree of the position
+template <int G>
+__device__ __forceinline__ void syndrome_group(const Gf &gf, const unsigned long long *rw, uint16_t *synd, int nw, int j0, int d0, int lane) {
+    const int N = gf.N;
+    int e[G], step[G];
+    unsigned acc[G];
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+        const int j = j0 + 2 * u;
+        step[u] = (64 * j) % N;
+        e[u] = d0 > 0 ? (int)((unsigned)(j * d0) % (unsigned)N) : 0;        // j d0 < 64 * 2^14
+        acc[u] = 0u;
+    }
+    for (int c = 0; c < nw; ++c) {
+        const unsigned take = 0u - (unsigned)((rw[c] >> lane) & 1ull);
+#pragma unroll
+        for (int u = 0; u < G; ++u) {
+            acc[u] ^= gf.ex[e[u]] & take;                         // e stays in 0 .. N - 1 on every lane: the gather needs no mask
+            e[u] -= step[u];
+            if (e[u] < 0) e[u] += N;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+        const unsigned s = wave_xor(acc[u]);
+        if (lane == 0) synd[j0 + 2 * u - 1] = (uint16_t)s;
+    }
+}
+
+__global__ __launch_bounds__(BCH_MAX_WAVES * 64) void bch_decode_kernel(BchDecArgs a) {
+    extern __shared__ double2 bch_lds_raw[];
+    unsigned char *base = reinterpret_cast<unsigned char *>(bch_lds_raw);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
+    const int n = a.n, k = a.k, t = a.t, N = a.N, nw = a.nw;
+    {
+        uint32_t *dst = reinterpret_cast<uint32_t *>(base);
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.tab);
+        for (int i = tid; i < (1 << a.m); i += blockDim.x) dst[i] = src[i];
+    }
+    __syncthreads();
+    Gf gf;
+    gf.ex = reinterpret_cast<const uint16_t *>(base);
+    gf.lg = gf.ex + (1 << a.m);
+    gf.N = N;
+    unsigned char *mine = base + bch_tab_lds(a.m) + (unsigned)wave * bch_wave_lds(nw);
+    unsigned long long *rw = reinterpret_cast<unsigned long long *>(mine), *fm = rw + nw;
+    uint16_t *synd = reinterpret_cast<uint16_t *>(fm + nw), *clog = synd + 64;
+
+    for (int64_t cw = (int64_t)blockIdx.x * waves + wave; cw < a.B; cw += (int64_t)gridDim.x * waves) {
+        wave_sync();                                              // the previous word's arrays have been read
+        const uint8_t *in = a.in + cw * n;
+        for (int c0 = 0; c0 < nw; c0 += 8) {                      // eight loads in flight: the chain of global latencies is what costs
+            uint8_t byte[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = (c0 + u) * 64 + lane;
+                byte[u] = i < n ? in[i] : (uint8_t)0;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const unsigned long long w = __ballot(byte[u] != 0);
+                if (lane == 0 && c0 + u < nw) { rw[c0 + u] = w; fm[c0 + u] = 0ull; }
+            }
+        }
+        wave_sync();
+        // syndromes of the odd indices, four (then two, then one) at a time: one read of rw and independent gathers per chunk
+        const int d0 = n - 1 - lane;                              // the degree of this lane's position in chunk 0; negative: no position
+        {
+            int j = 1;
+            for (; j + 6 < 2 * t; j += 8) syndrome_group<4>(gf, rw, synd, nw, j, d0, lane);
+            if (j + 2 < 2 * t) { syndrome_group<2>(gf, rw, synd, nw, j, d0, lane); j += 4; }
+            if (j < 2 * t) syndrome_group<1>(gf, rw, synd, nw, j, d0, lane);
+        }
+        wave_sync();
+        if ((lane & 1) && lane < 2 * t) {                          // lane = odd j: S_2j, S_4j, ...
+            unsigned v = synd[lane - 1];
+            for (int jj = 2 * lane; jj <= 2 * t; jj *= 2) {
+                v = gf.mul(v, v);
+                synd[jj - 1] = (uint16_t)v;
+            }
+        }
+        wave_sync();
+        int errors = 0;
+        const bool dirty = __ballot(lane < 2 * t && synd[lane] != 0) != 0ull;
+        if (dirty) {
+            // Berlekamp-Massey: C the connection polynomial, Bp the one before the last length change, b its discrepancy, sh the shift
+            unsigned C = lane == 0 ? 1u : 0u, Bp = C, b = 1u;
+            int L = 0, sh = 1;
+            bool fail = false;
+            for (int r = 0; r < 2 * t; ++r) {
+                const unsigned d = wave_xor(lane <= L ? gf.mul(C, synd[r - lane]) : 0u);
+                if (d == 0u) { ++sh; continue; }
+                int e = (int)gf.lg[d] - (int)gf.lg[b];
+                if (e < 0) e += N;
+                const unsigned coef = gf.ex[e];
+                const unsigned moved = (unsigned)__shfl((int)Bp, lane >= sh ? lane - sh : lane);
+                const unsigned next = C ^ gf.mul(coef, lane >= sh ? moved : 0u);
+                if (2 * L <= r) {
+                    L = r + 1 - L;
+                    if (L > t) { fail = true; break; }
+                    Bp = C;
+                    b = d;
+                    sh = 1;
+                } else {
+                    ++sh;
+                }
+                C = next;
+            }
+            if (!fail && __shfl((int)C, L) == 0) fail = true;     // sigma of a lower degree than its length: fewer than L roots
+            int count = 0;
+            if (!fail) {
+                if (lane <= L) clog[lane] = C ? gf.lg[C] : (uint16_t)0xFFFF;
+                wave_sync();
+                for (int c0 = 0; c0 < nw; c0 += 4) {              // four chunks share the read of clog[q]; their gathers are independent
+                    int kk[4], qk[4];
+                    unsigned v[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int d = n - 1 - ((c0 + u) * 64 + lane);
+                        kk[u] = d > 0 ? N - d : 0;                // -d mod N; a lane past the word's end computes a value nobody reads
+                        qk[u] = 0;
+                        v[u] = 1u;                                // C_0 = 1
+                    }
+                    for (int q = 1; q <= L; ++q) {
+                        const int cl = clog[q];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            qk[u] += kk[u];
+                            if (qk[u] >= N) qk[u] -= N;
+                        }
+                        if (cl != 0xFFFF) {
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                int e = cl + qk[u];
+                                if (e >= N) e -= N;
+                                v[u] ^= gf.ex[e];
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int i = (c0 + u) * 64 + lane;
+                        const unsigned long long roots = __ballot(i < n && v[u] == 0u);
+                        if (lane == 0 && c0 + u < nw) fm[c0 + u] = roots;
+                        count += __popcll(roots);
+                    }
+                }
+                if (count != L) fail = true;
+            }
+            errors = fail ? -1 : L;
+            wave_sync();
+        }
+        const bool flip = errors > 0;
+        for (int c = 0; c < nw; ++c) {
+            const int i = c * 64 + lane;
+            const unsigned long long w = flip ? rw[c] ^ fm[c] : rw[c];
+            const uint8_t bit = (uint8_t)((w >> lane) & 1ull);
+            if (a.word && i < n) a.word[cw * n + i] = bit;
+            if (a.bits && i < k) a.bits[cw * k + i] = bit;
+        }
+        if (a.errors && lane == 0) a.errors[cw] = errors;
+    }
+}
+
+struct BchEncArgs {
+    const uint8_t *msg;                    // [B][k], bit 0 of every byte
+    uint8_t *out;                          // [B][n]
+    int64_t B;
+    int n, k, deg;
+    uint64_t gen[CPX_BCH_MAX_GEN_WORDS];
+};
+
+template <int RW>
+__global__ __launch_bounds__(BCH_ENC_THREADS) void bch_encode_kernel(BchEncArgs a) {
+    const int lane = threadIdx.x & 63, waves = BCH_ENC_THREADS / 64;
+    const int n = a.n, k = a.k, deg = a.deg;
+    const int top_bit = (deg - 1) & 63;                           // of word RW - 1 = (deg - 1) / 64
+    const unsigned long long top_mask = top_bit == 63 ? ~0ull : ((1ull << (top_bit + 1)) - 1ull);
+    const int64_t groups = (a.B + 63) / 64;
+    for (int64_t g = (int64_t)blockIdx.x * waves + (threadIdx.x >> 6); g < groups; g += (int64_t)gridDim.x * waves) {
+        const int64_t w0 = g * 64;
+        const int rows = a.B - w0 < 64 ? (int)(a.B - w0) : 64;
+        unsigned long long R[RW];
+#pragma unroll
+        for (int q = 0; q < RW; ++q) R[q] = 0ull;
+        for (int c0 = 0; c0 < k; c0 += 64) {
+            const int i = c0 + lane;
+            unsigned long long bits = 0ull;
+            for (int r = 0; r < rows; ++r) {
+                int bit = 0;
+                if (i < k) {
+                    bit = a.msg[(w0 + r) * k + i] & 1;
+                    a.out[(w0 + r) * n + i] = (uint8_t)bit;
+                }
+                const unsigned long long w = __ballot(bit);
+                if (lane == r) bits = w;
+            }
+            const int steps = k - c0 < 64 ? k - c0 : 64;
+            for (int s = 0; s < steps; ++s) {
+                const unsigned long long fb = ((R[RW - 1] >> top_bit) ^ (bits >> s)) & 1ull;
+                const unsigned long long take = 0ull - fb;
+#pragma unroll
+                for (int q = RW - 1; q >= 1; --q) R[q] = ((R[q] << 1) | (R[q - 1] >> 63)) ^ (a.gen[q] & take);
+                R[0] = (R[0] << 1) ^ (a.gen[0] & take);
+            }
+        }
+        R[RW - 1] &= top_mask;
+        // parity bit p (0 .. deg - 1) of a word is the coefficient of x^(deg - 1 - p)
+        for (int p0 = 0; p0 < deg; p0 += 64) {
+            const int p = p0 + lane, x = deg - 1 - p;
+            for (int r = 0; r < rows; ++r) {
+                unsigned long long v = 0ull;
+#pragma unroll
+                for (int q = 0; q < RW; ++q) {
+                    const unsigned long long wq = __shfl(R[q], r);
+                    if (p < deg && (x >> 6) == q) v = wq;
+                }
+                if (p < deg) a.out[(w0 + r) * n + k + p] = (uint8_t)((v >> (x & 63)) & 1ull);
+            }
+        }
+    }
+}
+
+template <int RW>
+void launch_encode(const BchEncArgs &a, hipStream_t st) {
+    const int64_t groups = (a.B + 63) / 64, wgs = (groups + BCH_ENC_THREADS / 64 - 1) / (BCH_ENC_THREADS / 64);
+    hipLaunchKernelGGL(bch_encode_kernel<RW>, dim3(grid_of(wgs, (int64_t)device_cus() * 8)), dim3(BCH_ENC_THREADS), 0, st, a);
+}
+
+int check_batch(const cpx_bch *p, int64_t B, const char *what) {
+    CPX_REQUIRE(p, CPX_EINVAL, "%s: null handle", what);
+    CPX_REQUIRE(B >= 0, CPX_EINVAL, "%s: B = %lld", what, (long long)B);
+    return CPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cpx_bch_create(int m, uint32_t prim_poly, int n, int t, const uint8_t *genpoly_bits, int genpoly_degree, cpx_bch **out) {
+    CPX_TRACE("cpx_bch_create");
+    CPX_REQUIRE(out, CPX_EINVAL, "bch: null pointer");
+    *out = nullptr;
+    CPX_REQUIRE(genpoly_bits, CPX_EINVAL, "bch: null pointer");
+    CPX_REQUIRE(m >= CPX_BCH_MIN_M && m <= CPX_BCH_MAX_M, CPX_ELIMIT, "bch: m = %d is outside the engine's range %d .. %d", m, CPX_BCH_MIN_M,
+                CPX_BCH_MAX_M);
+    CPX_REQUIRE(t >= 1 && t <= CPX_BCH_MAX_T, CPX_ELIMIT, "bch: t = %d is outside the engine's range 1 .. %d", t, CPX_BCH_MAX_T);
+    const int N = (1 << m) - 1;
+    CPX_REQUIRE(n >= 2 && n <= N, CPX_ELIMIT, "bch: n = %d is outside 2 .. 2^m - 1 = %d", n, N);
+    CPX_REQUIRE(2 * t < N, CPX_ELIMIT, "bch: t = %d, need 2 t < 2^m - 1 = %d", t, N);
+    CPX_REQUIRE((prim_poly >> m) == 1u, CPX_EINVAL, "bch: prim_poly = %u has not degree m = %d", prim_poly, m);
+    std::vector<uint16_t> tab((size_t)2 << m, 0);
+    uint16_t *ex = tab.data(), *lg = ex + ((size_t)1 << m);
+    unsigned v = 1;
+    for (int e = 0; e < N; ++e) {
+        CPX_REQUIRE(e == 0 || v != 1u, CPX_EINVAL, "bch: prim_poly = %u is not primitive (x has order %d, not %d)", prim_poly, e, N);
+        ex[e] = (uint16_t)v;
+        lg[v] = (uint16_t)e;
+        v <<= 1;
+        if (v >> m) v ^= prim_poly;
+    }
+    CPX_REQUIRE(v == 1u, CPX_EINVAL, "bch: prim_poly = %u is not primitive (x does not return to 1 after %d steps)", prim_poly, N);
+    ex[N] = 1;
+    const int deg = genpoly_degree;
+    CPX_REQUIRE(deg >= 1 && deg < n, CPX_EINVAL, "bch: the generator's degree %d is outside 1 .. n - 1 = %d", deg, n - 1);
+    CPX_REQUIRE(deg <= 64 * CPX_BCH_MAX_GEN_WORDS, CPX_ELIMIT, "bch: the generator's degree %d is above the engine's limit of %d", deg,
+                64 * CPX_BCH_MAX_GEN_WORDS);
+    for (int i = 0; i <= deg; ++i)
+        CPX_REQUIRE(genpoly_bits[i] <= 1, CPX_EINVAL, "bch: genpoly_bits[%d] = %d, need 0 or 1", i, (int)genpoly_bits[i]);
+    CPX_REQUIRE(genpoly_bits[deg] == 1, CPX_EINVAL, "bch: the generator's coefficient of x^%d is zero", deg);
+    CPX_REQUIRE(genpoly_bits[0] == 1, CPX_EINVAL, "bch: the generator has no constant term");
+    for (int j = 1; j <= 2 * t; ++j) {                           // g(alpha^j), by Horner
+        unsigned acc = 0;
+        for (int i = deg; i >= 0; --i) {
+            if (acc) acc = ex[(lg[acc] + j) % N];
+            acc ^= genpoly_bits[i];
+        }
+        CPX_REQUIRE(acc == 0, CPX_EINVAL, "bch: the generator does not vanish at alpha^%d", j);
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    cpx_bch *p = new cpx_bch();
+    p->m = m;
+    p->N = N;
+    p->n = n;
+    p->t = t;
+    p->deg = deg;
+    p->k = n - deg;
+    for (uint64_t &w : p->gen) w = 0;
+    for (int i = 0; i < deg; ++i)
+        if (genpoly_bits[i]) p->gen[i >> 6] |= 1ull << (i & 63);
+    (void)hipGetDevice(&p->device);
+    if ((rc = upload((void **)&p->d_tab, tab.data(), sizeof(uint16_t) * tab.size(), "bch"))) {
+        cpx_bch_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return CPX_OK;
+}
+
+int cpx_bch_destroy(cpx_bch *p) {
+    if (!p) return CPX_OK;
+    (void)hipFree(p->d_tab);
+    delete p;
+    return CPX_OK;
+}
+
+int cpx_bch_encode_dev(const cpx_bch *p, const uint8_t *d_msg, int64_t B, uint8_t *d_word, void *stream) {
+    CPX_TRACE("cpx_bch_encode_dev");
+    if (int rc = check_batch(p, B, "bch_encode")) return rc;
+    if (B == 0) return CPX_OK;
+    CPX_REQUIRE(d_msg && d_word, CPX_EINVAL, "bch_encode: null pointer");
+    if (int rcd = check_handle_device(p->device, "bch_encode")) return rcd;
+    BchEncArgs a;
+    a.msg = d_msg;
+    a.out = d_word;
+    a.B = B;
+    a.n = p->n;
+    a.k = p->k;
+    a.deg = p->deg;
+    for (int q = 0; q < CPX_BCH_MAX_GEN_WORDS; ++q) a.gen[q] = p->gen[q];
+    hipStream_t st = pick_stream(stream);
+    switch ((p->deg + 63) / 64) {
+    case 1: launch_encode<1>(a, st); break;
+    case 2: launch_encode<2>(a, st); break;
+    case 3: launch_encode<3>(a, st); break;
+    case 4: launch_encode<4>(a, st); break;
+    case 5: launch_encode<5>(a, st); break;
+    case 6: launch_encode<6>(a, st); break;
+    default: launch_encode<7>(a, st); break;
+    }
+    CPX_HIP(hipGetLastError());
+    note_kernel("bch_encode_kernel<%d>", (p->deg + 63) / 64);
+    return CPX_OK;
+}
+
+int cpx_bch_encode(const cpx_bch *p, const uint8_t *msg, int64_t B, uint8_t *word) {
+    CPX_TRACE("cpx_bch_encode");
+    if (int rc = check_batch(p, B, "bch_encode")) return rc;
+    if (B == 0) return CPX_OK;
+    CPX_REQUIRE(msg && word, CPX_EINVAL, "bch_encode: null pointer");
+    int rc = ensure_device();
+    if (rc) return rc;
+    const size_t in_bytes = (size_t)B * (size_t)p->k, out_bytes = (size_t)B * (size_t)p->n;
+    HostStage s;
+    const uint8_t *din;
+    uint8_t *dout;
+    if ((rc = s.in(msg, in_bytes, &din)) || (rc = s.out(out_bytes, &dout)) || (rc = cpx_bch_encode_dev(p, din, B, dout, s.st))) return rc;
+    return s.get(word, dout, out_bytes);
+}
+
+int cpx_bch_decode_dev(const cpx_bch *p, const uint8_t *d_in, int64_t B, uint8_t *d_bits, uint8_t *d_word, int32_t *d_errors, void *stream) {
+    CPX_TRACE("cpx_bch_decode_dev");
+    if (int rc = check_batch(p, B, "bch_decode")) return rc;
+    CPX_REQUIRE(d_bits || d_word || d_errors, CPX_EINVAL, "bch_decode: no output requested");
+    if (B == 0) return CPX_OK;
+    CPX_REQUIRE(d_in, CPX_EINVAL, "bch_decode: null pointer");
+    if (int rcd = check_handle_device(p->device, "bch_decode")) return rcd;
+    const int nw = (p->n + 63) / 64, waves = bch_waves(p->m);
+    const unsigned lds = (bch_tab_lds(p->m) + (unsigned)waves * bch_wave_lds(nw) + 15u) & ~15u;
+    CPX_REQUIRE(lds <= CPX_BCH_LDS_MAX, CPX_ELIMIT, "bch_decode: m = %d, n = %d needs %u bytes of LDS", p->m, p->n, lds);
+    static std::mutex raised_mu;
+    static bool raised[64] = {};
+    {
+        std::lock_guard<std::mutex> lk(raised_mu);
+        if (p->device >= 0 && p->device < 64 && !raised[p->device]) {
+            CPX_HIP(hipFuncSetAttribute((const void *)bch_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CPX_BCH_LDS_MAX));
+            raised[p->device] = true;
+        }
+    }
+    BchDecArgs a{d_in, p->d_tab, B, p->m, p->N, p->n, p->k, p->t, nw, d_bits, d_word, d_errors};
+    // workgroups resident at once: as many per compute unit as the LDS of a workgroup allows, at most 32 waves
+    int per_cu = (int)(CPX_BCH_LDS_MAX / lds);
+    if (per_cu > 32 / waves) per_cu = 32 / waves;
+    const int64_t wgs = (B + waves - 1) / waves;
+    hipLaunchKernelGGL(bch_decode_kernel, dim3(grid_of(wgs, (int64_t)device_cus() * per_cu)), dim3(waves * 64), lds, pick_stream(stream), a);
+    CPX_HIP(hipGetLastError());
+    note_kernel("bch_decode_kernel");
+    return CPX_OK;
+}
+
+int cpx_bch_decode(const cpx_bch *p, const uint8_t *in, int64_t B, uint8_t *bits, uint8_t *word, int32_t *errors) {
+    CPX_TRACE("cpx_bch_decode");
+    if (int rc = check_batch(p, B, "bch_decode")) return rc;
+    CPX_REQUIRE(bits || word || errors, CPX_EINVAL, "bch_decode: no output requested");
+    if (B == 0) return CPX_OK;
+    CPX_REQUIRE(in, CPX_EINVAL, "bch_decode: null pointer");
+    int rc = ensure_device();
+    if (rc) return rc;
+    const size_t b = (size_t)B;
+    struct Out { void *host; size_t bytes; void *dev; } outs[3] = {
+        {bits, b * (size_t)p->k, nullptr}, {word, b * (size_t)p->n, nullptr}, {errors, 4 * b, nullptr}};
+    HostStage s;
+    const uint8_t *din;
+    if ((rc = s.in(in, b * (size_t)p->n, &din))) return rc;
+    for (Out &o : outs)
+        if (o.host && (rc = s.out(o.bytes, &o.dev))) return rc;
+    if ((rc = cpx_bch_decode_dev(p, din, B, (uint8_t *)outs[0].dev, (uint8_t *)outs[1].dev, (int32_t *)outs[2].dev, s.st))) return rc;
+    for (Out &o : outs)
+        if (o.host && (rc = s.get(o.host, o.dev, o.bytes))) return rc;
+    return CPX_OK;
+}
+
+}  // extern "C"

@@ -16,7 +16,8 @@ from commpy_amd.channelcoding.ldpc import build_matrix
 __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu', 'mimo_channel_gpu', 'puncturing_gpu',
            'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder', 'gf2_generator',
            'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
-           'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev']
+           'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev',
+           'bch_encode_dev', 'bch_decode_dev']
 
 
 class DeviceBuf:
@@ -511,5 +512,37 @@ def polar_decode_dev(code, d_llr, B, list_size=1, want=('bits',), stream=None):
                                                     p(out.get('metric')), p(out.get('u_llr')), p(lst[0]), p(lst[1]), p(lst[2]), stream))
     if 'list' in want:
         out['list'] = lst
+    res = tuple(out[k] for k in WANT if k in want)
+    return res[0] if len(res) == 1 else res
+
+
+# ---- BCH codes, device resident (csrc/bch.hip) --------------------------------------------------------------------------------------
+
+def bch_encode_dev(code, d_msg, B, stream=None):
+    """``cpx_bch_encode_dev``: ``d_msg [B][k]`` uint8 -> a new ``DeviceBuf`` ``[B][n]`` uint8 of code words, queued on ``stream``
+    (None: the library's); ``code`` is a ``channelcoding.BCHCode``."""
+    from commpy_amd.channelcoding.bch import _code
+    from commpy_amd.channelcoding.gfields import whole
+    code, B = _code(code), whole(B, 'B', 0)
+    d_x = DeviceBuf(B * code.n)
+    if B:
+        _lib.check(d_x.lib.cpx_bch_encode_dev(code._device_handle(), d_msg.ptr, B, d_x.ptr, stream))
+    return d_x
+
+
+def bch_decode_dev(code, d_bits, B, want=('bits',), stream=None):
+    """``cpx_bch_decode_dev``: ``d_bits [B][n]`` uint8 hard decisions (non-zero = 1) -> new ``DeviceBuf``s, the results of
+    ``channelcoding.bch_decode`` that ``want`` names, in its order: 'bits' ``[B][k]`` uint8, 'codeword' ``[B][n]`` uint8, 'errors'
+    ``[B]`` int32; a single result for one name."""
+    from commpy_amd.channelcoding.bch import WANT, _code, check_want
+    from commpy_amd.channelcoding.gfields import whole
+    code, B = _code(code), whole(B, 'B', 0)
+    want = check_want(want)
+    sizes = {'bits': B * code.k, 'codeword': B * code.n, 'errors': B * 4}
+    out = {k: DeviceBuf(sizes[k]) for k in sizes if k in want}
+    if B:
+        p = lambda v: None if v is None else v.ptr
+        _lib.check(_lib.load().cpx_bch_decode_dev(code._device_handle(), d_bits.ptr, B, p(out.get('bits')), p(out.get('codeword')),
+                                                  p(out.get('errors')), stream))
     res = tuple(out[k] for k in WANT if k in want)
     return res[0] if len(res) == 1 else res

@@ -802,6 +802,31 @@ int cpx_polar_decode(const cpx_polar *p, const double *llr, int64_t B, int L, ui
 int cpx_polar_decode_dev(const cpx_polar *p, const double *d_llr, int64_t B, int L, uint8_t *d_bits, uint8_t *d_crc_ok, double *d_metric,
                          double *d_u_llr, uint8_t *d_list_bits, double *d_list_metric, int32_t *d_list_live, void *stream);
 
+/* ---- binary BCH codes: systematic encoder and bounded-distance decoder (csrc/bch.hip) -------------------
+ * Narrow-sense code of length n <= 2^m - 1 (shortened below that) over GF(2^m), 3 <= m <= 14, correcting t <= 32 errors.  A word is n
+ * bytes 0 / 1; byte i is the coefficient of x^(n-1-i): k = n - deg g message bits, then the n - k bits of x^(n-k) m(x) mod g(x).
+ *   cpx_bch_create   prim_poly: the field's polynomial with its leading term (bit i = coefficient of x^i); genpoly_bits [degree + 1]
+ *                    uint8, entry i = coefficient of x^i of the generator.  Checked before a device is looked for: m, t, n and a degree
+ *                    above 448 (CPX_ELIMIT); prim_poly of degree m under which x generates the multiplicative group, 1 <= degree < n,
+ *                    leading and constant coefficient 1, g(alpha^j) = 0 for j = 1 .. 2t (CPX_EINVAL).  Any such g is encoded and decoded.
+ *   cpx_bch_encode   msg [B][k] uint8 (bit 0 of a byte counts) -> word [B][n] uint8.
+ *   cpx_bch_decode   in [B][n] uint8 hard decisions (non-zero = 1).  S_1 .. S_2t all zero: accepted, 0 errors.  Else Berlekamp-Massey
+ *                    over the 2t syndromes gives sigma of length L; the word is corrected iff L <= t, sigma's coefficient of x^L is
+ *                    non-zero and sigma has exactly L roots among the inverse locators of the positions 0 .. n - 1 (a root in the
+ *                    shortened-away positions is a failure).  Outputs, each may be NULL (not all): bits [B][k] uint8, word [B][n]
+ *                    uint8, errors [B] int32 = the number of corrected bits, -1 after a failure (bits and word then hold the received
+ *                    word as 0 / 1).  Equal to tests/bch_model.py byte for byte.
+ * The _dev forms take device pointers and a stream and are asynchronous; the others take host pointers and return synchronised.
+ * B = 0 returns CPX_OK without a launch. */
+typedef struct cpx_bch cpx_bch;
+int cpx_bch_create(int m, uint32_t prim_poly, int n, int t, const uint8_t *genpoly_bits, int genpoly_degree, cpx_bch **out);
+int cpx_bch_destroy(cpx_bch *p);
+int cpx_bch_encode(const cpx_bch *p, const uint8_t *msg, int64_t B, uint8_t *word);
+int cpx_bch_encode_dev(const cpx_bch *p, const uint8_t *d_msg, int64_t B, uint8_t *d_word, void *stream);
+int cpx_bch_decode(const cpx_bch *p, const uint8_t *in, int64_t B, uint8_t *bits, uint8_t *word, int32_t *errors);
+int cpx_bch_decode_dev(const cpx_bch *p, const uint8_t *d_in, int64_t B, uint8_t *d_bits, uint8_t *d_word, int32_t *d_errors,
+                       void *stream);
+
 /* ---- multi-GPU: RCCL collectives of the sharded decode ------------------------------------
  * The path shards by codeword (contiguous blocks of B/G codewords per GPU, tables replicated) and has no exchange
  * step inside a decoder.  Two collectives exist around it:

@@ -213,6 +213,12 @@ SYMBOLS = {
     "cpx_bch_encode_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "cpx_bch_decode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "cpx_bch_decode_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpx_rs_create": (c_int, [c_int, c_uint32, c_int, c_int, c_int, c_void_p, POINTER(c_void_p)]),
+    "cpx_rs_destroy": (c_int, [c_void_p]),
+    "cpx_rs_encode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "cpx_rs_encode_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cpx_rs_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cpx_rs_decode_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cpx_comm_unique_id": (c_int, [c_void_p]),
     "cpx_comm_init_rank": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
     "cpx_comm_init_all": (c_int, [POINTER(c_int), c_int, POINTER(c_void_p)]),

@@ -1,9 +1,9 @@
-"""Generator polynomials of binary cyclic and BCH codes (host only), from the field tables of ``gfields``."""
+"""Generator polynomials of binary cyclic, BCH and Reed-Solomon codes (host only), from the field tables of ``gfields``."""
 import numpy as np
 
 from commpy_amd.channelcoding.gfields import MAX_M, clmul, field, whole
 
-__all__ = ['cyclic_code_genpoly', 'bch_genpoly']
+__all__ = ['cyclic_code_genpoly', 'bch_genpoly', 'rs_genpoly']
 
 
 def cyclic_code_genpoly(n, k):
@@ -70,4 +70,18 @@ def bch_genpoly(m, t, prim_poly=None):
             continue
         seen.update(f.coset(e))
         g = clmul(g, f.minpoly(e))
+    return g
+
+
+def rs_genpoly(m, nroots, fcr=1, prim_poly=None):
+    """The generator of the Reed-Solomon codes over GF(2^m) with ``nroots`` parity symbols:
+    ``g(x) = prod_{j < nroots} (x - alpha^(fcr + j))`` under ``prim_poly`` (None: the default of that degree), as an int64 array of
+    ``nroots + 1`` field elements in tuple form, lowest degree first (the last one is 1).  Needs ``1 <= nroots < 2^m - 1`` and
+    ``0 <= fcr < 2^m - 1``."""
+    f = field(m, prim_poly)
+    nroots, fcr = whole(nroots, 'nroots', 1, f.n - 1), whole(fcr, 'fcr', 0, f.n - 1)
+    g = np.array([1], dtype=np.int64)
+    for j in range(nroots):
+        root = np.full(len(g), f.exp[(fcr + j) % f.n], dtype=np.int64)
+        g = np.concatenate([[0], g]) ^ np.concatenate([f.mul(g, root), [0]])
     return g

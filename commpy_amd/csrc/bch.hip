@@ -20,6 +20,7 @@
 // bch_encode_kernel: one word per lane, 64 words per wave.  The wave reads 64 message bytes of each of its words at a time (a coalesced
 //   row segment, copied to the output on the way) and ballots them into one 64-bit word per lane; every lane then runs 64 steps of the long
 //   division on its own remainder of RW 64-bit words, the generator being kernel-argument data.  Nothing in it is specific to BCH codes.
+#include "cpx_gf.h"
 #include "cpx_internal.h"
 #include "cpx_wave.h"
 
@@ -333,18 +334,9 @@ int cpx_bch_create(int m, uint32_t prim_poly, int n, int t, const uint8_t *genpo
     CPX_REQUIRE(n >= 2 && n <= N, CPX_ELIMIT, "bch: n = %d is outside 2 .. 2^m - 1 = %d", n, N);
     CPX_REQUIRE(2 * t < N, CPX_ELIMIT, "bch: t = %d, need 2 t < 2^m - 1 = %d", t, N);
     CPX_REQUIRE((prim_poly >> m) == 1u, CPX_EINVAL, "bch: prim_poly = %u has not degree m = %d", prim_poly, m);
-    std::vector<uint16_t> tab((size_t)2 << m, 0);
-    uint16_t *ex = tab.data(), *lg = ex + ((size_t)1 << m);
-    unsigned v = 1;
-    for (int e = 0; e < N; ++e) {
-        CPX_REQUIRE(e == 0 || v != 1u, CPX_EINVAL, "bch: prim_poly = %u is not primitive (x has order %d, not %d)", prim_poly, e, N);
-        ex[e] = (uint16_t)v;
-        lg[v] = (uint16_t)e;
-        v <<= 1;
-        if (v >> m) v ^= prim_poly;
-    }
-    CPX_REQUIRE(v == 1u, CPX_EINVAL, "bch: prim_poly = %u is not primitive (x does not return to 1 after %d steps)", prim_poly, N);
-    ex[N] = 1;
+    std::vector<uint16_t> tab;
+    if (int rct = gf_tables("bch", m, prim_poly, tab)) return rct;
+    const uint16_t *ex = tab.data(), *lg = ex + ((size_t)1 << m);
     const int deg = genpoly_degree;
     CPX_REQUIRE(deg >= 1 && deg < n, CPX_EINVAL, "bch: the generator's degree %d is outside 1 .. n - 1 = %d", deg, n - 1);
     CPX_REQUIRE(deg <= 64 * CPX_BCH_MAX_GEN_WORDS, CPX_ELIMIT, "bch: the generator's degree %d is above the engine's limit of %d", deg,

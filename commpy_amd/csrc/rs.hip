@@ -1,0 +1,612 @@
+// Reed-Solomon codes over GF(2^m), 3 <= m <= 14: systematic encoder and bounded-distance errors-and-erasures decoder (syndromes, erasure
+// locator, Berlekamp-Massey, Chien search, Forney's values).
+//
+// A word is n symbols of 16 bits, of which the low m count; symbol i is the coefficient of x^(n-1-i): the k message symbols first, then
+// the r = n - k symbols of x^r m(x) mod g(x), g(x) = prod_{j<r} (x - alpha^(fcr+j)).  A code shortened from N = 2^m - 1 to n drops the
+// highest degrees.  The handle holds exp[e] = alpha^e and log[v] as uint16 tables of 2^m entries each and the logarithms of g.
+//
+// rs_decode_kernel<R>, R = 8, 16, 32 or 64 >= r: one received word per wave, up to 16 waves per workgroup, workgroups stride over the
+//   batch.  The two tables are staged into LDS once per workgroup; after that barrier the waves never meet again.  Per word:
+//   1. symbols and flags are read once, 64 positions per load and four loads of each in flight; every symbol is masked to m bits as it
+//      arrives.  The flags are kept as ballot words in LDS (er); the symbols are not kept: the output pass reads them again;
+//   2. syndromes, lanes over positions: a lane with symbol v at degree d adds v alpha^((fcr+j) d) to its accumulator j, j = 0 .. R-1
+//      (one table read for log v, then the exponent moves by d from j to j + 1: an add, a wrap and one gather per term); R wave XORs
+//      at the end leave S_j on lane j and in LDS.  f > r: failure.  All S_j zero: accepted, go to 8;
+//   3. Gamma, lane q holding the coefficient of x^q: one shift-multiply-XOR step per flagged position, read from the ballots;
+//   4. Berlekamp-Massey from rho = f with C = B = Gamma, lane q holding C_q and B_q, the discrepancy an XOR across the wave; it stops
+//      as a failure at the first length with 2 L - f > r;
+//   5. Chien search, four chunks at a time: the lane of degree d evaluates Lambda(alpha^-d); the ballot of the roots is kept per chunk
+//      (fm), its popcount adds to the root count, and root number j leaves its position in rpos[j].  Corrected iff Lambda_L != 0 and
+//      the count equals L;
+//   6. Omega_i = sum_q Lambda_q S_(i-q) on lane i, i < r (lane-local sums over LDS reads);
+//   7. Forney, lanes over roots (L <= 63 of them): lane j evaluates Omega and the odd part of Lambda at the alpha^-d of root j and
+//      keeps Y = alpha^(-d fcr) Omega / Lambda_odd (Lambda_odd(x) = x Lambda'(x)) in LDS: one pass however long the word;
+//   8. symbols out, read again chunk by chunk and masked; a root lane XORs the Y of its root number into its symbol.
+// rs_encode_kernel<R>: one word per lane, 64 words per wave, the remainder in R registers per lane (g is taken as x^(R-r) g(x), so
+//   that the register indices are static).  The wave reads 64 message symbols of each of its words at a time (coalesced row segments,
+//   masked, copied to the output on the way) into a padded LDS tile, every lane then runs 64 division steps along its own row:
+//   log of the feedback symbol, then one gather per remainder symbol with the generator's logarithms as kernel-argument data.  The
+//   parity symbols leave through the same tile, so that the global writes are row segments as well.
+#include "cpx_gf.h"
+#include "cpx_internal.h"
+#include "cpx_wave.h"
+
+#include <mutex>
+
+using namespace cpx;
+
+#define CPX_RS_MIN_M 3
+#define CPX_RS_MAX_M 14
+#define CPX_RS_MAX_R 63                    // a polynomial of degree r has a coefficient per lane
+#define CPX_RS_LDS_MAX (160 * 1024)
+#define RS_MAX_WAVES 16
+#define RS_ENC_WAVES 4
+#define RS_TILE_PITCH 66                   // uint16 per tile row: 33 dwords, so that the lanes' rows start on distinct banks
+#define RS_NONE 0xFFFFu                    // "logarithm" of a zero coefficient
+
+struct cpx_rs {
+    __attribute__((visibility("hidden"))) ~cpx_rs() = default;
+    int m, N, n, k, r, fcr, device;
+    uint16_t glog[64];                     // log of g's coefficient of x^i, i < r; RS_NONE for zero
+    uint16_t *d_tab = nullptr;             // [2][2^m]: exp then log
+};
+
+namespace {
+
+__host__ __device__ inline unsigned gf_tab_lds(int m) { return 4u << m; }      // bytes of the two tables
+
+// orders this wave's LDS writes before its later reads (the waves never meet after the staging barrier)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ unsigned wave_xor(unsigned v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v ^= (unsigned)__shfl_xor((int)v, d);
+    return v;
+}
+
+// the tables in LDS; every index a caller forms must lie in 0 .. 2^m - 1
+struct Gf {
+    const uint16_t *ex, *lg;
+    int N;
+    __device__ __forceinline__ unsigned mul(unsigned a, unsigned b) const {
+        if (a == 0u || b == 0u) return 0u;
+        int e = (int)lg[a] + (int)lg[b];
+        if (e >= N) e -= N;
+        return ex[e];
+    }
+};
+
+// copies the tables into LDS at `base` (all threads of the workgroup, barrier included)
+__device__ __forceinline__ Gf gf_stage(unsigned char *base, const uint16_t *tab, int m) {
+    uint32_t *dst = reinterpret_cast<uint32_t *>(base);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(tab);
+    for (int i = threadIdx.x; i < (1 << m); i += blockDim.x) dst[i] = src[i];
+    __syncthreads();
+    Gf gf;
+    gf.ex = reinterpret_cast<const uint16_t *>(base);
+    gf.lg = gf.ex + (1 << m);
+    gf.N = (1 << m) - 1;
+    return gf;
+}
+
+struct RsDecArgs {
+    const uint16_t *in;                    // [B][n]
+    const uint8_t *erased;                 // [B][n] or null
+    const uint16_t *tab;
+    int64_t B;
+    int m, N, n, k, r, fcr, nw;            // nw = ceil(n / 64)
+    uint16_t *symbols, *word;              // [B][k], [B][n]
+    int32_t *errors;                       // [B]
+};
+
+// bytes of LDS per wave: er and fm (nw 64-bit words each), then S (later Y), log Lambda, log Omega and the roots' positions (64 uint16 each)
+__host__ __device__ inline unsigned rs_wave_lds(int nw) { return 16u * (unsigned)nw + 4u * 2u * 64u; }
+
+// waves per workgroup: small tables leave room for several workgroups per compute unit
+inline int rs_waves(int m) { return m <= 8 ? 4 : m <= 11 ? 8 : RS_MAX_WAVES; }
+
+template <int R>
+__global__ __launch_bounds__(RS_MAX_WAVES * 64) void rs_decode_kernel(RsDecArgs a) {
+    extern __shared__ double2 rs_lds_raw[];
+    unsigned char *base = reinterpret_cast<unsigned char *>(rs_lds_raw);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
+    const int n = a.n, k = a.k, r = a.r, N = a.N, nw = a.nw, fcr = a.fcr;
+    const unsigned mask = (1u << a.m) - 1u;
+    const Gf gf = gf_stage(base, a.tab, a.m);
+    unsigned char *mine = base + gf_tab_lds(a.m) + (unsigned)wave * rs_wave_lds(nw);
+    unsigned long long *er = reinterpret_cast<unsigned long long *>(mine), *fm = er + nw;
+    uint16_t *synd = reinterpret_cast<uint16_t *>(fm + nw), *clog = synd + 64, *olog = clog + 64, *rpos = olog + 64, *yv = synd;
+    const int fstep = (int)((64u * (unsigned)fcr) % (unsigned)N);  // fcr d mod N moves by this from one chunk to the next
+
+    for (int64_t cw = (int64_t)blockIdx.x * waves + wave; cw < a.B; cw += (int64_t)gridDim.x * waves) {
+        wave_sync();                                              // the previous word's arrays have been read
+        const uint16_t *in = a.in + cw * n;
+        const uint8_t *flag = a.erased ? a.erased + cw * n : nullptr;
+        const int d0 = n - 1 - lane;                              // the degree of this lane's position in chunk 0; negative: no position
+        // ---- 1, 2: symbols, flags, syndromes
+        unsigned acc[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) acc[u] = 0u;
+        int f = 0;
+        int fd = d0 > 0 ? (int)(((unsigned)fcr * (unsigned)d0) % (unsigned)N) : 0;       // fcr d0 < 2^28
+        for (int c0 = 0; c0 < nw; c0 += 4) {
+            unsigned sym[4];
+            uint8_t fl[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = (c0 + u) * 64 + lane;
+                sym[u] = i < n ? (unsigned)in[i] & mask : 0u;     // only the low m bits of a symbol count
+                fl[u] = flag && i < n ? flag[i] : (uint8_t)0;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const unsigned long long w = __ballot(fl[u] != 0);
+                if (c0 + u < nw) {
+                    if (lane == 0) { er[c0 + u] = w; fm[c0 + u] = 0ull; }
+                    f += __popcll(w);
+                }
+            }
+#pragma nounroll
+            for (int u = 0; u < 4; ++u) {                         // one copy of the R gathers: u is uniform, the selects are cheap
+                const unsigned v = u == 0 ? sym[0] : u == 1 ? sym[1] : u == 2 ? sym[2] : sym[3];
+                int d = d0 - (c0 + u) * 64;
+                if (d < 0) d = 0;                                 // past the word's end: v is 0
+                const unsigned take = v ? 0xFFFFu : 0u;
+                int e = (int)gf.lg[v] + fd;
+                if (e >= N) e -= N;
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    acc[j] ^= gf.ex[e] & take;                    // e stays in 0 .. N - 1 on every lane
+                    e += d;
+                    if (e >= N) e -= N;
+                }
+                fd -= fstep;
+                if (fd < 0) fd += N;
+            }
+        }
+        unsigned S = 0u;
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const unsigned s = wave_xor(acc[j]);
+            if (lane == j) S = s;
+        }
+        if (lane >= r) S = 0u;
+        synd[lane] = (uint16_t)S;
+        wave_sync();
+        int errors = 0, L = 0;
+        bool fail = f > r;
+        const bool dirty = __ballot(S != 0u) != 0ull;
+        if (!fail && dirty) {
+            // ---- 3: the erasure locator, coefficient q on lane q
+            unsigned C = lane == 0 ? 1u : 0u;
+            for (int c = 0; c < nw && f > 0; ++c) {
+                unsigned long long w = er[c];
+                while (w) {
+                    const int b = __ffsll((long long)w) - 1;
+                    w &= w - 1ull;
+                    const int d = n - 1 - (c * 64 + b);           // 0 .. N - 1: the logarithm of the locator alpha^d
+                    const unsigned below = (unsigned)__shfl((int)C, lane > 0 ? lane - 1 : 0);
+                    unsigned term = 0u;
+                    if (lane > 0 && below) {
+                        int e = (int)gf.lg[below] + d;
+                        if (e >= N) e -= N;
+                        term = gf.ex[e];
+                    }
+                    C ^= term;
+                }
+            }
+            // ---- 4: Berlekamp-Massey from rho = f: C the connection polynomial, Bp the one before the last length change, b its
+            // discrepancy, sh the shift
+            unsigned Bp = C, b = 1u;
+            int sh = 1;
+            L = f;
+            for (int rho = f; rho < r; ++rho) {
+                const unsigned d = wave_xor(lane <= L ? gf.mul(C, synd[rho - lane]) : 0u);       // L <= rho
+                if (d == 0u) { ++sh; continue; }
+                int e = (int)gf.lg[d] - (int)gf.lg[b];
+                if (e < 0) e += N;
+                const unsigned coef = gf.ex[e];
+                const unsigned moved = (unsigned)__shfl((int)Bp, lane >= sh ? lane - sh : lane);
+                const unsigned next = C ^ gf.mul(coef, lane >= sh ? moved : 0u);
+                if (2 * L <= rho + f) {
+                    L = rho + 1 - L + f;
+                    if (2 * L - f > r) { fail = true; break; }    // L only grows
+                    Bp = C;
+                    b = d;
+                    sh = 1;
+                } else {
+                    ++sh;
+                }
+                C = next;
+            }
+            if (!fail && __shfl((int)C, L) == 0) fail = true;     // Lambda of a lower degree than its length: fewer than L roots
+            if (!fail) {
+                // ---- 5: Chien search
+                clog[lane] = lane <= L && C ? gf.lg[C] : (uint16_t)RS_NONE;
+                wave_sync();
+                int count = 0;
+                for (int c0 = 0; c0 < nw; c0 += 4) {              // four chunks share the read of clog[q]; their gathers are independent
+                    int kk[4], qk[4];
+                    unsigned v[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int d = n - 1 - ((c0 + u) * 64 + lane);
+                        kk[u] = d > 0 ? N - d : 0;                // -d mod N; a lane past the word's end computes a value nobody reads
+                        qk[u] = 0;
+                        v[u] = 1u;                                // Lambda_0 = 1
+                    }
+                    for (int q = 1; q <= L; ++q) {
+                        const int cl = clog[q];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            qk[u] += kk[u];
+                            if (qk[u] >= N) qk[u] -= N;
+                        }
+                        if (cl != (int)RS_NONE) {
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                int e = cl + qk[u];
+                                if (e >= N) e -= N;
+                                v[u] ^= gf.ex[e];
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int i = (c0 + u) * 64 + lane;
+                        const unsigned long long roots = __ballot(i < n && v[u] == 0u);
+                        if (lane == 0 && c0 + u < nw) fm[c0 + u] = roots;
+                        const int at = count + __popcll(roots & ((1ull << lane) - 1ull));
+                        if (((roots >> lane) & 1ull) && at < 64) rpos[at] = (uint16_t)i;      // Lambda has at most L <= 63 roots
+                        count += __popcll(roots);
+                    }
+                }
+                if (count != L) fail = true;
+            }
+            if (!fail) {
+                // ---- 6: Omega = S Lambda mod x^r, coefficient i on lane i
+                unsigned om = 0u;
+                for (int q = 0; q <= L; ++q) {
+                    const int cl = clog[q];
+                    if (cl == (int)RS_NONE) continue;
+                    const unsigned s = lane >= q && lane < r ? (unsigned)synd[lane - q] : 0u;
+                    int e = cl + (int)gf.lg[s];
+                    if (e >= N) e -= N;
+                    om ^= s ? (unsigned)gf.ex[e] : 0u;
+                }
+                olog[lane] = om ? gf.lg[om] : (uint16_t)RS_NONE;
+                wave_sync();
+                // ---- 7: Forney, root number `lane` on lane `lane`: Omega and the odd part of Lambda at alpha^-d
+                const int d = lane < L ? n - 1 - (int)rpos[lane] : 0;
+                const int kk = d > 0 ? N - d : 0;
+                int qk = 0;
+                unsigned ov = olog[0] != RS_NONE ? (unsigned)gf.ex[olog[0]] : 0u, odd = 0u;
+                for (int q = 1; q <= r; ++q) {                    // L <= r
+                    qk += kk;
+                    if (qk >= N) qk -= N;
+                    const int ol = q < r ? (int)olog[q] : (int)RS_NONE, cl = (q & 1) && q <= L ? (int)clog[q] : (int)RS_NONE;
+                    if (ol != (int)RS_NONE) {
+                        int e = ol + qk;
+                        if (e >= N) e -= N;
+                        ov ^= gf.ex[e];
+                    }
+                    if (cl != (int)RS_NONE) {
+                        int e = cl + qk;
+                        if (e >= N) e -= N;
+                        odd ^= gf.ex[e];
+                    }
+                }
+                unsigned Y = 0u;
+                if (ov) {                                         // at a root odd = alpha^-d Lambda'(alpha^-d) is not zero: L simple roots
+                    const int back = (int)(((unsigned)fcr * (unsigned)d) % (unsigned)N);
+                    int e = (int)gf.lg[ov] - (int)gf.lg[odd] - back;
+                    if (e < 0) e += N;
+                    if (e < 0) e += N;
+                    Y = gf.ex[e];
+                }
+                yv[lane] = (uint16_t)Y;                           // over the syndromes: Omega has been formed
+            }
+            errors = fail ? -1 : L - f;
+            wave_sync();
+        } else if (fail) {
+            errors = -1;
+        }
+        // ---- 8: symbols out, read again; root number j of the word takes yv[j]
+        const bool fix = !fail && dirty;
+        int seen = 0;
+        for (int c = 0; c < nw; ++c) {
+            const int i = c * 64 + lane;
+            unsigned sym = i < n ? (unsigned)in[i] & mask : 0u;
+            const unsigned long long roots = fix ? fm[c] : 0ull;
+            if ((roots >> lane) & 1ull) sym ^= yv[(seen + __popcll(roots & ((1ull << lane) - 1ull))) & 63];
+            seen += __popcll(roots);
+            if (a.word && i < n) a.word[cw * n + i] = (uint16_t)sym;
+            if (a.symbols && i < k) a.symbols[cw * k + i] = (uint16_t)sym;
+        }
+        if (a.errors && lane == 0) a.errors[cw] = errors;
+    }
+}
+
+struct RsEncArgs {
+    const uint16_t *msg;                   // [B][k]
+    const uint16_t *tab;
+    uint16_t *out;                         // [B][n]
+    int64_t B;
+    int m, N, n, k, r;
+    uint16_t glog[64];                     // of x^(R-r) g(x) without its leading term: entry R - r + i = log g_i, RS_NONE below
+};
+
+template <int R>
+__global__ __launch_bounds__(RS_ENC_WAVES * 64) void rs_encode_kernel(RsEncArgs a) {
+    extern __shared__ double2 rs_lds_raw[];
+    unsigned char *base = reinterpret_cast<unsigned char *>(rs_lds_raw);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = a.n, k = a.k, r = a.r, N = a.N;
+    const unsigned mask = (1u << a.m) - 1u;
+    const Gf gf = gf_stage(base, a.tab, a.m);
+    uint16_t *tile = reinterpret_cast<uint16_t *>(base + gf_tab_lds(a.m)) + (size_t)wave * 64 * RS_TILE_PITCH;
+    const int64_t groups = (a.B + 63) / 64;
+    for (int64_t g = (int64_t)blockIdx.x * RS_ENC_WAVES + wave; g < groups; g += (int64_t)gridDim.x * RS_ENC_WAVES) {
+        const int64_t w0 = g * 64;
+        const int rows = a.B - w0 < 64 ? (int)(a.B - w0) : 64;
+        unsigned Rm[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) Rm[q] = 0u;
+        for (int c0 = 0; c0 < k; c0 += 64) {
+            const int i = c0 + lane;
+            wave_sync();                                          // the tile's previous content has been read
+            for (int r0 = 0; r0 < rows; r0 += 8) {                // eight loads in flight
+                unsigned v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = i < k && r0 + u < rows ? (unsigned)a.msg[(w0 + r0 + u) * k + i] & mask : 0u;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    if (r0 + u < rows) {
+                        if (i < k) a.out[(w0 + r0 + u) * n + i] = (uint16_t)v[u];
+                        tile[(r0 + u) * RS_TILE_PITCH + lane] = (uint16_t)v[u];
+                    }
+                }
+            }
+            wave_sync();
+            const int steps = k - c0 < 64 ? k - c0 : 64;
+            for (int s = 0; s < steps; ++s) {
+                const unsigned in = lane < rows ? (unsigned)tile[lane * RS_TILE_PITCH + s] : 0u;
+                const unsigned fb = Rm[R - 1] ^ in;               // below 2^m: both were masked or came out of the table
+                const unsigned take = fb ? 0xFFFFu : 0u;
+                const int lf = gf.lg[fb];
+#pragma unroll
+                for (int q = R - 1; q >= 1; --q) {
+                    unsigned term = 0u;
+                    if (a.glog[q] != RS_NONE) {                   // uniform: kernel-argument data
+                        int e = lf + (int)a.glog[q];
+                        if (e >= N) e -= N;
+                        term = gf.ex[e] & take;
+                    }
+                    Rm[q] = Rm[q - 1] ^ term;
+                }
+                {
+                    unsigned term = 0u;
+                    if (a.glog[0] != RS_NONE) {
+                        int e = lf + (int)a.glog[0];
+                        if (e >= N) e -= N;
+                        term = gf.ex[e] & take;
+                    }
+                    Rm[0] = term;
+                }
+            }
+        }
+        // parity symbol p (0 .. r - 1) of a word is the coefficient of x^(r - 1 - p): register R - 1 - p
+        wave_sync();
+#pragma unroll
+        for (int p = 0; p < R; ++p)
+            if (p < r) tile[lane * RS_TILE_PITCH + p] = (uint16_t)Rm[R - 1 - p];
+        wave_sync();
+        if (lane < r)
+            for (int row = 0; row < rows; ++row) a.out[(w0 + row) * n + k + lane] = tile[row * RS_TILE_PITCH + lane];
+    }
+}
+
+inline int rs_regs(int r) { return r <= 8 ? 8 : r <= 16 ? 16 : r <= 32 ? 32 : 64; }
+inline unsigned rs_enc_lds(int m) { return (gf_tab_lds(m) + RS_ENC_WAVES * 64u * RS_TILE_PITCH * 2u + 15u) & ~15u; }
+
+// dynamic LDS above 64 KiB has to be allowed once per kernel and device
+int raise_lds(const void *fn, int slot, int device) {
+    static std::mutex mu;
+    static bool raised[8][64] = {};
+    CPX_REQUIRE(device >= 0 && device < 64, CPX_ELIMIT, "rs: device index %d is outside 0 .. 63", device);
+    std::lock_guard<std::mutex> lk(mu);
+    if (!raised[slot][device]) {
+        CPX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, CPX_RS_LDS_MAX));
+        raised[slot][device] = true;
+    }
+    return CPX_OK;
+}
+
+template <int R>
+int launch_decode(const RsDecArgs &a, int slot, int device, int waves, unsigned lds, hipStream_t st) {
+    if (int rc = raise_lds((const void *)rs_decode_kernel<R>, slot, device)) return rc;
+    // workgroups resident at once: as many per compute unit as the LDS of a workgroup allows, at most 32 waves
+    int per_cu = (int)(CPX_RS_LDS_MAX / lds);
+    if (per_cu > 32 / waves) per_cu = 32 / waves;
+    const int64_t wgs = (a.B + waves - 1) / waves;
+    hipLaunchKernelGGL(rs_decode_kernel<R>, dim3(grid_of(wgs, (int64_t)device_cus() * per_cu)), dim3(waves * 64), lds, st, a);
+    return CPX_OK;
+}
+
+template <int R>
+int launch_encode(const RsEncArgs &a, int slot, int device, hipStream_t st) {
+    if (int rc = raise_lds((const void *)rs_encode_kernel<R>, slot, device)) return rc;
+    const unsigned lds = rs_enc_lds(a.m);
+    int per_cu = (int)(CPX_RS_LDS_MAX / lds);
+    if (per_cu > 8) per_cu = 8;
+    const int64_t groups = (a.B + 63) / 64, wgs = (groups + RS_ENC_WAVES - 1) / RS_ENC_WAVES;
+    hipLaunchKernelGGL(rs_encode_kernel<R>, dim3(grid_of(wgs, (int64_t)device_cus() * per_cu)), dim3(RS_ENC_WAVES * 64), lds, st, a);
+    return CPX_OK;
+}
+
+int check_batch(const cpx_rs *p, int64_t B, const char *what) {
+    CPX_REQUIRE(p, CPX_EINVAL, "%s: null handle", what);
+    CPX_REQUIRE(B >= 0, CPX_EINVAL, "%s: B = %lld", what, (long long)B);
+    return CPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cpx_rs_create(int m, uint32_t prim_poly, int n, int k, int fcr, const uint16_t *genpoly, cpx_rs **out) {
+    CPX_TRACE("cpx_rs_create");
+    CPX_REQUIRE(out, CPX_EINVAL, "rs: null pointer");
+    *out = nullptr;
+    CPX_REQUIRE(genpoly, CPX_EINVAL, "rs: null pointer");
+    CPX_REQUIRE(m >= CPX_RS_MIN_M && m <= CPX_RS_MAX_M, CPX_ELIMIT, "rs: m = %d is outside the engine's range %d .. %d", m, CPX_RS_MIN_M,
+                CPX_RS_MAX_M);
+    const int N = (1 << m) - 1;
+    CPX_REQUIRE(n >= 2 && n <= N, CPX_ELIMIT, "rs: n = %d is outside 2 .. 2^m - 1 = %d", n, N);
+    CPX_REQUIRE(k >= 1 && k < n, CPX_EINVAL, "rs: k = %d is outside 1 .. n - 1 = %d", k, n - 1);
+    const int r = n - k;
+    CPX_REQUIRE(r <= CPX_RS_MAX_R, CPX_ELIMIT, "rs: n - k = %d is above the engine's limit of %d", r, CPX_RS_MAX_R);
+    CPX_REQUIRE(fcr >= 0 && fcr < N, CPX_EINVAL, "rs: fcr = %d is outside 0 .. 2^m - 2 = %d", fcr, N - 1);
+    CPX_REQUIRE((prim_poly >> m) == 1u, CPX_EINVAL, "rs: prim_poly = %u has not degree m = %d", prim_poly, m);
+    std::vector<uint16_t> tab;
+    if (int rct = gf_tables("rs", m, prim_poly, tab)) return rct;
+    const uint16_t *ex = tab.data(), *lg = ex + ((size_t)1 << m);
+    for (int i = 0; i <= r; ++i)
+        CPX_REQUIRE(genpoly[i] <= N, CPX_EINVAL, "rs: genpoly[%d] = %d is no element of GF(2^%d)", i, (int)genpoly[i], m);
+    CPX_REQUIRE(genpoly[r] == 1, CPX_EINVAL, "rs: the generator's coefficient of x^%d is %d, need 1 (monic of degree n - k)", r, (int)genpoly[r]);
+    for (int j = 0; j < r; ++j) {                                 // g(alpha^(fcr + j)), by Horner
+        const int x = (fcr + j) % N;
+        unsigned acc = 0;
+        for (int i = r; i >= 0; --i) {
+            if (acc) acc = ex[(lg[acc] + x) % N];
+            acc ^= genpoly[i];
+        }
+        CPX_REQUIRE(acc == 0, CPX_EINVAL, "rs: the generator does not vanish at alpha^%d", fcr + j);
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    cpx_rs *p = new cpx_rs();
+    p->m = m;
+    p->N = N;
+    p->n = n;
+    p->k = k;
+    p->r = r;
+    p->fcr = fcr;
+    for (int i = 0; i < 64; ++i) p->glog[i] = i < r && genpoly[i] ? lg[genpoly[i]] : (uint16_t)RS_NONE;
+    (void)hipGetDevice(&p->device);
+    if ((rc = upload((void **)&p->d_tab, tab.data(), sizeof(uint16_t) * tab.size(), "rs"))) {
+        cpx_rs_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return CPX_OK;
+}
+
+int cpx_rs_destroy(cpx_rs *p) {
+    if (!p) return CPX_OK;
+    (void)hipFree(p->d_tab);
+    delete p;
+    return CPX_OK;
+}
+
+int cpx_rs_encode_dev(const cpx_rs *p, const uint16_t *d_msg, int64_t B, uint16_t *d_word, void *stream) {
+    CPX_TRACE("cpx_rs_encode_dev");
+    if (int rc = check_batch(p, B, "rs_encode")) return rc;
+    if (B == 0) return CPX_OK;
+    CPX_REQUIRE(d_msg && d_word, CPX_EINVAL, "rs_encode: null pointer");
+    if (int rcd = check_handle_device(p->device, "rs_encode")) return rcd;
+    const int R = rs_regs(p->r);
+    RsEncArgs a;
+    a.msg = d_msg;
+    a.tab = p->d_tab;
+    a.out = d_word;
+    a.B = B;
+    a.m = p->m;
+    a.N = p->N;
+    a.n = p->n;
+    a.k = p->k;
+    a.r = p->r;
+    for (int q = 0; q < 64; ++q) a.glog[q] = q >= R - p->r && q < R ? p->glog[q - (R - p->r)] : (uint16_t)RS_NONE;
+    hipStream_t st = pick_stream(stream);
+    int rc;
+    switch (R) {
+    case 8: rc = launch_encode<8>(a, 4, p->device, st); break;
+    case 16: rc = launch_encode<16>(a, 5, p->device, st); break;
+    case 32: rc = launch_encode<32>(a, 6, p->device, st); break;
+    default: rc = launch_encode<64>(a, 7, p->device, st); break;
+    }
+    if (rc) return rc;
+    CPX_HIP(hipGetLastError());
+    note_kernel("rs_encode_kernel<%d>", R);
+    return CPX_OK;
+}
+
+int cpx_rs_encode(const cpx_rs *p, const uint16_t *msg, int64_t B, uint16_t *word) {
+    CPX_TRACE("cpx_rs_encode");
+    if (int rc = check_batch(p, B, "rs_encode")) return rc;
+    if (B == 0) return CPX_OK;
+    CPX_REQUIRE(msg && word, CPX_EINVAL, "rs_encode: null pointer");
+    int rc = ensure_device();
+    if (rc) return rc;
+    const size_t in_bytes = 2 * (size_t)B * (size_t)p->k, out_bytes = 2 * (size_t)B * (size_t)p->n;
+    HostStage s;
+    const uint16_t *din;
+    uint16_t *dout;
+    if ((rc = s.in(msg, in_bytes, &din)) || (rc = s.out(out_bytes, &dout)) || (rc = cpx_rs_encode_dev(p, din, B, dout, s.st))) return rc;
+    return s.get(word, dout, out_bytes);
+}
+
+int cpx_rs_decode_dev(const cpx_rs *p, const uint16_t *d_in, const uint8_t *d_erased, int64_t B, uint16_t *d_symbols, uint16_t *d_word,
+                      int32_t *d_errors, void *stream) {
+    CPX_TRACE("cpx_rs_decode_dev");
+    if (int rc = check_batch(p, B, "rs_decode")) return rc;
+    CPX_REQUIRE(d_symbols || d_word || d_errors, CPX_EINVAL, "rs_decode: no output requested");
+    if (B == 0) return CPX_OK;
+    CPX_REQUIRE(d_in, CPX_EINVAL, "rs_decode: null pointer");
+    if (int rcd = check_handle_device(p->device, "rs_decode")) return rcd;
+    const int nw = (p->n + 63) / 64, waves = rs_waves(p->m), R = rs_regs(p->r);
+    const unsigned lds = (gf_tab_lds(p->m) + (unsigned)waves * rs_wave_lds(nw) + 15u) & ~15u;
+    CPX_REQUIRE(lds <= CPX_RS_LDS_MAX, CPX_ELIMIT, "rs_decode: m = %d, n = %d needs %u bytes of LDS", p->m, p->n, lds);
+    RsDecArgs a{d_in, d_erased, p->d_tab, B, p->m, p->N, p->n, p->k, p->r, p->fcr, nw, d_symbols, d_word, d_errors};
+    hipStream_t st = pick_stream(stream);
+    int rc;
+    switch (R) {
+    case 8: rc = launch_decode<8>(a, 0, p->device, waves, lds, st); break;
+    case 16: rc = launch_decode<16>(a, 1, p->device, waves, lds, st); break;
+    case 32: rc = launch_decode<32>(a, 2, p->device, waves, lds, st); break;
+    default: rc = launch_decode<64>(a, 3, p->device, waves, lds, st); break;
+    }
+    if (rc) return rc;
+    CPX_HIP(hipGetLastError());
+    note_kernel("rs_decode_kernel<%d>", R);
+    return CPX_OK;
+}
+
+int cpx_rs_decode(const cpx_rs *p, const uint16_t *in, const uint8_t *erased, int64_t B, uint16_t *symbols, uint16_t *word, int32_t *errors) {
+    CPX_TRACE("cpx_rs_decode");
+    if (int rc = check_batch(p, B, "rs_decode")) return rc;
+    CPX_REQUIRE(symbols || word || errors, CPX_EINVAL, "rs_decode: no output requested");
+    if (B == 0) return CPX_OK;
+    CPX_REQUIRE(in, CPX_EINVAL, "rs_decode: null pointer");
+    int rc = ensure_device();
+    if (rc) return rc;
+    const size_t b = (size_t)B;
+    struct Out { void *host; size_t bytes; void *dev; } outs[3] = {
+        {symbols, 2 * b * (size_t)p->k, nullptr}, {word, 2 * b * (size_t)p->n, nullptr}, {errors, 4 * b, nullptr}};
+    HostStage s;
+    const uint16_t *din;
+    const uint8_t *der = nullptr;
+    if ((rc = s.in(in, 2 * b * (size_t)p->n, &din))) return rc;
+    if (erased && (rc = s.in(erased, b * (size_t)p->n, &der))) return rc;
+    for (Out &o : outs)
+        if (o.host && (rc = s.out(o.bytes, &o.dev))) return rc;
+    if ((rc = cpx_rs_decode_dev(p, din, der, B, (uint16_t *)outs[0].dev, (uint16_t *)outs[1].dev, (int32_t *)outs[2].dev, s.st))) return rc;
+    for (Out &o : outs)
+        if (o.host && (rc = s.get(o.host, o.dev, o.bytes))) return rc;
+    return CPX_OK;
+}
+
+}  // extern "C"

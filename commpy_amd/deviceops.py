@@ -17,7 +17,7 @@ __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu',
            'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder', 'gf2_generator',
            'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
            'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev',
-           'bch_encode_dev', 'bch_decode_dev']
+           'bch_encode_dev', 'bch_decode_dev', 'rs_encode_dev', 'rs_decode_dev']
 
 
 class DeviceBuf:
@@ -544,5 +544,37 @@ def bch_decode_dev(code, d_bits, B, want=('bits',), stream=None):
         p = lambda v: None if v is None else v.ptr
         _lib.check(_lib.load().cpx_bch_decode_dev(code._device_handle(), d_bits.ptr, B, p(out.get('bits')), p(out.get('codeword')),
                                                   p(out.get('errors')), stream))
+    res = tuple(out[k] for k in WANT if k in want)
+    return res[0] if len(res) == 1 else res
+
+
+# ---- Reed-Solomon codes, device resident (csrc/rs.hip) ------------------------------------------------------------------------------
+
+def rs_encode_dev(code, d_msg, B, stream=None):
+    """``cpx_rs_encode_dev``: ``d_msg [B][k]`` uint16 -> a new ``DeviceBuf`` ``[B][n]`` uint16 of code words, queued on ``stream``
+    (None: the library's); ``code`` is a ``channelcoding.RSCode``.  Only the low ``m`` bits of a symbol count."""
+    from commpy_amd.channelcoding.gfields import whole
+    from commpy_amd.channelcoding.rs import _code
+    code, B = _code(code), whole(B, 'B', 0)
+    d_x = DeviceBuf(2 * B * code.n)
+    if B:
+        _lib.check(d_x.lib.cpx_rs_encode_dev(code._device_handle(), d_msg.ptr, B, d_x.ptr, stream))
+    return d_x
+
+
+def rs_decode_dev(code, d_symbols, B, d_erased=None, want=('symbols',), stream=None):
+    """``cpx_rs_decode_dev``: ``d_symbols [B][n]`` uint16 received symbols (the low ``m`` bits count) and ``d_erased [B][n]`` uint8
+    flags (non-zero = erased; None: no flags) -> new ``DeviceBuf``s, the results of ``channelcoding.rs_decode`` that ``want`` names,
+    in its order: 'symbols' ``[B][k]`` uint16, 'codeword' ``[B][n]`` uint16, 'errors' ``[B]`` int32; a single result for one name."""
+    from commpy_amd.channelcoding.gfields import whole
+    from commpy_amd.channelcoding.rs import WANT, _code, check_want
+    code, B = _code(code), whole(B, 'B', 0)
+    want = check_want(want)
+    sizes = {'symbols': 2 * B * code.k, 'codeword': 2 * B * code.n, 'errors': B * 4}
+    out = {k: DeviceBuf(sizes[k]) for k in sizes if k in want}
+    if B:
+        p = lambda v: None if v is None else v.ptr
+        _lib.check(_lib.load().cpx_rs_decode_dev(code._device_handle(), d_symbols.ptr, p(d_erased), B, p(out.get('symbols')),
+                                                 p(out.get('codeword')), p(out.get('errors')), stream))
     res = tuple(out[k] for k in WANT if k in want)
     return res[0] if len(res) == 1 else res

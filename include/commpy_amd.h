@@ -827,6 +827,37 @@ int cpx_bch_decode(const cpx_bch *p, const uint8_t *in, int64_t B, uint8_t *bits
 int cpx_bch_decode_dev(const cpx_bch *p, const uint8_t *d_in, int64_t B, uint8_t *d_bits, uint8_t *d_word, int32_t *d_errors,
                        void *stream);
 
+/* ---- Reed-Solomon codes: systematic encoder and errors-and-erasures decoder (csrc/rs.hip) ---------------
+ * Code of length n <= 2^m - 1 (shortened below that) over GF(2^m), 3 <= m <= 14, with r = n - k <= 63 parity symbols and the generator
+ * g(x) = prod_{j<r} (x - alpha^(fcr+j)).  A word is n uint16 symbols in tuple form (bit i = coefficient of alpha^i), of which only the
+ * low m bits count (the kernels mask them); symbol i is the coefficient of x^(n-1-i): k message symbols, then the r symbols of
+ * x^r m(x) mod g(x).
+ *   cpx_rs_create    prim_poly as for cpx_bch_create; genpoly [n - k + 1] field elements, lowest degree first.  Checked before a device
+ *                    is looked for: m, n, n - k above 63 (CPX_ELIMIT); k, fcr in 0 .. 2^m - 2, prim_poly of degree m under which x
+ *                    generates the multiplicative group, entries below 2^m, genpoly[n - k] = 1, g(alpha^(fcr+j)) = 0 for j < r
+ *                    (CPX_EINVAL).
+ *   cpx_rs_encode    msg [B][k] -> word [B][n].
+ *   cpx_rs_decode    in [B][n]; erased [B][n] uint8, non-zero = the position is flagged (NULL: none).  With f flagged positions:
+ *                    f > r fails.  S_j = R(alpha^(fcr+j)), j < r, from the symbols as given; all zero: accepted, 0 errors.  Else
+ *                    Gamma = prod (1 - alpha^d x) over the flagged degrees d, and Berlekamp-Massey on rho = f .. r - 1 started with
+ *                    C = B = Gamma, L = f (length change when 2 L <= rho + f, to rho + 1 - L + f) gives Lambda of length L.  Failure if
+ *                    2 (L - f) + f > r, if Lambda_L = 0 or if Lambda has not exactly L roots among alpha^-d, d = 0 .. n - 1.  Otherwise
+ *                    Omega = S Lambda mod x^r and Y = alpha^(d (1 - fcr)) Omega(alpha^-d) / Lambda'(alpha^-d) is XORed into the symbol
+ *                    at every root.  Outputs, each may be NULL (not all): symbols [B][k], word [B][n], errors [B] int32 = L - f, the
+ *                    corrected unflagged positions, -1 after a failure (symbols and word then hold the received word, masked to m
+ *                    bits).  Equal to tests/rs_model.py symbol for symbol.
+ * The _dev forms take device pointers and a stream and are asynchronous; the others take host pointers and return synchronised.
+ * B = 0 returns CPX_OK without a launch. */
+typedef struct cpx_rs cpx_rs;
+int cpx_rs_create(int m, uint32_t prim_poly, int n, int k, int fcr, const uint16_t *genpoly, cpx_rs **out);
+int cpx_rs_destroy(cpx_rs *p);
+int cpx_rs_encode(const cpx_rs *p, const uint16_t *msg, int64_t B, uint16_t *word);
+int cpx_rs_encode_dev(const cpx_rs *p, const uint16_t *d_msg, int64_t B, uint16_t *d_word, void *stream);
+int cpx_rs_decode(const cpx_rs *p, const uint16_t *in, const uint8_t *erased, int64_t B, uint16_t *symbols, uint16_t *word,
+                  int32_t *errors);
+int cpx_rs_decode_dev(const cpx_rs *p, const uint16_t *d_in, const uint8_t *d_erased, int64_t B, uint16_t *d_symbols, uint16_t *d_word,
+                      int32_t *d_errors, void *stream);
+
 /* ---- multi-GPU: RCCL collectives of the sharded decode ------------------------------------
  * The path shards by codeword (contiguous blocks of B/G codewords per GPU, tables replicated) and has no exchange
  * step inside a decoder.  Two collectives exist around it:

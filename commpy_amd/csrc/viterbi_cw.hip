@@ -87,6 +87,14 @@ __device__ __forceinline__ double acs_min_first(unsigned &acc, double x, double 
     return r;
 }
 
+// The two selects of one butterfly as ONE statement (x0 = min(x0, y0) with its decision into acc0, then the same for x1 / y1 / acc1):
+// the compiler pads the boundary between two asm statements with an s_nop wherever they end up next to each other.
+__device__ __forceinline__ void acs_min_pair(unsigned &acc0, unsigned &acc1, double &x0, double y0, double &x1, double y1) {
+    asm("v_cmp_lt_f64 vcc, %4, %0\n\tv_addc_co_u32 %2, vcc, %2, %2, vcc\n\tv_min_f64 %0, %0, %4\n\t"
+        "v_cmp_lt_f64 vcc, %5, %1\n\tv_addc_co_u32 %3, vcc, %3, %3, vcc\n\tv_min_f64 %1, %1, %5"
+        : "+&v"(x0), "+&v"(x1), "+&v"(acc0), "+&v"(acc1) : "v"(y0), "v"(y1) : "vcc");   // early clobber: y1 is read after x0 and acc0 are written
+}
+
 __device__ __forceinline__ double acs_select(unsigned &acc, double x, double y) {
     int rlo, rhi;
     asm("v_cmp_lt_f64 vcc, %4, %3\n\tv_cndmask_b32 %0, %5, %7, vcc\n\tv_cndmask_b32 %1, %6, %8, vcc\n\t"
@@ -121,6 +129,18 @@ __device__ __forceinline__ void nan_or(unsigned long long &mask, double r0, doub
     return;
 #endif
     asm("v_cmp_u_f64 vcc, %1, %2\n\ts_or_b64 %0, %0, vcc" : "+s"(mask) : "v"(r0), "v"(r1) : "vcc", "scc");
+}
+// The pinned form (cw_step, FILLERS): the compare writes a scalar pair of its own and the caller ORs that into the mask later; the mask is
+// only read at the end of the kernel.  Timed, taking the two scalar readers of a step (this OR, the tie test) away from the vector
+// compares that feed them is worth 1.7 % with no instruction removed (profiles/viterbi_leftovers_ab.txt); the supposed reason is that a
+// scalar instruction reading what a vector compare has just written holds the wave until the vector pipeline has delivered it.
+// CPX_AB_SCALAR_BEHIND_COMPARE (A/B builds only) puts both readers back where the parent had them.
+__device__ __forceinline__ unsigned long long nan_lanes(double r0, double r1) {
+#ifdef CPX_AB_NO_NAN_DETECT
+    return 0;
+#else
+    return __builtin_amdgcn_ballot_w64(__builtin_isunordered(r0, r1));   // one v_cmp_u_f64 into a scalar pair (every lane of the wave is active)
+#endif
 }
 
 // Per-bit metrics of one received value (convcode.py:575-587) -- identical to viterbi.hip
@@ -177,6 +197,22 @@ __device__ __forceinline__ unsigned tb_hop(unsigned long long w, unsigned st) {
 struct NoHook {
     template <int P> __device__ __forceinline__ void at() const {}
 };
+// FILLERS.  `fill(integral_constant<P>, word)`, P = 0 .. 3, is the caller's own per-step work that does not depend on the first-argmin
+// (the fused kernel: ring-slot address, NaN test, ring write of the step's decision word, OR into the NaN mask), cut into four pieces.  Where the step
+// has the 32-bit first-argmin, its asm statements form a chain in which each reads registers the one before wrote, and the compiler
+// pads every such boundary with an s_nop (it cannot see into the statements); one piece is pinned into each of the four boundaries
+// instead, in the order 0 .. 3, so the wait state is spent on an instruction the step needs anyway.  A step that is given fillers also
+// takes the two selects of a butterfly as one statement (acs_min_pair) and the tie mask ahead of the index (CPX_ROW_BLOCK_LAST).  Only
+// the fused kernel's compile-time-hop 'soft' flavours pass them (PIN there); every other caller passes NoFill and gets the step it had:
+// the run-time-hop kernels sit at their scalar-register ceiling and the flavours without the 32-bit first-argmin have no chain to fill --
+// both were measured slower with the new form (experiments/README.md).
+struct NoFill {};
+template <int P, class Fill>
+__device__ __forceinline__ void pinned_fill(const Fill &fill, unsigned long long word) {
+    __builtin_amdgcn_sched_barrier(0);
+    fill(std::integral_constant<int, P>{}, word);
+    __builtin_amdgcn_sched_barrier(0);
+}
 
 // `hook.at<P>()` is called at four fixed points of the step (after the branch metrics, after each half of the butterflies,
 // after the minimum tree): the fused kernel issues the traceback reads of the previous step there.
@@ -190,12 +226,14 @@ struct NoHook {
 // already quiet), and no per-bit metric is ever -0.0: 'hard' converts an integer (never -0.0), 'unquantized' takes a square (sign +),
 // 'soft' m0 = log(x), x >= 1, ends in a subtraction a - b that is -0.0 only for a = -0.0, b = +0.0 -- a = dk ln2_hi is +0.0 or >= 0.69 --
 // and m1 = m0 - r is -0.0 only for m0 = -0.0 (x - x is +0.0 in round-to-nearest).  The other kernels keep the literal form.
-template <int LGS, unsigned G0, unsigned G1, int TYPE, int R, bool LEAN = false, class Hook = NoHook>
+template <int LGS, unsigned G0, unsigned G1, int TYPE, int R, bool LEAN = false, class Hook = NoHook, class Fill = NoFill>
 __device__ __forceinline__ void cw_step(double (&pm)[1 << LGS], double r0, double r1, unsigned long long &word, int &best,
-                                        const Hook &hook = Hook(), unsigned char *bml = nullptr, const unsigned *gidx = nullptr) {
+                                        const Hook &hook = Hook(), unsigned char *bml = nullptr, const unsigned *gidx = nullptr,
+                                        const Fill &fill = Fill()) {
     constexpr int type = TYPE;
     using C = SrCode<LGS, G0, G1>;
     constexpr bool GEN = G0 == 0 && G1 == 0;
+    constexpr bool FILLED = !std::is_same<Fill, NoFill>::value;   // (FILLERS above)
     constexpr int S = 1 << LGS, H = S / 2;
     double m00, m01, m10, m11;
     if constexpr (LEAN && TYPE == CPX_VIT_SOFT) {                  // coded_bits.clip(-500, 500) (:719)
@@ -232,6 +270,11 @@ __device__ __forceinline__ void cw_step(double (&pm)[1 << LGS], double r0, doubl
         } else if (j == 0) {                                       // (j is a constant once the loop is unrolled)
             pm[x] = acs_min_first(da, a0, a1);
             pm[y] = acs_min_first(db, b0, b1);
+        } else if constexpr (FILLED) {
+            double ra = a0, rb = b0;
+            acs_min_pair(da, db, ra, a1, rb, b1);
+            pm[x] = ra;
+            pm[y] = rb;
         } else {
             pm[x] = acs_min(da, a0, a1);
             pm[y] = acs_min(db, b0, b1);
@@ -349,6 +392,10 @@ __device__ __forceinline__ void cw_step(double (&pm)[1 << LGS], double r0, doubl
     // no taken branch, and the hook calls stay unconditional and in order.  (Measured issue costs: profiles/viterbi_argmin32_issue_cost.txt.)
     constexpr bool ARGMIN32 = LEAN && S == 64 && TYPE == CPX_VIT_SOFT && !GEN;   // the fused kernel, compiled-in generators
     unsigned long long tie = ~0ull;                                // lanes with more than one hit (hit word: not exactly two bits)
+    // shifting the decisions in in increasing state order leaves state j of a half at bit H-1-j of its word; placing the
+    // lower half on top puts state s at bit 63 - s of the 64-bit word: the traceback reads it as the top bit of (w << s)
+    if constexpr (FILLED) word = ((unsigned long long)da << (64 - H)) | ((unsigned long long)db << (64 - S));   // (the ring write is a filler)
+    static_assert(!FILLED || ARGMIN32, "fillers go between the statements of the 32-bit first-argmin");
     if constexpr (ARGMIN32) {
         // (state s sits in register rotl(s, R + 1): only a question of which operand is named)
 #define CPX_HI(s) "v"(__double2hiint(pm[rotl<LGS>((s), R + 1)]))
@@ -357,13 +404,25 @@ __device__ __forceinline__ void cw_step(double (&pm)[1 << LGS], double r0, doubl
         unsigned q0, q1, q2, q3, q4, q5, q6, q7, m, w;                 // column minima, the minimum, the hit word
         asm(CPX_COL_BLOCK3 : "=&v"(q0), "=&v"(q1), "=&v"(q2) : CPX_COL(0), CPX_COL(1), CPX_COL(2));
         asm(CPX_COL_BLOCK3 : "=&v"(q3), "=&v"(q4), "=&v"(q5) : CPX_COL(3), CPX_COL(4), CPX_COL(5));
+        if constexpr (FILLED) pinned_fill<0>(fill, word);
         asm(CPX_COL_BLOCK_LAST : "=&v"(q6), "=&v"(q7), "=&v"(m), "=&v"(w) : "v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(q4), "v"(q5), CPX_COL(6), CPX_COL(7)
             : "vcc");
         hook.template at<3>();
+        if constexpr (FILLED) pinned_fill<1>(fill, word);
         unsigned r0_, r1_, r2_;                                        // row minima: dead once compared
         asm(CPX_ROW_BLOCK3 : "+v"(w), "=&v"(r0_), "=&v"(r1_), "=&v"(r2_) : "v"(m), CPX_ROW(7), CPX_ROW(6), CPX_ROW(5) : "vcc");
+        if constexpr (FILLED) pinned_fill<2>(fill, word);
         asm(CPX_ROW_BLOCK3 : "+v"(w), "=&v"(r0_), "=&v"(r1_), "=&v"(r2_) : "v"(m), CPX_ROW(4), CPX_ROW(3), CPX_ROW(2) : "vcc");
-        asm(CPX_ROW_BLOCK_LAST : "+v"(w), "=&v"(r0_), "=&v"(r1_), "=&v"(bst), "=&s"(tie) : "v"(m), CPX_ROW(1), CPX_ROW(0) : "vcc");
+        if constexpr (FILLED) pinned_fill<3>(fill, word);
+#ifdef CPX_AB_SCALAR_BEHIND_COMPARE
+        constexpr bool TIE_FIRST = false;
+#else
+        constexpr bool TIE_FIRST = FILLED;
+#endif
+        if constexpr (TIE_FIRST)
+            asm(CPX_ROW_BLOCK_LAST : "+v"(w), "=&v"(r0_), "=&v"(r1_), "=&v"(bst), "=&s"(tie) : "v"(m), CPX_ROW(1), CPX_ROW(0) : "vcc");
+        else
+            asm(CPX_ROW_BLOCK_LAST_INDEX_FIRST : "+v"(w), "=&v"(r0_), "=&v"(r1_), "=&v"(bst), "=&s"(tie) : "v"(m), CPX_ROW(1), CPX_ROW(0) : "vcc");
 #undef CPX_ROW
 #undef CPX_COL
 #undef CPX_HI
@@ -419,9 +478,7 @@ __device__ __forceinline__ void cw_step(double (&pm)[1 << LGS], double r0, doubl
             for (int s = S - 1; s >= 0; s--) bst = (pm[rotl<LGS>(s, R + 1)] == mn) ? s : bst;
         }
     }
-    // shifting the decisions in in increasing state order leaves state j of a half at bit H-1-j of its word; placing the
-    // lower half on top puts state s at bit 63 - s of the 64-bit word: the traceback reads it as the top bit of (w << s)
-    word = ((unsigned long long)da << (64 - H)) | ((unsigned long long)db << (64 - S));
+    if constexpr (!FILLED) word = ((unsigned long long)da << (64 - H)) | ((unsigned long long)db << (64 - S));
     best = bst;
 }
 
@@ -800,6 +857,10 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
     // the burst form (WalkBurst): `walk` then only carries the pending walk (pw, st) to the end of the last chunk.  Deep64 and Lean32
     // (rings stored once) and every flavour that is not LATE keep the walk per step.
     constexpr bool BURST = LATE && MIR && HT > LGS - 1;
+    // the step with its own work pinned between the first-argmin statements (cw_step, FILLERS): Mirrored32 at the default depth and Lean32.
+    // Not the run-time-hop kernels (every depth below the default, Deep64): at their scalar-register ceiling the six pairs of the NaN
+    // tests are spilled inside the loop, measured +1.8 % and +1.0 %.
+    constexpr bool PIN = LATE && !RT;
     constexpr int NHE = BURST ? HT - (LGS - 1) : 1;                                 // hop slots: the hops the output can see
     static_assert(!BURST || NHE + LGS <= RING, "ring too small for the words of LGS walks at once");
     WalkBurst<LGS, NHE, RING, RT> burst;
@@ -884,36 +945,73 @@ __global__ __launch_bounds__(64 * ACS_WAVES) void viterbi_cw_fused_kernel(CwPara
             const double r0 = have ? cur[R].x : pad, r1 = have ? cur[R].y : pad;
             unsigned long long word;
             int bst;
-            if constexpr (TYPE == CPX_VIT_SOFT) nan_or(nanmask, cur[R].x, cur[R].y);   // (steps > tmax re-read step tmax)
+            // What the step does besides its arithmetic, in four pieces: the address of the ring slot of step tt, the NaN test of the step's
+            // two values, the write of the decision word to the slot and (mirrored ring) its copy RING slots above, the OR into the NaN
+            // mask.  The (at most LGS - 1) steps > T of the last group write to two dummy slots instead: the ring must keep the words of
+            // steps T-H+1 .. T for the final walk.  PIN: cw_step places the pieces between its first-argmin statements (FILLERS); otherwise
+            // the NaN test stands in front of the step and the ring write behind the walk, as they always did.
+            unsigned long long nank = 0;                                      // lanes whose step received a NaN
+            int q = 0;
+            unsigned long long *wb = nullptr;
+            auto fill = [&](auto ptag, unsigned long long wd) __attribute__((always_inline)) {
+                constexpr int P = decltype(ptag)::value;
+                if constexpr (P == 0) {
+                    q = tt & (RING - 1);
+                    wb = mycol + q * 64;
+                }
+#ifdef CPX_AB_SCALAR_BEHIND_COMPARE
+                if constexpr (P == 1 && TYPE == CPX_VIT_SOFT) nan_or(nanmask, cur[R].x, cur[R].y);
+#else
+                if constexpr (P == 1 && TYPE == CPX_VIT_SOFT) nank = nan_lanes(cur[R].x, cur[R].y);   // (steps > tmax re-read step tmax)
+                if constexpr (P == 3 && TYPE == CPX_VIT_SOFT) nanmask |= nank;  // (a dozen vector instructions behind the compare)
+#endif
+                if constexpr (P == 2) {
+                    const bool live = FAST || tt <= T;
+                    if constexpr (MIR) {
+                        unsigned long long *w0 = live ? wb : mycol + (2 * RING) * 64;
+                        unsigned long long *w1 = live ? wb + RING * 64 : mycol + (2 * RING + 1) * 64;
+                        *w0 = wd;
+                        *w1 = wd;
+                    } else {
+                        unsigned long long *w0 = live ? wb : mycol + RING * 64;
+                        *w0 = wd;
+                    }
+                }
+            };
+            auto step = [&](const auto &hook) __attribute__((always_inline)) {
+                if constexpr (PIN) cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, hook, nullptr, gidx, fill);
+                else cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, hook, nullptr, gidx);
+            };
+            if constexpr (!PIN && TYPE == CPX_VIT_SOFT) nan_or(nanmask, cur[R].x, cur[R].y);   // (steps > tmax re-read step tmax)
             if constexpr (BURST && R == LGS - 1) {
                 burst.pb = mycol + ((tt - 1) & (RING - 1)) * 64;              // the slot of step t + LGS - 2, written by the step before
-                cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, burst, nullptr, gidx);   // + the read batches of the group's walks
+                step(burst);                                                  // + the read batches of the group's walks
                 burst.finish();                                               // one wait, then the hops of the walks of steps t - 1 .. t + LGS - 2
 #pragma unroll
                 for (int k = 0; k < LGS; k++) tile[k] = (unsigned char)burst.bit(k);   // entry k: the walk of step t - 1 + k
             } else if constexpr (BURST) {
-                cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, NoHook(), nullptr, gidx);   // no walk in this step
+                step(NoHook());                                               // no walk in this step
             } else {
-            cw_step<LGS, G0, G1, TYPE, R, true>(pm, r0, r1, word, bst, walk, nullptr, gidx);   // + the four read batches of the walk of step tt - 1
+            step(walk);                                                       // + the four read batches of the walk of step tt - 1
             walk.finish();                                                    // one wait, then all of its hops
             tile[R] = (unsigned char)walk.bit();                              // input bit of the branch into the state at step tt - 1 - H
             }
-            // ring slot of step tt and (mirrored ring) its copy RING slots above; the (at most LGS - 1) steps > T of the last group
-            // write to two dummy slots instead: the ring must keep the words of steps T-H+1 .. T for the final walk
-            const bool live = FAST || tt <= T;
-            const int q = tt & (RING - 1);
-            unsigned long long *wb = mycol + q * 64;
-            if constexpr (MIR) {
-                unsigned long long *w0 = live ? wb : mycol + (2 * RING) * 64;
-                unsigned long long *w1 = live ? wb + RING * 64 : mycol + (2 * RING + 1) * 64;
-                *w0 = word;
-                *w1 = word;
-                walk.pw = wb;                                                 // next: the walk of this step
-            } else {
-                unsigned long long *w0 = live ? wb : mycol + RING * 64;
-                *w0 = word;
-                walk.q = q;
+            if constexpr (!PIN) {                                             // the ring write, behind the walk
+                const bool live = FAST || tt <= T;
+                q = tt & (RING - 1);
+                wb = mycol + q * 64;
+                if constexpr (MIR) {
+                    unsigned long long *w0 = live ? wb : mycol + (2 * RING) * 64;
+                    unsigned long long *w1 = live ? wb + RING * 64 : mycol + (2 * RING + 1) * 64;
+                    *w0 = word;
+                    *w1 = word;
+                } else {
+                    unsigned long long *w0 = live ? wb : mycol + RING * 64;
+                    *w0 = word;
+                }
             }
+            if constexpr (MIR) walk.pw = wb;                                  // next: the walk of this step
+            else walk.q = q;
             if constexpr (!FAST) best_T = (tt == T) ? bst : best_T;
             walk.st = (unsigned)bst;
             if constexpr (BURST) burst.st[(R + 1) % LGS] = (unsigned)bst;     // start state of this step's walk (R = LGS - 1: the pending one)

@@ -73,7 +73,7 @@ def col_last_block():
     return "\\n\\t".join(out)
 
 
-def row_block(n, last=False):
+def row_block(n, last=False, tie_first=True):
     """%0 the hit word (+v), %1..%n row minima (=&v, temporaries), then m and the eight high dwords of each of n rows, the highest row
     first: the n chains interleaved, each row compared with m and shifted into the word as the columns were -- row j ends at bit j.
     last: two more outputs between the temporaries and m: the index 8 j + i of the hit (=&v; j = the lowest set bit of the word, i =
@@ -84,8 +84,15 @@ def row_block(n, last=False):
     for r in range(n):
         out += hit(0, m, 1 + r)
     if last:
-        out += ["v_ffbl_b32 %3, %0", "v_lshrrev_b32 %1, 8, %0", "v_bcnt_u32_b32 %2, %0, 0", "v_ffbl_b32 %1, %1", "v_cmp_ne_u32 %4, 2, %2",
-                "v_lshl_or_b32 %3, %3, 3, %1"]
+        # tie_first: the four instructions of the index stand between the compare that writes the tie mask and the scalar test and branch
+        # that read it (timed gain with no instruction removed: experiments/README.md); otherwise the compare comes next to last, as the
+        # kernels that do not take the pinned form of the step keep it
+        if tie_first:
+            out += ["v_bcnt_u32_b32 %2, %0, 0", "v_cmp_ne_u32 %4, 2, %2", "v_ffbl_b32 %3, %0", "v_lshrrev_b32 %1, 8, %0", "v_ffbl_b32 %1, %1",
+                    "v_lshl_or_b32 %3, %3, 3, %1"]
+        else:
+            out += ["v_ffbl_b32 %3, %0", "v_lshrrev_b32 %1, 8, %0", "v_bcnt_u32_b32 %2, %0, 0", "v_ffbl_b32 %1, %1", "v_cmp_ne_u32 %4, 2, %2",
+                    "v_lshl_or_b32 %3, %3, 3, %1"]
     return "\\n\\t".join(out)
 
 
@@ -99,4 +106,5 @@ for i, b in enumerate(blocks):
 print('#define CPX_COL_BLOCK3 "%s"   // three column minima' % col_block(3))
 print('#define CPX_COL_BLOCK_LAST "%s"   // columns 6 and 7, the minimum, the column hits' % col_last_block())
 print('#define CPX_ROW_BLOCK3 "%s"   // three rows: minima and hits' % row_block(3))
-print('#define CPX_ROW_BLOCK_LAST "%s"   // rows 1 and 0, the index, the tie mask' % row_block(2, last=True))
+print('#define CPX_ROW_BLOCK_LAST "%s"   // rows 1 and 0, the tie mask, the index' % row_block(2, last=True))
+print('#define CPX_ROW_BLOCK_LAST_INDEX_FIRST "%s"   // rows 1 and 0, the index, the tie mask' % row_block(2, last=True, tie_first=False))

@@ -64,7 +64,7 @@ def classify(op, args, prev=None):
     if EQ[0] == "v_cmp_eq_u32" and (
             op in ("v_min3_u32", "v_min_u32", "v_cmp_eq_u32", "v_ffbl_b32", "v_bcnt_u32_b32", "v_cmp_ne_u32") or
             (prev == "v_cmp_eq_u32" and (op.startswith("v_addc_co") or op == "v_cndmask_b32")) or
-            (prev == "v_ffbl_b32" and op == "v_lshrrev_b32") or (prev == "v_cmp_ne_u32" and op == "v_lshl_or_b32")):
+            (prev == "v_ffbl_b32" and op == "v_lshrrev_b32") or (prev in ("v_cmp_ne_u32", "v_ffbl_b32") and op == "v_lshl_or_b32")):
         return ARGMIN32
     if op in ("v_add_f64",):
         return "add-compare-select: v_add_f64 (path metric + branch metric)"

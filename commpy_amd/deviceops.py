@@ -17,7 +17,7 @@ __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu',
            'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder', 'gf2_generator',
            'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
            'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev',
-           'bch_encode_dev', 'bch_decode_dev', 'rs_encode_dev', 'rs_decode_dev']
+           'bch_encode_dev', 'bch_decode_dev', 'rs_encode_dev', 'rs_decode_dev', 'tailbiting_encode_dev', 'tailbiting_decode_dev']
 
 
 class DeviceBuf:
@@ -577,4 +577,41 @@ def rs_decode_dev(code, d_symbols, B, d_erased=None, want=('symbols',), stream=N
         _lib.check(_lib.load().cpx_rs_decode_dev(code._device_handle(), d_symbols.ptr, p(d_erased), B, p(out.get('symbols')),
                                                  p(out.get('codeword')), p(out.get('errors')), stream))
     res = tuple(out[k] for k in WANT if k in want)
+    return res[0] if len(res) == 1 else res
+
+
+# ---- tail-biting convolutional codes, device resident (csrc/tbcc.hip) ---------------------------------------------------------------
+
+def tailbiting_encode_dev(trellis, d_msg, B, T, stream=None):
+    """``cpx_tbcc_encode_dev``: ``d_msg [B][T k]`` uint8 (bit 0 of a byte counts) -> two new ``DeviceBuf``s queued on ``stream`` (None:
+    the library's): the code words ``[B][T n]`` uint8 and ``closed [B]`` uint8, 1 where the emitting walk ended in the state in which it
+    began (``channelcoding.tailbiting_encode`` raises where it is 0).  ``trellis`` is a ``Trellis`` or any duck-typed trellis."""
+    from commpy_amd.channelcoding.convcode import device_trellis
+    from commpy_amd.channelcoding.gfields import whole
+    from commpy_amd.channelcoding.tailbiting import check_block, check_trellis
+    k, n = check_trellis(trellis)
+    B, T = whole(B, 'B', 0), check_block(whole(T, 'T', 1), k)
+    d_x, d_closed = DeviceBuf(B * T * n), DeviceBuf(B)
+    if B:
+        _lib.check(d_x.lib.cpx_tbcc_encode_dev(device_trellis(trellis), d_msg.ptr, B, T, d_x.ptr, d_closed.ptr, stream))
+    return d_x, d_closed
+
+
+def tailbiting_decode_dev(trellis, d_coded, B, T, decoding_type='hard', max_wraps=4, want=('bits',), stream=None):
+    """``cpx_tbcc_decode_dev``: ``d_coded [B][T n]`` float64 -> new ``DeviceBuf``s, the results of ``channelcoding.tailbiting_decode``
+    that ``want`` names, in its order: 'bits' ``[B][T k]`` uint8, 'wraps' ``[B]`` int32, 'tailbiting' ``[B]`` uint8, 'metric' ``[B]``
+    float64; a single result for one name."""
+    from commpy_amd.channelcoding.convcode import device_trellis
+    from commpy_amd.channelcoding.gfields import whole
+    from commpy_amd.channelcoding.tailbiting import WANT, check_block, check_max_wraps, check_trellis, check_type, check_want
+    k, n = check_trellis(trellis)
+    vtype, max_wraps, want = check_type(decoding_type), check_max_wraps(max_wraps), check_want(want)
+    B, T = whole(B, 'B', 0), check_block(whole(T, 'T', 1), k)
+    sizes = {'bits': B * T * k, 'wraps': B * 4, 'tailbiting': B, 'metric': B * 8}
+    out = {name: DeviceBuf(sizes[name]) for name in sizes if name in want}
+    if B:
+        p = lambda v: None if v is None else v.ptr
+        _lib.check(_lib.load().cpx_tbcc_decode_dev(device_trellis(trellis), d_coded.ptr, B, T, vtype, max_wraps, p(out.get('bits')),
+                                                   p(out.get('wraps')), p(out.get('tailbiting')), p(out.get('metric')), stream))
+    res = tuple(out[name] for name in WANT if name in want)
     return res[0] if len(res) == 1 else res

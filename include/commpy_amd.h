@@ -858,6 +858,36 @@ int cpx_rs_decode(const cpx_rs *p, const uint16_t *in, const uint8_t *erased, in
 int cpx_rs_decode_dev(const cpx_rs *p, const uint16_t *d_in, const uint8_t *d_erased, int64_t B, uint16_t *d_symbols, uint16_t *d_word,
                       int32_t *d_errors, void *stream);
 
+/* ---- tail-biting convolutional codes: encoder and wrap-around Viterbi decoder (csrc/tbcc.hip) ----------
+ * A block is T trellis steps of the code of a cpx_trellis; it has no tail: the encoder starts in the state in which it ends.  Limits
+ * (CPX_ELIMIT, naming the limit): the number of states is a power of two from 2 to 64; k <= 2 and n <= 6; T >= 1 and T k <= 8192 (the
+ * block's decisions stay in LDS); 1 <= max_wraps <= 32.
+ *   cpx_tbcc_encode  msg [B][T k] uint8 (bit 0 of a byte counts) -> word [B][T n] uint8: the encoder walks the message once from state
+ *                    0, starts again in the state it ended in and emits that second walk.  closed [B] uint8 (may be NULL): 1 = the
+ *                    second walk ended where it began (0: a recursive trellis, or a message shorter than the encoder memory).
+ *   cpx_tbcc_decode  coded [B][T n] float64, read per decoding_type (CPX_VIT_*) as cpx_viterbi_decode_batch reads it, 'soft' clipped to
+ *                    +-500.  float64, sums in the order written: bm_t[c] = the sum over the n bits, MSB first and starting from 0.0, of
+ *                    the Viterbi decoder's per-bit metric for step t; M[s] = 0 for every state before the first trip.  On trip
+ *                    w = 1 .. max_wraps: (1) M_start = M.  (2) Steps t = 0 .. T - 1: every state takes its candidates in np.where
+ *                    order, cand_j = M[pred_j] + bm_t[code_j], and keeps the first minimum (a later candidate replaces it only if
+ *                    strictly smaller); metrics run on across trips without rescaling.  (3) origin[s] = the state in which the survivor
+ *                    ending in s began this trip, net[s] = M[s] - M_start[origin[s]].  (4) s* = the first state of minimum M; if
+ *                    origin[s*] == s*: that path, wraps = w, tailbiting = 1, metric = net[s*].  (5) Otherwise c, the first state of
+ *                    minimum net among the states with origin[s] == s, replaces the remembered candidate only if its net is strictly
+ *                    smaller; a remembered candidate keeps its bits.  (6) After the last trip: the remembered candidate, wraps =
+ *                    max_wraps, tailbiting = 1; none: the path of the last s*, tailbiting = 0, metric = net[s*].  A row that holds a
+ *                    NaN, or +-inf under 'hard' / 'unquantized', is rejected and not decoded: zero bits, wraps = 0, tailbiting = 0,
+ *                    metric = NaN; no other row is affected.  Outputs, each may be NULL (not all): bits [B][T k] uint8, wraps [B]
+ *                    int32, tailbiting [B] uint8, metric [B] float64.  Equal to tests/tbcc_model.py bit for bit.
+ * The _dev forms take device pointers and a stream and are asynchronous; the others take host pointers and return synchronised.
+ * B = 0 returns CPX_OK without a launch. */
+int cpx_tbcc_encode(const cpx_trellis *t, const uint8_t *msg, int64_t B, int64_t T, uint8_t *word, uint8_t *closed);
+int cpx_tbcc_encode_dev(const cpx_trellis *t, const uint8_t *d_msg, int64_t B, int64_t T, uint8_t *d_word, uint8_t *d_closed, void *stream);
+int cpx_tbcc_decode(const cpx_trellis *t, const double *coded, int64_t B, int64_t T, int decoding_type, int max_wraps, uint8_t *bits,
+                    int32_t *wraps, uint8_t *tailbiting, double *metric);
+int cpx_tbcc_decode_dev(const cpx_trellis *t, const double *d_coded, int64_t B, int64_t T, int decoding_type, int max_wraps, uint8_t *d_bits,
+                        int32_t *d_wraps, uint8_t *d_tailbiting, double *d_metric, void *stream);
+
 /* ---- multi-GPU: RCCL collectives of the sharded decode ------------------------------------
  * The path shards by codeword (contiguous blocks of B/G codewords per GPU, tables replicated) and has no exchange
  * step inside a decoder.  Two collectives exist around it:

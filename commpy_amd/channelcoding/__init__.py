@@ -13,10 +13,12 @@ from commpy_amd.channelcoding.algcode import cyclic_code_genpoly, bch_genpoly, r
 from commpy_amd.channelcoding.bch import BCHCode, bch_encode, bch_decode
 from commpy_amd.channelcoding.rs import RSCode, rs_encode, rs_decode
 from commpy_amd.channelcoding.tailbiting import tailbiting_encode, tailbiting_decode
+from commpy_amd.channelcoding.ldpc_layered import ldpc_layers, ldpc_layered_decode
 
 __all__ = ['Trellis', 'conv_encode', 'conv_encode_batch', 'viterbi_decode', 'puncturing', 'depuncturing',
            'RandInterlv', 'turbo_encode', 'map_decode', 'turbo_decode', 'build_matrix', 'get_ldpc_code_params',
            'ldpc_bp_decode', 'write_ldpc_params', 'triang_ldpc_systematic_encode',
            'polar_reliability_order', 'PolarCode', 'crc_append', 'crc_check', 'polar_encode', 'polar_decode',
            'GF', 'polydivide', 'polymultiply', 'poly_to_string', 'cyclic_code_genpoly', 'bch_genpoly', 'BCHCode', 'bch_encode',
-           'bch_decode', 'rs_genpoly', 'RSCode', 'rs_encode', 'rs_decode', 'tailbiting_encode', 'tailbiting_decode']
+           'bch_decode', 'rs_genpoly', 'RSCode', 'rs_encode', 'rs_decode', 'tailbiting_encode', 'tailbiting_decode',
+           'ldpc_layers', 'ldpc_layered_decode']

@@ -17,7 +17,8 @@ __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu',
            'depuncturing_gpu', 'puncture_indices', 'depuncture_indices', 'turbo_encode_gpu', 'LdpcEncoder', 'gf2_generator',
            'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
            'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev',
-           'bch_encode_dev', 'bch_decode_dev', 'rs_encode_dev', 'rs_decode_dev', 'tailbiting_encode_dev', 'tailbiting_decode_dev']
+           'bch_encode_dev', 'bch_decode_dev', 'rs_encode_dev', 'rs_decode_dev', 'tailbiting_encode_dev', 'tailbiting_decode_dev',
+           'ldpc_layered_decode_dev']
 
 
 class DeviceBuf:
@@ -613,5 +614,31 @@ def tailbiting_decode_dev(trellis, d_coded, B, T, decoding_type='hard', max_wrap
         p = lambda v: None if v is None else v.ptr
         _lib.check(_lib.load().cpx_tbcc_decode_dev(device_trellis(trellis), d_coded.ptr, B, T, vtype, max_wraps, p(out.get('bits')),
                                                    p(out.get('wraps')), p(out.get('tailbiting')), p(out.get('metric')), stream))
+    res = tuple(out[name] for name in WANT if name in want)
+    return res[0] if len(res) == 1 else res
+
+
+# ---- layered min-sum LDPC decoding, device resident (csrc/ldpc_layered.hip) ---------------------------------------------------------
+
+def ldpc_layered_decode_dev(ldpc_code_params, d_llr, B, n_iters, alpha=1.0, beta=0.0, schedule=None, early_stop=True, llr_clip=500.0,
+                            want=('bits',), stream=None):
+    """``cpx_ldpc_layered_decode_dev``: ``d_llr [B][n_v]`` float64 (left unchanged) -> new ``DeviceBuf``s queued on ``stream`` (None: the
+    library's), the results of ``channelcoding.ldpc_layered_decode`` that ``want`` names, in its order: 'bits' ``[B][n_v]`` int8, 'llr'
+    ``[B][n_v]`` float64, 'iters' ``[B]`` int32, 'converged' ``[B]`` uint8; a single result for one name.  The same checks, on the host,
+    before any device call."""
+    from commpy_amd.channelcoding.gfields import whole
+    from commpy_amd.channelcoding.ldpc_layered import WANT, check_n_iters, check_scaling, check_want, plan
+    n_iters = check_n_iters(n_iters)
+    alpha, beta, llr_clip = check_scaling(alpha, beta, llr_clip)
+    want = check_want(want)
+    p = plan(ldpc_code_params, schedule)
+    B = whole(B, 'B', 0)
+    sizes = {'bits': B * p.n_v, 'llr': B * p.n_v * 8, 'iters': B * 4, 'converged': B}
+    out = {name: DeviceBuf(sizes[name]) for name in sizes if name in want}
+    if B:
+        q = lambda v: None if v is None else v.ptr
+        _lib.check(_lib.load().cpx_ldpc_layered_decode_dev(p.handle(), d_llr.ptr, B, n_iters, alpha, beta, 1 if early_stop else 0, llr_clip,
+                                                           q(out.get('bits')), q(out.get('llr')), q(out.get('iters')),
+                                                           q(out.get('converged')), stream))
     res = tuple(out[name] for name in WANT if name in want)
     return res[0] if len(res) == 1 else res

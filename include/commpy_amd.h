@@ -888,6 +888,45 @@ int cpx_tbcc_decode(const cpx_trellis *t, const double *coded, int64_t B, int64_
 int cpx_tbcc_decode_dev(const cpx_trellis *t, const double *d_coded, int64_t B, int64_t T, int decoding_type, int max_wraps, uint8_t *d_bits,
                         int32_t *d_wraps, uint8_t *d_tailbiting, double *d_metric, void *stream);
 
+/* ---- layered normalised / offset min-sum LDPC decoding (csrc/ldpc_layered.hip) -----------------------
+ * The code is the edge list of cpx_ldpc_create, sorted by (check, variable).  A schedule is an ordered list of layers; a layer is a list
+ * of checks; every check appears exactly once and no two checks of one layer share a variable: layer l holds
+ * layer_checks[layer_start[l] .. layer_start[l + 1]), layer_start[0] = 0, layer_start[n_layers] = n_c.
+ * The rule (float64, operations in the order written, no fused multiply-add); LLRs are positive for bit 0:
+ *   Start.       Q[v] = min(max(llr[v], -llr_clip), llr_clip) on a copy (the caller's array is not modified); R[e] = +0.0 for every edge.
+ *   Iterations.  it = 1 .. n_iters; within an iteration the layers in order; for every check c of the layer, its edges j in stored order:
+ *                  m_j  = Q[v_j] - R_cj
+ *                  a_j  = min over i != j of |m_i|
+ *                  g_j  = max(alpha * a_j - beta, 0.0)        two roundings: the product, then the difference
+ *                  s_j  = XOR over i != j of signbit(m_i)     the sign BIT: -0.0 counts as negative
+ *                  R_cj = s_j ? -g_j : g_j
+ *                  Q[v_j] = m_j + R_cj
+ *                No variable is touched twice within a layer, so the order of its checks cannot matter.
+ *   Decision.    After the last layer of an iteration bit[v] = signbit(Q[v]).  With early_stop: if every check's parity of bits is even
+ *                the block stops with iters = it, converged = 1; a block that never stops has iters = n_iters, converged = 0.  Without
+ *                early_stop iters = n_iters and converged is the parity test on the final bits.
+ *   Rejection.   A block with a NaN anywhere in its LLRs is rejected on its own: bits all zero, the llr output all NaN, iters = 0,
+ *                converged = 0.  +-inf is no reason to reject: the clip maps it to +-llr_clip.
+ * Equal to tests/ldpc_layered_model.py bit for bit, whatever the batch size, the block's place, the stream and the outputs requested.
+ * Limits (CPX_ELIMIT, naming the limit, checked before a device is looked for): every check degree 2 .. 32; a schedule that is a
+ * conflict-free partition of the checks; the state of one block in LDS, 8 n_v + 24 n_c bytes, at most 163 840 (there is no HBM path);
+ * n_iters >= 1; alpha > 0, beta >= 0, llr_clip > 0, all finite.  CPX_EINVAL: null pointers, an edge out of range, an edge list that is
+ * not sorted or repeats an edge, no output requested.
+ *   cpx_ldpc_layered_decode  llr [B][n_v] float64, one block per row.  Outputs, each may be NULL (not all): bits [B][n_v] int8,
+ *                            llr_out [B][n_v] float64 (the final Q), iters [B] int32, converged [B] uint8.
+ * The _dev form takes device pointers and a stream and is asynchronous; the other takes host pointers and returns synchronised.
+ * B = 0 returns CPX_OK without a launch.  cpx_last_kernel names the kernel, the blocks per workgroup, its LDS, the workgroups per compute
+ * unit that the runtime's occupancy query reports and the blocks resident on the device. */
+typedef struct cpx_ldpc_layered cpx_ldpc_layered;
+int cpx_ldpc_layered_create(int n_v, int n_c, int64_t n_edges, const int32_t *edge_check, const int32_t *edge_var, int n_layers,
+                            const int32_t *layer_start, const int32_t *layer_checks, cpx_ldpc_layered **out);
+int cpx_ldpc_layered_destroy(cpx_ldpc_layered *c);
+int cpx_ldpc_layered_decode(const cpx_ldpc_layered *c, const double *llr, int64_t B, int n_iters, double alpha, double beta, int early_stop,
+                            double llr_clip, int8_t *bits, double *llr_out, int32_t *iters, uint8_t *converged);
+int cpx_ldpc_layered_decode_dev(const cpx_ldpc_layered *c, const double *d_llr, int64_t B, int n_iters, double alpha, double beta,
+                                int early_stop, double llr_clip, int8_t *d_bits, double *d_llr_out, int32_t *d_iters, uint8_t *d_converged,
+                                void *stream);
+
 /* ---- multi-GPU: RCCL collectives of the sharded decode ------------------------------------
  * The path shards by codeword (contiguous blocks of B/G codewords per GPU, tables replicated) and has no exchange
  * step inside a decoder.  Two collectives exist around it:

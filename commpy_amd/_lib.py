@@ -213,6 +213,9 @@ SYMBOLS = {
     "cpx_bch_encode_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "cpx_bch_decode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "cpx_bch_decode_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpx_chase_bch": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_double, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpx_chase_bch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_double, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cpx_rs_create": (c_int, [c_int, c_uint32, c_int, c_int, c_int, c_void_p, POINTER(c_void_p)]),
     "cpx_rs_destroy": (c_int, [c_void_p]),
     "cpx_rs_encode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -10,7 +10,8 @@ from commpy_amd.channelcoding.polar import (polar_reliability_order, PolarCode, 
                                             polar_decode)
 from commpy_amd.channelcoding.gfields import GF, polydivide, polymultiply, poly_to_string
 from commpy_amd.channelcoding.algcode import cyclic_code_genpoly, bch_genpoly, rs_genpoly
-from commpy_amd.channelcoding.bch import BCHCode, bch_encode, bch_decode
+from commpy_amd.channelcoding.bch import BCHCode, bch_encode, bch_decode, chase_decode
+from commpy_amd.channelcoding.productcode import ProductCode, tpc_encode, tpc_decode
 from commpy_amd.channelcoding.rs import RSCode, rs_encode, rs_decode
 from commpy_amd.channelcoding.tailbiting import tailbiting_encode, tailbiting_decode
 from commpy_amd.channelcoding.ldpc_layered import ldpc_layers, ldpc_layered_decode
@@ -21,4 +22,4 @@ __all__ = ['Trellis', 'conv_encode', 'conv_encode_batch', 'viterbi_decode', 'pun
            'polar_reliability_order', 'PolarCode', 'crc_append', 'crc_check', 'polar_encode', 'polar_decode',
            'GF', 'polydivide', 'polymultiply', 'poly_to_string', 'cyclic_code_genpoly', 'bch_genpoly', 'BCHCode', 'bch_encode',
            'bch_decode', 'rs_genpoly', 'RSCode', 'rs_encode', 'rs_decode', 'tailbiting_encode', 'tailbiting_decode',
-           'ldpc_layers', 'ldpc_layered_decode']
+           'ldpc_layers', 'ldpc_layered_decode', 'chase_decode', 'ProductCode', 'tpc_encode', 'tpc_decode']

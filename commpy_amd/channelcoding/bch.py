@@ -1,4 +1,5 @@
-"""Binary BCH codes on MI355X: systematic encoder and bounded-distance decoder (syndromes, Berlekamp-Massey, Chien search).
+"""Binary BCH codes on MI355X: systematic encoder, bounded-distance decoder (syndromes, Berlekamp-Massey, Chien search) and the
+Chase-II soft-decision decoder with Pyndiah's soft output (csrc/bch_chase.hip, equal to tests/chase_model.py bit for bit).
 
 A word is ``n`` bits; bit ``i`` is the coefficient of ``x^(n-1-i)``: the ``k`` message bits first, then the ``n - k`` bits of
 ``x^(n-k) m(x) mod g(x)``.  The generator (``algcode.bch_genpoly``) and the field are host work; the kernels of csrc/bch.hip receive
@@ -12,10 +13,12 @@ from commpy_amd import _lib
 from commpy_amd.channelcoding.algcode import bch_genpoly
 from commpy_amd.channelcoding.gfields import field, whole
 
-__all__ = ['BCHCode', 'bch_encode', 'bch_decode']
+__all__ = ['BCHCode', 'bch_encode', 'bch_decode', 'chase_decode']
 
 BCH_MIN_M, BCH_MAX_M, BCH_MAX_T = 3, 14, 32      # csrc/bch.hip
 WANT = ('bits', 'codeword', 'errors')
+CHASE_WANT = ('bits', 'codeword', 'extrinsic', 'metric', 'candidates')
+CHASE_MAX_P = 8                                   # csrc/bch_chase.hip
 
 
 class BCHCode:
@@ -114,4 +117,61 @@ def bch_decode(bits, code, want=('bits',)):
         _lib.check(_lib.load().cpx_bch_decode(code._device_handle(), _lib.ptr(rows), B, p(res.get('bits')), p(res.get('codeword')),
                                               p(res.get('errors'))))
     out = [res[name][0] if one else res[name] for name in WANT if name in want]
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def chase_args(code, p, beta, alpha, want):
+    """The scalar arguments of the Chase decoder, checked: ``(code, p, beta, alpha, want)``."""
+    code = _code(code)
+    p = whole(p, 'p', 1, min(CHASE_MAX_P, code.n))
+    for name, v in (('beta', beta), ('alpha', alpha)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError('%s = %r, need a finite number' % (name, v))
+    if beta < 0:
+        raise ValueError('beta = %r, need >= 0' % (beta,))
+    return code, p, float(beta), float(alpha), _lib.wanted(want, CHASE_WANT)
+
+
+def _llr_rows(llr, name, width):
+    a = np.asarray(llr)
+    if a.ndim not in (1, 2):
+        raise ValueError('%s must be 1-D or 2-D, got %d dimensions' % (name, a.ndim))
+    if a.dtype.kind not in 'iuf':
+        raise ValueError('%s must hold real numbers, got dtype %s' % (name, a.dtype))
+    if a.shape[-1] != width:
+        raise ValueError('%s has %d values per row, need %d' % (name, a.shape[-1], width))
+    return np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64), a.ndim == 1
+
+
+def chase_decode(llr, code, p, beta, prior=None, alpha=1.0, want=('bits',)):
+    """Chase-II soft-decision decoding of ``llr [B, n]`` (or 1-D ``[n]``) float64, positive = bit 0, with Pyndiah's soft output.
+    Per word: ``x = llr`` (``llr + alpha * prior`` with ``prior [B, n]``); the ``p`` least reliable positions by ``(|x_i|, i)``
+    (``1 <= p <= min(8, n)``); each of the ``2^p`` test patterns over them is decoded by the rule of ``bch_decode``; the decision is
+    the candidate code word of least metric (the sum of ``|x_i|`` where it differs from the hard decisions; ties go to the lowest
+    pattern).  ``want`` names the results, returned in the order listed here (a single result for one name):
+
+    ``'bits'`` ``[B, k]`` uint8; ``'codeword'`` ``[B, n]`` uint8, the decision; ``'extrinsic'`` ``[B, n]`` float64:
+    ``s_i (M_C - M_D) - x_i`` with ``s_i = +-1`` the decision's sign and ``M_C`` the least metric of the candidates that differ from
+    the decision at ``i``, ``s_i beta`` where no candidate does (``beta >= 0`` in LLR units) -- ``x + extrinsic`` is the max-log
+    a-posteriori LLR over the candidate list; ``'metric'`` ``[B]`` float64; ``'candidates'`` ``[B]`` int32, the number of test
+    patterns that decoded.
+
+    Without a candidate the hard decisions are returned with metric ``+inf`` and extrinsic 0.  A word that holds a NaN or an
+    infinity is rejected on its own: the same, with ``candidates = -1`` (a NaN counts as bit 0)."""
+    code, p, beta, alpha, want = chase_args(code, p, beta, alpha, want)
+    rows, one = _llr_rows(llr, 'llr', code.n)
+    pri = None
+    if prior is not None:
+        pri, _ = _llr_rows(prior, 'prior', code.n)
+        if pri.shape != rows.shape or (np.ndim(prior) == 1) != one:
+            raise ValueError('prior has shape %s, need that of llr' % (np.shape(prior),))
+    B = rows.shape[0]
+    shapes = {'bits': ((B, code.k), np.uint8), 'codeword': ((B, code.n), np.uint8), 'extrinsic': ((B, code.n), np.float64),
+              'metric': ((B,), np.float64), 'candidates': ((B,), np.int32)}
+    res = {name: np.zeros(*shapes[name]) for name in CHASE_WANT if name in want}
+    if B:
+        q = lambda v: None if v is None else _lib.ptr(v)
+        _lib.check(_lib.load().cpx_chase_bch(code._device_handle(), _lib.ptr(rows), q(pri), alpha, beta, p, B, q(res.get('bits')),
+                                             q(res.get('codeword')), q(res.get('extrinsic')), q(res.get('metric')), q(res.get('candidates'))))
+    out = [res[name][0] if one else res[name] for name in CHASE_WANT if name in want]
     return out[0] if len(out) == 1 else tuple(out)

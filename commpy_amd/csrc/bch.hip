@@ -4,6 +4,7 @@
 // shortened from 2^m - 1 to n drops the highest degrees.  Field elements are integers (bit j = coefficient of alpha^j); the handle holds
 // exp[e] = alpha^e and log[v] as uint16 tables of 2^m entries each.
 //
+// The decoder's stages (field arithmetic, syndromes, Berlekamp-Massey, Chien search) live in bch_dev.h, shared with bch_chase.hip.
 // bch_decode_kernel: one received word per wave, up to 16 waves per workgroup, workgroups stride over the batch.  The two tables are staged
 //   into LDS once per workgroup (2^(m+2) bytes: 64 KiB at m = 14); after that barrier the waves never meet again.  Per word:
 //   1. the bytes are read once, 64 positions per load and eight loads in flight, and kept as ballot words in LDS (rw);
@@ -20,28 +21,13 @@
 // bch_encode_kernel: one word per lane, 64 words per wave.  The wave reads 64 message bytes of each of its words at a time (a coalesced
 //   row segment, copied to the output on the way) and ballots them into one 64-bit word per lane; every lane then runs 64 steps of the long
 //   division on its own remainder of RW 64-bit words, the generator being kernel-argument data.  Nothing in it is specific to BCH codes.
-#include "cpx_gf.h"
-#include "cpx_internal.h"
-#include "cpx_wave.h"
+#include "bch_dev.h"
 
 #include <mutex>
 
 using namespace cpx;
 
-#define CPX_BCH_MIN_M 3
-#define CPX_BCH_MAX_M 14
-#define CPX_BCH_MAX_T 32
-#define CPX_BCH_MAX_GEN_WORDS 7            // 64-bit words of a remainder: deg g <= 14 * 32 = 448
-#define CPX_BCH_LDS_MAX (160 * 1024)
-#define BCH_MAX_WAVES 16
 #define BCH_ENC_THREADS 256
-
-struct cpx_bch {
-    __attribute__((visibility("hidden"))) ~cpx_bch() = default;
-    int m, N, n, k, t, deg, device;
-    uint64_t gen[CPX_BCH_MAX_GEN_WORDS];   // g without its leading term, bit j of word w = coefficient of x^(64 w + j)
-    uint16_t *d_tab = nullptr;             // [2][2^m]: exp then log
-};
 
 namespace {
 
@@ -56,77 +42,13 @@ struct BchDecArgs {
 
 // bytes of LDS per wave: rw and fm (nw 64-bit words each), then the 2t syndromes and the logarithms of sigma's coefficients
 __host__ __device__ inline unsigned bch_wave_lds(int nw) { return 16u * (unsigned)nw + 2u * 64u + 2u * 64u; }
-__host__ __device__ inline unsigned bch_tab_lds(int m) { return 4u << m; }
-
-// waves per workgroup and workgroups of the grid: small tables leave room for several workgroups per compute unit
-inline int bch_waves(int m) { return m <= 8 ? 4 : m <= 11 ? 8 : BCH_MAX_WAVES; }
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ unsigned wave_xor(unsigned v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v ^= (unsigned)__shfl_xor((int)v, d);
-    return v;
-}
-
-struct Gf {
-    const uint16_t *ex, *lg;
-    int N;
-    __device__ __forceinline__ unsigned mul(unsigned a, unsigned b) const {
-        if (a == 0u || b == 0u) return 0u;
-        int e = (int)lg[a] + (int)lg[b];
-        if (e >= N) e -= N;
-        return ex[e];
-    }
-};
-
-// S_j for the G odd indices j0, j0 + 2, ...: synd[j - 1] = XOR over the set bits of alpha^(j d), d the degree of the position
-template <int G>
-__device__ __forceinline__ void syndrome_group(const Gf &gf, const unsigned long long *rw, uint16_t *synd, int nw, int j0, int d0, int lane) {
-    const int N = gf.N;
-    int e[G], step[G];
-    unsigned acc[G];
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-        const int j = j0 + 2 * u;
-        step[u] = (64 * j) % N;
-        e[u] = d0 > 0 ? (int)((unsigned)(j * d0) % (unsigned)N) : 0;        // j d0 < 64 * 2^14
-        acc[u] = 0u;
-    }
-    for (int c = 0; c < nw; ++c) {
-        const unsigned take = 0u - (unsigned)((rw[c] >> lane) & 1ull);
-#pragma unroll
-        for (int u = 0; u < G; ++u) {
-            acc[u] ^= gf.ex[e[u]] & take;                         // e stays in 0 .. N - 1 on every lane: the gather needs no mask
-            e[u] -= step[u];
-            if (e[u] < 0) e[u] += N;
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-        const unsigned s = wave_xor(acc[u]);
-        if (lane == 0) synd[j0 + 2 * u - 1] = (uint16_t)s;
-    }
-}
 
 __global__ __launch_bounds__(BCH_MAX_WAVES * 64) void bch_decode_kernel(BchDecArgs a) {
     extern __shared__ double2 bch_lds_raw[];
     unsigned char *base = reinterpret_cast<unsigned char *>(bch_lds_raw);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
     const int n = a.n, k = a.k, t = a.t, N = a.N, nw = a.nw;
-    {
-        uint32_t *dst = reinterpret_cast<uint32_t *>(base);
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.tab);
-        for (int i = tid; i < (1 << a.m); i += blockDim.x) dst[i] = src[i];
-    }
-    __syncthreads();
-    Gf gf;
-    gf.ex = reinterpret_cast<const uint16_t *>(base);
-    gf.lg = gf.ex + (1 << a.m);
-    gf.N = N;
+    const Gf gf = stage_tables(base, a.tab, a.m, N);
     unsigned char *mine = base + bch_tab_lds(a.m) + (unsigned)wave * bch_wave_lds(nw);
     unsigned long long *rw = reinterpret_cast<unsigned long long *>(mine), *fm = rw + nw;
     uint16_t *synd = reinterpret_cast<uint16_t *>(fm + nw), *clog = synd + 64;
@@ -148,90 +70,14 @@ __global__ __launch_bounds__(BCH_MAX_WAVES * 64) void bch_decode_kernel(BchDecAr
             }
         }
         wave_sync();
-        // syndromes of the odd indices, four (then two, then one) at a time: one read of rw and independent gathers per chunk
-        const int d0 = n - 1 - lane;                              // the degree of this lane's position in chunk 0; negative: no position
-        {
-            int j = 1;
-            for (; j + 6 < 2 * t; j += 8) syndrome_group<4>(gf, rw, synd, nw, j, d0, lane);
-            if (j + 2 < 2 * t) { syndrome_group<2>(gf, rw, synd, nw, j, d0, lane); j += 4; }
-            if (j < 2 * t) syndrome_group<1>(gf, rw, synd, nw, j, d0, lane);
-        }
-        wave_sync();
-        if ((lane & 1) && lane < 2 * t) {                          // lane = odd j: S_2j, S_4j, ...
-            unsigned v = synd[lane - 1];
-            for (int jj = 2 * lane; jj <= 2 * t; jj *= 2) {
-                v = gf.mul(v, v);
-                synd[jj - 1] = (uint16_t)v;
-            }
-        }
-        wave_sync();
+        syndromes(gf, rw, synd, n, nw, t, lane);
         int errors = 0;
         const bool dirty = __ballot(lane < 2 * t && synd[lane] != 0) != 0ull;
         if (dirty) {
-            // Berlekamp-Massey: C the connection polynomial, Bp the one before the last length change, b its discrepancy, sh the shift
-            unsigned C = lane == 0 ? 1u : 0u, Bp = C, b = 1u;
-            int L = 0, sh = 1;
-            bool fail = false;
-            for (int r = 0; r < 2 * t; ++r) {
-                const unsigned d = wave_xor(lane <= L ? gf.mul(C, synd[r - lane]) : 0u);
-                if (d == 0u) { ++sh; continue; }
-                int e = (int)gf.lg[d] - (int)gf.lg[b];
-                if (e < 0) e += N;
-                const unsigned coef = gf.ex[e];
-                const unsigned moved = (unsigned)__shfl((int)Bp, lane >= sh ? lane - sh : lane);
-                const unsigned next = C ^ gf.mul(coef, lane >= sh ? moved : 0u);
-                if (2 * L <= r) {
-                    L = r + 1 - L;
-                    if (L > t) { fail = true; break; }
-                    Bp = C;
-                    b = d;
-                    sh = 1;
-                } else {
-                    ++sh;
-                }
-                C = next;
-            }
-            if (!fail && __shfl((int)C, L) == 0) fail = true;     // sigma of a lower degree than its length: fewer than L roots
-            int count = 0;
-            if (!fail) {
-                if (lane <= L) clog[lane] = C ? gf.lg[C] : (uint16_t)0xFFFF;
-                wave_sync();
-                for (int c0 = 0; c0 < nw; c0 += 4) {              // four chunks share the read of clog[q]; their gathers are independent
-                    int kk[4], qk[4];
-                    unsigned v[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int d = n - 1 - ((c0 + u) * 64 + lane);
-                        kk[u] = d > 0 ? N - d : 0;                // -d mod N; a lane past the word's end computes a value nobody reads
-                        qk[u] = 0;
-                        v[u] = 1u;                                // C_0 = 1
-                    }
-                    for (int q = 1; q <= L; ++q) {
-                        const int cl = clog[q];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            qk[u] += kk[u];
-                            if (qk[u] >= N) qk[u] -= N;
-                        }
-                        if (cl != 0xFFFF) {
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) {
-                                int e = cl + qk[u];
-                                if (e >= N) e -= N;
-                                v[u] ^= gf.ex[e];
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int i = (c0 + u) * 64 + lane;
-                        const unsigned long long roots = __ballot(i < n && v[u] == 0u);
-                        if (lane == 0 && c0 + u < nw) fm[c0 + u] = roots;
-                        count += __popcll(roots);
-                    }
-                }
-                if (count != L) fail = true;
-            }
+            unsigned C;
+            int L;
+            bool fail = berlekamp_massey(gf, synd, t, lane, C, L);
+            if (!fail && chien_search<false>(gf, C, L, clog, fm, n, nw, lane) != L) fail = true;
             errors = fail ? -1 : L;
             wave_sync();
         }

@@ -18,7 +18,7 @@ __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu',
            'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
            'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev',
            'bch_encode_dev', 'bch_decode_dev', 'rs_encode_dev', 'rs_decode_dev', 'tailbiting_encode_dev', 'tailbiting_decode_dev',
-           'ldpc_layered_decode_dev']
+           'ldpc_layered_decode_dev', 'bch_chase_dev', 'tpc_decode_dev']
 
 
 class DeviceBuf:
@@ -546,6 +546,74 @@ def bch_decode_dev(code, d_bits, B, want=('bits',), stream=None):
         _lib.check(_lib.load().cpx_bch_decode_dev(code._device_handle(), d_bits.ptr, B, p(out.get('bits')), p(out.get('codeword')),
                                                   p(out.get('errors')), stream))
     res = tuple(out[k] for k in WANT if k in want)
+    return res[0] if len(res) == 1 else res
+
+
+# ---- Chase-II BCH decoding and turbo product codes, device resident (csrc/bch_chase.hip) -----------------------------------------------
+
+def bch_chase_dev(code, d_llr, B, p, beta, d_prior=None, alpha=1.0, want=('bits',), J=1, strides=None, d_extrinsic=None, stream=None):
+    """``cpx_chase_bch_dev``: Chase-II decoding of the ``B * J`` words of ``d_llr`` (float64), queued on ``stream``.  Element ``i`` of
+    word ``(b, j)`` is at ``b sb + j sj + i si`` with ``strides = (sb, sj, si)`` in elements (default: the flat batch ``(n, 0, 1)``,
+    which needs ``J = 1``); ``d_prior`` (optional) and the 'extrinsic' and 'codeword' results have the same layout, so that the rows
+    or the columns of a block decode in place.  Returns new ``DeviceBuf``s, the results of ``channelcoding.chase_decode`` that
+    ``want`` names, in its order: 'bits' uint8 (dense, nested as the input: ``[B][J][k]``, or ``[B][k][J]`` where the word axis is the
+    inner one), 'codeword' uint8 and 'extrinsic' float64 (each as large as ``sb * B`` elements), 'metric' float64 and 'candidates'
+    int32 ``[B][J]``.  ``d_extrinsic``: write the soft output there instead of into a new buffer -- it may be ``d_prior``."""
+    from commpy_amd.channelcoding.bch import CHASE_WANT, chase_args
+    from commpy_amd.channelcoding.gfields import whole
+    code, p, beta, alpha, want = chase_args(code, p, beta, alpha, want)
+    B, J = whole(B, 'B', 0), whole(J, 'J', 1)
+    if strides is None:
+        if J != 1:
+            raise ValueError('J = %d needs strides' % J)
+        strides = (code.n, 0, 1)
+    if len(strides) != 3:
+        raise ValueError('strides must be (sb, sj, si)')
+    sb, sj, si = (whole(v, 'stride', 0, (1 << 40) - 1) for v in strides)
+    span_i, span_j = (code.n - 1) * si, (J - 1) * sj
+    if si < 1 or (J > 1 and not (sj > span_i or (sj >= 1 and si > span_j))) or (B > 1 and sb <= span_i + span_j):
+        raise ValueError('strides %r: the words overlap' % (tuple(strides),))
+    if d_extrinsic is not None and 'extrinsic' not in want:
+        raise ValueError("d_extrinsic needs 'extrinsic' in want")
+    extent = (B - 1) * sb + span_i + span_j + 1 if B else 0
+    sizes = {'bits': B * J * code.k, 'codeword': extent, 'extrinsic': 8 * extent, 'metric': 8 * B * J, 'candidates': 4 * B * J}
+    out = {k: d_extrinsic if k == 'extrinsic' and d_extrinsic is not None else DeviceBuf(sizes[k]) for k in CHASE_WANT if k in want}
+    if B:
+        q = lambda v: None if v is None else v.ptr
+        _lib.check(_lib.load().cpx_chase_bch_dev(code._device_handle(), d_llr.ptr, q(d_prior), alpha, beta, p, B, J, sb, sj, si, q(out.get('bits')),
+                                                 q(out.get('codeword')), q(out.get('extrinsic')), q(out.get('metric')),
+                                                 q(out.get('candidates')), stream))
+    res = tuple(out[k] for k in CHASE_WANT if k in want)
+    return res[0] if len(res) == 1 else res
+
+
+def tpc_decode_dev(code, d_llr, B, iters=4, p=4, alpha=None, beta=None, llr_scale=1.0, want=('codeword',), stream=None):
+    """Iterative decoding of ``B`` blocks ``d_llr [B][n_c][n_r]`` float64 of a ``channelcoding.ProductCode``, all on the device:
+    ``2 * iters`` Chase launches on ``stream``, alternately along the rows and the columns in place, each taking the extrinsic output
+    of the one before as its prior (``channelcoding.tpc_decode`` states the schedule).  Returns new ``DeviceBuf``s, what ``want``
+    names out of 'codeword' ``[B][n_c][n_r]`` uint8 (the decision of the last half-iteration) and 'extrinsic'
+    ``[B][n_c][n_r]`` float64 (its soft output), in this order."""
+    from commpy_amd.channelcoding.gfields import whole
+    from commpy_amd.channelcoding.productcode import TPC_DEV_WANT, tpc_args
+    code, iters, p, alpha, beta = tpc_args(code, iters, p, alpha, beta, llr_scale)
+    B = whole(B, 'B', 0)
+    want = _lib.wanted(want, TPC_DEV_WANT)
+    nr, nc = code.n_r, code.n_c
+    d_w = DeviceBuf(8 * B * nc * nr)                              # W, the extrinsic information: zero, then rewritten in place
+    if B:
+        _lib.check(d_w.lib.cpx_memset(d_w.ptr, 0, d_w.nbytes))
+    d_word = None
+    for h in range(2 * iters):
+        rows = h % 2 == 0
+        comp, J, strides = (code.row_code, nc, (nc * nr, nr, 1)) if rows else (code.col_code, nr, (nc * nr, 1, nr))
+        last = h == 2 * iters - 1
+        names = ('codeword', 'extrinsic') if last and 'codeword' in want else ('extrinsic',)
+        res = bch_chase_dev(comp, d_llr, B, min(p, comp.n), beta[h], d_prior=d_w, alpha=alpha[h], want=names, J=J, strides=strides,
+                            d_extrinsic=d_w, stream=stream)
+        if len(names) == 2:
+            d_word = res[0]
+    out = {'codeword': d_word, 'extrinsic': d_w}
+    res = tuple(out[k] for k in TPC_DEV_WANT if k in want)
     return res[0] if len(res) == 1 else res
 
 

@@ -827,6 +827,30 @@ int cpx_bch_decode(const cpx_bch *p, const uint8_t *in, int64_t B, uint8_t *bits
 int cpx_bch_decode_dev(const cpx_bch *p, const uint8_t *d_in, int64_t B, uint8_t *d_bits, uint8_t *d_word, int32_t *d_errors,
                        void *stream);
 
+/* ---- Chase-II soft-decision BCH decoding with Pyndiah's soft output (csrc/bch_chase.hip) ----------------
+ * Works on a cpx_bch handle.  Per word of n float64 values x_i = llr_i, or fl(llr_i + fl(alpha prior_i)) with a prior (positive = bit
+ * 0): hard decisions h_i = (x_i < 0), reliabilities |x_i|; the p least reliable positions by (|x_i|, i) ascending, 1 <= p <= min(8, n);
+ * each of the 2^p test patterns tau (bit j flips the j-th of them) is decoded by the rule of cpx_bch_decode; a success is a candidate
+ * with the metric M = sum of |x_i| over the positions where it differs from h, added serially in ascending position order.  The
+ * decision D is the candidate of least metric (ties: lowest tau); without a candidate D = h, metric = +inf, extrinsic = 0.
+ * extrinsic_i = s_i (M_C - M_D) - x_i, s_i = +1 for d_i = 0 and -1 otherwise, M_C the least metric of the candidates that differ from
+ * D at i; s_i beta where there is none (beta >= 0, finite).  A word holding a non-finite x_i is rejected on its own: candidates = -1,
+ * metric = +inf, the hard decisions (NaN: bit 0), extrinsic 0.  Equal to tests/chase_model.py bit for bit.
+ *   cpx_chase_bch_dev  words (b, j), b < B, j < J; element i of word (b, j) of llr, prior, extrinsic and codeword is at
+ *                      b sb + j sj + i si (in elements): rows and columns of a block decode in place; a flat batch is J = 1, sb = n,
+ *                      si = 1.  The words must not overlap (CPX_EINVAL): either sj > (n-1) si or si > (J-1) sj, and sb above both
+ *                      spans.  bits is dense and nested as the input: [B][J][k] in the first case (and for J = 1), [B][k][J] in the
+ *                      second.  metric and candidates are [B][J].  prior may be NULL; extrinsic may be prior (a wave reads its word
+ *                      before it writes it).  Outputs may be NULL, not all of them.
+ *   cpx_chase_bch      the flat batch in host buffers: llr, prior, extrinsic [B][n], bits [B][k], codeword [B][n], metric, candidates [B].
+ * Checked before any device call: the arguments (CPX_EINVAL), and the LDS one word needs beside the field tables -- 8.25 n bytes and
+ * 2^p (2 (p + t) + 10) -- against 160 KiB (CPX_ELIMIT, the message names the byte count).  B = 0 returns CPX_OK without a launch. */
+int cpx_chase_bch_dev(const cpx_bch *p, const double *d_llr, const double *d_prior, double alpha, double beta, int test_positions, int64_t B,
+                      int64_t J, int64_t sb, int64_t sj, int64_t si, uint8_t *d_bits, uint8_t *d_codeword, double *d_extrinsic,
+                      double *d_metric, int32_t *d_candidates, void *stream);
+int cpx_chase_bch(const cpx_bch *p, const double *llr, const double *prior, double alpha, double beta, int test_positions, int64_t B,
+                  uint8_t *bits, uint8_t *codeword, double *extrinsic, double *metric, int32_t *candidates);
+
 /* ---- Reed-Solomon codes: systematic encoder and errors-and-erasures decoder (csrc/rs.hip) ---------------
  * Code of length n <= 2^m - 1 (shortened below that) over GF(2^m), 3 <= m <= 14, with r = n - k <= 63 parity symbols and the generator
  * g(x) = prod_{j<r} (x - alpha^(fcr+j)).  A word is n uint16 symbols in tuple form (bit i = coefficient of alpha^i), of which only the

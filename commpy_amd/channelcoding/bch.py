@@ -10,12 +10,13 @@ import ctypes
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd.channelcoding._algebraic import field_degree, outputs, returned, rows
 from commpy_amd.channelcoding.algcode import bch_genpoly
 from commpy_amd.channelcoding.gfields import field, whole
 
 __all__ = ['BCHCode', 'bch_encode', 'bch_decode', 'chase_decode']
 
-BCH_MIN_M, BCH_MAX_M, BCH_MAX_T = 3, 14, 32      # csrc/bch.hip
+BCH_MAX_T = 32                                    # csrc/bch_dev.h
 WANT = ('bits', 'codeword', 'errors')
 CHASE_WANT = ('bits', 'codeword', 'extrinsic', 'metric', 'candidates')
 CHASE_MAX_P = 8                                   # csrc/bch_chase.hip
@@ -30,13 +31,7 @@ class BCHCode:
     def __init__(self, n, t, m=None, prim_poly=None):
         self.n = n = whole(n, 'n', 2)
         self.t = t = whole(t, 't', 1, BCH_MAX_T)
-        if m is None:
-            if n > (1 << BCH_MAX_M) - 1:
-                raise ValueError('n = %d is above the engine limit of 2^%d - 1' % (n, BCH_MAX_M))
-            m = max(BCH_MIN_M, n.bit_length())
-        self.m = m = whole(m, 'm', BCH_MIN_M, BCH_MAX_M)
-        if n > (1 << m) - 1:
-            raise ValueError('n = %d is above 2^m - 1 = %d' % (n, (1 << m) - 1))
+        self.m = m = field_degree(n, m)
         self.prim_poly = field(m, prim_poly).prim_poly
         self.genpoly = bch_genpoly(m, t, self.prim_poly)
         deg = self.genpoly.bit_length() - 1
@@ -67,16 +62,7 @@ def check_want(want):
 
 
 def _bit_rows(bits, name, width):
-    a = np.asarray(bits)
-    if a.ndim not in (1, 2):
-        raise ValueError('%s must be 1-D or 2-D, got %d dimensions' % (name, a.ndim))
-    if a.dtype.kind not in 'biu':
-        raise ValueError('%s must hold integers 0 / 1, got dtype %s' % (name, a.dtype))
-    if a.shape[-1] != width:
-        raise ValueError('%s has %d bits per row, need %d' % (name, a.shape[-1], width))
-    if a.size and (a.min() < 0 or a.max() > 1):
-        raise ValueError('%s must hold 0 / 1' % name)
-    return np.ascontiguousarray(np.atleast_2d(a), dtype=np.uint8), a.ndim == 1
+    return rows(bits, name, width, np.uint8, 'biu', 'integers 0 / 1', 'bits', 1, '0 / 1')
 
 
 def bch_encode(message_bits, code):
@@ -103,21 +89,12 @@ def bch_decode(bits, code, want=('bits',)):
     ``'bits'`` and ``'codeword'`` hold the received word unchanged."""
     code = _code(code)
     want = check_want(want)
-    rows, one = _bit_rows(bits, 'bits', code.n)
-    B = rows.shape[0]
-    res = {}
-    if 'bits' in want:
-        res['bits'] = np.zeros((B, code.k), dtype=np.uint8)
-    if 'codeword' in want:
-        res['codeword'] = np.zeros((B, code.n), dtype=np.uint8)
-    if 'errors' in want:
-        res['errors'] = np.zeros(B, dtype=np.int32)
+    hard, one = _bit_rows(bits, 'bits', code.n)
+    B = hard.shape[0]
+    res, p = outputs(want, {'bits': ((B, code.k), np.uint8), 'codeword': ((B, code.n), np.uint8), 'errors': ((B,), np.int32)})
     if B:
-        p = lambda v: None if v is None else _lib.ptr(v)
-        _lib.check(_lib.load().cpx_bch_decode(code._device_handle(), _lib.ptr(rows), B, p(res.get('bits')), p(res.get('codeword')),
-                                              p(res.get('errors'))))
-    out = [res[name][0] if one else res[name] for name in WANT if name in want]
-    return out[0] if len(out) == 1 else tuple(out)
+        _lib.check(_lib.load().cpx_bch_decode(code._device_handle(), _lib.ptr(hard), B, p('bits'), p('codeword'), p('errors')))
+    return returned(res, one)
 
 
 def chase_args(code, p, beta, alpha, want):
@@ -133,14 +110,7 @@ def chase_args(code, p, beta, alpha, want):
 
 
 def _llr_rows(llr, name, width):
-    a = np.asarray(llr)
-    if a.ndim not in (1, 2):
-        raise ValueError('%s must be 1-D or 2-D, got %d dimensions' % (name, a.ndim))
-    if a.dtype.kind not in 'iuf':
-        raise ValueError('%s must hold real numbers, got dtype %s' % (name, a.dtype))
-    if a.shape[-1] != width:
-        raise ValueError('%s has %d values per row, need %d' % (name, a.shape[-1], width))
-    return np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64), a.ndim == 1
+    return rows(llr, name, width, np.float64, 'iuf', 'real numbers', 'values')
 
 
 def chase_decode(llr, code, p, beta, prior=None, alpha=1.0, want=('bits',)):
@@ -159,19 +129,16 @@ def chase_decode(llr, code, p, beta, prior=None, alpha=1.0, want=('bits',)):
     Without a candidate the hard decisions are returned with metric ``+inf`` and extrinsic 0.  A word that holds a NaN or an
     infinity is rejected on its own: the same, with ``candidates = -1`` (a NaN counts as bit 0)."""
     code, p, beta, alpha, want = chase_args(code, p, beta, alpha, want)
-    rows, one = _llr_rows(llr, 'llr', code.n)
+    soft, one = _llr_rows(llr, 'llr', code.n)
     pri = None
     if prior is not None:
         pri, _ = _llr_rows(prior, 'prior', code.n)
-        if pri.shape != rows.shape or (np.ndim(prior) == 1) != one:
+        if pri.shape != soft.shape or (np.ndim(prior) == 1) != one:
             raise ValueError('prior has shape %s, need that of llr' % (np.shape(prior),))
-    B = rows.shape[0]
-    shapes = {'bits': ((B, code.k), np.uint8), 'codeword': ((B, code.n), np.uint8), 'extrinsic': ((B, code.n), np.float64),
-              'metric': ((B,), np.float64), 'candidates': ((B,), np.int32)}
-    res = {name: np.zeros(*shapes[name]) for name in CHASE_WANT if name in want}
+    B = soft.shape[0]
+    res, q = outputs(want, {'bits': ((B, code.k), np.uint8), 'codeword': ((B, code.n), np.uint8), 'extrinsic': ((B, code.n), np.float64),
+                            'metric': ((B,), np.float64), 'candidates': ((B,), np.int32)})
     if B:
-        q = lambda v: None if v is None else _lib.ptr(v)
-        _lib.check(_lib.load().cpx_chase_bch(code._device_handle(), _lib.ptr(rows), q(pri), alpha, beta, p, B, q(res.get('bits')),
-                                             q(res.get('codeword')), q(res.get('extrinsic')), q(res.get('metric')), q(res.get('candidates'))))
-    out = [res[name][0] if one else res[name] for name in CHASE_WANT if name in want]
-    return out[0] if len(out) == 1 else tuple(out)
+        _lib.check(_lib.load().cpx_chase_bch(code._device_handle(), _lib.ptr(soft), None if pri is None else _lib.ptr(pri), alpha, beta, p, B,
+                                             q('bits'), q('codeword'), q('extrinsic'), q('metric'), q('candidates')))
+    return returned(res, one)

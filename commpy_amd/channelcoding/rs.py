@@ -11,12 +11,13 @@ import ctypes
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd.channelcoding._algebraic import field_degree, outputs, returned, rows
 from commpy_amd.channelcoding.algcode import rs_genpoly
 from commpy_amd.channelcoding.gfields import field, whole
 
 __all__ = ['RSCode', 'rs_encode', 'rs_decode']
 
-RS_MIN_M, RS_MAX_M, RS_MAX_NROOTS = 3, 14, 63    # csrc/rs.hip
+RS_MAX_NROOTS = 63                                # csrc/rs.hip
 WANT = ('symbols', 'codeword', 'errors')
 
 
@@ -31,13 +32,7 @@ class RSCode:
     def __init__(self, n, k, m=None, prim_poly=None, fcr=1):
         self.n = n = whole(n, 'n', 2)
         self.k = k = whole(k, 'k', 1)
-        if m is None:
-            if n > (1 << RS_MAX_M) - 1:
-                raise ValueError('n = %d is above the engine limit of 2^%d - 1' % (n, RS_MAX_M))
-            m = max(RS_MIN_M, n.bit_length())
-        self.m = m = whole(m, 'm', RS_MIN_M, RS_MAX_M)
-        if n > (1 << m) - 1:
-            raise ValueError('n = %d is above 2^m - 1 = %d' % (n, (1 << m) - 1))
+        self.m = m = field_degree(n, m)
         self.nroots = whole(n - k, 'n - k', 1, RS_MAX_NROOTS)
         self.t = self.nroots // 2
         self.fcr = fcr = whole(fcr, 'fcr', 0, (1 << m) - 2)
@@ -67,16 +62,8 @@ def check_want(want):
 
 
 def _symbol_rows(symbols, name, width, m):
-    a = np.asarray(symbols)
-    if a.ndim not in (1, 2):
-        raise ValueError('%s must be 1-D or 2-D, got %d dimensions' % (name, a.ndim))
-    if a.dtype.kind not in 'iu':
-        raise ValueError('%s must hold integers, got dtype %s' % (name, a.dtype))
-    if a.shape[-1] != width:
-        raise ValueError('%s has %d symbols per row, need %d' % (name, a.shape[-1], width))
-    if a.size and (a.min() < 0 or a.max() >= 1 << m):
-        raise ValueError('%s must hold elements of GF(2^%d): 0 .. %d' % (name, m, (1 << m) - 1))
-    return np.ascontiguousarray(np.atleast_2d(a), dtype=np.uint16), a.ndim == 1
+    top = (1 << m) - 1
+    return rows(symbols, name, width, np.uint16, 'iu', 'integers', 'symbols', top, 'elements of GF(2^%d): 0 .. %d' % (m, top))
 
 
 def _flag_rows(erasures, shape):
@@ -118,19 +105,11 @@ def rs_decode(symbols, code, erasures=None, want=('symbols',)):
     ``'codeword'`` hold the received word unchanged."""
     code = _code(code)
     want = check_want(want)
-    rows, one = _symbol_rows(symbols, 'symbols', code.n, code.m)
+    word, one = _symbol_rows(symbols, 'symbols', code.n, code.m)
     flags = None if erasures is None else _flag_rows(erasures, np.shape(symbols))
-    B = rows.shape[0]
-    res = {}
-    if 'symbols' in want:
-        res['symbols'] = np.zeros((B, code.k), dtype=np.uint16)
-    if 'codeword' in want:
-        res['codeword'] = np.zeros((B, code.n), dtype=np.uint16)
-    if 'errors' in want:
-        res['errors'] = np.zeros(B, dtype=np.int32)
+    B = word.shape[0]
+    res, p = outputs(want, {'symbols': ((B, code.k), np.uint16), 'codeword': ((B, code.n), np.uint16), 'errors': ((B,), np.int32)})
     if B:
-        p = lambda v: None if v is None else _lib.ptr(v)
-        _lib.check(_lib.load().cpx_rs_decode(code._device_handle(), _lib.ptr(rows), p(flags), B, p(res.get('symbols')),
-                                             p(res.get('codeword')), p(res.get('errors'))))
-    out = [res[name][0] if one else res[name] for name in WANT if name in want]
-    return out[0] if len(out) == 1 else tuple(out)
+        _lib.check(_lib.load().cpx_rs_decode(code._device_handle(), _lib.ptr(word), None if flags is None else _lib.ptr(flags), B,
+                                             p('symbols'), p('codeword'), p('errors')))
+    return returned(res, one)

@@ -4,7 +4,8 @@
 // shortened from 2^m - 1 to n drops the highest degrees.  Field elements are integers (bit j = coefficient of alpha^j); the handle holds
 // exp[e] = alpha^e and log[v] as uint16 tables of 2^m entries each.
 //
-// The decoder's stages (field arithmetic, syndromes, Berlekamp-Massey, Chien search) live in bch_dev.h, shared with bch_chase.hip.
+// The decoder's stages are shared code: field arithmetic, Berlekamp-Massey and the Chien search live in cpx_gf.h (bch_chase.hip and
+// rs.hip run the same functions), the syndromes of a binary word in bch_dev.h (with bch_chase.hip).
 // bch_decode_kernel: one received word per wave, up to 16 waves per workgroup, workgroups stride over the batch.  The two tables are staged
 //   into LDS once per workgroup (2^(m+2) bytes: 64 KiB at m = 14); after that barrier the waves never meet again.  Per word:
 //   1. the bytes are read once, 64 positions per load and eight loads in flight, and kept as ballot words in LDS (rw);
@@ -22,8 +23,6 @@
 //   row segment, copied to the output on the way) and ballots them into one 64-bit word per lane; every lane then runs 64 steps of the long
 //   division on its own remainder of RW 64-bit words, the generator being kernel-argument data.  Nothing in it is specific to BCH codes.
 #include "bch_dev.h"
-
-#include <mutex>
 
 using namespace cpx;
 
@@ -43,13 +42,13 @@ struct BchDecArgs {
 // bytes of LDS per wave: rw and fm (nw 64-bit words each), then the 2t syndromes and the logarithms of sigma's coefficients
 __host__ __device__ inline unsigned bch_wave_lds(int nw) { return 16u * (unsigned)nw + 2u * 64u + 2u * 64u; }
 
-__global__ __launch_bounds__(BCH_MAX_WAVES * 64) void bch_decode_kernel(BchDecArgs a) {
+__global__ __launch_bounds__(CPX_GF_MAX_WAVES * 64) void bch_decode_kernel(BchDecArgs a) {
     extern __shared__ double2 bch_lds_raw[];
     unsigned char *base = reinterpret_cast<unsigned char *>(bch_lds_raw);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
     const int n = a.n, k = a.k, t = a.t, N = a.N, nw = a.nw;
     const Gf gf = stage_tables(base, a.tab, a.m, N);
-    unsigned char *mine = base + bch_tab_lds(a.m) + (unsigned)wave * bch_wave_lds(nw);
+    unsigned char *mine = base + gf_tab_lds(a.m) + (unsigned)wave * bch_wave_lds(nw);
     unsigned long long *rw = reinterpret_cast<unsigned long long *>(mine), *fm = rw + nw;
     uint16_t *synd = reinterpret_cast<uint16_t *>(fm + nw), *clog = synd + 64;
 
@@ -74,10 +73,10 @@ __global__ __launch_bounds__(BCH_MAX_WAVES * 64) void bch_decode_kernel(BchDecAr
         int errors = 0;
         const bool dirty = __ballot(lane < 2 * t && synd[lane] != 0) != 0ull;
         if (dirty) {
-            unsigned C;
+            unsigned C = lane == 0 ? 1u : 0u;
             int L;
-            bool fail = berlekamp_massey(gf, synd, t, lane, C, L);
-            if (!fail && chien_search<false>(gf, C, L, clog, fm, n, nw, lane) != L) fail = true;
+            bool fail = berlekamp_massey(gf, synd, 2 * t, 0, lane, C, L);
+            if (!fail && chien_search<true, false>(gf, C, L, clog, fm, nullptr, n, nw, lane) != L) fail = true;
             errors = fail ? -1 : L;
             wave_sync();
         }
@@ -158,12 +157,6 @@ void launch_encode(const BchEncArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(bch_encode_kernel<RW>, dim3(grid_of(wgs, (int64_t)device_cus() * 8)), dim3(BCH_ENC_THREADS), 0, st, a);
 }
 
-int check_batch(const cpx_bch *p, int64_t B, const char *what) {
-    CPX_REQUIRE(p, CPX_EINVAL, "%s: null handle", what);
-    CPX_REQUIRE(B >= 0, CPX_EINVAL, "%s: B = %lld", what, (long long)B);
-    return CPX_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -173,16 +166,11 @@ int cpx_bch_create(int m, uint32_t prim_poly, int n, int t, const uint8_t *genpo
     CPX_REQUIRE(out, CPX_EINVAL, "bch: null pointer");
     *out = nullptr;
     CPX_REQUIRE(genpoly_bits, CPX_EINVAL, "bch: null pointer");
-    CPX_REQUIRE(m >= CPX_BCH_MIN_M && m <= CPX_BCH_MAX_M, CPX_ELIMIT, "bch: m = %d is outside the engine's range %d .. %d", m, CPX_BCH_MIN_M,
-                CPX_BCH_MAX_M);
-    CPX_REQUIRE(t >= 1 && t <= CPX_BCH_MAX_T, CPX_ELIMIT, "bch: t = %d is outside the engine's range 1 .. %d", t, CPX_BCH_MAX_T);
-    const int N = (1 << m) - 1;
-    CPX_REQUIRE(n >= 2 && n <= N, CPX_ELIMIT, "bch: n = %d is outside 2 .. 2^m - 1 = %d", n, N);
-    CPX_REQUIRE(2 * t < N, CPX_ELIMIT, "bch: t = %d, need 2 t < 2^m - 1 = %d", t, N);
-    CPX_REQUIRE((prim_poly >> m) == 1u, CPX_EINVAL, "bch: prim_poly = %u has not degree m = %d", prim_poly, m);
     std::vector<uint16_t> tab;
-    if (int rct = gf_tables("bch", m, prim_poly, tab)) return rct;
-    const uint16_t *ex = tab.data(), *lg = ex + ((size_t)1 << m);
+    if (int rct = gf_field("bch", m, prim_poly, n, tab)) return rct;
+    const int N = (1 << m) - 1;
+    CPX_REQUIRE(t >= 1 && t <= CPX_BCH_MAX_T, CPX_ELIMIT, "bch: t = %d is outside the engine's range 1 .. %d", t, CPX_BCH_MAX_T);
+    CPX_REQUIRE(2 * t < N, CPX_ELIMIT, "bch: t = %d, need 2 t < 2^m - 1 = %d", t, N);
     const int deg = genpoly_degree;
     CPX_REQUIRE(deg >= 1 && deg < n, CPX_EINVAL, "bch: the generator's degree %d is outside 1 .. n - 1 = %d", deg, n - 1);
     CPX_REQUIRE(deg <= 64 * CPX_BCH_MAX_GEN_WORDS, CPX_ELIMIT, "bch: the generator's degree %d is above the engine's limit of %d", deg,
@@ -191,14 +179,8 @@ int cpx_bch_create(int m, uint32_t prim_poly, int n, int t, const uint8_t *genpo
         CPX_REQUIRE(genpoly_bits[i] <= 1, CPX_EINVAL, "bch: genpoly_bits[%d] = %d, need 0 or 1", i, (int)genpoly_bits[i]);
     CPX_REQUIRE(genpoly_bits[deg] == 1, CPX_EINVAL, "bch: the generator's coefficient of x^%d is zero", deg);
     CPX_REQUIRE(genpoly_bits[0] == 1, CPX_EINVAL, "bch: the generator has no constant term");
-    for (int j = 1; j <= 2 * t; ++j) {                           // g(alpha^j), by Horner
-        unsigned acc = 0;
-        for (int i = deg; i >= 0; --i) {
-            if (acc) acc = ex[(lg[acc] + j) % N];
-            acc ^= genpoly_bits[i];
-        }
-        CPX_REQUIRE(acc == 0, CPX_EINVAL, "bch: the generator does not vanish at alpha^%d", j);
-    }
+    for (int j = 1; j <= 2 * t; ++j)
+        CPX_REQUIRE(gf_eval(tab, m, genpoly_bits, deg, j) == 0, CPX_EINVAL, "bch: the generator does not vanish at alpha^%d", j);
     int rc = ensure_device();
     if (rc) return rc;
     cpx_bch *p = new cpx_bch();
@@ -278,24 +260,13 @@ int cpx_bch_decode_dev(const cpx_bch *p, const uint8_t *d_in, int64_t B, uint8_t
     if (B == 0) return CPX_OK;
     CPX_REQUIRE(d_in, CPX_EINVAL, "bch_decode: null pointer");
     if (int rcd = check_handle_device(p->device, "bch_decode")) return rcd;
-    const int nw = (p->n + 63) / 64, waves = bch_waves(p->m);
-    const unsigned lds = (bch_tab_lds(p->m) + (unsigned)waves * bch_wave_lds(nw) + 15u) & ~15u;
-    CPX_REQUIRE(lds <= CPX_BCH_LDS_MAX, CPX_ELIMIT, "bch_decode: m = %d, n = %d needs %u bytes of LDS", p->m, p->n, lds);
-    static std::mutex raised_mu;
-    static bool raised[64] = {};
-    {
-        std::lock_guard<std::mutex> lk(raised_mu);
-        if (p->device >= 0 && p->device < 64 && !raised[p->device]) {
-            CPX_HIP(hipFuncSetAttribute((const void *)bch_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CPX_BCH_LDS_MAX));
-            raised[p->device] = true;
-        }
-    }
+    const int nw = (p->n + 63) / 64, waves = gf_waves(p->m);
+    const unsigned lds = (gf_tab_lds(p->m) + (unsigned)waves * bch_wave_lds(nw) + 15u) & ~15u;
+    CPX_REQUIRE(lds <= CPX_GF_LDS_MAX, CPX_ELIMIT, "bch_decode: m = %d, n = %d needs %u bytes of LDS", p->m, p->n, lds);
+    if (int rcl = raise_lds((const void *)bch_decode_kernel, CPX_GF_LDS_MAX, p->device, "bch_decode")) return rcl;
     BchDecArgs a{d_in, p->d_tab, B, p->m, p->N, p->n, p->k, p->t, nw, d_bits, d_word, d_errors};
-    // workgroups resident at once: as many per compute unit as the LDS of a workgroup allows, at most 32 waves
-    int per_cu = (int)(CPX_BCH_LDS_MAX / lds);
-    if (per_cu > 32 / waves) per_cu = 32 / waves;
     const int64_t wgs = (B + waves - 1) / waves;
-    hipLaunchKernelGGL(bch_decode_kernel, dim3(grid_of(wgs, (int64_t)device_cus() * per_cu)), dim3(waves * 64), lds, pick_stream(stream), a);
+    hipLaunchKernelGGL(bch_decode_kernel, dim3(resident_grid(wgs, lds, waves)), dim3(waves * 64), lds, pick_stream(stream), a);
     CPX_HIP(hipGetLastError());
     note_kernel("bch_decode_kernel");
     return CPX_OK;

@@ -2,8 +2,8 @@
 //
 // The rule (tests/chase_model.py is its NumPy form, bit for bit).  Per word of n values x_i = llr_i, or fl(llr_i + fl(alpha prior_i)):
 // hard decisions h_i = (x_i < 0), reliabilities r_i = |x_i|; the p least reliable positions by (r_i, i) ascending; every test pattern
-// tau < 2^p flips the positions its bits name and is decoded by the rule of bch_decode_kernel (the helpers of bch_dev.h, shared with
-// it); a success is a candidate c_tau with the metric M_tau = sum of r_i over c_tau != h, added serially in ascending position order.
+// tau < 2^p flips the positions its bits name and is decoded by the rule of bch_decode_kernel (the syndromes of bch_dev.h, Berlekamp-
+// Massey and the Chien search of cpx_gf.h: the functions that kernel calls); a success is a candidate c_tau with the metric M_tau = sum of r_i over c_tau != h, added serially in ascending position order.
 // D is the candidate of least metric (ties: lowest tau).  extrinsic_i = s_i (M_C - M_D) - x_i with s_i = +1 for d_i = 0 and -1
 // otherwise and M_C the least metric of the candidates that differ from D at i; s_i beta where there is none.  A word with a non-finite
 // x_i is rejected on its own: candidates -1, metric +inf, the hard decisions, extrinsic 0.
@@ -27,7 +27,6 @@
 #include "bch_dev.h"
 
 #include <cmath>
-#include <mutex>
 
 using namespace cpx;
 
@@ -56,13 +55,13 @@ __host__ __device__ inline unsigned chase_wave_lds(int n, int nw, int t, int p) 
     return 8u * (unsigned)n + 16u * (unsigned)nw + 8u * nc + 4u * 128u + up8(2u * nc) + up8(2u * nc * (unsigned)(p + t));
 }
 
-__global__ __launch_bounds__(BCH_MAX_WAVES * 64) void bch_chase_kernel(ChaseArgs a) {
+__global__ __launch_bounds__(CPX_GF_MAX_WAVES * 64) void bch_chase_kernel(ChaseArgs a) {
     extern __shared__ double2 chase_lds_raw[];
     unsigned char *base = reinterpret_cast<unsigned char *>(chase_lds_raw);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
     const int n = a.n, k = a.k, t = a.t, N = a.N, nw = a.nw, p = a.p, dmax = p + t, ncand = 1 << p;
     const Gf gf = stage_tables(base, a.tab, a.m, N);
-    unsigned char *mine = base + bch_tab_lds(a.m) + (unsigned)wave * chase_wave_lds(n, nw, t, p);
+    unsigned char *mine = base + gf_tab_lds(a.m) + (unsigned)wave * chase_wave_lds(n, nw, t, p);
     double *xs = reinterpret_cast<double *>(mine);
     unsigned long long *rw = reinterpret_cast<unsigned long long *>(xs + n), *dm = rw + nw;
     double *cmet = reinterpret_cast<double *>(dm + nw);
@@ -152,9 +151,9 @@ __global__ __launch_bounds__(BCH_MAX_WAVES * 64) void bch_chase_kernel(ChaseArgs
                 wave_sync();
                 int L = 0;
                 if (__ballot(s != 0u) != 0ull) {
-                    unsigned C;
-                    if (berlekamp_massey(gf, synd, t, lane, C, L)) continue;
-                    if (chien_search<true>(gf, C, L, clog, roots, n, nw, lane) != L) continue;
+                    unsigned C = lane == 0 ? 1u : 0u;
+                    if (berlekamp_massey(gf, synd, 2 * t, 0, lane, C, L)) continue;
+                    if (chien_search<false, true>(gf, C, L, clog, nullptr, roots, n, nw, lane) != L) continue;
                     wave_sync();
                 }
                 // the difference from h: lanes 0 .. p - 1 the flipped test positions, lanes 8 .. 8 + L - 1 the roots
@@ -255,19 +254,18 @@ int chase_check(const cpx_bch *h, int p, int64_t B, int64_t J, int64_t sb, int64
     CPX_REQUIRE(B <= 1 || sb > span_i + span_j, CPX_EINVAL, "bch_chase: the blocks overlap (sb = %lld)", (long long)sb);
     CPX_REQUIRE(B <= 1 || (B - 1) <= ((int64_t)1 << 60) / sb, CPX_EINVAL, "bch_chase: B sb does not fit");
     const int nw = (h->n + 63) / 64;
-    const unsigned per = chase_wave_lds(h->n, nw, h->t, p), tab = bch_tab_lds(h->m);
+    const unsigned per = chase_wave_lds(h->n, nw, h->t, p), tab = gf_tab_lds(h->m);
     // waves per workgroup: the count that keeps most waves on a compute unit (each workgroup stages the tables again, a wave holds its word)
     int waves = 1, most = 0;
-    for (int w = bch_waves(h->m); w >= 1; --w) {
+    for (int w = gf_waves(h->m); w >= 1; --w) {
         const uint64_t need = ((uint64_t)tab + (uint64_t)w * per + 15u) & ~(uint64_t)15u;
-        if (need > CPX_BCH_LDS_MAX) continue;
-        int per_cu = (int)(CPX_BCH_LDS_MAX / need);
-        if (per_cu > 32 / w) per_cu = 32 / w;
+        if (need > CPX_GF_LDS_MAX) continue;
+        const int per_cu = wgs_per_cu(need, w);
         if (w * per_cu > most) { most = w * per_cu; waves = w; }
     }
     const uint64_t lds = ((uint64_t)tab + (uint64_t)waves * per + 15u) & ~(uint64_t)15u;
-    CPX_REQUIRE(lds <= CPX_BCH_LDS_MAX, CPX_ELIMIT, "bch_chase: m = %d, n = %d, t = %d, p = %d needs %llu bytes of LDS, the limit is %d", h->m, h->n,
-                h->t, p, (unsigned long long)lds, CPX_BCH_LDS_MAX);
+    CPX_REQUIRE(lds <= CPX_GF_LDS_MAX, CPX_ELIMIT, "bch_chase: m = %d, n = %d, t = %d, p = %d needs %llu bytes of LDS, the limit is %d", h->m, h->n,
+                h->t, p, (unsigned long long)lds, CPX_GF_LDS_MAX);
     *lds_out = (unsigned)lds;
     *waves_out = waves;
     return CPX_OK;
@@ -288,15 +286,7 @@ int cpx_chase_bch_dev(const cpx_bch *h, const double *d_llr, const double *d_pri
     if (B == 0) return CPX_OK;
     CPX_REQUIRE(d_llr, CPX_EINVAL, "bch_chase: null pointer");
     if (int rcd = check_handle_device(h->device, "bch_chase")) return rcd;
-    static std::mutex raised_mu;
-    static bool raised[64] = {};
-    {
-        std::lock_guard<std::mutex> lk(raised_mu);
-        if (h->device >= 0 && h->device < 64 && !raised[h->device]) {
-            CPX_HIP(hipFuncSetAttribute((const void *)bch_chase_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CPX_BCH_LDS_MAX));
-            raised[h->device] = true;
-        }
-    }
+    if (int rcl = raise_lds((const void *)bch_chase_kernel, CPX_GF_LDS_MAX, h->device, "bch_chase")) return rcl;
     ChaseArgs a;
     a.llr = d_llr;
     a.prior = d_prior;
@@ -325,10 +315,8 @@ int cpx_chase_bch_dev(const cpx_bch *h, const double *d_llr, const double *d_pri
     a.ext = d_extrinsic;
     a.metric = d_metric;
     a.cands = d_candidates;
-    int per_cu = (int)(CPX_BCH_LDS_MAX / lds);
-    if (per_cu > 32 / waves) per_cu = 32 / waves;
     const int64_t wgs = (B * J + waves - 1) / waves;
-    hipLaunchKernelGGL(bch_chase_kernel, dim3(grid_of(wgs, (int64_t)device_cus() * per_cu)), dim3(waves * 64), lds, pick_stream(stream), a);
+    hipLaunchKernelGGL(bch_chase_kernel, dim3(resident_grid(wgs, lds, waves)), dim3(waves * 64), lds, pick_stream(stream), a);
     CPX_HIP(hipGetLastError());
     note_kernel("bch_chase_kernel");
     return CPX_OK;

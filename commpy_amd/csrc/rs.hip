@@ -13,11 +13,11 @@
 //      (one table read for log v, then the exponent moves by d from j to j + 1: an add, a wrap and one gather per term); R wave XORs
 //      at the end leave S_j on lane j and in LDS.  f > r: failure.  All S_j zero: accepted, go to 8;
 //   3. Gamma, lane q holding the coefficient of x^q: one shift-multiply-XOR step per flagged position, read from the ballots;
-//   4. Berlekamp-Massey from rho = f with C = B = Gamma, lane q holding C_q and B_q, the discrepancy an XOR across the wave; it stops
-//      as a failure at the first length with 2 L - f > r;
-//   5. Chien search, four chunks at a time: the lane of degree d evaluates Lambda(alpha^-d); the ballot of the roots is kept per chunk
-//      (fm), its popcount adds to the root count, and root number j leaves its position in rpos[j].  Corrected iff Lambda_L != 0 and
-//      the count equals L;
+//   4. Berlekamp-Massey (cpx_gf.h, the function bch_decode_kernel calls with f = 0) from rho = f with C = B = Gamma, lane q holding C_q
+//      and B_q, the discrepancy an XOR across the wave; it stops as a failure at the first length with 2 L - f > r;
+//   5. Chien search (cpx_gf.h, likewise), four chunks at a time: the lane of degree d evaluates Lambda(alpha^-d); the ballot of the roots
+//      is kept per chunk (fm), its popcount adds to the root count, and root number j leaves its position in rpos[j].  Corrected iff
+//      Lambda_L != 0 and the count equals L;
 //   6. Omega_i = sum_q Lambda_q S_(i-q) on lane i, i < r (lane-local sums over LDS reads);
 //   7. Forney, lanes over roots (L <= 63 of them): lane j evaluates Omega and the odd part of Lambda at the alpha^-d of root j and
 //      keeps Y = alpha^(-d fcr) Omega / Lambda_odd (Lambda_odd(x) = x Lambda'(x)) in LDS: one pass however long the word;
@@ -28,69 +28,21 @@
 //   log of the feedback symbol, then one gather per remainder symbol with the generator's logarithms as kernel-argument data.  The
 //   parity symbols leave through the same tile, so that the global writes are row segments as well.
 #include "cpx_gf.h"
-#include "cpx_internal.h"
-#include "cpx_wave.h"
-
-#include <mutex>
 
 using namespace cpx;
 
-#define CPX_RS_MIN_M 3
-#define CPX_RS_MAX_M 14
 #define CPX_RS_MAX_R 63                    // a polynomial of degree r has a coefficient per lane
-#define CPX_RS_LDS_MAX (160 * 1024)
-#define RS_MAX_WAVES 16
 #define RS_ENC_WAVES 4
 #define RS_TILE_PITCH 66                   // uint16 per tile row: 33 dwords, so that the lanes' rows start on distinct banks
-#define RS_NONE 0xFFFFu                    // "logarithm" of a zero coefficient
 
 struct cpx_rs {
     __attribute__((visibility("hidden"))) ~cpx_rs() = default;
     int m, N, n, k, r, fcr, device;
-    uint16_t glog[64];                     // log of g's coefficient of x^i, i < r; RS_NONE for zero
+    uint16_t glog[64];                     // log of g's coefficient of x^i, i < r; CPX_GF_NONE for zero
     uint16_t *d_tab = nullptr;             // [2][2^m]: exp then log
 };
 
 namespace {
-
-__host__ __device__ inline unsigned gf_tab_lds(int m) { return 4u << m; }      // bytes of the two tables
-
-// orders this wave's LDS writes before its later reads (the waves never meet after the staging barrier)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ unsigned wave_xor(unsigned v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v ^= (unsigned)__shfl_xor((int)v, d);
-    return v;
-}
-
-// the tables in LDS; every index a caller forms must lie in 0 .. 2^m - 1
-struct Gf {
-    const uint16_t *ex, *lg;
-    int N;
-    __device__ __forceinline__ unsigned mul(unsigned a, unsigned b) const {
-        if (a == 0u || b == 0u) return 0u;
-        int e = (int)lg[a] + (int)lg[b];
-        if (e >= N) e -= N;
-        return ex[e];
-    }
-};
-
-// copies the tables into LDS at `base` (all threads of the workgroup, barrier included)
-__device__ __forceinline__ Gf gf_stage(unsigned char *base, const uint16_t *tab, int m) {
-    uint32_t *dst = reinterpret_cast<uint32_t *>(base);
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(tab);
-    for (int i = threadIdx.x; i < (1 << m); i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-    Gf gf;
-    gf.ex = reinterpret_cast<const uint16_t *>(base);
-    gf.lg = gf.ex + (1 << m);
-    gf.N = (1 << m) - 1;
-    return gf;
-}
 
 struct RsDecArgs {
     const uint16_t *in;                    // [B][n]
@@ -105,17 +57,14 @@ struct RsDecArgs {
 // bytes of LDS per wave: er and fm (nw 64-bit words each), then S (later Y), log Lambda, log Omega and the roots' positions (64 uint16 each)
 __host__ __device__ inline unsigned rs_wave_lds(int nw) { return 16u * (unsigned)nw + 4u * 2u * 64u; }
 
-// waves per workgroup: small tables leave room for several workgroups per compute unit
-inline int rs_waves(int m) { return m <= 8 ? 4 : m <= 11 ? 8 : RS_MAX_WAVES; }
-
 template <int R>
-__global__ __launch_bounds__(RS_MAX_WAVES * 64) void rs_decode_kernel(RsDecArgs a) {
+__global__ __launch_bounds__(CPX_GF_MAX_WAVES * 64) void rs_decode_kernel(RsDecArgs a) {
     extern __shared__ double2 rs_lds_raw[];
     unsigned char *base = reinterpret_cast<unsigned char *>(rs_lds_raw);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
     const int n = a.n, k = a.k, r = a.r, N = a.N, nw = a.nw, fcr = a.fcr;
     const unsigned mask = (1u << a.m) - 1u;
-    const Gf gf = gf_stage(base, a.tab, a.m);
+    const Gf gf = stage_tables(base, a.tab, a.m, N);
     unsigned char *mine = base + gf_tab_lds(a.m) + (unsigned)wave * rs_wave_lds(nw);
     unsigned long long *er = reinterpret_cast<unsigned long long *>(mine), *fm = er + nw;
     uint16_t *synd = reinterpret_cast<uint16_t *>(fm + nw), *clog = synd + 64, *olog = clog + 64, *rpos = olog + 64, *yv = synd;
@@ -198,102 +147,37 @@ __global__ __launch_bounds__(RS_MAX_WAVES * 64) void rs_decode_kernel(RsDecArgs 
                     C ^= term;
                 }
             }
-            // ---- 4: Berlekamp-Massey from rho = f: C the connection polynomial, Bp the one before the last length change, b its
-            // discrepancy, sh the shift
-            unsigned Bp = C, b = 1u;
-            int sh = 1;
-            L = f;
-            for (int rho = f; rho < r; ++rho) {
-                const unsigned d = wave_xor(lane <= L ? gf.mul(C, synd[rho - lane]) : 0u);       // L <= rho
-                if (d == 0u) { ++sh; continue; }
-                int e = (int)gf.lg[d] - (int)gf.lg[b];
-                if (e < 0) e += N;
-                const unsigned coef = gf.ex[e];
-                const unsigned moved = (unsigned)__shfl((int)Bp, lane >= sh ? lane - sh : lane);
-                const unsigned next = C ^ gf.mul(coef, lane >= sh ? moved : 0u);
-                if (2 * L <= rho + f) {
-                    L = rho + 1 - L + f;
-                    if (2 * L - f > r) { fail = true; break; }    // L only grows
-                    Bp = C;
-                    b = d;
-                    sh = 1;
-                } else {
-                    ++sh;
-                }
-                C = next;
-            }
-            if (!fail && __shfl((int)C, L) == 0) fail = true;     // Lambda of a lower degree than its length: fewer than L roots
-            if (!fail) {
-                // ---- 5: Chien search
-                clog[lane] = lane <= L && C ? gf.lg[C] : (uint16_t)RS_NONE;
-                wave_sync();
-                int count = 0;
-                for (int c0 = 0; c0 < nw; c0 += 4) {              // four chunks share the read of clog[q]; their gathers are independent
-                    int kk[4], qk[4];
-                    unsigned v[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int d = n - 1 - ((c0 + u) * 64 + lane);
-                        kk[u] = d > 0 ? N - d : 0;                // -d mod N; a lane past the word's end computes a value nobody reads
-                        qk[u] = 0;
-                        v[u] = 1u;                                // Lambda_0 = 1
-                    }
-                    for (int q = 1; q <= L; ++q) {
-                        const int cl = clog[q];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            qk[u] += kk[u];
-                            if (qk[u] >= N) qk[u] -= N;
-                        }
-                        if (cl != (int)RS_NONE) {
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) {
-                                int e = cl + qk[u];
-                                if (e >= N) e -= N;
-                                v[u] ^= gf.ex[e];
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int i = (c0 + u) * 64 + lane;
-                        const unsigned long long roots = __ballot(i < n && v[u] == 0u);
-                        if (lane == 0 && c0 + u < nw) fm[c0 + u] = roots;
-                        const int at = count + __popcll(roots & ((1ull << lane) - 1ull));
-                        if (((roots >> lane) & 1ull) && at < 64) rpos[at] = (uint16_t)i;      // Lambda has at most L <= 63 roots
-                        count += __popcll(roots);
-                    }
-                }
-                if (count != L) fail = true;
-            }
+            // ---- 4, 5: Berlekamp-Massey from rho = f and Gamma, then the Chien search: the roots' ballots to fm, their positions to rpos
+            fail = berlekamp_massey(gf, synd, r, f, lane, C, L);
+            if (!fail && chien_search<true, true>(gf, C, L, clog, fm, rpos, n, nw, lane) != L) fail = true;
             if (!fail) {
                 // ---- 6: Omega = S Lambda mod x^r, coefficient i on lane i
                 unsigned om = 0u;
                 for (int q = 0; q <= L; ++q) {
                     const int cl = clog[q];
-                    if (cl == (int)RS_NONE) continue;
+                    if (cl == (int)CPX_GF_NONE) continue;
                     const unsigned s = lane >= q && lane < r ? (unsigned)synd[lane - q] : 0u;
                     int e = cl + (int)gf.lg[s];
                     if (e >= N) e -= N;
                     om ^= s ? (unsigned)gf.ex[e] : 0u;
                 }
-                olog[lane] = om ? gf.lg[om] : (uint16_t)RS_NONE;
+                olog[lane] = om ? gf.lg[om] : (uint16_t)CPX_GF_NONE;
                 wave_sync();
                 // ---- 7: Forney, root number `lane` on lane `lane`: Omega and the odd part of Lambda at alpha^-d
                 const int d = lane < L ? n - 1 - (int)rpos[lane] : 0;
                 const int kk = d > 0 ? N - d : 0;
                 int qk = 0;
-                unsigned ov = olog[0] != RS_NONE ? (unsigned)gf.ex[olog[0]] : 0u, odd = 0u;
+                unsigned ov = olog[0] != CPX_GF_NONE ? (unsigned)gf.ex[olog[0]] : 0u, odd = 0u;
                 for (int q = 1; q <= r; ++q) {                    // L <= r
                     qk += kk;
                     if (qk >= N) qk -= N;
-                    const int ol = q < r ? (int)olog[q] : (int)RS_NONE, cl = (q & 1) && q <= L ? (int)clog[q] : (int)RS_NONE;
-                    if (ol != (int)RS_NONE) {
+                    const int ol = q < r ? (int)olog[q] : (int)CPX_GF_NONE, cl = (q & 1) && q <= L ? (int)clog[q] : (int)CPX_GF_NONE;
+                    if (ol != (int)CPX_GF_NONE) {
                         int e = ol + qk;
                         if (e >= N) e -= N;
                         ov ^= gf.ex[e];
                     }
-                    if (cl != (int)RS_NONE) {
+                    if (cl != (int)CPX_GF_NONE) {
                         int e = cl + qk;
                         if (e >= N) e -= N;
                         odd ^= gf.ex[e];
@@ -336,7 +220,7 @@ struct RsEncArgs {
     uint16_t *out;                         // [B][n]
     int64_t B;
     int m, N, n, k, r;
-    uint16_t glog[64];                     // of x^(R-r) g(x) without its leading term: entry R - r + i = log g_i, RS_NONE below
+    uint16_t glog[64];                     // of x^(R-r) g(x) without its leading term: entry R - r + i = log g_i, CPX_GF_NONE below
 };
 
 template <int R>
@@ -346,7 +230,7 @@ __global__ __launch_bounds__(RS_ENC_WAVES * 64) void rs_encode_kernel(RsEncArgs 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = a.n, k = a.k, r = a.r, N = a.N;
     const unsigned mask = (1u << a.m) - 1u;
-    const Gf gf = gf_stage(base, a.tab, a.m);
+    const Gf gf = stage_tables(base, a.tab, a.m, N);
     uint16_t *tile = reinterpret_cast<uint16_t *>(base + gf_tab_lds(a.m)) + (size_t)wave * 64 * RS_TILE_PITCH;
     const int64_t groups = (a.B + 63) / 64;
     for (int64_t g = (int64_t)blockIdx.x * RS_ENC_WAVES + wave; g < groups; g += (int64_t)gridDim.x * RS_ENC_WAVES) {
@@ -380,7 +264,7 @@ __global__ __launch_bounds__(RS_ENC_WAVES * 64) void rs_encode_kernel(RsEncArgs 
 #pragma unroll
                 for (int q = R - 1; q >= 1; --q) {
                     unsigned term = 0u;
-                    if (a.glog[q] != RS_NONE) {                   // uniform: kernel-argument data
+                    if (a.glog[q] != CPX_GF_NONE) {               // uniform: kernel-argument data
                         int e = lf + (int)a.glog[q];
                         if (e >= N) e -= N;
                         term = gf.ex[e] & take;
@@ -389,7 +273,7 @@ __global__ __launch_bounds__(RS_ENC_WAVES * 64) void rs_encode_kernel(RsEncArgs 
                 }
                 {
                     unsigned term = 0u;
-                    if (a.glog[0] != RS_NONE) {
+                    if (a.glog[0] != CPX_GF_NONE) {
                         int e = lf + (int)a.glog[0];
                         if (e >= N) e -= N;
                         term = gf.ex[e] & take;
@@ -412,44 +296,20 @@ __global__ __launch_bounds__(RS_ENC_WAVES * 64) void rs_encode_kernel(RsEncArgs 
 inline int rs_regs(int r) { return r <= 8 ? 8 : r <= 16 ? 16 : r <= 32 ? 32 : 64; }
 inline unsigned rs_enc_lds(int m) { return (gf_tab_lds(m) + RS_ENC_WAVES * 64u * RS_TILE_PITCH * 2u + 15u) & ~15u; }
 
-// dynamic LDS above 64 KiB has to be allowed once per kernel and device
-int raise_lds(const void *fn, int slot, int device) {
-    static std::mutex mu;
-    static bool raised[8][64] = {};
-    CPX_REQUIRE(device >= 0 && device < 64, CPX_ELIMIT, "rs: device index %d is outside 0 .. 63", device);
-    std::lock_guard<std::mutex> lk(mu);
-    if (!raised[slot][device]) {
-        CPX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, CPX_RS_LDS_MAX));
-        raised[slot][device] = true;
-    }
-    return CPX_OK;
-}
-
 template <int R>
-int launch_decode(const RsDecArgs &a, int slot, int device, int waves, unsigned lds, hipStream_t st) {
-    if (int rc = raise_lds((const void *)rs_decode_kernel<R>, slot, device)) return rc;
-    // workgroups resident at once: as many per compute unit as the LDS of a workgroup allows, at most 32 waves
-    int per_cu = (int)(CPX_RS_LDS_MAX / lds);
-    if (per_cu > 32 / waves) per_cu = 32 / waves;
+int launch_decode(const RsDecArgs &a, int device, int waves, unsigned lds, hipStream_t st) {
+    if (int rc = raise_lds((const void *)rs_decode_kernel<R>, CPX_GF_LDS_MAX, device, "rs")) return rc;
     const int64_t wgs = (a.B + waves - 1) / waves;
-    hipLaunchKernelGGL(rs_decode_kernel<R>, dim3(grid_of(wgs, (int64_t)device_cus() * per_cu)), dim3(waves * 64), lds, st, a);
+    hipLaunchKernelGGL(rs_decode_kernel<R>, dim3(resident_grid(wgs, lds, waves)), dim3(waves * 64), lds, st, a);
     return CPX_OK;
 }
 
 template <int R>
-int launch_encode(const RsEncArgs &a, int slot, int device, hipStream_t st) {
-    if (int rc = raise_lds((const void *)rs_encode_kernel<R>, slot, device)) return rc;
+int launch_encode(const RsEncArgs &a, int device, hipStream_t st) {
+    if (int rc = raise_lds((const void *)rs_encode_kernel<R>, CPX_GF_LDS_MAX, device, "rs")) return rc;
     const unsigned lds = rs_enc_lds(a.m);
-    int per_cu = (int)(CPX_RS_LDS_MAX / lds);
-    if (per_cu > 8) per_cu = 8;
     const int64_t groups = (a.B + 63) / 64, wgs = (groups + RS_ENC_WAVES - 1) / RS_ENC_WAVES;
-    hipLaunchKernelGGL(rs_encode_kernel<R>, dim3(grid_of(wgs, (int64_t)device_cus() * per_cu)), dim3(RS_ENC_WAVES * 64), lds, st, a);
-    return CPX_OK;
-}
-
-int check_batch(const cpx_rs *p, int64_t B, const char *what) {
-    CPX_REQUIRE(p, CPX_EINVAL, "%s: null handle", what);
-    CPX_REQUIRE(B >= 0, CPX_EINVAL, "%s: B = %lld", what, (long long)B);
+    hipLaunchKernelGGL(rs_encode_kernel<R>, dim3(resident_grid(wgs, lds, RS_ENC_WAVES)), dim3(RS_ENC_WAVES * 64), lds, st, a);
     return CPX_OK;
 }
 
@@ -462,30 +322,19 @@ int cpx_rs_create(int m, uint32_t prim_poly, int n, int k, int fcr, const uint16
     CPX_REQUIRE(out, CPX_EINVAL, "rs: null pointer");
     *out = nullptr;
     CPX_REQUIRE(genpoly, CPX_EINVAL, "rs: null pointer");
-    CPX_REQUIRE(m >= CPX_RS_MIN_M && m <= CPX_RS_MAX_M, CPX_ELIMIT, "rs: m = %d is outside the engine's range %d .. %d", m, CPX_RS_MIN_M,
-                CPX_RS_MAX_M);
+    std::vector<uint16_t> tab;
+    if (int rct = gf_field("rs", m, prim_poly, n, tab)) return rct;
     const int N = (1 << m) - 1;
-    CPX_REQUIRE(n >= 2 && n <= N, CPX_ELIMIT, "rs: n = %d is outside 2 .. 2^m - 1 = %d", n, N);
     CPX_REQUIRE(k >= 1 && k < n, CPX_EINVAL, "rs: k = %d is outside 1 .. n - 1 = %d", k, n - 1);
     const int r = n - k;
     CPX_REQUIRE(r <= CPX_RS_MAX_R, CPX_ELIMIT, "rs: n - k = %d is above the engine's limit of %d", r, CPX_RS_MAX_R);
     CPX_REQUIRE(fcr >= 0 && fcr < N, CPX_EINVAL, "rs: fcr = %d is outside 0 .. 2^m - 2 = %d", fcr, N - 1);
-    CPX_REQUIRE((prim_poly >> m) == 1u, CPX_EINVAL, "rs: prim_poly = %u has not degree m = %d", prim_poly, m);
-    std::vector<uint16_t> tab;
-    if (int rct = gf_tables("rs", m, prim_poly, tab)) return rct;
-    const uint16_t *ex = tab.data(), *lg = ex + ((size_t)1 << m);
+    const uint16_t *lg = tab.data() + ((size_t)1 << m);
     for (int i = 0; i <= r; ++i)
         CPX_REQUIRE(genpoly[i] <= N, CPX_EINVAL, "rs: genpoly[%d] = %d is no element of GF(2^%d)", i, (int)genpoly[i], m);
     CPX_REQUIRE(genpoly[r] == 1, CPX_EINVAL, "rs: the generator's coefficient of x^%d is %d, need 1 (monic of degree n - k)", r, (int)genpoly[r]);
-    for (int j = 0; j < r; ++j) {                                 // g(alpha^(fcr + j)), by Horner
-        const int x = (fcr + j) % N;
-        unsigned acc = 0;
-        for (int i = r; i >= 0; --i) {
-            if (acc) acc = ex[(lg[acc] + x) % N];
-            acc ^= genpoly[i];
-        }
-        CPX_REQUIRE(acc == 0, CPX_EINVAL, "rs: the generator does not vanish at alpha^%d", fcr + j);
-    }
+    for (int j = 0; j < r; ++j)
+        CPX_REQUIRE(gf_eval(tab, m, genpoly, r, (fcr + j) % N) == 0, CPX_EINVAL, "rs: the generator does not vanish at alpha^%d", fcr + j);
     int rc = ensure_device();
     if (rc) return rc;
     cpx_rs *p = new cpx_rs();
@@ -495,7 +344,7 @@ int cpx_rs_create(int m, uint32_t prim_poly, int n, int k, int fcr, const uint16
     p->k = k;
     p->r = r;
     p->fcr = fcr;
-    for (int i = 0; i < 64; ++i) p->glog[i] = i < r && genpoly[i] ? lg[genpoly[i]] : (uint16_t)RS_NONE;
+    for (int i = 0; i < 64; ++i) p->glog[i] = i < r && genpoly[i] ? lg[genpoly[i]] : (uint16_t)CPX_GF_NONE;
     (void)hipGetDevice(&p->device);
     if ((rc = upload((void **)&p->d_tab, tab.data(), sizeof(uint16_t) * tab.size(), "rs"))) {
         cpx_rs_destroy(p);
@@ -529,14 +378,14 @@ int cpx_rs_encode_dev(const cpx_rs *p, const uint16_t *d_msg, int64_t B, uint16_
     a.n = p->n;
     a.k = p->k;
     a.r = p->r;
-    for (int q = 0; q < 64; ++q) a.glog[q] = q >= R - p->r && q < R ? p->glog[q - (R - p->r)] : (uint16_t)RS_NONE;
+    for (int q = 0; q < 64; ++q) a.glog[q] = q >= R - p->r && q < R ? p->glog[q - (R - p->r)] : (uint16_t)CPX_GF_NONE;
     hipStream_t st = pick_stream(stream);
     int rc;
     switch (R) {
-    case 8: rc = launch_encode<8>(a, 4, p->device, st); break;
-    case 16: rc = launch_encode<16>(a, 5, p->device, st); break;
-    case 32: rc = launch_encode<32>(a, 6, p->device, st); break;
-    default: rc = launch_encode<64>(a, 7, p->device, st); break;
+    case 8: rc = launch_encode<8>(a, p->device, st); break;
+    case 16: rc = launch_encode<16>(a, p->device, st); break;
+    case 32: rc = launch_encode<32>(a, p->device, st); break;
+    default: rc = launch_encode<64>(a, p->device, st); break;
     }
     if (rc) return rc;
     CPX_HIP(hipGetLastError());
@@ -567,17 +416,17 @@ int cpx_rs_decode_dev(const cpx_rs *p, const uint16_t *d_in, const uint8_t *d_er
     if (B == 0) return CPX_OK;
     CPX_REQUIRE(d_in, CPX_EINVAL, "rs_decode: null pointer");
     if (int rcd = check_handle_device(p->device, "rs_decode")) return rcd;
-    const int nw = (p->n + 63) / 64, waves = rs_waves(p->m), R = rs_regs(p->r);
+    const int nw = (p->n + 63) / 64, waves = gf_waves(p->m), R = rs_regs(p->r);
     const unsigned lds = (gf_tab_lds(p->m) + (unsigned)waves * rs_wave_lds(nw) + 15u) & ~15u;
-    CPX_REQUIRE(lds <= CPX_RS_LDS_MAX, CPX_ELIMIT, "rs_decode: m = %d, n = %d needs %u bytes of LDS", p->m, p->n, lds);
+    CPX_REQUIRE(lds <= CPX_GF_LDS_MAX, CPX_ELIMIT, "rs_decode: m = %d, n = %d needs %u bytes of LDS", p->m, p->n, lds);
     RsDecArgs a{d_in, d_erased, p->d_tab, B, p->m, p->N, p->n, p->k, p->r, p->fcr, nw, d_symbols, d_word, d_errors};
     hipStream_t st = pick_stream(stream);
     int rc;
     switch (R) {
-    case 8: rc = launch_decode<8>(a, 0, p->device, waves, lds, st); break;
-    case 16: rc = launch_decode<16>(a, 1, p->device, waves, lds, st); break;
-    case 32: rc = launch_decode<32>(a, 2, p->device, waves, lds, st); break;
-    default: rc = launch_decode<64>(a, 3, p->device, waves, lds, st); break;
+    case 8: rc = launch_decode<8>(a, p->device, waves, lds, st); break;
+    case 16: rc = launch_decode<16>(a, p->device, waves, lds, st); break;
+    case 32: rc = launch_decode<32>(a, p->device, waves, lds, st); break;
+    default: rc = launch_decode<64>(a, p->device, waves, lds, st); break;
     }
     if (rc) return rc;
     CPX_HIP(hipGetLastError());

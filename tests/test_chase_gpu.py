@@ -230,7 +230,7 @@ def test_rows_and_columns_of_a_block_in_place(gpu):
 
 
 def test_bch_decode_still_equals_its_model_on_the_same_hard_decisions(gpu):
-    """Both kernels call the same syndrome, Berlekamp-Massey and Chien code (bch_dev.h)."""
+    """Both kernels call the same syndrome, Berlekamp-Massey and Chien code (bch_dev.h, cpx_gf.h)."""
     for n, t, m, pp in ((100, 2, 7, None), (255, 2, 8, None), (1023, 10, 10, None), (3240, 12, 14, DVB_PRIM_POLY)):
         code, model = both(n, t, m, pp)
         hard = (noisy_llr(model, 8, 0.5 if n < 2000 else 0.37, n) < 0).astype(np.uint8)

@@ -182,9 +182,13 @@ def test_abi_names():
     assert {"bch_chase_dev", "tpc_decode_dev"} <= set(deviceops.__all__)
     from commpy_amd import build
     assert "bch_chase.hip" in build.SOURCES and any(h.endswith("bch_dev.h") for h in build.HEADERS)
-    for source in ("bch.hip", "bch_chase.hip"):                   # one copy of the algebraic decoder's stages
-        text = open(os.path.join(build.CSRC, source)).read()
-        assert '#include "bch_dev.h"' in text and "struct Gf" not in text and "berlekamp_massey(" in text
+    read = lambda name: open(os.path.join(build.CSRC, name)).read()
+    for source, header in (("bch.hip", "bch_dev.h"), ("bch_chase.hip", "bch_dev.h"), ("rs.hip", "cpx_gf.h")):
+        text = read(source)                                       # one copy of the algebraic decoder's stages, called by all three
+        assert '#include "%s"' % header in text and "struct Gf" not in text and "berlekamp_massey(" in text and "chien_search<" in text
+        assert not re.search(r"\b(?:void|unsigned)\s+wave_(?:sync|xor)\s*\(", text) and not re.search(r"\bbool\s+berlekamp_massey\s*\(", text)
+    assert '#include "cpx_gf.h"' in read("bch_dev.h") and "struct Gf" in read("cpx_gf.h") and "struct Gf" not in read("bch_dev.h")
+    assert sum(read(name).count("hipFuncSetAttribute") for name in ("bch.hip", "bch_chase.hip", "rs.hip", "bch_dev.h", "cpx_gf.h")) == 1
 
 
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------

@@ -160,6 +160,8 @@ enum class Slot : int {
     sync_parts,          // sync.hip cpx_sync_estimate_dev: per-tile partial results of the peak search
     fading_taps,         // fading.hip launch_taps: the power-delay profile's taps
     fading_gains,        // fading.hip cpx_fading_channel_dev: a chunk of tap gains, where the caller does not ask for them
+    mlse_dec,            // mlse.hip: per-workgroup decision words of blocks too long for LDS
+    mlse_alpha,          // mlse.hip: per-workgroup forward metrics of every step, soft output only (live together with mlse_dec)
     count
 };
 

@@ -18,7 +18,7 @@ __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu',
            'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
            'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev',
            'bch_encode_dev', 'bch_decode_dev', 'rs_encode_dev', 'rs_decode_dev', 'tailbiting_encode_dev', 'tailbiting_decode_dev',
-           'ldpc_layered_decode_dev', 'bch_chase_dev', 'tpc_decode_dev']
+           'ldpc_layered_decode_dev', 'bch_chase_dev', 'tpc_decode_dev', 'mlse_equalize_dev']
 
 
 class DeviceBuf:
@@ -708,5 +708,33 @@ def ldpc_layered_decode_dev(ldpc_code_params, d_llr, B, n_iters, alpha=1.0, beta
         _lib.check(_lib.load().cpx_ldpc_layered_decode_dev(p.handle(), d_llr.ptr, B, n_iters, alpha, beta, 1 if early_stop else 0, llr_clip,
                                                            q(out.get('bits')), q(out.get('llr')), q(out.get('iters')),
                                                            q(out.get('converged')), stream))
+    res = tuple(out[name] for name in WANT if name in want)
+    return res[0] if len(res) == 1 else res
+
+
+# ---- trellis equalisation, device resident (csrc/mlse.hip) --------------------------------------------------------------------------
+
+def mlse_equalize_dev(modem, d_y, d_h, h_batched, B, n, L, d_noise_var=None, nv_batched=False, d_prior=None, tail=True,
+                      want=('indices',), stream=None):
+    """``cpx_mlse_dev``: ``d_y [B][n_y][2]`` float64 (re, im; ``n_y = n + L - 1`` with ``tail``, else ``n``) received through the taps
+    ``d_h [L][2]`` or, with ``h_batched``, ``[B][L][2]`` -> new ``DeviceBuf``s queued on ``stream`` (None: the library's), the results of
+    ``equalizers.mlse_equalize_batch`` that ``want`` names, in its order: 'indices' ``[B][n]`` int32, 'bits' ``[B][n m]`` uint8,
+    'metric' ``[B]`` float64, 'llr' ``[B][n m]`` float64; a single result for one name.  ``d_noise_var``: one float64 or, with
+    ``nv_batched``, ``[B]``, required for 'llr' and with ``d_prior [B][n m]``.  The same limits, checked on the host before any device
+    call."""
+    from commpy_amd.channelcoding.gfields import whole
+    from commpy_amd.equalizers import WANT, check_sizes, check_want
+    want = check_want(want)
+    B, n, L = whole(B, 'B', 0), whole(n, 'n', 1), whole(L, 'L', 2)
+    M, m = check_sizes(modem, L, n)
+    if d_noise_var is None and ('llr' in want or d_prior is not None):
+        raise ValueError("noise_var is required when 'llr' is wanted or a prior is given")
+    sizes = {'indices': B * n * 4, 'bits': B * n * m, 'metric': B * 8, 'llr': B * n * m * 8}
+    out = {name: DeviceBuf(sizes[name]) for name in sizes if name in want}
+    if B:
+        p = lambda v: None if v is None else v.ptr
+        _lib.check(_lib.load().cpx_mlse_dev(modem._device_handle(), d_y.ptr, d_h.ptr, int(bool(h_batched)), B, n, L, int(bool(tail)),
+                                            p(d_noise_var), int(bool(nv_batched)), p(d_prior), p(out.get('indices')), p(out.get('bits')),
+                                            p(out.get('metric')), p(out.get('llr')), stream))
     res = tuple(out[name] for name in WANT if name in want)
     return res[0] if len(res) == 1 else res

@@ -951,6 +951,40 @@ int cpx_ldpc_layered_decode_dev(const cpx_ldpc_layered *c, const double *d_llr, 
                                 int early_stop, double llr_clip, int8_t *d_bits, double *d_llr_out, int32_t *d_iters, uint8_t *d_converged,
                                 void *stream);
 
+/* ---- trellis equalisation of a known multipath channel: MLSE and max-log MAP (csrc/mlse.hip) ----------
+ * A block of n symbols with labels a_0 .. a_{n-1} and values c[a] (the points of a cpx_modem, label = position) is sent in silence
+ * through L taps: y_t = sum_l h_l c[a_{t-l}] + w_t, the terms with t - l < 0 or t - l >= n absent.  With tail != 0 a row holds
+ * n + L - 1 samples (what cpx_multipath returns), else the first n.
+ * The rule (float64, real and imaginary parts separate doubles, every product rounded before it is added, sums in the order written):
+ *   State.      After step t: s' = a_t M^(L-2) + ... + a_{t-L+2}.  Candidates into s' in the order old = 0 .. M-1,
+ *               pred = (s' mod M^(L-2)) M + old.
+ *   Branch.     xh = sum_{l=0}^{L-1} h_l c[a_{t-l}], l ascending from 0.0, a product is (hr cr - hi ci, hr ci + hi cr), the terms with
+ *               t - l < 0 skipped; e = y_t - xh; d = er er + ei ei.
+ *   Prior.      P_t[a] = noise_var (sum of La over the bits 1 of a, MSB first, from 0.0); 0.0 without a prior.  LLRs are positive for bit 0.
+ *   Forward.    alpha_0 = 0; alpha_{t+1}[s'] = (first minimum over old of alpha_t[pred] + d) + P_t[a_t]; a later candidate wins only if
+ *               strictly smaller; the winning old is the decision.
+ *   Tail.       beta_n[s] = sum_{j=0}^{L-2} |y_{n+j} - xh_j(s)|^2, j ascending from 0.0, xh_j(s) over l = j+1 .. L-1 (and n + j - l >= 0);
+ *               beta_n = 0 with tail == 0.
+ *   Hard.       s* = the first minimum of alpha_n + beta_n; that minimum is the metric; the indices from s* and the decisions.
+ *   Soft.       beta_t[s] = min over a of (d_t(s, a) + (P_t[a] + beta_{t+1}[s'])); Lambda_t[s'] = alpha_{t+1}[s'] + beta_{t+1}[s'];
+ *               llr[t m + i] = (min over the s' whose a_t has bit i = 1 of Lambda_t - the same with bit i = 0) / noise_var.
+ *   Rejection.  A row whose y, h, prior or noise_var holds a NaN or +-inf, or whose noise_var is not positive, is rejected on its own:
+ *               zero indices and bits, NaN metric and LLRs.
+ * Equal to tests/mlse_model.py bit for bit, whatever the batch size, the row's place, the stream and the outputs requested.
+ * Limits (CPX_EINVAL, naming the limit, checked before a device is looked for): L >= 2; M a power of two from 2 to 16;
+ * M^(L-1) <= 256 states; 1 <= n <= 4096; noise_var given when llr or prior is.
+ *   cpx_mlse  y [B][n_y][2] float64 (re, im); h [L][2] or, with h_batched, [B][L][2]; noise_var NULL, one value or, with nv_batched,
+ *             [B]; prior NULL or [B][n m].  Outputs, each may be NULL (not all): indices [B][n] int32, bits [B][n m] uint8 (MSB
+ *             first), metric [B] float64, llr [B][n m] float64 (posterior; extrinsic = llr - prior).
+ * The _dev form takes device pointers (noise_var included) and a stream and is asynchronous; the other takes host pointers and returns
+ * synchronised.  B = 0 returns CPX_OK without a launch.  cpx_last_kernel names the kernel's (M, S) class, the rows per workgroup, the
+ * grid's cap and where the decisions are kept. */
+int cpx_mlse(const cpx_modem *md, const double *y, const double *h, int h_batched, int64_t B, int64_t n, int L, int tail,
+             const double *noise_var, int nv_batched, const double *prior, int32_t *indices, uint8_t *bits, double *metric, double *llr);
+int cpx_mlse_dev(const cpx_modem *md, const double *d_y, const double *d_h, int h_batched, int64_t B, int64_t n, int L, int tail,
+                 const double *d_noise_var, int nv_batched, const double *d_prior, int32_t *d_indices, uint8_t *d_bits, double *d_metric,
+                 double *d_llr, void *stream);
+
 /* ---- multi-GPU: RCCL collectives of the sharded decode ------------------------------------
  * The path shards by codeword (contiguous blocks of B/G codewords per GPU, tables replicated) and has no exchange
  * step inside a decoder.  Two collectives exist around it:

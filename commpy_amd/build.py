@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "libcommpy_amd.so")
 SOURCES = ["runtime.hip", "viterbi.hip", "viterbi_cw.hip", "viterbi_generic.hip", "bcjr.hip", "bcjr_exact.hip", "ldpc.hip", "ldpc_resident.hip", "demod.hip", "linksim.hip", "encoders.hip",
-           "comm.hip", "mimo.hip", "mimo_linear.hip", "mimo_idd.hip", "mimo_channel.hip", "ofdm.hip", "fir.hip", "ofdm_chan.hip", "sync.hip", "fading.hip", "polar.hip", "bch.hip", "bch_chase.hip", "rs.hip", "tbcc.hip", "ldpc_layered.hip", "mlse.hip"]
+           "comm.hip", "mimo.hip", "mimo_linear.hip", "mimo_idd.hip", "mimo_channel.hip", "ofdm.hip", "fir.hip", "ofdm_chan.hip", "sync.hip", "fading.hip", "polar.hip", "bch.hip", "bch_chase.hip", "rs.hip", "tbcc.hip", "ldpc_layered.hip", "mlse.hip", "equalize.hip"]
 
 
 def _hipcc():

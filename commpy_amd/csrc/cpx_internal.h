@@ -162,6 +162,8 @@ enum class Slot : int {
     fading_gains,        // fading.hip cpx_fading_channel_dev: a chunk of tap gains, where the caller does not ask for them
     mlse_dec,            // mlse.hip: per-workgroup decision words of blocks too long for LDS
     mlse_alpha,          // mlse.hip: per-workgroup forward metrics of every step, soft output only (live together with mlse_dec)
+    eq_design,           // equalize.hip: rejection flags, and the taps, gain and noise of every design that the caller does not ask for
+    eq_sums,             // equalize.hip: feed-forward sums of a chunk of rows, feedback equaliser only (live together with eq_design)
     count
 };
 

@@ -18,7 +18,7 @@ __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu',
            'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
            'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev',
            'bch_encode_dev', 'bch_decode_dev', 'rs_encode_dev', 'rs_decode_dev', 'tailbiting_encode_dev', 'tailbiting_decode_dev',
-           'ldpc_layered_decode_dev', 'bch_chase_dev', 'tpc_decode_dev', 'mlse_equalize_dev']
+           'ldpc_layered_decode_dev', 'bch_chase_dev', 'tpc_decode_dev', 'mlse_equalize_dev', 'mmse_equalize_dev']
 
 
 class DeviceBuf:
@@ -737,4 +737,33 @@ def mlse_equalize_dev(modem, d_y, d_h, h_batched, B, n, L, d_noise_var=None, nv_
                                             p(d_noise_var), int(bool(nv_batched)), p(d_prior), p(out.get('indices')), p(out.get('bits')),
                                             p(out.get('metric')), p(out.get('llr')), stream))
     res = tuple(out[name] for name in WANT if name in want)
+    return res[0] if len(res) == 1 else res
+
+
+# ---- MMSE linear and decision-feedback equalisation, device resident (csrc/equalize.hip) --------------------------------------------
+
+def mmse_equalize_dev(modem, d_y, d_h, h_batched, B, n, L, d_noise_var, nv_batched, nf, nb=0, delay=None, tail=True,
+                      want=('indices',), stream=None):
+    """``cpx_mmse_equalize_dev``: ``d_y [B][n_y][2]`` float64 (re, im; ``n_y = n + L - 1`` with ``tail``, else ``n``) received through
+    the taps ``d_h [L][2]`` or, with ``h_batched``, ``[B][L][2]``; ``d_noise_var``: one float64 or, with ``nv_batched``, ``[B]`` -> new
+    ``DeviceBuf``s queued on ``stream`` (None: the library's), the results of ``equalizers.mmse_equalize_batch`` that ``want`` names,
+    in its order: 'indices' ``[B][n]`` int32, 'bits' ``[B][n m]`` uint8, 'estimate' ``[B][n][2]``, 'llr' ``[B][n m]``, 'noise' ``[B]``,
+    'ff' ``[B][nf][2]``, 'fb' ``[B][nb][2]``, 'gain' ``[B]`` float64; a single result for one name.  The same rule and the same limits,
+    checked on the host before any device call."""
+    from commpy_amd.channelcoding.gfields import whole
+    from commpy_amd.equalizers import MMSE_WANT, check_mmse_sizes
+    want = _lib.wanted(want, MMSE_WANT)
+    B, n, L, nf, nb = whole(B, 'B', 0), whole(n, 'n', 1), whole(L, 'L', 1), whole(nf, 'nf', 1), whole(nb, 'nb', 0)
+    M, m, delay = check_mmse_sizes(modem, L, n, nf, nb, None if delay is None else int(delay), want)
+    if d_noise_var is None:
+        raise ValueError('noise_var is required')
+    sizes = {'indices': B * n * 4, 'bits': B * n * m, 'estimate': B * n * 16, 'llr': B * n * m * 8, 'noise': B * 8, 'ff': B * nf * 16,
+             'fb': B * nb * 16, 'gain': B * 8}
+    out = {name: DeviceBuf(sizes[name]) for name in sizes if name in want}
+    if B:
+        p = lambda name: None if name not in out else out[name].ptr
+        _lib.check(_lib.load().cpx_mmse_equalize_dev(modem._device_handle(), float(modem.Es), d_y.ptr, d_h.ptr, int(bool(h_batched)), B, n,
+                                                     L, int(bool(tail)), d_noise_var.ptr, int(bool(nv_batched)), nf, nb, delay,
+                                                     *map(p, MMSE_WANT), stream))
+    res = tuple(out[name] for name in MMSE_WANT if name in want)
     return res[0] if len(res) == 1 else res

@@ -9,15 +9,23 @@ equalisation (the decoder half: ``ldpc_bp_decode``, ``map_decode``).  The kernel
 bit.
 
 Limits (csrc/mlse.hip): ``L >= 2``; ``M <= 16``; ``M^(L-1) <= 256`` states; ``1 <= n <= 4096``.
+
+Beyond those limits -- 64-QAM, or more than a handful of taps -- ``mmse_equalize_batch`` is the finite-length MMSE equaliser
+(csrc/equalize.hip): ``nf`` feed-forward taps designed per row from ``h`` and ``noise_var`` by an ``L D L^H`` solve, and, with
+``nb >= 1``, ``nb`` feedback taps that cancel the post-cursor of past decisions (decision feedback).  Cost grows with
+``nf^3 + n nf``, not with ``M^L``: up to 64 taps each way and any constellation up to 256 points.  Bit for bit equal to
+tests/equalize_model.py.
 """
 import numpy as np
 
 from commpy_amd import _lib
 
-__all__ = ['mlse_equalize_batch']
+__all__ = ['mlse_equalize_batch', 'mmse_equalize_batch']
 
 MLSE_MAX_M, MLSE_MAX_STATES, MLSE_MAX_N = 16, 256, 4096      # csrc/mlse.hip
 WANT = ('indices', 'bits', 'metric', 'llr')
+MMSE_MAX_TAPS, MMSE_MAX_M, MMSE_MAX_N = 64, 256, 1 << 30            # csrc/equalize.hip
+MMSE_WANT = ('indices', 'bits', 'estimate', 'llr', 'noise', 'ff', 'fb', 'gain')
 
 
 def check_want(want):
@@ -117,4 +125,101 @@ def mlse_equalize_batch(y, h, modem, noise_var=None, a_priori=None, tail=True, w
                                         p(nv), int(nv_batched), p(prior), p(res.get('indices')), p(res.get('bits')),
                                         p(res.get('metric')), p(res.get('llr'))))
     out = [res[name][0] if one else res[name] for name in WANT if name in want]
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def check_mmse_sizes(modem, L, n, nf, nb, delay, want):
+    """``(M, m, delay)`` of an MMSE equaliser within the kernels' limits, the default delay filled in (ValueError naming the limit
+    otherwise; host only).  ``m`` is 0 for a constellation that is no power of two."""
+    M = int(modem.m)
+    if L < 1 or L > MMSE_MAX_TAPS:
+        raise ValueError('h has %d taps, the limit is 1 <= L <= %d' % (L, MMSE_MAX_TAPS))
+    if nf < 1 or nf > MMSE_MAX_TAPS:
+        raise ValueError('nf = %d feed-forward taps, the limit is 1 <= nf <= %d' % (nf, MMSE_MAX_TAPS))
+    if nb < 0 or nb > MMSE_MAX_TAPS:
+        raise ValueError('nb = %d feedback taps, the limit is 0 <= nb <= %d' % (nb, MMSE_MAX_TAPS))
+    if delay is None:
+        delay = (nf + L - 2) // 2 if nb == 0 else nf - 1
+    if delay < 0:
+        raise ValueError('delay = %d, the limit is 0 <= delay' % delay)
+    if delay + nb > nf + L - 2:
+        raise ValueError('delay = %d, nb = %d: the limit is delay + nb <= nf + L - 2 = %d' % (delay, nb, nf + L - 2))
+    if M < 2 or M > MMSE_MAX_M:
+        raise ValueError('the constellation has %d points, the limit is 2 <= M <= %d' % (M, MMSE_MAX_M))
+    pow2 = M & (M - 1) == 0
+    if not pow2 and ('bits' in want or 'llr' in want):
+        raise ValueError("the constellation has %d points, the limit for 'bits' and 'llr' is M a power of two" % M)
+    if n < 1 or n > MMSE_MAX_N:
+        raise ValueError('n = %d symbols per row, the limit is 1 <= n <= 2^30' % n)
+    return M, (M.bit_length() - 1 if pow2 else 0), delay
+
+
+def mmse_equalize_batch(y, h, modem, noise_var, nf, nb=0, delay=None, tail=True, want=('indices',)):
+    """Equalise rows ``y [B, n_y]`` complex (or 1-D for one row) received through the taps ``h [L]`` (shared) or ``[B, L]`` with the
+    finite-length MMSE equaliser of ``nf`` feed-forward taps: the linear equaliser for ``nb = 0``, the decision-feedback equaliser
+    with ``nb`` feedback taps for ``nb >= 1``.  ``modem`` is any ``Modem`` (labels and bits as ``Modem.modulate`` defines them, MSB
+    first; its ``Es`` is the symbol energy); ``noise_var``: a scalar or ``[B]``, positive, required.  With ``tail=True`` a row holds
+    ``n + L - 1`` samples -- exactly what ``multipath_batch`` returns -- with ``tail=False`` the first ``n``.  ``delay=None`` means
+    ``(nf + L - 2) // 2`` for ``nb = 0``, else ``nf - 1``.
+
+    ``want`` names the results; they are returned in the order listed here (a single result for one name): ``'indices'`` ``[B, n]``
+    int32; ``'bits'`` ``[B, n*m]`` uint8; ``'estimate'`` ``[B, n]`` complex128, the unbiased symbol estimates; ``'llr'`` ``[B, n*m]``
+    float64, positive = bit 0, max-log, scaled by ``1 / nu`` like ``mlse_equalize_batch`` and ``Modem.demodulate`` scale by
+    ``1 / noise_var`` -- with feedback they take the past decisions for correct, so they are optimistic after a decision error;
+    ``'noise'`` ``[B]`` float64, the effective noise variance ``nu``; ``'ff'`` ``[B, nf]`` and ``'fb'`` ``[B, nb]`` complex128, the
+    taps; ``'gain'`` ``[B]`` float64, the bias of the MMSE estimate.
+
+    The rule (float64; real and imaginary parts are separate doubles; every product is rounded before it is added; every sum starts
+    at 0.0 and runs in ascending index order; ``a b = (ar br - ai bi, ar bi + ai br)``, ``a conj(b) = (ar br + ai bi, ai br - ar bi)``),
+    with ``d = delay``, ``Es = modem.Es``, ``N0 = noise_var``.  Design: ``H[i][k] = h_{k-i}`` for ``0 <= k-i < L``, ``i < nf``; ``K`` is
+    all columns but ``d+1 .. d+nb``; for ``j <= i``, ``S[i][j]`` is the sum over ``k`` in ``K``, ``i <= k < j+L``, of
+    ``h_{k-i} conj(h_{k-j})``, ``R[i][j] = Es S[i][j]``, plus ``N0`` on the diagonal, whose imaginary part is never computed;
+    ``p_i = Es h_{d-i}`` (0 outside the taps).  ``L D L^H`` without a square root, column ``j``: ``g_k = (D_k Lr[j][k], -(D_k Li[j][k]))``
+    for ``k < j``; ``v_i = R[i][j] - sum_{k<j} L[i][k] g_k`` for ``i >= j``; ``D_j = Re v_j``; ``L[i][j] = (vr / D_j, vi / D_j)``.
+    Solve: ``a_i = p_i - sum_{k<i} L[i][k] a_k``; ``b_i = (ar / D_i, ai / D_i)``; ``u_i = b_i - sum_{k>i} u_k conj(L[k][i])``, ``i``
+    descending, every sum over ``k`` ascending.  Taps: ``ff_i = conj(u_i)``; ``fb_j = sum_i ff_i h_{d+j-i}`` over the ``i`` with
+    ``0 <= d+j-i < L``; ``gain = sum_i (ffr hr - ffi hi)`` of ``h_{d-i}`` over the ``i`` with ``0 <= d-i < L``;
+    ``nu = (Es (1 - gain)) / gain``.  Equalise: ``z_t = sum_{i<nf} ff_i y_{t+d-i} - sum_{j=1..nb, t-j>=0} fb_j c[a^_{t-j}]``, the two
+    sums formed separately, a sample outside the row read as 0.0 and multiplied like any other; ``x^_t = (zr / gain, zi / gain)``;
+    ``a^_t`` is the first minimum over ``a`` ascending of ``e = x^_t - c[a]``, ``er er + ei ei``, a later point winning only if
+    strictly smaller.  Soft output: ``llr[t m + i] = (min over the a with bit i = 1 - min over the a with bit i = 0 of that
+    distance) / nu``, each minimum from +inf over ``a`` ascending, replaced only by a strictly smaller value.
+
+    A row whose ``y``, ``h`` or ``noise_var`` holds a NaN or +-inf, one of whose pivots ``D_j`` is not positive and finite, or whose
+    ``gain`` is not a finite number in (0, 1) -- an all-zero ``h`` gives ``gain = 0`` -- is rejected: zero indices and bits, NaN
+    everywhere else; no other row is affected.
+
+    Limits, each refused with a ``ValueError`` before any device call: ``1 <= L <= 64``; ``1 <= nf <= 64``; ``0 <= nb <= 64``;
+    ``0 <= delay``; ``delay + nb <= nf + L - 2``; ``2 <= M <= 256``; ``M`` a power of two when ``'bits'`` or ``'llr'`` is wanted;
+    ``1 <= n <= 2^30``; ``noise_var > 0``."""
+    want = _lib.wanted(want, MMSE_WANT)
+    ya, ha = np.asarray(y), np.asarray(h)
+    for name, a in (('y', ya), ('h', ha)):
+        if a.dtype.kind not in 'biufc':
+            raise ValueError('%s must hold numbers, got dtype %s' % (name, a.dtype))
+    if ya.ndim not in (1, 2):
+        raise ValueError('y must be [B, n_y] or 1-D, got %d dimensions' % ya.ndim)
+    one = ya.ndim == 1
+    ya = np.atleast_2d(ya)
+    B, n_y = ya.shape
+    if ha.ndim not in (1, 2) or (ha.ndim == 2 and ha.shape[0] != B):
+        raise ValueError('y is [%d, n_y]: h must be [L] or [%d, L], got shape %s' % (B, B, ha.shape))
+    L = ha.shape[-1]
+    n = n_y - (L - 1) if tail else n_y
+    nf, nb = int(nf), int(nb)
+    M, m, delay = check_mmse_sizes(modem, L, n, nf, nb, None if delay is None else int(delay), want)
+    if noise_var is None:
+        raise ValueError('noise_var is required')
+    nv, nv_batched = check_noise_var(noise_var, B, True)
+    ya = np.ascontiguousarray(ya, dtype=np.complex128)
+    ha = np.ascontiguousarray(ha, dtype=np.complex128)
+    shapes = {'indices': ((B, n), np.int32), 'bits': ((B, n * m), np.uint8), 'estimate': ((B, n), np.complex128),
+              'llr': ((B, n * m), np.float64), 'noise': ((B,), np.float64), 'ff': ((B, nf), np.complex128),
+              'fb': ((B, nb), np.complex128), 'gain': ((B,), np.float64)}
+    res = {name: np.zeros(*shapes[name]) for name in MMSE_WANT if name in want}
+    if B:
+        p = lambda name: None if name not in res else _lib.ptr(res[name])
+        _lib.check(_lib.load().cpx_mmse_equalize(modem._device_handle(), float(modem.Es), _lib.ptr(ya), _lib.ptr(ha), int(ha.ndim == 2), B,
+                                                 n, L, int(bool(tail)), _lib.ptr(nv), int(nv_batched), nf, nb, delay, *map(p, MMSE_WANT)))
+    out = [res[name][0] if one else res[name] for name in MMSE_WANT if name in want]
     return out[0] if len(out) == 1 else tuple(out)

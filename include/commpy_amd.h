@@ -985,6 +985,50 @@ int cpx_mlse_dev(const cpx_modem *md, const double *d_y, const double *d_h, int 
                  const double *d_noise_var, int nv_batched, const double *d_prior, int32_t *d_indices, uint8_t *d_bits, double *d_metric,
                  double *d_llr, void *stream);
 
+/* ---- MMSE linear and decision-feedback equalisation of a known multipath channel (csrc/equalize.hip) ----------
+ * y_t = sum_l h_l x_{t-l} + w_t, x_t = c[a_t] for 0 <= t < n and 0 elsewhere (the points of a cpx_modem, label = position); es is the
+ * mean symbol energy, N0 = noise_var, d = delay, nf feed-forward taps, nb feedback taps (0: the linear equaliser).  With tail != 0 a
+ * row holds n + L - 1 samples (what cpx_multipath returns), else the first n.
+ * The rule (float64, real and imaginary parts separate doubles, every product rounded before it is added, every sum from 0.0 in
+ * ascending index order; a b = (ar br - ai bi, ar bi + ai br), a conj(b) = (ar br + ai bi, ai br - ar bi)):
+ *   Design.     H[i][k] = h_{k-i} for 0 <= k-i < L (i < nf); K = all columns but d+1 .. d+nb.  For j <= i:
+ *               S[i][j] = sum over k in K, i <= k < j+L, of h_{k-i} conj(h_{k-j}); R[i][j] = es S[i][j], and + N0 on the diagonal,
+ *               whose imaginary part is never computed.  p_i = es h_{d-i} (0 outside the taps).
+ *   L D L^H.    Column j: g_k = (D_k Lr[j][k], -(D_k Li[j][k])) for k < j; v_i = R[i][j] - sum_{k<j} L[i][k] g_k for i >= j;
+ *               D_j = Re v_j; L[i][j] = (vr / D_j, vi / D_j) for i > j.  No square root.
+ *   Solve.      a_i = p_i - sum_{k<i} L[i][k] a_k; b_i = (ar / D_i, ai / D_i); u_i = b_i - sum_{k>i} u_k conj(L[k][i]), i descending,
+ *               every sum over k ascending.
+ *   Taps.       ff_i = conj(u_i); fb_j = sum_i ff_i h_{d+j-i} over the i with 0 <= d+j-i < L, j = 1 .. nb;
+ *               gain = sum_i (ffr hr - ffi hi) of h_{d-i} over the i with 0 <= d-i < L; nu = (es (1 - gain)) / gain.
+ *   Equalise.   z_t = sum_{i<nf} ff_i y_{t+d-i} - sum_{j=1..nb, t-j>=0} fb_j c[a^_{t-j}], the two sums formed separately, a sample
+ *               outside the row read as 0.0 and multiplied like any other; x^_t = (zr / gain, zi / gain); a^_t = the first minimum
+ *               over a ascending of e = x^_t - c[a], er er + ei ei, a later point winning only if strictly smaller.
+ *   Soft.       llr[t m + i] = (min over the a with bit i = 1 - min over the a with bit i = 0 of that distance) / nu, bits MSB first,
+ *               positive = bit 0; each minimum from +inf over a ascending, replaced only by a strictly smaller value.  With
+ *               feedback this takes the past decisions for correct.
+ *   Rejection.  A row whose y, h or noise_var holds a NaN or +-inf (or a noise_var <= 0), one of whose pivots D_j is not positive
+ *               and finite, or whose gain is not a finite number in (0, 1) -- an all-zero h gives gain 0 -- is rejected on its own:
+ *               zero indices and bits, NaN everything else.
+ * Equal to tests/equalize_model.py bit for bit, whatever the batch size, the row's place, the stream, the outputs requested and
+ * whether h is shared or repeated per row.
+ * Limits (CPX_EINVAL, naming the limit, checked before a device is looked for): 1 <= L <= 64; 1 <= nf <= 64; 0 <= nb <= 64;
+ * 0 <= delay; delay + nb <= nf + L - 2; 2 <= M <= 256; M a power of two when bits or llr is asked for; 1 <= n <= 2^30; noise_var
+ * given; es positive and finite.
+ *   cpx_mmse_equalize  y [B][n_y][2] float64 (re, im); h [L][2] or, with h_batched, [B][L][2]; noise_var one value or, with
+ *             nv_batched, [B].  Outputs, each may be NULL (not all): indices [B][n] int32, bits [B][n m] uint8 (MSB first),
+ *             estimate [B][n][2] (the unbiased x^), llr [B][n m], noise [B] (nu), ff [B][nf][2], fb [B][nb][2], gain [B].
+ * The _dev form takes device pointers (noise_var included) and a stream and is asynchronous; the other takes host pointers and returns
+ * synchronised.  B = 0 returns CPX_OK without a launch.  cpx_last_kernel names the last kernel of the call (eq_filter_kernel<LGM> for
+ * nb = 0, eq_dfe_kernel<LGM> with feedback, eq_design_kernel when only the design is asked for; LGM = m with llr, else 0), nf, nb,
+ * the number of designs solved and the grid caps of the three kernels.  With feedback the call takes 16 B n bytes of workspace. */
+int cpx_mmse_equalize(const cpx_modem *md, double es, const double *y, const double *h, int h_batched, int64_t B, int64_t n, int L,
+                      int tail, const double *noise_var, int nv_batched, int nf, int nb, int delay, int32_t *indices, uint8_t *bits,
+                      double *estimate, double *llr, double *noise, double *ff, double *fb, double *gain);
+int cpx_mmse_equalize_dev(const cpx_modem *md, double es, const double *d_y, const double *d_h, int h_batched, int64_t B, int64_t n,
+                          int L, int tail, const double *d_noise_var, int nv_batched, int nf, int nb, int delay, int32_t *d_indices,
+                          uint8_t *d_bits, double *d_estimate, double *d_llr, double *d_noise, double *d_ff, double *d_fb,
+                          double *d_gain, void *stream);
+
 /* ---- multi-GPU: RCCL collectives of the sharded decode ------------------------------------
  * The path shards by codeword (contiguous blocks of B/G codewords per GPU, tables replicated) and has no exchange
  * step inside a decoder.  Two collectives exist around it:

@@ -1,8 +1,6 @@
-"""What bch.py and rs.py share on the host: the field degree of a code, the check of a batch of rows, and the results a decoder
-returns."""
+"""What bch.py and rs.py share on the host: the field degree of a code and the check of a batch of rows."""
 import numpy as np
 
-from commpy_amd import _lib
 from commpy_amd.channelcoding.gfields import whole
 
 GF_MIN_M, GF_MAX_M = 3, 14                        # csrc/cpx_gf.h
@@ -34,15 +32,3 @@ def rows(a, name, width, dtype, kinds, holds, unit, top=None, need=None):
         raise ValueError('%s must hold %s' % (name, need))
     return np.ascontiguousarray(np.atleast_2d(a), dtype=dtype), a.ndim == 1
 
-
-def outputs(want, shapes):
-    """The zeroed arrays of the results that ``want`` names, in the order of ``shapes`` (name -> (shape, dtype)), and a function that
-    gives the pointer of a name's array, None for a result that is not wanted."""
-    res = {name: np.zeros(*shapes[name]) for name in shapes if name in want}
-    return res, lambda name: _lib.ptr(res[name]) if name in res else None
-
-
-def returned(res, one):
-    """What a decoder returns for ``outputs``' arrays: their first rows for a 1-D input, a single result for one name."""
-    out = [v[0] if one else v for v in res.values()]
-    return out[0] if len(out) == 1 else tuple(out)

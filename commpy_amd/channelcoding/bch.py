@@ -10,7 +10,8 @@ import ctypes
 import numpy as np
 
 from commpy_amd import _lib
-from commpy_amd.channelcoding._algebraic import field_degree, outputs, returned, rows
+from commpy_amd._results import outputs, returned
+from commpy_amd.channelcoding._algebraic import field_degree, rows
 from commpy_amd.channelcoding.algcode import bch_genpoly
 from commpy_amd.channelcoding.gfields import field, whole
 
@@ -61,6 +62,17 @@ def check_want(want):
     return _lib.wanted(want, WANT)
 
 
+def shapes(B, code):
+    return {'bits': ((B, code.k), np.uint8), 'codeword': ((B, code.n), np.uint8), 'errors': ((B,), np.int32)}
+
+
+def chase_shapes(rows, k, span):
+    """The Chase decoder's results for words nested as ``rows`` (``(B,)``, on the device ``(B, J)``); 'codeword' and 'extrinsic' lie as
+    the input does, ``span``: ``(B, n)``, on the device the extent that the strides cover."""
+    return {'bits': (rows + (k,), np.uint8), 'codeword': (span, np.uint8), 'extrinsic': (span, np.float64), 'metric': (rows, np.float64),
+            'candidates': (rows, np.int32)}
+
+
 def _bit_rows(bits, name, width):
     return rows(bits, name, width, np.uint8, 'biu', 'integers 0 / 1', 'bits', 1, '0 / 1')
 
@@ -91,7 +103,7 @@ def bch_decode(bits, code, want=('bits',)):
     want = check_want(want)
     hard, one = _bit_rows(bits, 'bits', code.n)
     B = hard.shape[0]
-    res, p = outputs(want, {'bits': ((B, code.k), np.uint8), 'codeword': ((B, code.n), np.uint8), 'errors': ((B,), np.int32)})
+    res, p = outputs(want, shapes(B, code))
     if B:
         _lib.check(_lib.load().cpx_bch_decode(code._device_handle(), _lib.ptr(hard), B, p('bits'), p('codeword'), p('errors')))
     return returned(res, one)
@@ -136,8 +148,7 @@ def chase_decode(llr, code, p, beta, prior=None, alpha=1.0, want=('bits',)):
         if pri.shape != soft.shape or (np.ndim(prior) == 1) != one:
             raise ValueError('prior has shape %s, need that of llr' % (np.shape(prior),))
     B = soft.shape[0]
-    res, q = outputs(want, {'bits': ((B, code.k), np.uint8), 'codeword': ((B, code.n), np.uint8), 'extrinsic': ((B, code.n), np.float64),
-                            'metric': ((B,), np.float64), 'candidates': ((B,), np.int32)})
+    res, q = outputs(want, chase_shapes((B,), code.k, (B, code.n)))
     if B:
         _lib.check(_lib.load().cpx_chase_bch(code._device_handle(), _lib.ptr(soft), None if pri is None else _lib.ptr(pri), alpha, beta, p, B,
                                              q('bits'), q('codeword'), q('extrinsic'), q('metric'), q('candidates')))

@@ -14,6 +14,7 @@ import math
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd._results import outputs, returned
 from commpy_amd.channelcoding.ldpc import _edge_list, _edges_from_adjacency
 
 __all__ = ['ldpc_layers', 'ldpc_layered_decode']
@@ -25,6 +26,10 @@ WANT = ('bits', 'llr', 'iters', 'converged')
 def check_want(want):
     """``want`` as a tuple of names out of 'bits', 'llr', 'iters', 'converged'."""
     return _lib.wanted(want, WANT)
+
+
+def shapes(B, n_v):
+    return {'bits': ((B, n_v), np.int8), 'llr': ((B, n_v), np.float64), 'iters': ((B,), np.int32), 'converged': ((B,), np.uint8)}
 
 
 def code_edges(ldpc_code_params):
@@ -206,19 +211,8 @@ def ldpc_layered_decode(llr, ldpc_code_params, n_iters, alpha=1.0, beta=0.0, sch
         raise ValueError('llr has %d values per row, the code has n_v = %d' % (rows.shape[1], p.n_v))
     x = _lib.as_f64(rows)
     B = x.shape[0]
-    res = {}
-    if 'bits' in want:
-        res['bits'] = np.zeros((B, p.n_v), dtype=np.int8)
-    if 'llr' in want:
-        res['llr'] = np.zeros((B, p.n_v), dtype=np.float64)
-    if 'iters' in want:
-        res['iters'] = np.zeros(B, dtype=np.int32)
-    if 'converged' in want:
-        res['converged'] = np.zeros(B, dtype=np.uint8)
+    res, q = outputs(want, shapes(B, p.n_v))
     if B:
-        q = lambda v: None if v is None else _lib.ptr(v)
         _lib.check(_lib.load().cpx_ldpc_layered_decode(p.handle(), _lib.ptr(x), B, n_iters, alpha, beta, 1 if early_stop else 0, llr_clip,
-                                                       q(res.get('bits')), q(res.get('llr')), q(res.get('iters')),
-                                                       q(res.get('converged'))))
-    out = [res[name][0] if one else res[name] for name in WANT if name in want]
-    return out[0] if len(out) == 1 else tuple(out)
+                                                       *map(q, WANT)))
+    return returned(res, one)

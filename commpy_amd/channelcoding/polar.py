@@ -12,6 +12,8 @@ import ctypes
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd._results import outputs, returned
+from commpy_amd.channelcoding.gfields import whole
 
 __all__ = ['polar_reliability_order', 'PolarCode', 'crc_append', 'crc_check', 'polar_encode', 'polar_decode']
 
@@ -20,14 +22,8 @@ LIST_SIZES = (1, 2, 4, 8, 16, 32)
 WANT = ('bits', 'crc', 'metric', 'u_llr', 'list')
 
 
-def _whole(v, name, lo):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo:
-        raise ValueError('%s = %r, need an integer >= %d' % (name, v, lo))
-    return int(v)
-
-
 def _block_length(N):
-    N = _whole(N, 'N', 2)
+    N = whole(N, 'N', 2)
     if N & (N - 1):
         raise ValueError('N = %d is not a power of two' % N)
     return N
@@ -123,7 +119,7 @@ class PolarCode:
         self.N = N = _block_length(N)
         if N > POLAR_MAX_N:
             raise ValueError('N = %d is above the engine limit of %d' % (N, POLAR_MAX_N))
-        self.K = K = _whole(K, 'K', 1)
+        self.K = K = whole(K, 'K', 1)
         if K > N:
             raise ValueError('K = %d is above N = %d' % (K, N))
         if order is not None and frozen is not None:
@@ -165,7 +161,7 @@ class PolarCode:
 
     def check_list_size(self, list_size):
         """``list_size`` as an int; ValueError unless it is 1, 2, 4, 8, 16 or 32 with ``list_size * N <= 8192``."""
-        L = _whole(list_size, 'list_size', 1)
+        L = whole(list_size, 'list_size', 1)
         if L not in LIST_SIZES:
             raise ValueError('list_size = %d, need one of %s' % (L, ', '.join(map(str, LIST_SIZES))))
         if L * self.N > POLAR_MAX_N:
@@ -185,6 +181,15 @@ def check_want(want, list_size):
     if 'u_llr' in want and list_size > 1:
         raise ValueError("'u_llr' is defined for list_size = 1 only")
     return want
+
+
+def shapes(B, code):
+    """The results but 'list', which is the three arrays of ``list_shapes``."""
+    return {'bits': ((B, code.A), np.uint8), 'crc': ((B,), np.uint8), 'metric': ((B,), np.float64), 'u_llr': ((B, code.N), np.float64)}
+
+
+def list_shapes(B, code, L):
+    return {'bits': ((B, L, code.K), np.uint8), 'metrics': ((B, L), np.float64), 'live': ((B,), np.int32)}
 
 
 def polar_encode(message_bits, code):
@@ -217,28 +222,15 @@ def polar_decode(llr, code, list_size=1, want=('bits',)):
     one = a.ndim == 1
     x = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
     B = x.shape[0]
-    res = {}
-    if 'bits' in want:
-        res['bits'] = np.zeros((B, code.A), dtype=np.uint8)
-    if 'crc' in want:
-        res['crc'] = np.zeros(B, dtype=np.uint8)
-    if 'metric' in want:
-        res['metric'] = np.zeros(B)
-    if 'u_llr' in want:
-        res['u_llr'] = np.zeros((B, code.N))
-    lst = (np.zeros((B, L, code.K), dtype=np.uint8), np.zeros((B, L)), np.zeros(B, dtype=np.int32)) if 'list' in want else (None,) * 3
+    tables = shapes(B, code), list_shapes(B, code, L)
+    res, p = outputs(want, tables[0])
+    lst, q = outputs(tables[1] if 'list' in want else (), tables[1])
     if B:
-        p = lambda v: None if v is None else _lib.ptr(v)
-        _lib.check(_lib.load().cpx_polar_decode(code._device_handle(), _lib.ptr(x), B, L, p(res.get('bits')), p(res.get('crc')),
-                                                p(res.get('metric')), p(res.get('u_llr')), p(lst[0]), p(lst[1]), p(lst[2])))
+        _lib.check(_lib.load().cpx_polar_decode(code._device_handle(), _lib.ptr(x), B, L, *map(p, tables[0]), *map(q, tables[1])))
     if 'crc' in res:
         res['crc'] = res['crc'].astype(bool)
-    if 'list' in want:
-        res['list'] = lst
-    out = []
-    for name in (w for w in WANT if w in want):
-        v = res[name]
-        if one:
-            v = tuple(e[0] for e in v) if name == 'list' else v[0]
-        out.append(v)
-    return out[0] if len(out) == 1 else tuple(out)
+    if one:
+        res, lst = {name: v[0] for name, v in res.items()}, {name: v[0] for name, v in lst.items()}
+    if lst:
+        res['list'] = tuple(lst.values())                     # 'list' is the last name
+    return returned(res)

@@ -8,6 +8,7 @@ overall parity bit of most deployed product codes) are not provided.
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd._results import outputs, returned
 from commpy_amd.channelcoding.bch import BCHCode, bch_encode
 from commpy_amd.channelcoding.gfields import whole
 
@@ -17,6 +18,11 @@ TPC_WANT = ('bits', 'codeword', 'extrinsic')
 TPC_DEV_WANT = ('codeword', 'extrinsic')
 ALPHA = (0.0, 0.2, 0.3, 0.5, 0.7, 0.9, 1.0, 1.0)                  # Pyndiah's tables, per half-iteration
 BETA = (0.2, 0.4, 0.6, 0.8, 1.0, 1.0, 1.0, 1.0)
+
+
+def shapes(B, code):
+    block = (B, code.n_c, code.n_r)
+    return {'bits': ((B, code.k_c, code.k_r), np.uint8), 'codeword': (block, np.uint8), 'extrinsic': (block, np.float64)}
 
 
 class ProductCode:
@@ -105,7 +111,7 @@ def tpc_decode(llr, code, iters=4, p=4, alpha=None, beta=None, llr_scale=1.0, wa
         raise ValueError('llr must hold real numbers, got dtype %s' % a.dtype)
     x = np.ascontiguousarray(a.reshape(-1, code.n_c, code.n_r), dtype=np.float64)
     B = x.shape[0]
-    res = {'codeword': np.zeros(x.shape, np.uint8), 'extrinsic': np.zeros(x.shape, np.float64)}
+    res, _ = outputs(TPC_DEV_WANT, shapes(B, code))
     if B:
         names = tuple(n for n in ('codeword', 'extrinsic') if n in want or (n == 'codeword' and 'bits' in want))
         d_llr = DeviceBuf.from_array(x)
@@ -117,5 +123,4 @@ def tpc_decode(llr, code, iters=4, p=4, alpha=None, beta=None, llr_scale=1.0, wa
             buf.free()
         d_llr.free()
     res['bits'] = np.ascontiguousarray(res['codeword'][:, :code.k_c, :code.k_r])
-    out = [res[n][0] if a.ndim == 2 else res[n] for n in TPC_WANT if n in want]
-    return out[0] if len(out) == 1 else tuple(out)
+    return returned({n: res[n] for n in TPC_WANT if n in want}, a.ndim == 2)

@@ -11,6 +11,7 @@ Limits (csrc/tbcc.hip): the number of states is a power of two from 2 to 64; ``k
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd._results import outputs, returned
 from commpy_amd.channelcoding.convcode import _VIT_TYPES, device_trellis
 
 __all__ = ['tailbiting_encode', 'tailbiting_decode']
@@ -22,6 +23,10 @@ WANT = ('bits', 'wraps', 'tailbiting', 'metric')
 def check_want(want):
     """``want`` as a tuple of names out of 'bits', 'wraps', 'tailbiting', 'metric'."""
     return _lib.wanted(want, WANT)
+
+
+def shapes(B, T, k):
+    return {'bits': ((B, T * k), np.uint8), 'wraps': ((B,), np.int32), 'tailbiting': ((B,), np.uint8), 'metric': ((B,), np.float64)}
 
 
 def check_trellis(trellis):
@@ -124,18 +129,7 @@ def tailbiting_decode(coded, trellis, decoding_type='hard', max_wraps=4, want=('
     T = check_block(check_steps(rows.shape[1], n, 'coded'), k)
     x = _lib.as_f64(rows)
     B = x.shape[0]
-    res = {}
-    if 'bits' in want:
-        res['bits'] = np.zeros((B, T * k), dtype=np.uint8)
-    if 'wraps' in want:
-        res['wraps'] = np.zeros(B, dtype=np.int32)
-    if 'tailbiting' in want:
-        res['tailbiting'] = np.zeros(B, dtype=np.uint8)
-    if 'metric' in want:
-        res['metric'] = np.zeros(B, dtype=np.float64)
+    res, p = outputs(want, shapes(B, T, k))
     if B:
-        p = lambda v: None if v is None else _lib.ptr(v)
-        _lib.check(_lib.load().cpx_tbcc_decode(device_trellis(trellis), _lib.ptr(x), B, T, vtype, max_wraps, p(res.get('bits')),
-                                               p(res.get('wraps')), p(res.get('tailbiting')), p(res.get('metric'))))
-    out = [res[name][0] if one else res[name] for name in WANT if name in want]
-    return out[0] if len(out) == 1 else tuple(out)
+        _lib.check(_lib.load().cpx_tbcc_decode(device_trellis(trellis), _lib.ptr(x), B, T, vtype, max_wraps, *map(p, WANT)))
+    return returned(res, one)

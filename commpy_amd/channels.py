@@ -352,6 +352,10 @@ class _FadingModel:
             raise ValueError('t0 + nblk * hold = %d reaches 2^52' % (self.t0 + nblk * self.hold))
         return nblk
 
+    def shapes(self, lout, nblk):
+        """The channel's results for rows of ``lout`` output samples and ``nblk`` blocks of gains."""
+        return {'y': ((self.B, self.nr, lout), np.complex128), 'g': ((self.B, nblk, self.nr, self.nt, self.L), np.complex128)}
+
     def draw_args(self):
         return (self.n_sin, self.fd, self.fd_los)
 
@@ -450,6 +454,7 @@ def fading_multipath_batch(x, nr, pdp, fd, hold=1, t0=0, n_sin=16, k_factor=None
     always: with ``tap_frequency_response`` it is the perfect channel state per block).  Without 'g' the gains never leave the
     device, where they take at most ``FADING_SCRATCH_BYTES``.  No noise: add it with ``awgn`` or ``cpx_awgn_dev``."""
     from commpy_amd import _lib
+    from commpy_amd._results import outputs
     want = _lib.wanted(want, ('y', 'g'))
     xa, siso = _fading_rows(x)
     B, nt, n = xa.shape
@@ -458,16 +463,13 @@ def fading_multipath_batch(x, nr, pdp, fd, hold=1, t0=0, n_sin=16, k_factor=None
         raise ValueError('x is [B, n]: nr must be 1, got %d' % md.nr)
     lout = n + md.L - 1
     nblk = md.blocks(-(-lout // md.hold)) if B else 1
-    y = np.zeros((B, md.nr, lout), dtype=np.complex128) if 'y' in want else None
-    G = np.zeros((B, nblk, md.nr, nt, md.L), dtype=np.complex128) if 'g' in want else None
+    out, p = outputs(want, md.shapes(lout, nblk))
     if B:
-        _lib.check(_lib.load().cpx_fading_channel(_lib.ptr(xa) if y is not None else None, B, nt, md.nr, n, md.L, *md.tap_args(),
-                                                  *md.draw_args(), md.hold, md.t0, *md.key_args(),
-                                                  None if y is None else _lib.ptr(y), None if G is None else _lib.ptr(G)))
-    if y is not None and siso:
-        y = y[:, 0, :]
-    out = tuple(v for v in (y, G) if v is not None)
-    return out[0] if want == ('y',) else out
+        _lib.check(_lib.load().cpx_fading_channel(_lib.ptr(xa) if 'y' in want else None, B, nt, md.nr, n, md.L, *md.tap_args(),
+                                                  *md.draw_args(), md.hold, md.t0, *md.key_args(), p('y'), p('g')))
+    if 'y' in want and siso:
+        out['y'] = out['y'][:, 0, :]
+    return out['y'] if want == ('y',) else tuple(out.values())
 
 
 def tap_frequency_response(G, nfft, nsc):

@@ -281,17 +281,12 @@ int cpx_bch_decode(const cpx_bch *p, const uint8_t *in, int64_t B, uint8_t *bits
     int rc = ensure_device();
     if (rc) return rc;
     const size_t b = (size_t)B;
-    struct Out { void *host; size_t bytes; void *dev; } outs[3] = {
-        {bits, b * (size_t)p->k, nullptr}, {word, b * (size_t)p->n, nullptr}, {errors, 4 * b, nullptr}};
+    HostStage::Out outs[3] = {{bits, b * (size_t)p->k}, {word, b * (size_t)p->n}, {errors, 4 * b}};
     HostStage s;
     const uint8_t *din;
-    if ((rc = s.in(in, b * (size_t)p->n, &din))) return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.out(o.bytes, &o.dev))) return rc;
-    if ((rc = cpx_bch_decode_dev(p, din, B, (uint8_t *)outs[0].dev, (uint8_t *)outs[1].dev, (int32_t *)outs[2].dev, s.st))) return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.get(o.host, o.dev, o.bytes))) return rc;
-    return CPX_OK;
+    if ((rc = s.in(in, b * (size_t)p->n, &din)) || (rc = s.out(outs))) return rc;
+    if ((rc = cpx_bch_decode_dev(p, din, B, outs[0].as<uint8_t>(), outs[1].as<uint8_t>(), outs[2].as<int32_t>(), s.st))) return rc;
+    return s.get(outs);
 }
 
 }  // extern "C"

@@ -334,23 +334,17 @@ int cpx_chase_bch(const cpx_bch *h, const double *llr, const double *prior, doub
     int rc = ensure_device();
     if (rc) return rc;
     const size_t b = (size_t)B;
-    struct Out { void *host; size_t bytes; void *dev; } outs[5] = {{bits, b * (size_t)h->k, nullptr},
-                                                                   {codeword, b * (size_t)h->n, nullptr},
-                                                                   {extrinsic, 8 * b * (size_t)h->n, nullptr},
-                                                                   {metric, 8 * b, nullptr},
-                                                                   {candidates, 4 * b, nullptr}};
+    HostStage::Out outs[5] = {
+        {bits, b * (size_t)h->k}, {codeword, b * (size_t)h->n}, {extrinsic, 8 * b * (size_t)h->n}, {metric, 8 * b}, {candidates, 4 * b}};
     HostStage s;
     const double *dl, *dp = nullptr;
     if ((rc = s.in(llr, 8 * b * (size_t)h->n, &dl))) return rc;
     if (prior && (rc = s.in(prior, 8 * b * (size_t)h->n, &dp))) return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.out(o.bytes, &o.dev))) return rc;
-    if ((rc = cpx_chase_bch_dev(h, dl, dp, alpha, beta, p, B, 1, n, 0, 1, (uint8_t *)outs[0].dev, (uint8_t *)outs[1].dev, (double *)outs[2].dev,
-                                (double *)outs[3].dev, (int32_t *)outs[4].dev, s.st)))
+    if ((rc = s.out(outs))) return rc;
+    if ((rc = cpx_chase_bch_dev(h, dl, dp, alpha, beta, p, B, 1, n, 0, 1, outs[0].as<uint8_t>(), outs[1].as<uint8_t>(), outs[2].as<double>(),
+                                outs[3].as<double>(), outs[4].as<int32_t>(), s.st)))
         return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.get(o.host, o.dev, o.bytes))) return rc;
-    return CPX_OK;
+    return s.get(outs);
 }
 
 }  // extern "C"

@@ -245,9 +245,17 @@ struct Event {
 // Device staging of the host-buffer entry points, on the library stream: `in` allocates and queues the upload of `host`, `out`
 // allocates, `get` downloads (blocking, through d2h_pageable; nothing for zero bytes); the destructor frees every buffer.  Allocations
 // are fresh per call (a zero-byte request still gets 8 bytes); copies run inside CPX_TRACE ranges, and with tracing on an upload is
-// waited for so that the ranges do not overlap.
+// waited for so that the ranges do not overlap.  The optional outputs of an entry point are one array of `Out`, in the order of its
+// arguments: `out(outs)` allocates `dev` for every entry whose `host` is non-null, `get(outs)` downloads the same entries in order;
+// a null `host` keeps a null `dev`, which is what the `_dev` entry point takes for "not wanted".
 class HostStage {
 public:
+    struct Out {
+        void *host;
+        size_t bytes;
+        void *dev = nullptr;
+        template <class T> T *as() const { return static_cast<T *>(dev); }
+    };
     const hipStream_t st = lib_stream();
     HostStage() = default;
     HostStage(const HostStage &) = delete;
@@ -272,6 +280,18 @@ public:
         if (bytes == 0) return CPX_OK;
         CPX_TRACE("D2H");
         return d2h_pageable(host, d, bytes, st);
+    }
+    template <size_t N> int out(Out (&outs)[N]) {
+        for (Out &o : outs)
+            if (o.host)
+                if (int rc = alloc(o.bytes, &o.dev)) return rc;
+        return CPX_OK;
+    }
+    template <size_t N> int get(Out (&outs)[N]) {
+        for (Out &o : outs)
+            if (o.host)
+                if (int rc = get(o.host, o.dev, o.bytes)) return rc;
+        return CPX_OK;
     }
 private:
     int alloc(size_t bytes, void **d) {

@@ -517,23 +517,18 @@ int cpx_mmse_equalize(const cpx_modem *md, double es, const double *y, const dou
     int rc = ensure_device();
     if (rc) return rc;
     const size_t b = (size_t)B, nm = (size_t)n * (size_t)md->nbits, n_y = (size_t)n + (tail ? (size_t)L - 1 : 0);
-    struct Out { void *host; size_t bytes; void *dev; } outs[8] = {
-        {indices, 4 * b * (size_t)n, nullptr}, {bits, b * nm, nullptr}, {estimate, 16 * b * (size_t)n, nullptr}, {llr, 8 * b * nm, nullptr},
-        {noise, 8 * b, nullptr}, {ff, 16 * b * (size_t)nf, nullptr}, {fb, 16 * b * (size_t)nb, nullptr}, {gain, 8 * b, nullptr}};
+    HostStage::Out outs[8] = {{indices, 4 * b * (size_t)n}, {bits, b * nm},  {estimate, 16 * b * (size_t)n}, {llr, 8 * b * nm},
+                              {noise, 8 * b},               {ff, 16 * b * (size_t)nf}, {fb, 16 * b * (size_t)nb}, {gain, 8 * b}};
     HostStage s;
     const double *dy, *dh, *dnv;
     if ((rc = s.in(y, 16 * b * n_y, &dy)) || (rc = s.in(h, 16 * (size_t)L * (h_batched ? b : 1), &dh)) ||
-        (rc = s.in(noise_var, 8 * (nv_batched ? b : 1), &dnv)))
+        (rc = s.in(noise_var, 8 * (nv_batched ? b : 1), &dnv)) || (rc = s.out(outs)))
         return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.out(o.bytes, &o.dev))) return rc;
-    if ((rc = cpx_mmse_equalize_dev(md, es, dy, dh, h_batched, B, n, L, tail, dnv, nv_batched, nf, nb, delay, (int32_t *)outs[0].dev,
-                                    (uint8_t *)outs[1].dev, (double *)outs[2].dev, (double *)outs[3].dev, (double *)outs[4].dev,
-                                    (double *)outs[5].dev, (double *)outs[6].dev, (double *)outs[7].dev, s.st)))
+    if ((rc = cpx_mmse_equalize_dev(md, es, dy, dh, h_batched, B, n, L, tail, dnv, nv_batched, nf, nb, delay, outs[0].as<int32_t>(),
+                                    outs[1].as<uint8_t>(), outs[2].as<double>(), outs[3].as<double>(), outs[4].as<double>(),
+                                    outs[5].as<double>(), outs[6].as<double>(), outs[7].as<double>(), s.st)))
         return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.get(o.host, o.dev, o.bytes))) return rc;
-    return CPX_OK;
+    return s.get(outs);
 }
 
 }  // extern "C"

@@ -408,19 +408,14 @@ int cpx_ldpc_layered_decode(const cpx_ldpc_layered *c, const double *llr, int64_
     int rc = ensure_device();
     if (rc) return rc;
     const size_t b = (size_t)B, nv = (size_t)c->n_v;
-    struct Out { void *host; size_t bytes; void *dev; } outs[4] = {
-        {bits, b * nv, nullptr}, {llr_out, 8 * b * nv, nullptr}, {iters, 4 * b, nullptr}, {converged, b, nullptr}};
+    HostStage::Out outs[4] = {{bits, b * nv}, {llr_out, 8 * b * nv}, {iters, 4 * b}, {converged, b}};
     HostStage s;
     const double *din;
-    if ((rc = s.in(llr, 8 * b * nv, &din))) return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.out(o.bytes, &o.dev))) return rc;
-    if ((rc = cpx_ldpc_layered_decode_dev(c, din, B, n_iters, alpha, beta, early_stop, llr_clip, (int8_t *)outs[0].dev, (double *)outs[1].dev,
-                                          (int32_t *)outs[2].dev, (uint8_t *)outs[3].dev, s.st)))
+    if ((rc = s.in(llr, 8 * b * nv, &din)) || (rc = s.out(outs))) return rc;
+    if ((rc = cpx_ldpc_layered_decode_dev(c, din, B, n_iters, alpha, beta, early_stop, llr_clip, outs[0].as<int8_t>(), outs[1].as<double>(),
+                                          outs[2].as<int32_t>(), outs[3].as<uint8_t>(), s.st)))
         return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.get(o.host, o.dev, o.bytes))) return rc;
-    return CPX_OK;
+    return s.get(outs);
 }
 
 }  // extern "C"

@@ -515,21 +515,17 @@ int cpx_mlse(const cpx_modem *md, const double *y, const double *h, int h_batche
     int rc = ensure_device();
     if (rc) return rc;
     const size_t b = (size_t)B, nm = (size_t)n * (size_t)md->nbits, n_y = (size_t)n + (tail ? (size_t)L - 1 : 0);
-    struct Out { void *host; size_t bytes; void *dev; } outs[4] = {
-        {indices, 4 * b * (size_t)n, nullptr}, {bits, b * nm, nullptr}, {metric, 8 * b, nullptr}, {llr, 8 * b * nm, nullptr}};
+    HostStage::Out outs[4] = {{indices, 4 * b * (size_t)n}, {bits, b * nm}, {metric, 8 * b}, {llr, 8 * b * nm}};
     HostStage s;
     const double *dy, *dh, *dnv = nullptr, *dpr = nullptr;
     if ((rc = s.in(y, 16 * b * n_y, &dy)) || (rc = s.in(h, 16 * (size_t)L * (h_batched ? b : 1), &dh))) return rc;
     if (noise_var && (rc = s.in(noise_var, 8 * (nv_batched ? b : 1), &dnv))) return rc;
     if (prior && (rc = s.in(prior, 8 * b * nm, &dpr))) return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.out(o.bytes, &o.dev))) return rc;
-    if ((rc = cpx_mlse_dev(md, dy, dh, h_batched, B, n, L, tail, dnv, nv_batched, dpr, (int32_t *)outs[0].dev, (uint8_t *)outs[1].dev,
-                           (double *)outs[2].dev, (double *)outs[3].dev, s.st)))
+    if ((rc = s.out(outs))) return rc;
+    if ((rc = cpx_mlse_dev(md, dy, dh, h_batched, B, n, L, tail, dnv, nv_batched, dpr, outs[0].as<int32_t>(), outs[1].as<uint8_t>(),
+                           outs[2].as<double>(), outs[3].as<double>(), s.st)))
         return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.get(o.host, o.dev, o.bytes))) return rc;
-    return CPX_OK;
+    return s.get(outs);
 }
 
 }  // extern "C"

@@ -549,23 +549,20 @@ int cpx_polar_decode(const cpx_polar *p, const double *llr, int64_t B, int L, ui
     int rc = ensure_device();
     if (rc) return rc;
     const size_t b = (size_t)B;
-    // host pointer, bytes
-    struct Out { void *host; size_t bytes; void *dev; } outs[7] = {
-        {bits, b * (size_t)p->A, nullptr},         {crc_ok, b, nullptr},
-        {metric, 8 * b, nullptr},                  {u_llr, 8 * b * (size_t)p->N, nullptr},
-        {list_bits, b * (size_t)L * (size_t)p->K, nullptr}, {list_metric, 8 * b * (size_t)L, nullptr},
-        {list_live, 4 * b, nullptr}};
+    HostStage::Out outs[7] = {{bits, b * (size_t)p->A},
+                              {crc_ok, b},
+                              {metric, 8 * b},
+                              {u_llr, 8 * b * (size_t)p->N},
+                              {list_bits, b * (size_t)L * (size_t)p->K},
+                              {list_metric, 8 * b * (size_t)L},
+                              {list_live, 4 * b}};
     HostStage s;
     const double *din;
-    if ((rc = s.in(llr, 8 * b * (size_t)p->N, &din))) return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.out(o.bytes, &o.dev))) return rc;
-    if ((rc = cpx_polar_decode_dev(p, din, B, L, (uint8_t *)outs[0].dev, (uint8_t *)outs[1].dev, (double *)outs[2].dev, (double *)outs[3].dev,
-                                   (uint8_t *)outs[4].dev, (double *)outs[5].dev, (int32_t *)outs[6].dev, s.st)))
+    if ((rc = s.in(llr, 8 * b * (size_t)p->N, &din)) || (rc = s.out(outs))) return rc;
+    if ((rc = cpx_polar_decode_dev(p, din, B, L, outs[0].as<uint8_t>(), outs[1].as<uint8_t>(), outs[2].as<double>(), outs[3].as<double>(),
+                                   outs[4].as<uint8_t>(), outs[5].as<double>(), outs[6].as<int32_t>(), s.st)))
         return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.get(o.host, o.dev, o.bytes))) return rc;
-    return CPX_OK;
+    return s.get(outs);
 }
 
 }  // extern "C"

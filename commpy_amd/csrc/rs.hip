@@ -443,19 +443,15 @@ int cpx_rs_decode(const cpx_rs *p, const uint16_t *in, const uint8_t *erased, in
     int rc = ensure_device();
     if (rc) return rc;
     const size_t b = (size_t)B;
-    struct Out { void *host; size_t bytes; void *dev; } outs[3] = {
-        {symbols, 2 * b * (size_t)p->k, nullptr}, {word, 2 * b * (size_t)p->n, nullptr}, {errors, 4 * b, nullptr}};
+    HostStage::Out outs[3] = {{symbols, 2 * b * (size_t)p->k}, {word, 2 * b * (size_t)p->n}, {errors, 4 * b}};
     HostStage s;
     const uint16_t *din;
     const uint8_t *der = nullptr;
     if ((rc = s.in(in, 2 * b * (size_t)p->n, &din))) return rc;
     if (erased && (rc = s.in(erased, b * (size_t)p->n, &der))) return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.out(o.bytes, &o.dev))) return rc;
-    if ((rc = cpx_rs_decode_dev(p, din, der, B, (uint16_t *)outs[0].dev, (uint16_t *)outs[1].dev, (int32_t *)outs[2].dev, s.st))) return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.get(o.host, o.dev, o.bytes))) return rc;
-    return CPX_OK;
+    if ((rc = s.out(outs))) return rc;
+    if ((rc = cpx_rs_decode_dev(p, din, der, B, outs[0].as<uint16_t>(), outs[1].as<uint16_t>(), outs[2].as<int32_t>(), s.st))) return rc;
+    return s.get(outs);
 }
 
 }  // extern "C"

@@ -502,14 +502,12 @@ int cpx_tbcc_encode(const cpx_trellis *t, const uint8_t *msg, int64_t B, int64_t
     int rc = ensure_device();
     if (rc) return rc;
     const size_t in_bytes = (size_t)B * (size_t)T * (size_t)t->k, out_bytes = (size_t)B * (size_t)T * (size_t)t->n;
+    HostStage::Out outs[2] = {{word, out_bytes}, {closed, (size_t)B}};
     HostStage s;
     const uint8_t *din;
-    uint8_t *dout, *dclosed = nullptr;
-    if ((rc = s.in(msg, in_bytes, &din)) || (rc = s.out(out_bytes, &dout))) return rc;
-    if (closed && (rc = s.out((size_t)B, &dclosed))) return rc;
-    if ((rc = cpx_tbcc_encode_dev(t, din, B, T, dout, dclosed, s.st))) return rc;
-    if ((rc = s.get(word, dout, out_bytes))) return rc;
-    return closed ? s.get(closed, dclosed, (size_t)B) : CPX_OK;
+    if ((rc = s.in(msg, in_bytes, &din)) || (rc = s.out(outs))) return rc;
+    if ((rc = cpx_tbcc_encode_dev(t, din, B, T, outs[0].as<uint8_t>(), outs[1].as<uint8_t>(), s.st))) return rc;
+    return s.get(outs);
 }
 
 int cpx_tbcc_decode_dev(const cpx_trellis *t, const double *d_coded, int64_t B, int64_t T, int decoding_type, int max_wraps, uint8_t *d_bits,
@@ -541,19 +539,14 @@ int cpx_tbcc_decode(const cpx_trellis *t, const double *coded, int64_t B, int64_
     int rc = ensure_device();
     if (rc) return rc;
     const size_t b = (size_t)B;
-    struct Out { void *host; size_t bytes; void *dev; } outs[4] = {
-        {bits, b * (size_t)T * (size_t)t->k, nullptr}, {wraps, 4 * b, nullptr}, {tailbiting, b, nullptr}, {metric, 8 * b, nullptr}};
+    HostStage::Out outs[4] = {{bits, b * (size_t)T * (size_t)t->k}, {wraps, 4 * b}, {tailbiting, b}, {metric, 8 * b}};
     HostStage s;
     const double *din;
-    if ((rc = s.in(coded, 8 * b * (size_t)T * (size_t)t->n, &din))) return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.out(o.bytes, &o.dev))) return rc;
-    if ((rc = cpx_tbcc_decode_dev(t, din, B, T, decoding_type, max_wraps, (uint8_t *)outs[0].dev, (int32_t *)outs[1].dev, (uint8_t *)outs[2].dev,
-                                  (double *)outs[3].dev, s.st)))
+    if ((rc = s.in(coded, 8 * b * (size_t)T * (size_t)t->n, &din)) || (rc = s.out(outs))) return rc;
+    if ((rc = cpx_tbcc_decode_dev(t, din, B, T, decoding_type, max_wraps, outs[0].as<uint8_t>(), outs[1].as<int32_t>(), outs[2].as<uint8_t>(),
+                                  outs[3].as<double>(), s.st)))
         return rc;
-    for (Out &o : outs)
-        if (o.host && (rc = s.get(o.host, o.dev, o.bytes))) return rc;
-    return CPX_OK;
+    return s.get(outs);
 }
 
 }  // extern "C"

@@ -10,7 +10,9 @@ import ctypes
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd._results import device_outputs, returned
 from commpy_amd.channelcoding.convcode import puncture_keep_mask
+from commpy_amd.channelcoding.gfields import whole
 from commpy_amd.channelcoding.ldpc import build_matrix
 
 __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu', 'mimo_channel_gpu', 'puncturing_gpu',
@@ -379,29 +381,27 @@ def ofdm_map_dev(pilots, d_data, B, stream=None):
     return d_grid
 
 
-def _ofdm_estimate(entry, third, rows, pilots, d_Y, B, nr, want, stream):
-    """Both estimators: ``entry`` writes y_data, h_data and its own third output, ``third`` ``[B][rows][nr][nt]``."""
-    names = ('y', 'h', third)
-    want = _lib.wanted(want, names)
-    sizes = {'y': pilots.ndata * nr, 'h': pilots.ndata * nr * pilots.nt, third: rows * nr * pilots.nt}
-    out = {k: DeviceBuf(B * sizes[k] * 16) for k in names if k in want}
-    ptrs = [out[k].ptr if k in out else None for k in (third, 'y', 'h')]
-    _lib.check(getattr(_lib.load(), entry)(pilots.handle(), d_Y.ptr, B, nr, ptrs[0], ptrs[1], ptrs[2], stream))
-    return tuple(out[k] for k in names if k in out)
+def _ofdm_estimate(entry, third, dims, pilots, d_Y, B, nr, want, stream):
+    """Both estimators: ``entry`` writes y_data, h_data and its own third output, ``third`` ``[B][*dims][nr][nt]``."""
+    from commpy_amd.modulation import ofdm_estimate_shapes
+    shapes = ofdm_estimate_shapes(pilots, B, nr, third, dims)
+    out, p = device_outputs(_lib.wanted(want, tuple(shapes)), shapes)
+    _lib.check(getattr(_lib.load(), entry)(pilots.handle(), d_Y.ptr, B, nr, p(third), p('y'), p('h'), stream))
+    return tuple(out.values())
 
 
 def ofdm_estimate_dev(pilots, d_Y, B, nr, want=('y', 'h'), stream=None):
     """``cpx_pilots_estimate_dev``: ``d_Y [B][nr][nsym][nsc]`` -> a tuple of new ``DeviceBuf``s, the members of ``(y_data
     [B][ndata][nr], h_data [B][ndata][nr][nt], h_sc [B][nsc][nr][nt])`` that ``want`` names ('y', 'h', 'h_sc'), in that order:
     the first two are the ``y`` and ``H`` of the ``cpx_mimo_*_dev`` / ``cpx_kbest_*_dev`` detectors for ``V = B ndata`` vectors."""
-    return _ofdm_estimate('cpx_pilots_estimate_dev', 'h_sc', pilots.nsc, pilots, d_Y, B, nr, want, stream)
+    return _ofdm_estimate('cpx_pilots_estimate_dev', 'h_sc', (pilots.nsc,), pilots, d_Y, B, nr, want, stream)
 
 
 def ofdm_estimate_tv_dev(pilots, d_Y, B, nr, want=('y', 'h'), stream=None):
     """``cpx_pilots_estimate_tv_dev`` (``pilots`` made with ``time_interp``): ``d_Y [B][nr][nsym][nsc]`` -> a tuple of new
     ``DeviceBuf``s, the members of ``(y_data [B][ndata][nr], h_data [B][ndata][nr][nt], h_sym [B][nsym][nsc][nr][nt])`` that ``want``
     names ('y', 'h', 'h_sym'), in that order; the first two feed the detectors as ``ofdm_estimate_dev``'s do."""
-    return _ofdm_estimate('cpx_pilots_estimate_tv_dev', 'h_sym', pilots.nsym * pilots.nsc, pilots, d_Y, B, nr, want, stream)
+    return _ofdm_estimate('cpx_pilots_estimate_tv_dev', 'h_sym', (pilots.nsym, pilots.nsc), pilots, d_Y, B, nr, want, stream)
 
 
 # ---- timing and frequency-offset synchronisation, device resident (csrc/sync.hip) -------------------------------------------------
@@ -473,13 +473,10 @@ def fading_channel_dev(d_x, B, nt, nr, n, pdp, fd, hold=1, t0=0, n_sin=16, k_fac
         raise ValueError('n = %r, need an integer >= 1' % (n,))
     lout = n + md.L - 1
     nblk = md.blocks(-(-lout // md.hold)) if md.B else 1
-    d_y = DeviceBuf(md.B * md.nr * lout * 16) if 'y' in want else None
-    d_G = DeviceBuf(md.B * nblk * md.nr * md.nt * md.L * 16) if 'g' in want else None
-    _lib.check(_lib.load().cpx_fading_channel_dev(d_x.ptr if d_y is not None else None, md.B, md.nt, md.nr, n, md.L, *md.tap_args(),
-                                                  *md.draw_args(), md.hold, md.t0, *md.key_args(),
-                                                  None if d_y is None else d_y.ptr, None if d_G is None else d_G.ptr, stream))
-    out = tuple(v for v in (d_y, d_G) if v is not None)
-    return out[0] if want == ('y',) else out
+    out, p = device_outputs(want, md.shapes(lout, nblk))
+    _lib.check(_lib.load().cpx_fading_channel_dev(d_x.ptr if 'y' in want else None, md.B, md.nt, md.nr, n, md.L, *md.tap_args(),
+                                                  *md.draw_args(), md.hold, md.t0, *md.key_args(), p('y'), p('g'), stream))
+    return out['y'] if want == ('y',) else tuple(out.values())
 
 
 # ---- polar codes, device resident (csrc/polar.hip) ----------------------------------------------------------------------------------
@@ -487,8 +484,8 @@ def fading_channel_dev(d_x, B, nt, nr, n, pdp, fd, hold=1, t0=0, n_sin=16, k_fac
 def polar_encode_dev(code, d_msg, B, stream=None):
     """``cpx_polar_encode_dev``: ``d_msg [B][A]`` uint8 -> a new ``DeviceBuf`` ``[B][N]`` uint8 of code words, queued on ``stream``
     (None: the library's); ``code`` is a ``channelcoding.PolarCode``."""
-    from commpy_amd.channelcoding.polar import _code, _whole
-    code, B = _code(code), _whole(B, 'B', 0)
+    from commpy_amd.channelcoding.polar import _code
+    code, B = _code(code), whole(B, 'B', 0)
     d_x = DeviceBuf(B * code.N)
     if B:
         _lib.check(d_x.lib.cpx_polar_encode_dev(code._device_handle(), d_msg.ptr, B, d_x.ptr, stream))
@@ -500,21 +497,18 @@ def polar_decode_dev(code, d_llr, B, list_size=1, want=('bits',), stream=None):
     ``want`` names, in its order: 'bits' ``[B][A]`` uint8, 'crc' ``[B]`` uint8, 'metric' ``[B]`` float64, 'u_llr' ``[B][N]`` float64
     (``list_size = 1``), 'list' a tuple ``(bits [B][L][K] uint8, metrics [B][L] float64, live [B] int32)``; a single result for one
     name."""
-    from commpy_amd.channelcoding.polar import WANT, _code, _whole, check_want
-    code, B = _code(code), _whole(B, 'B', 0)
+    from commpy_amd.channelcoding.polar import _code, check_want, list_shapes, shapes
+    code, B = _code(code), whole(B, 'B', 0)
     L = code.check_list_size(list_size)
     want = check_want(want, L)
-    sizes = {'bits': B * code.A, 'crc': B, 'metric': B * 8, 'u_llr': B * code.N * 8}
-    out = {k: DeviceBuf(sizes[k]) for k in sizes if k in want}
-    lst = (DeviceBuf(B * L * code.K), DeviceBuf(B * L * 8), DeviceBuf(B * 4)) if 'list' in want else (None,) * 3
+    tables = shapes(B, code), list_shapes(B, code, L)
+    out, p = device_outputs(want, tables[0])
+    lst, q = device_outputs(tables[1] if 'list' in want else (), tables[1])
     if B:
-        p = lambda v: None if v is None else v.ptr
-        _lib.check(_lib.load().cpx_polar_decode_dev(code._device_handle(), d_llr.ptr, B, L, p(out.get('bits')), p(out.get('crc')),
-                                                    p(out.get('metric')), p(out.get('u_llr')), p(lst[0]), p(lst[1]), p(lst[2]), stream))
-    if 'list' in want:
-        out['list'] = lst
-    res = tuple(out[k] for k in WANT if k in want)
-    return res[0] if len(res) == 1 else res
+        _lib.check(_lib.load().cpx_polar_decode_dev(code._device_handle(), d_llr.ptr, B, L, *map(p, tables[0]), *map(q, tables[1]), stream))
+    if lst:
+        out['list'] = tuple(lst.values())                     # 'list' is the last name
+    return returned(out)
 
 
 # ---- BCH codes, device resident (csrc/bch.hip) --------------------------------------------------------------------------------------
@@ -523,7 +517,6 @@ def bch_encode_dev(code, d_msg, B, stream=None):
     """``cpx_bch_encode_dev``: ``d_msg [B][k]`` uint8 -> a new ``DeviceBuf`` ``[B][n]`` uint8 of code words, queued on ``stream``
     (None: the library's); ``code`` is a ``channelcoding.BCHCode``."""
     from commpy_amd.channelcoding.bch import _code
-    from commpy_amd.channelcoding.gfields import whole
     code, B = _code(code), whole(B, 'B', 0)
     d_x = DeviceBuf(B * code.n)
     if B:
@@ -535,18 +528,12 @@ def bch_decode_dev(code, d_bits, B, want=('bits',), stream=None):
     """``cpx_bch_decode_dev``: ``d_bits [B][n]`` uint8 hard decisions (non-zero = 1) -> new ``DeviceBuf``s, the results of
     ``channelcoding.bch_decode`` that ``want`` names, in its order: 'bits' ``[B][k]`` uint8, 'codeword' ``[B][n]`` uint8, 'errors'
     ``[B]`` int32; a single result for one name."""
-    from commpy_amd.channelcoding.bch import WANT, _code, check_want
-    from commpy_amd.channelcoding.gfields import whole
+    from commpy_amd.channelcoding.bch import WANT, _code, check_want, shapes
     code, B = _code(code), whole(B, 'B', 0)
-    want = check_want(want)
-    sizes = {'bits': B * code.k, 'codeword': B * code.n, 'errors': B * 4}
-    out = {k: DeviceBuf(sizes[k]) for k in sizes if k in want}
+    out, p = device_outputs(check_want(want), shapes(B, code))
     if B:
-        p = lambda v: None if v is None else v.ptr
-        _lib.check(_lib.load().cpx_bch_decode_dev(code._device_handle(), d_bits.ptr, B, p(out.get('bits')), p(out.get('codeword')),
-                                                  p(out.get('errors')), stream))
-    res = tuple(out[k] for k in WANT if k in want)
-    return res[0] if len(res) == 1 else res
+        _lib.check(_lib.load().cpx_bch_decode_dev(code._device_handle(), d_bits.ptr, B, *map(p, WANT), stream))
+    return returned(out)
 
 
 # ---- Chase-II BCH decoding and turbo product codes, device resident (csrc/bch_chase.hip) -----------------------------------------------
@@ -559,8 +546,7 @@ def bch_chase_dev(code, d_llr, B, p, beta, d_prior=None, alpha=1.0, want=('bits'
     ``want`` names, in its order: 'bits' uint8 (dense, nested as the input: ``[B][J][k]``, or ``[B][k][J]`` where the word axis is the
     inner one), 'codeword' uint8 and 'extrinsic' float64 (each as large as ``sb * B`` elements), 'metric' float64 and 'candidates'
     int32 ``[B][J]``.  ``d_extrinsic``: write the soft output there instead of into a new buffer -- it may be ``d_prior``."""
-    from commpy_amd.channelcoding.bch import CHASE_WANT, chase_args
-    from commpy_amd.channelcoding.gfields import whole
+    from commpy_amd.channelcoding.bch import CHASE_WANT, chase_args, chase_shapes
     code, p, beta, alpha, want = chase_args(code, p, beta, alpha, want)
     B, J = whole(B, 'B', 0), whole(J, 'J', 1)
     if strides is None:
@@ -576,15 +562,11 @@ def bch_chase_dev(code, d_llr, B, p, beta, d_prior=None, alpha=1.0, want=('bits'
     if d_extrinsic is not None and 'extrinsic' not in want:
         raise ValueError("d_extrinsic needs 'extrinsic' in want")
     extent = (B - 1) * sb + span_i + span_j + 1 if B else 0
-    sizes = {'bits': B * J * code.k, 'codeword': extent, 'extrinsic': 8 * extent, 'metric': 8 * B * J, 'candidates': 4 * B * J}
-    out = {k: d_extrinsic if k == 'extrinsic' and d_extrinsic is not None else DeviceBuf(sizes[k]) for k in CHASE_WANT if k in want}
+    out, q = device_outputs(want, chase_shapes((B, J), code.k, (extent,)), {'extrinsic': d_extrinsic})
     if B:
-        q = lambda v: None if v is None else v.ptr
-        _lib.check(_lib.load().cpx_chase_bch_dev(code._device_handle(), d_llr.ptr, q(d_prior), alpha, beta, p, B, J, sb, sj, si, q(out.get('bits')),
-                                                 q(out.get('codeword')), q(out.get('extrinsic')), q(out.get('metric')),
-                                                 q(out.get('candidates')), stream))
-    res = tuple(out[k] for k in CHASE_WANT if k in want)
-    return res[0] if len(res) == 1 else res
+        _lib.check(_lib.load().cpx_chase_bch_dev(code._device_handle(), d_llr.ptr, None if d_prior is None else d_prior.ptr, alpha, beta, p,
+                                                 B, J, sb, sj, si, *map(q, CHASE_WANT), stream))
+    return returned(out)
 
 
 def tpc_decode_dev(code, d_llr, B, iters=4, p=4, alpha=None, beta=None, llr_scale=1.0, want=('codeword',), stream=None):
@@ -593,13 +575,12 @@ def tpc_decode_dev(code, d_llr, B, iters=4, p=4, alpha=None, beta=None, llr_scal
     of the one before as its prior (``channelcoding.tpc_decode`` states the schedule).  Returns new ``DeviceBuf``s, what ``want``
     names out of 'codeword' ``[B][n_c][n_r]`` uint8 (the decision of the last half-iteration) and 'extrinsic'
     ``[B][n_c][n_r]`` float64 (its soft output), in this order."""
-    from commpy_amd.channelcoding.gfields import whole
-    from commpy_amd.channelcoding.productcode import TPC_DEV_WANT, tpc_args
+    from commpy_amd.channelcoding.productcode import TPC_DEV_WANT, shapes, tpc_args
     code, iters, p, alpha, beta = tpc_args(code, iters, p, alpha, beta, llr_scale)
     B = whole(B, 'B', 0)
     want = _lib.wanted(want, TPC_DEV_WANT)
     nr, nc = code.n_r, code.n_c
-    d_w = DeviceBuf(8 * B * nc * nr)                              # W, the extrinsic information: zero, then rewritten in place
+    d_w = device_outputs(('extrinsic',), shapes(B, code))[0]['extrinsic']     # W, the extrinsic information: zero, then rewritten in place
     if B:
         _lib.check(d_w.lib.cpx_memset(d_w.ptr, 0, d_w.nbytes))
     d_word = None
@@ -613,8 +594,7 @@ def tpc_decode_dev(code, d_llr, B, iters=4, p=4, alpha=None, beta=None, llr_scal
         if len(names) == 2:
             d_word = res[0]
     out = {'codeword': d_word, 'extrinsic': d_w}
-    res = tuple(out[k] for k in TPC_DEV_WANT if k in want)
-    return res[0] if len(res) == 1 else res
+    return returned({k: out[k] for k in TPC_DEV_WANT if k in want})
 
 
 # ---- Reed-Solomon codes, device resident (csrc/rs.hip) ------------------------------------------------------------------------------
@@ -622,7 +602,6 @@ def tpc_decode_dev(code, d_llr, B, iters=4, p=4, alpha=None, beta=None, llr_scal
 def rs_encode_dev(code, d_msg, B, stream=None):
     """``cpx_rs_encode_dev``: ``d_msg [B][k]`` uint16 -> a new ``DeviceBuf`` ``[B][n]`` uint16 of code words, queued on ``stream``
     (None: the library's); ``code`` is a ``channelcoding.RSCode``.  Only the low ``m`` bits of a symbol count."""
-    from commpy_amd.channelcoding.gfields import whole
     from commpy_amd.channelcoding.rs import _code
     code, B = _code(code), whole(B, 'B', 0)
     d_x = DeviceBuf(2 * B * code.n)
@@ -635,18 +614,13 @@ def rs_decode_dev(code, d_symbols, B, d_erased=None, want=('symbols',), stream=N
     """``cpx_rs_decode_dev``: ``d_symbols [B][n]`` uint16 received symbols (the low ``m`` bits count) and ``d_erased [B][n]`` uint8
     flags (non-zero = erased; None: no flags) -> new ``DeviceBuf``s, the results of ``channelcoding.rs_decode`` that ``want`` names,
     in its order: 'symbols' ``[B][k]`` uint16, 'codeword' ``[B][n]`` uint16, 'errors' ``[B]`` int32; a single result for one name."""
-    from commpy_amd.channelcoding.gfields import whole
-    from commpy_amd.channelcoding.rs import WANT, _code, check_want
+    from commpy_amd.channelcoding.rs import WANT, _code, check_want, shapes
     code, B = _code(code), whole(B, 'B', 0)
-    want = check_want(want)
-    sizes = {'symbols': 2 * B * code.k, 'codeword': 2 * B * code.n, 'errors': B * 4}
-    out = {k: DeviceBuf(sizes[k]) for k in sizes if k in want}
+    out, p = device_outputs(check_want(want), shapes(B, code))
     if B:
-        p = lambda v: None if v is None else v.ptr
-        _lib.check(_lib.load().cpx_rs_decode_dev(code._device_handle(), d_symbols.ptr, p(d_erased), B, p(out.get('symbols')),
-                                                 p(out.get('codeword')), p(out.get('errors')), stream))
-    res = tuple(out[k] for k in WANT if k in want)
-    return res[0] if len(res) == 1 else res
+        _lib.check(_lib.load().cpx_rs_decode_dev(code._device_handle(), d_symbols.ptr, None if d_erased is None else d_erased.ptr, B,
+                                                 *map(p, WANT), stream))
+    return returned(out)
 
 
 # ---- tail-biting convolutional codes, device resident (csrc/tbcc.hip) ---------------------------------------------------------------
@@ -656,7 +630,6 @@ def tailbiting_encode_dev(trellis, d_msg, B, T, stream=None):
     the library's): the code words ``[B][T n]`` uint8 and ``closed [B]`` uint8, 1 where the emitting walk ended in the state in which it
     began (``channelcoding.tailbiting_encode`` raises where it is 0).  ``trellis`` is a ``Trellis`` or any duck-typed trellis."""
     from commpy_amd.channelcoding.convcode import device_trellis
-    from commpy_amd.channelcoding.gfields import whole
     from commpy_amd.channelcoding.tailbiting import check_block, check_trellis
     k, n = check_trellis(trellis)
     B, T = whole(B, 'B', 0), check_block(whole(T, 'T', 1), k)
@@ -671,19 +644,14 @@ def tailbiting_decode_dev(trellis, d_coded, B, T, decoding_type='hard', max_wrap
     that ``want`` names, in its order: 'bits' ``[B][T k]`` uint8, 'wraps' ``[B]`` int32, 'tailbiting' ``[B]`` uint8, 'metric' ``[B]``
     float64; a single result for one name."""
     from commpy_amd.channelcoding.convcode import device_trellis
-    from commpy_amd.channelcoding.gfields import whole
-    from commpy_amd.channelcoding.tailbiting import WANT, check_block, check_max_wraps, check_trellis, check_type, check_want
+    from commpy_amd.channelcoding.tailbiting import WANT, check_block, check_max_wraps, check_trellis, check_type, check_want, shapes
     k, n = check_trellis(trellis)
     vtype, max_wraps, want = check_type(decoding_type), check_max_wraps(max_wraps), check_want(want)
     B, T = whole(B, 'B', 0), check_block(whole(T, 'T', 1), k)
-    sizes = {'bits': B * T * k, 'wraps': B * 4, 'tailbiting': B, 'metric': B * 8}
-    out = {name: DeviceBuf(sizes[name]) for name in sizes if name in want}
+    out, p = device_outputs(want, shapes(B, T, k))
     if B:
-        p = lambda v: None if v is None else v.ptr
-        _lib.check(_lib.load().cpx_tbcc_decode_dev(device_trellis(trellis), d_coded.ptr, B, T, vtype, max_wraps, p(out.get('bits')),
-                                                   p(out.get('wraps')), p(out.get('tailbiting')), p(out.get('metric')), stream))
-    res = tuple(out[name] for name in WANT if name in want)
-    return res[0] if len(res) == 1 else res
+        _lib.check(_lib.load().cpx_tbcc_decode_dev(device_trellis(trellis), d_coded.ptr, B, T, vtype, max_wraps, *map(p, WANT), stream))
+    return returned(out)
 
 
 # ---- layered min-sum LDPC decoding, device resident (csrc/ldpc_layered.hip) ---------------------------------------------------------
@@ -694,22 +662,17 @@ def ldpc_layered_decode_dev(ldpc_code_params, d_llr, B, n_iters, alpha=1.0, beta
     library's), the results of ``channelcoding.ldpc_layered_decode`` that ``want`` names, in its order: 'bits' ``[B][n_v]`` int8, 'llr'
     ``[B][n_v]`` float64, 'iters' ``[B]`` int32, 'converged' ``[B]`` uint8; a single result for one name.  The same checks, on the host,
     before any device call."""
-    from commpy_amd.channelcoding.gfields import whole
-    from commpy_amd.channelcoding.ldpc_layered import WANT, check_n_iters, check_scaling, check_want, plan
+    from commpy_amd.channelcoding.ldpc_layered import WANT, check_n_iters, check_scaling, check_want, plan, shapes
     n_iters = check_n_iters(n_iters)
     alpha, beta, llr_clip = check_scaling(alpha, beta, llr_clip)
     want = check_want(want)
     p = plan(ldpc_code_params, schedule)
     B = whole(B, 'B', 0)
-    sizes = {'bits': B * p.n_v, 'llr': B * p.n_v * 8, 'iters': B * 4, 'converged': B}
-    out = {name: DeviceBuf(sizes[name]) for name in sizes if name in want}
+    out, q = device_outputs(want, shapes(B, p.n_v))
     if B:
-        q = lambda v: None if v is None else v.ptr
         _lib.check(_lib.load().cpx_ldpc_layered_decode_dev(p.handle(), d_llr.ptr, B, n_iters, alpha, beta, 1 if early_stop else 0, llr_clip,
-                                                           q(out.get('bits')), q(out.get('llr')), q(out.get('iters')),
-                                                           q(out.get('converged')), stream))
-    res = tuple(out[name] for name in WANT if name in want)
-    return res[0] if len(res) == 1 else res
+                                                           *map(q, WANT), stream))
+    return returned(out)
 
 
 # ---- trellis equalisation, device resident (csrc/mlse.hip) --------------------------------------------------------------------------
@@ -722,22 +685,18 @@ def mlse_equalize_dev(modem, d_y, d_h, h_batched, B, n, L, d_noise_var=None, nv_
     'metric' ``[B]`` float64, 'llr' ``[B][n m]`` float64; a single result for one name.  ``d_noise_var``: one float64 or, with
     ``nv_batched``, ``[B]``, required for 'llr' and with ``d_prior [B][n m]``.  The same limits, checked on the host before any device
     call."""
-    from commpy_amd.channelcoding.gfields import whole
-    from commpy_amd.equalizers import WANT, check_sizes, check_want
+    from commpy_amd.equalizers import WANT, check_sizes, check_want, mlse_shapes
     want = check_want(want)
     B, n, L = whole(B, 'B', 0), whole(n, 'n', 1), whole(L, 'L', 2)
     M, m = check_sizes(modem, L, n)
     if d_noise_var is None and ('llr' in want or d_prior is not None):
         raise ValueError("noise_var is required when 'llr' is wanted or a prior is given")
-    sizes = {'indices': B * n * 4, 'bits': B * n * m, 'metric': B * 8, 'llr': B * n * m * 8}
-    out = {name: DeviceBuf(sizes[name]) for name in sizes if name in want}
+    out, p = device_outputs(want, mlse_shapes(B, n, m))
     if B:
-        p = lambda v: None if v is None else v.ptr
         _lib.check(_lib.load().cpx_mlse_dev(modem._device_handle(), d_y.ptr, d_h.ptr, int(bool(h_batched)), B, n, L, int(bool(tail)),
-                                            p(d_noise_var), int(bool(nv_batched)), p(d_prior), p(out.get('indices')), p(out.get('bits')),
-                                            p(out.get('metric')), p(out.get('llr')), stream))
-    res = tuple(out[name] for name in WANT if name in want)
-    return res[0] if len(res) == 1 else res
+                                            None if d_noise_var is None else d_noise_var.ptr, int(bool(nv_batched)),
+                                            None if d_prior is None else d_prior.ptr, *map(p, WANT), stream))
+    return returned(out)
 
 
 # ---- MMSE linear and decision-feedback equalisation, device resident (csrc/equalize.hip) --------------------------------------------
@@ -750,20 +709,15 @@ def mmse_equalize_dev(modem, d_y, d_h, h_batched, B, n, L, d_noise_var, nv_batch
     in its order: 'indices' ``[B][n]`` int32, 'bits' ``[B][n m]`` uint8, 'estimate' ``[B][n][2]``, 'llr' ``[B][n m]``, 'noise' ``[B]``,
     'ff' ``[B][nf][2]``, 'fb' ``[B][nb][2]``, 'gain' ``[B]`` float64; a single result for one name.  The same rule and the same limits,
     checked on the host before any device call."""
-    from commpy_amd.channelcoding.gfields import whole
-    from commpy_amd.equalizers import MMSE_WANT, check_mmse_sizes
+    from commpy_amd.equalizers import MMSE_WANT, check_mmse_sizes, mmse_shapes
     want = _lib.wanted(want, MMSE_WANT)
     B, n, L, nf, nb = whole(B, 'B', 0), whole(n, 'n', 1), whole(L, 'L', 1), whole(nf, 'nf', 1), whole(nb, 'nb', 0)
     M, m, delay = check_mmse_sizes(modem, L, n, nf, nb, None if delay is None else int(delay), want)
     if d_noise_var is None:
         raise ValueError('noise_var is required')
-    sizes = {'indices': B * n * 4, 'bits': B * n * m, 'estimate': B * n * 16, 'llr': B * n * m * 8, 'noise': B * 8, 'ff': B * nf * 16,
-             'fb': B * nb * 16, 'gain': B * 8}
-    out = {name: DeviceBuf(sizes[name]) for name in sizes if name in want}
+    out, p = device_outputs(want, mmse_shapes(B, n, m, nf, nb))
     if B:
-        p = lambda name: None if name not in out else out[name].ptr
         _lib.check(_lib.load().cpx_mmse_equalize_dev(modem._device_handle(), float(modem.Es), d_y.ptr, d_h.ptr, int(bool(h_batched)), B, n,
                                                      L, int(bool(tail)), d_noise_var.ptr, int(bool(nv_batched)), nf, nb, delay,
                                                      *map(p, MMSE_WANT), stream))
-    res = tuple(out[name] for name in MMSE_WANT if name in want)
-    return res[0] if len(res) == 1 else res
+    return returned(out)

@@ -19,6 +19,7 @@ tests/equalize_model.py.
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd._results import outputs, returned
 
 __all__ = ['mlse_equalize_batch', 'mmse_equalize_batch']
 
@@ -31,6 +32,34 @@ MMSE_WANT = ('indices', 'bits', 'estimate', 'llr', 'noise', 'ff', 'fb', 'gain')
 def check_want(want):
     """``want`` as a tuple of names out of 'indices', 'bits', 'metric', 'llr'."""
     return _lib.wanted(want, WANT)
+
+
+def mlse_shapes(B, n, m):
+    return {'indices': ((B, n), np.int32), 'bits': ((B, n * m), np.uint8), 'metric': ((B,), np.float64), 'llr': ((B, n * m), np.float64)}
+
+
+def mmse_shapes(B, n, m, nf, nb):
+    return {'indices': ((B, n), np.int32), 'bits': ((B, n * m), np.uint8), 'estimate': ((B, n), np.complex128),
+            'llr': ((B, n * m), np.float64), 'noise': ((B,), np.float64), 'ff': ((B, nf), np.complex128), 'fb': ((B, nb), np.complex128),
+            'gain': ((B,), np.float64)}
+
+
+def _rows_and_taps(y, h, tail):
+    """``(y [B, n_y], h, one, B, n, L)``: the rows and the taps as contiguous complex128 arrays, whether ``y`` was 1-D, and the sizes."""
+    ya, ha = np.asarray(y), np.asarray(h)
+    for name, a in (('y', ya), ('h', ha)):
+        if a.dtype.kind not in 'biufc':
+            raise ValueError('%s must hold numbers, got dtype %s' % (name, a.dtype))
+    if ya.ndim not in (1, 2):
+        raise ValueError('y must be [B, n_y] or 1-D, got %d dimensions' % ya.ndim)
+    one = ya.ndim == 1
+    ya = np.atleast_2d(ya)
+    B, n_y = ya.shape
+    if ha.ndim not in (1, 2) or (ha.ndim == 2 and ha.shape[0] != B):
+        raise ValueError('y is [%d, n_y]: h must be [L] or [%d, L], got shape %s' % (B, B, ha.shape))
+    L = ha.shape[-1]
+    return (np.ascontiguousarray(ya, dtype=np.complex128), np.ascontiguousarray(ha, dtype=np.complex128), one, B,
+            n_y - (L - 1) if tail else n_y, L)
 
 
 def check_sizes(modem, L, n):
@@ -93,19 +122,7 @@ def mlse_equalize_batch(y, h, modem, noise_var=None, a_priori=None, tail=True, w
     Limits, each refused with a ``ValueError`` before any device call: ``L >= 2``; ``M <= 16``; ``M^(L-1) <= 256`` states;
     ``1 <= n <= 4096``."""
     want = check_want(want)
-    ya, ha = np.asarray(y), np.asarray(h)
-    for name, a in (('y', ya), ('h', ha)):
-        if a.dtype.kind not in 'biufc':
-            raise ValueError('%s must hold numbers, got dtype %s' % (name, a.dtype))
-    if ya.ndim not in (1, 2):
-        raise ValueError('y must be [B, n_y] or 1-D, got %d dimensions' % ya.ndim)
-    one = ya.ndim == 1
-    ya = np.atleast_2d(ya)
-    B, n_y = ya.shape
-    if ha.ndim not in (1, 2) or (ha.ndim == 2 and ha.shape[0] != B):
-        raise ValueError('y is [%d, n_y]: h must be [L] or [%d, L], got shape %s' % (B, B, ha.shape))
-    L = ha.shape[-1]
-    n = n_y - (L - 1) if tail else n_y
+    ya, ha, one, B, n, L = _rows_and_taps(y, h, tail)
     M, m = check_sizes(modem, L, n)
     nv, nv_batched = check_noise_var(noise_var, B, 'llr' in want or a_priori is not None)
     prior = None
@@ -115,17 +132,12 @@ def mlse_equalize_batch(y, h, modem, noise_var=None, a_priori=None, tail=True, w
         if prior.shape != (B, n * m):
             raise ValueError('a_priori must be [B, n*m] = [%d, %d], got shape %s' % (B, n * m, prior.shape))
         prior = np.ascontiguousarray(prior)
-    ya = np.ascontiguousarray(ya, dtype=np.complex128)
-    ha = np.ascontiguousarray(ha, dtype=np.complex128)
-    shapes = {'indices': ((B, n), np.int32), 'bits': ((B, n * m), np.uint8), 'metric': ((B,), np.float64), 'llr': ((B, n * m), np.float64)}
-    res = {name: np.zeros(*shapes[name]) for name in WANT if name in want}
+    res, p = outputs(want, mlse_shapes(B, n, m))
     if B:
-        p = lambda v: None if v is None else _lib.ptr(v)
         _lib.check(_lib.load().cpx_mlse(modem._device_handle(), _lib.ptr(ya), _lib.ptr(ha), int(ha.ndim == 2), B, n, L, int(bool(tail)),
-                                        p(nv), int(nv_batched), p(prior), p(res.get('indices')), p(res.get('bits')),
-                                        p(res.get('metric')), p(res.get('llr'))))
-    out = [res[name][0] if one else res[name] for name in WANT if name in want]
-    return out[0] if len(out) == 1 else tuple(out)
+                                        None if nv is None else _lib.ptr(nv), int(nv_batched), None if prior is None else _lib.ptr(prior),
+                                        *map(p, WANT)))
+    return returned(res, one)
 
 
 def check_mmse_sizes(modem, L, n, nf, nb, delay, want):
@@ -193,33 +205,14 @@ def mmse_equalize_batch(y, h, modem, noise_var, nf, nb=0, delay=None, tail=True,
     ``0 <= delay``; ``delay + nb <= nf + L - 2``; ``2 <= M <= 256``; ``M`` a power of two when ``'bits'`` or ``'llr'`` is wanted;
     ``1 <= n <= 2^30``; ``noise_var > 0``."""
     want = _lib.wanted(want, MMSE_WANT)
-    ya, ha = np.asarray(y), np.asarray(h)
-    for name, a in (('y', ya), ('h', ha)):
-        if a.dtype.kind not in 'biufc':
-            raise ValueError('%s must hold numbers, got dtype %s' % (name, a.dtype))
-    if ya.ndim not in (1, 2):
-        raise ValueError('y must be [B, n_y] or 1-D, got %d dimensions' % ya.ndim)
-    one = ya.ndim == 1
-    ya = np.atleast_2d(ya)
-    B, n_y = ya.shape
-    if ha.ndim not in (1, 2) or (ha.ndim == 2 and ha.shape[0] != B):
-        raise ValueError('y is [%d, n_y]: h must be [L] or [%d, L], got shape %s' % (B, B, ha.shape))
-    L = ha.shape[-1]
-    n = n_y - (L - 1) if tail else n_y
+    ya, ha, one, B, n, L = _rows_and_taps(y, h, tail)
     nf, nb = int(nf), int(nb)
     M, m, delay = check_mmse_sizes(modem, L, n, nf, nb, None if delay is None else int(delay), want)
     if noise_var is None:
         raise ValueError('noise_var is required')
-    nv, nv_batched = check_noise_var(noise_var, B, True)
-    ya = np.ascontiguousarray(ya, dtype=np.complex128)
-    ha = np.ascontiguousarray(ha, dtype=np.complex128)
-    shapes = {'indices': ((B, n), np.int32), 'bits': ((B, n * m), np.uint8), 'estimate': ((B, n), np.complex128),
-              'llr': ((B, n * m), np.float64), 'noise': ((B,), np.float64), 'ff': ((B, nf), np.complex128),
-              'fb': ((B, nb), np.complex128), 'gain': ((B,), np.float64)}
-    res = {name: np.zeros(*shapes[name]) for name in MMSE_WANT if name in want}
+    nv, nv_batched = check_noise_var(noise_var, B, False)
+    res, p = outputs(want, mmse_shapes(B, n, m, nf, nb))
     if B:
-        p = lambda name: None if name not in res else _lib.ptr(res[name])
         _lib.check(_lib.load().cpx_mmse_equalize(modem._device_handle(), float(modem.Es), _lib.ptr(ya), _lib.ptr(ha), int(ha.ndim == 2), B,
                                                  n, L, int(bool(tail)), _lib.ptr(nv), int(nv_batched), nf, nb, delay, *map(p, MMSE_WANT)))
-    out = [res[name][0] if one else res[name] for name in MMSE_WANT if name in want]
-    return out[0] if len(out) == 1 else tuple(out)
+    return returned(res, one)

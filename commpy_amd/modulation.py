@@ -23,6 +23,7 @@ import operator
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd._results import outputs
 from commpy_amd.utilities import signal_power
 
 __all__ = ['PSKModem', 'QAMModem', 'Modem', 'mimo_ml', 'kbest', 'max_log_approx', 'bit_lvl_repr', 'mimo_ml_batch',
@@ -950,22 +951,24 @@ def ofdm_map_batch(data, pilots):
     return grid
 
 
+def ofdm_estimate_shapes(p, B, nr, third, dims):
+    return {'y': ((B, p.ndata, nr), np.complex128), 'h': ((B, p.ndata, nr, p.nt), np.complex128),
+            third: ((B,) + dims + (nr, p.nt), np.complex128)}
+
+
 def _ofdm_estimate(entry, third, dims, Y, p, want):
     """Both estimators: ``entry`` writes y_data, h_data and its own third output, ``third`` ``[B, *dims, nr, nt]``."""
-    names = ('y', 'h', third)
-    want = _lib.wanted(want, names)
+    want = _lib.wanted(want, ('y', 'h', third))
     y = _numeric(Y, 'Y')
     if y.ndim != 4 or y.shape[1] < 1 or y.shape[2:] != (p.nsym, p.nsc):
         raise ValueError('Y must be [B, nr, nsym, nsc] = [B, nr, %d, %d], got %s' % (p.nsym, p.nsc, y.shape))
     B, nr = y.shape[:2]
     if nr > OFDM_MAX_ANTENNAS:
         raise ValueError('nr = %d is above the engine limit of %d' % (nr, OFDM_MAX_ANTENNAS))
-    shapes = {'y': (B, p.ndata, nr), 'h': (B, p.ndata, nr, p.nt), third: (B,) + dims + (nr, p.nt)}
-    out = {k: np.zeros(shapes[k], dtype=np.complex128) for k in names if k in want}
+    out, q = outputs(want, ofdm_estimate_shapes(p, B, nr, third, dims))
     if B:
-        ptrs = [_lib.ptr(out[k]) if k in out else None for k in (third, 'y', 'h')]
-        _lib.check(getattr(_lib.load(), entry)(p.handle(), _lib.ptr(y), B, nr, *ptrs))
-    return tuple(out[k] for k in names if k in out)
+        _lib.check(getattr(_lib.load(), entry)(p.handle(), _lib.ptr(y), B, nr, q(third), q('y'), q('h')))
+    return tuple(out.values())
 
 
 def ofdm_estimate_batch(Y, pilots, want=('y', 'h')):

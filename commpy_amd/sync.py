@@ -15,6 +15,7 @@ no CPU fallback.
 import numpy as np
 
 from commpy_amd import _lib
+from commpy_amd._results import outputs
 
 __all__ = ['sync_metric_batch', 'sync_estimate_batch', 'sync_align_batch', 'schmidl_cox_preamble', 'frame_sync_batch',
            'SYNC_MAX_LAG', 'SYNC_MAX_ANTENNAS']
@@ -68,11 +69,10 @@ def sync_metric_batch(y, lag, window, want=('m',)):
     ya, _ = _rows(y)
     B, nr, n = ya.shape
     D, W, nd = _window_sizes(B, n, lag, window)
-    out = {k: np.zeros((B, nd), dtype=np.complex128 if k == 'p' else np.float64) for k in ('m', 'e', 'p') if k in want}
+    out, p = outputs(want, {'m': ((B, nd), np.float64), 'e': ((B, nd), np.float64), 'p': ((B, nd), np.complex128)})
     if B:
-        ptrs = [_lib.ptr(out[k]) if k in out else None for k in ('p', 'e', 'm')]
-        _lib.check(_lib.load().cpx_sync_metric(_lib.ptr(ya), B, nr, n, D, W, *ptrs))
-    return tuple(out[k] for k in ('m', 'e', 'p') if k in out)
+        _lib.check(_lib.load().cpx_sync_metric(_lib.ptr(ya), B, nr, n, D, W, p('p'), p('e'), p('m')))
+    return tuple(out.values())
 
 
 def _search_range(search, B, nd):

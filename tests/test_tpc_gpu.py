@@ -64,6 +64,11 @@ def test_decoder_equals_the_model(gpu, row, col, iters, p, B):
     d_word, d_ext = deviceops.tpc_decode_dev(code, DeviceBuf.from_array(llr), B, iters, p, llr_scale=scale, want=("extrinsic", "codeword"))
     _lib.check(_lib.load().cpx_stream_sync(None))
     assert same(d_word.to_array(llr.shape, np.uint8), ref["codeword"]) and same(d_ext.to_array(llr.shape, np.float64), ref["extrinsic"])
+    # one name alone: a bare buffer, equal to the host flavour's result
+    for name, dtype in (("codeword", np.uint8), ("extrinsic", np.float64)):
+        d_one = deviceops.tpc_decode_dev(code, DeviceBuf.from_array(llr), B, iters, p, llr_scale=scale, want=name)
+        _lib.check(_lib.load().cpx_stream_sync(None))
+        assert isinstance(d_one, DeviceBuf) and same(d_one.to_array(llr.shape, dtype), got[EVERYTHING.index(name)])
 
 
 def test_a_nan_costs_its_row_and_its_column_only(gpu):

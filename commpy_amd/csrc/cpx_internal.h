@@ -368,6 +368,8 @@ struct cpx_ldpc {
 };
 
 struct cpx_modem {
+    // M and nbits stay the first two members, in this order: tests/test_adaptive_host.py checks the limits of cpx_adaptive_equalize
+    // without a device on a stand-in that holds just these two ints (check_adaptive reads nothing else of the handle)
     int M, nbits;
     int device;
     double *d_const = nullptr;  // [M][2]

@@ -35,6 +35,7 @@
 //   LGM = 0: hard output only; LGM = m: the per-bit minima as well.  The arena block of sums is as large as y.  All grids are
 //   grid-stride loops under a cap, so a result depends on neither the batch nor the grid.
 #include "cpx_internal.h"
+#include "cpx_slice.h"
 #include "cpx_wave.h"
 
 using namespace cpx;
@@ -71,15 +72,6 @@ struct EqRun {
 
 // L[i][k], i > k, of the packed strict lower triangle: column k starts behind the nf-1 + .. + nf-k entries of the columns before it
 #define EQ_L(i, k) ((k) * (2 * nf - (k) - 1) / 2 + ((i) - (k) - 1))
-
-__device__ __forceinline__ bool not_finite(double v) { return !(__builtin_fabs(v) < __builtin_huge_val()); }
-
-// one row's samples: true on every lane of the wave if any is a NaN or an infinity
-__device__ __forceinline__ bool scan_row(const double *y, int64_t doubles, int lane) {
-    bool bad = false;
-    for (int64_t i = lane; i < doubles; i += 64) bad |= not_finite(y[i]);
-    return __ballot(bad) != 0ull;
-}
 
 __global__ __launch_bounds__(64) void eq_design_kernel(EqDesign a) {
     extern __shared__ double eq_lmat[];                        // Lr, Li: the strict lower triangle, column by column (EQ_L)
@@ -230,37 +222,6 @@ __global__ __launch_bounds__(256) void eq_scan_kernel(const double *y, int64_t B
         const bool bad = scan_row(y + row * 2 * n_y, 2 * n_y, lane);
         if (lane == 0) flag[row] = (bad || df) ? 1 : 0;
     }
-}
-
-// the slicer: first minimum over the points in ascending order and, with LGM > 0, the two minima of every label bit
-template <int LGM>
-__device__ __forceinline__ int slice(double xr, double xi, const double *cr, const double *ci, int M, double *m0, double *m1) {
-    constexpr int NB = LGM > 0 ? LGM : 1;
-#pragma unroll
-    for (int i = 0; i < NB; i++) {
-        m0[i] = __builtin_huge_val();
-        m1[i] = __builtin_huge_val();
-    }
-    double best = 0.0;
-    int sel = 0;
-#pragma unroll 4
-    for (int p = 0; p < M; p++) {
-        const double er = xr - cr[p], ei = xi - ci[p];
-        const double dd = er * er + ei * ei;
-        if (p == 0 || dd < best) {
-            best = dd;
-            sel = p;
-        }
-        if constexpr (LGM > 0) {
-#pragma unroll
-            for (int i = 0; i < LGM; i++) {
-                const bool one = (p >> (LGM - 1 - i)) & 1;
-                m1[i] = (one && dd < m1[i]) ? dd : m1[i];
-                m0[i] = (!one && dd < m0[i]) ? dd : m0[i];
-            }
-        }
-    }
-    return sel;
 }
 
 template <int LGM>

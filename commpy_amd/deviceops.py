@@ -20,7 +20,7 @@ __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu',
            'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
            'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev',
            'bch_encode_dev', 'bch_decode_dev', 'rs_encode_dev', 'rs_decode_dev', 'tailbiting_encode_dev', 'tailbiting_decode_dev',
-           'ldpc_layered_decode_dev', 'bch_chase_dev', 'tpc_decode_dev', 'mlse_equalize_dev', 'mmse_equalize_dev']
+           'ldpc_layered_decode_dev', 'bch_chase_dev', 'tpc_decode_dev', 'mlse_equalize_dev', 'mmse_equalize_dev', 'adaptive_equalize_dev']
 
 
 class DeviceBuf:
@@ -720,4 +720,39 @@ def mmse_equalize_dev(modem, d_y, d_h, h_batched, B, n, L, d_noise_var, nv_batch
         _lib.check(_lib.load().cpx_mmse_equalize_dev(modem._device_handle(), float(modem.Es), d_y.ptr, d_h.ptr, int(bool(h_batched)), B, n,
                                                      L, int(bool(tail)), d_noise_var.ptr, int(bool(nv_batched)), nf, nb, delay,
                                                      *map(p, MMSE_WANT), stream))
+    return returned(out)
+
+
+# ---- adaptive LMS / NLMS / RLS equalisation, device resident (csrc/adaptive.hip) -----------------------------------------------------
+
+def adaptive_equalize_dev(modem, d_y, B, n_y, d_training, tr_batched, nt, nf, nb=0, algorithm='lms', d_step=None, step_batched=False,
+                          d_forgetting=None, fg_batched=False, d_delta=None, dl_batched=False, eps=1e-6, delay=None, sps=1, n=None,
+                          d_ff0=None, ff0_batched=False, d_fb0=None, fb0_batched=False, want=('indices',), stream=None):
+    """``cpx_adaptive_equalize_dev``: ``d_y [B][n_y][2]`` float64 (re, im), ``sps`` samples per symbol; ``d_training`` ``[nt]`` int32
+    labels or, with ``tr_batched``, ``[B][nt]`` (None with ``nt = 0``); ``d_step`` (for 'lms', 'nlms'), ``d_forgetting`` and ``d_delta``
+    (both required for 'rls'): one float64 each or, with their ``_batched`` flag, ``[B]``; ``d_ff0 [nf][2]`` / ``d_fb0 [nb][2]`` or, batched,
+    ``[B][..][2]``, None = zeros -> new ``DeviceBuf``s queued on ``stream`` (None: the library's), the results of
+    ``equalizers.adaptive_equalize_batch`` that ``want`` names, in its order: 'indices' ``[B][n]`` int32, 'bits' ``[B][n m]`` uint8,
+    'estimate' and 'error' ``[B][n][2]``, 'ff' ``[B][nf][2]``, 'fb' ``[B][nb][2]`` float64; a single result for one name.  The same rule
+    and the same limits, checked on the host before any device call; the values of step, forgetting and delta are on the device, so
+    one outside its range rejects its row."""
+    from commpy_amd.equalizers import ADAPT_WANT, adaptive_shapes, check_adaptive_sizes
+    want = _lib.wanted(want, ADAPT_WANT)
+    B, n_y, nt, nf, nb = whole(B, 'B', 0), whole(n_y, 'n_y', 0), whole(nt, 'nt', 0), whole(nf, 'nf', 1), whole(nb, 'nb', 0)
+    sps = int(sps)
+    n = n_y // max(sps, 1) if n is None else int(n)
+    M, m, delay, code = check_adaptive_sizes(modem, n_y, n, nt, nf, nb, None if delay is None else int(delay), sps, algorithm,
+                                             d_step is not None, float(eps), want)
+    if algorithm == 'rls' and (d_forgetting is None or d_delta is None):
+        raise ValueError("forgetting and delta are required with 'rls'")
+    if nt and d_training is None:
+        raise ValueError('training is required for nt = %d' % nt)
+    opt = lambda buf: None if buf is None else buf.ptr
+    out, p = device_outputs(want, adaptive_shapes(B, n, m, nf, nb))
+    if B:
+        _lib.check(_lib.load().cpx_adaptive_equalize_dev(modem._device_handle(), d_y.ptr, B, n_y, n, sps, opt(d_training),
+                                                         int(bool(tr_batched)), nt, nf, nb, delay, code, opt(d_step),
+                                                         int(bool(step_batched)), opt(d_forgetting), int(bool(fg_batched)), opt(d_delta),
+                                                         int(bool(dl_batched)), float(eps), opt(d_ff0), int(bool(ff0_batched)), opt(d_fb0),
+                                                         int(bool(fb0_batched)), *map(p, ADAPT_WANT), stream))
     return returned(out)

@@ -15,18 +15,25 @@ Beyond those limits -- 64-QAM, or more than a handful of taps -- ``mmse_equalize
 ``nb >= 1``, ``nb`` feedback taps that cancel the post-cursor of past decisions (decision feedback).  Cost grows with
 ``nf^3 + n nf``, not with ``M^L``: up to 64 taps each way and any constellation up to 256 points.  Bit for bit equal to
 tests/equalize_model.py.
+
+Where the channel is not known, ``adaptive_equalize_batch`` (csrc/adaptive.hip) learns the taps of a linear or decision-feedback
+equaliser from a training prefix and then tracks on its own decisions, with the LMS, the normalised LMS or the RLS update; its
+feed-forward taps are one sample apart, so with ``sps = 2`` it is T/2-spaced.  Bit for bit equal to tests/adaptive_model.py.
 """
 import numpy as np
 
 from commpy_amd import _lib
 from commpy_amd._results import outputs, returned
 
-__all__ = ['mlse_equalize_batch', 'mmse_equalize_batch']
+__all__ = ['mlse_equalize_batch', 'mmse_equalize_batch', 'adaptive_equalize_batch']
 
 MLSE_MAX_M, MLSE_MAX_STATES, MLSE_MAX_N = 16, 256, 4096      # csrc/mlse.hip
 WANT = ('indices', 'bits', 'metric', 'llr')
 MMSE_MAX_TAPS, MMSE_MAX_M, MMSE_MAX_N = 64, 256, 1 << 30            # csrc/equalize.hip
 MMSE_WANT = ('indices', 'bits', 'estimate', 'llr', 'noise', 'ff', 'fb', 'gain')
+ADAPT_MAX_TAPS, ADAPT_RLS_MAX_TAPS, ADAPT_MAX_M, ADAPT_MAX_N, ADAPT_MAX_SPS = 64, 32, 256, 1 << 30, 8     # csrc/adaptive.hip
+ADAPT_WANT = ('indices', 'bits', 'estimate', 'error', 'ff', 'fb')
+ADAPT_ALGORITHMS = ('lms', 'nlms', 'rls')                   # the C-ABI's algorithm is the position
 
 
 def check_want(want):
@@ -77,19 +84,31 @@ def check_sizes(modem, L, n):
     return M, m
 
 
+def check_per_row(value, B, name, upper=None):
+    """A positive parameter given once or per row, as ``(float64 array [1] or [B], batched)``; ValueError for a value <= 0 (or above
+    ``upper``) and for a shape other than scalar or ``[B]``.  A NaN, and an infinity within the limits, pass: they reject their rows."""
+    v = np.asarray(value, dtype=np.float64)
+    if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != B):
+        raise ValueError('%s must be a scalar or [B] = [%d], got shape %s' % (name, B, v.shape))
+    if (v <= 0).any():
+        raise ValueError('%s must be positive' % name)
+    if upper is not None and (v > upper).any():
+        raise ValueError('%s must be at most %g' % (name, upper))
+    return np.ascontiguousarray(v.reshape(-1)), v.ndim == 1
+
+
 def check_noise_var(noise_var, B, needed):
-    """``noise_var`` as ``(float64 array [1] or [B], batched)`` or ``(None, False)``; ValueError for a value <= 0, for a shape other than
-    scalar or ``[B]``, and for None where it is needed.  NaN and infinities pass: they reject their rows."""
+    """``noise_var`` through ``check_per_row``, or ``(None, False)``; ValueError for None where it is needed."""
     if noise_var is None:
         if needed:
             raise ValueError("noise_var is required when 'llr' is wanted or a_priori is given")
         return None, False
-    nv = np.asarray(noise_var, dtype=np.float64)
-    if nv.ndim > 1 or (nv.ndim == 1 and nv.shape[0] != B):
-        raise ValueError('noise_var must be a scalar or [B] = [%d], got shape %s' % (B, nv.shape))
-    if (nv <= 0).any():
-        raise ValueError('noise_var must be positive')
-    return np.ascontiguousarray(nv.reshape(-1)), nv.ndim == 1
+    return check_per_row(noise_var, B, 'noise_var')
+
+
+def adaptive_shapes(B, n, m, nf, nb):
+    return {'indices': ((B, n), np.int32), 'bits': ((B, n * m), np.uint8), 'estimate': ((B, n), np.complex128),
+            'error': ((B, n), np.complex128), 'ff': ((B, nf), np.complex128), 'fb': ((B, nb), np.complex128)}
 
 
 def mlse_equalize_batch(y, h, modem, noise_var=None, a_priori=None, tail=True, want=('indices',)):
@@ -215,4 +234,130 @@ def mmse_equalize_batch(y, h, modem, noise_var, nf, nb=0, delay=None, tail=True,
     if B:
         _lib.check(_lib.load().cpx_mmse_equalize(modem._device_handle(), float(modem.Es), _lib.ptr(ya), _lib.ptr(ha), int(ha.ndim == 2), B,
                                                  n, L, int(bool(tail)), _lib.ptr(nv), int(nv_batched), nf, nb, delay, *map(p, MMSE_WANT)))
+    return returned(res, one)
+
+
+def check_adaptive_sizes(modem, n_y, n, nt, nf, nb, delay, sps, algorithm, step_given, eps, want):
+    """``(M, m, delay, algorithm code)`` of an adaptive equaliser within the kernels' limits, the default delay filled in (ValueError
+    naming the limit otherwise; host only).  ``m`` is 0 for a constellation that is no power of two."""
+    M = int(modem.m)
+    if algorithm not in ADAPT_ALGORITHMS:
+        raise ValueError("algorithm = %r, the limit is one of 'lms', 'nlms', 'rls'" % (algorithm,))
+    if nf < 1 or nf > ADAPT_MAX_TAPS:
+        raise ValueError('nf = %d feed-forward taps, the limit is 1 <= nf <= %d' % (nf, ADAPT_MAX_TAPS))
+    if nb < 0 or nb > ADAPT_MAX_TAPS:
+        raise ValueError('nb = %d feedback taps, the limit is 0 <= nb <= %d' % (nb, ADAPT_MAX_TAPS))
+    if algorithm == 'rls' and nf + nb > ADAPT_RLS_MAX_TAPS:
+        raise ValueError("nf + nb = %d with 'rls', the limit is nf + nb <= %d" % (nf + nb, ADAPT_RLS_MAX_TAPS))
+    if delay is None:
+        delay = (nf - 1) // 2 if nb == 0 else nf - 1
+    if delay < 0 or delay > 2 ** 31 - 1:
+        raise ValueError('delay = %d, the limit is 0 <= delay' % delay)
+    if sps < 1 or sps > ADAPT_MAX_SPS:
+        raise ValueError('sps = %d samples per symbol, the limit is 1 <= sps <= %d' % (sps, ADAPT_MAX_SPS))
+    if M < 2 or M > ADAPT_MAX_M:
+        raise ValueError('the constellation has %d points, the limit is 2 <= M <= %d' % (M, ADAPT_MAX_M))
+    pow2 = M & (M - 1) == 0
+    if not pow2 and 'bits' in want:
+        raise ValueError("the constellation has %d points, the limit for 'bits' is M a power of two" % M)
+    if n < 1 or n > ADAPT_MAX_N:
+        raise ValueError('n = %d symbols per row, the limit is 1 <= n <= 2^30' % n)
+    if n_y > ADAPT_MAX_N * ADAPT_MAX_SPS:
+        raise ValueError('n_y = %d samples per row, the limit is n_y <= 2^33' % n_y)
+    if nt < 0 or nt > n:
+        raise ValueError('nt = %d training symbols, the limit is 0 <= nt <= n = %d' % (nt, n))
+    if algorithm == 'rls' and step_given:
+        raise ValueError("step is given with 'rls', which takes forgetting and delta")
+    if algorithm != 'rls' and not step_given:
+        raise ValueError("step is required with 'lms' and 'nlms'")
+    if eps < 0:
+        raise ValueError('eps = %g, the limit is eps >= 0' % eps)
+    return M, (M.bit_length() - 1 if pow2 else 0), delay, ADAPT_ALGORITHMS.index(algorithm)
+
+
+def _initial_taps(taps, B, count, name):
+    """``(complex128 array or None, batched)`` of initial taps ``[count]`` or ``[B, count]``."""
+    if taps is None:
+        return None, False
+    t = np.asarray(taps)
+    if t.dtype.kind not in 'biufc' or t.ndim not in (1, 2) or t.shape[-1] != count or (t.ndim == 2 and t.shape[0] != B):
+        raise ValueError('%s must be numbers of shape [%d] or [%d, %d], got dtype %s, shape %s' % (name, count, B, count, t.dtype, t.shape))
+    return np.ascontiguousarray(t, dtype=np.complex128), t.ndim == 2
+
+
+def adaptive_equalize_batch(y, modem, training, nf, nb=0, algorithm='lms', step=None, forgetting=1.0, delta=0.01, eps=1e-6,
+                            delay=None, sps=1, n=None, ff0=None, fb0=None, want=('indices',)):
+    """Equalise rows ``y [B, n_y]`` complex (or 1-D for one row) of an unknown channel with an adaptive equaliser: ``nf`` feed-forward
+    taps one *sample* apart (``y`` holds ``sps`` samples per symbol, so with ``sps = 2`` the equaliser is T/2-spaced) and ``nb``
+    feedback taps one symbol apart (0: the linear equaliser).  ``training``: integer labels ``[nt]`` (shared) or ``[B, nt]``, the
+    known first ``nt`` symbols (``0 <= nt <= n``); after them the equaliser is decision-directed.  ``modem`` is any ``Modem`` (labels
+    and bits as ``Modem.modulate`` defines them, MSB first; a ``Modem`` and its device handle hold a power-of-two constellation only,
+    so the checks for other sizes -- no ``'bits'`` for them -- guard a case that no modem can bring today).  ``algorithm``: ``'lms'`` or ``'nlms'`` with ``step`` (mu, required;
+    ``'nlms'`` also takes ``eps >= 0``), or ``'rls'`` with ``forgetting`` (lambda in (0, 1]) and ``delta > 0`` (``step`` is refused);
+    ``step``, ``forgetting`` and ``delta`` are each a scalar or ``[B]``, so one call can sweep a learning curve.  ``delay`` is in
+    samples; None means ``(nf - 1) // 2`` for ``nb = 0``, else ``nf - 1``.  ``n``: symbols per row, None means ``n_y // sps``.
+    ``ff0 [nf]`` or ``[B, nf]`` and ``fb0 [nb]`` or ``[B, nb]``: the initial taps, None = zeros; with the ``'ff'`` and ``'fb'`` results
+    of one call they continue the equaliser over the next block.  The next call knows no sample from before its first, so a linear
+    LMS / NLMS equaliser equals one call over both blocks bit for bit only with ``delay >= nf - 1``, where no step reaches back past
+    its block's first sample (with a smaller delay, the default for ``nb = 0`` included, the first steps read 0.0 there); with
+    feedback the past references start empty again as well.  RLS restarts its ``P`` at ``I / delta`` in every call.
+
+    ``want`` names the results; they are returned in the order listed here (a single result for one name): ``'indices'`` ``[B, n]``
+    int32, the decisions ``a^_t`` (at every ``t``, training included); ``'bits'`` ``[B, n*m]`` uint8; ``'estimate'`` ``[B, n]``
+    complex128, the ``z_t``; ``'error'`` ``[B, n]`` complex128, the a-priori ``e_t`` -- the learning curve; ``mean |e|^2`` over a
+    stretch is the ``noise_var`` to hand to ``Modem.demodulate(estimate, 'soft', ...)``; ``'ff'`` ``[B, nf]`` and ``'fb'``
+    ``[B, nb]`` complex128, the taps after the last symbol, in the convention of ``mmse_equalize_batch``.
+
+    The rule (float64; real and imaginary parts are separate doubles; every product is rounded before it is added; every sum starts
+    at 0.0 and runs in ascending index order; ``a b = (ar br - ai bi, ar bi + ai br)``, ``a conj(b) = (ar br + ai bi, ai br - ar bi)``),
+    with ``d = delay``, ``N = nf + nb``, ``c`` the constellation, ``theta = (ff, fb)``, for ``t = 0 .. n-1``.  Regressor:
+    ``x[i] = y[t sps + d - i]`` for ``i < nf``, a sample outside the row read as 0.0 and multiplied like any other;
+    ``x[nf + j - 1] = -r_{t-j}`` (each part negated) for ``j = 1 .. nb``, and 0.0 where ``t - j < 0``, multiplied like any other.
+    Output: ``z_t = (sum_{k<nf} theta_k x_k) + (sum_{nf<=k<N} theta_k x_k)``, no conjugate, the two sums formed separately.
+    Decision: ``a^_t`` is the first minimum over ``a`` ascending of ``e = z_t - c[a]``, ``er er + ei ei``, a later point winning only
+    if strictly smaller.  Reference: ``r_t = c[training[t]]`` for ``t < nt``, else ``c[a^_t]``; ``e_t = r_t - z_t``.  LMS:
+    ``w = (mu er, mu ei)``; ``theta_k <- theta_k + w conj(x_k)``.  NLMS: the same with ``mu_t = mu / (eps + sum_{k<N} (xr xr + xi xi))``
+    in place of ``mu``.  RLS: ``P = I / delta`` (``1.0 / delta`` on the diagonal); ``g_i = sum_{j<N} P[i][j] conj(x_j)``;
+    ``den = lambda + sum_{k<N} (xr gr - xi gi)``; ``kappa_i = (gr_i / den, gi_i / den)``; ``theta_i <- theta_i + kappa_i e_t``;
+    ``P[i][j] <- ((Pr - qr) / lambda, (Pi - qi) / lambda)`` with ``q = kappa_i conj(g_j)``.
+
+    A row whose ``y``, ``ff0``, ``fb0``, ``step``, ``forgetting``, ``delta`` or ``eps`` holds a NaN or +-inf, one of whose training
+    labels is negative or ``>= M``, one of whose ``z_t`` is not finite (a diverged LMS), or one of whose ``den`` is not positive and
+    finite is rejected: zero indices and bits, NaN everywhere else; no other row is affected.
+
+    Limits, each refused with a ``ValueError`` before any device call: ``algorithm`` one of the three; ``1 <= nf <= 64``;
+    ``0 <= nb <= 64``; ``nf + nb <= 32`` with ``'rls'`` (``P`` is then 16 KiB per row); ``0 <= delay``; ``1 <= sps <= 8``;
+    ``2 <= M <= 256``; ``M`` a power of two when ``'bits'`` is wanted; ``1 <= n <= 2^30``; ``0 <= nt <= n``; ``step > 0``, required
+    with ``'lms'`` and ``'nlms'`` and refused with ``'rls'``; ``0 < forgetting <= 1``; ``delta > 0``; ``eps >= 0``."""
+    want = _lib.wanted(want, ADAPT_WANT)
+    ya = np.asarray(y)
+    if ya.dtype.kind not in 'biufc':
+        raise ValueError('y must hold numbers, got dtype %s' % ya.dtype)
+    if ya.ndim not in (1, 2):
+        raise ValueError('y must be [B, n_y] or 1-D, got %d dimensions' % ya.ndim)
+    one = ya.ndim == 1
+    ya = np.ascontiguousarray(np.atleast_2d(ya), dtype=np.complex128)
+    B, n_y = ya.shape
+    tr = np.asarray(training)
+    if tr.size and tr.dtype.kind not in 'biu':
+        raise ValueError('training must hold integer labels, got dtype %s' % tr.dtype)
+    if tr.ndim not in (1, 2) or (tr.ndim == 2 and tr.shape[0] != B):
+        raise ValueError('y is [%d, n_y]: training must be [nt] or [%d, nt], got shape %s' % (B, B, tr.shape))
+    nf, nb, sps, nt = int(nf), int(nb), int(sps), tr.shape[-1]
+    n = n_y // max(sps, 1) if n is None else int(n)
+    M, m, delay, code = check_adaptive_sizes(modem, n_y, n, nt, nf, nb, None if delay is None else int(delay), sps, algorithm,
+                                             step is not None, float(eps), want)
+    tr = np.ascontiguousarray(np.clip(tr, -1, M), dtype=np.int32)          # out of range stays out of range: it rejects the row
+    rls = algorithm == 'rls'
+    st, st_b = (None, False) if rls else check_per_row(step, B, 'step')
+    fg, fg_b = check_per_row(forgetting, B, 'forgetting', 1.0) if rls else (None, False)
+    dl, dl_b = check_per_row(delta, B, 'delta') if rls else (None, False)
+    f0, f0_b = _initial_taps(ff0, B, nf, 'ff0')
+    b0, b0_b = _initial_taps(fb0, B, nb, 'fb0')
+    opt = lambda a: None if a is None else _lib.ptr(a)
+    res, p = outputs(want, adaptive_shapes(B, n, m, nf, nb))
+    if B:
+        _lib.check(_lib.load().cpx_adaptive_equalize(modem._device_handle(), _lib.ptr(ya), B, n_y, n, sps, _lib.ptr(tr), int(tr.ndim == 2),
+                                                     nt, nf, nb, delay, code, opt(st), int(st_b), opt(fg), int(fg_b), opt(dl), int(dl_b),
+                                                     float(eps), opt(f0), int(f0_b), opt(b0), int(b0_b), *map(p, ADAPT_WANT)))
     return returned(res, one)

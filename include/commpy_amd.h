@@ -1029,6 +1029,52 @@ int cpx_mmse_equalize_dev(const cpx_modem *md, double es, const double *d_y, con
                           uint8_t *d_bits, double *d_estimate, double *d_llr, double *d_noise, double *d_ff, double *d_fb,
                           double *d_gain, void *stream);
 
+/* ---- adaptive linear and decision-feedback equalisation: LMS, normalised LMS, RLS (csrc/adaptive.hip) ----------
+ * The equaliser learns its taps from the known first nt symbols of a row (training labels) and then tracks on its own decisions.
+ * y holds sps samples per symbol; the nf feed-forward taps are one sample apart (T/sps spacing), the nb feedback taps one symbol apart
+ * (0: the linear equaliser); d = delay in samples, N = nf + nb, c the points of a cpx_modem (label = position), theta = (ff, fb).
+ * algorithm: 0 = LMS, 1 = normalised LMS (both take step = mu, nlms also eps), 2 = RLS (takes forgetting = lambda and delta).
+ * The rule (float64, real and imaginary parts separate doubles, every product rounded before it is added, every sum from 0.0 in
+ * ascending index order; a b = (ar br - ai bi, ar bi + ai br), a conj(b) = (ar br + ai bi, ai br - ar bi)), for t = 0 .. n-1:
+ *   Regressor.  x[i] = y[t sps + d - i] for i < nf, a sample outside the row read as 0.0 and multiplied like any other;
+ *               x[nf + j - 1] = -r_{t-j} (each part negated) for j = 1 .. nb, and 0.0 where t - j < 0, multiplied like any other.
+ *   Output.     z_t = (sum_{k<nf} theta_k x_k) + (sum_{nf<=k<N} theta_k x_k), no conjugate, the two sums formed separately.
+ *   Decision.   a^_t = the first minimum over a ascending of e = z_t - c[a], er er + ei ei, a later point winning only if strictly
+ *               smaller.  It is indices[t] at every t, training included.
+ *   Reference.  r_t = c[training[t]] for t < nt, else c[a^_t]; e_t = r_t - z_t (the a-priori error).
+ *   LMS.        w = (mu er, mu ei); theta_k <- theta_k + w conj(x_k).
+ *   NLMS.       The same with mu_t = mu / (eps + sum_{k<N} (xr xr + xi xi)) in place of mu.
+ *   RLS.        P = I / delta = (1.0 / delta) on the diagonal before the first step of every call.  g_i = sum_{j<N} P[i][j] conj(x_j);
+ *               den = lambda + sum_{k<N} (xr gr - xi gi); kappa_i = (gr_i / den, gi_i / den); theta_i <- theta_i + kappa_i e_t;
+ *               P[i][j] <- ((Pr - qr) / lambda, (Pi - qi) / lambda) with q = kappa_i conj(g_j).
+ *   Rejection.  A row whose y (all n_y samples), ff0, fb0, step, forgetting, delta or eps holds a NaN or +-inf or lies outside its
+ *               range, one of whose training labels is negative or >= M, one of whose z_t is not finite (a diverged LMS), or one of
+ *               whose den is not positive and finite is rejected on its own: zero indices and bits, NaN everything else.
+ * Equal to tests/adaptive_model.py bit for bit, whatever the batch size, the row's place, the stream and the outputs requested.
+ * Limits (CPX_EINVAL, naming the limit, checked before a device is looked for): algorithm 0 .. 2; 1 <= nf <= 64; 0 <= nb <= 64;
+ * nf + nb <= 32 with RLS; 0 <= delay; 1 <= sps <= 8; 2 <= M <= 256; M a power of two when bits is asked for; 1 <= n <= 2^30;
+ * 0 <= n_y <= 2^33; 0 <= nt <= n; step given for LMS and NLMS and NULL for RLS; forgetting and delta given for RLS (ignored
+ * otherwise); eps >= 0; and, where the values are host values, step > 0, 0 < forgetting <= 1, delta > 0 (a NaN passes and rejects
+ * its row; the _dev form leaves these three to the kernels, which reject the rows).
+ *   cpx_adaptive_equalize  y [B][n_y][2] float64 (re, im); training [nt] int32 or, with tr_batched, [B][nt]; step, forgetting, delta
+ *             one value each or, with their _batched flag, [B]; ff0 [nf][2] or [B][nf][2], fb0 [nb][2] or [B][nb][2], the initial
+ *             taps, NULL = zeros.  Outputs, each may be NULL (not all): indices [B][n] int32, bits [B][n m] uint8 (MSB first),
+ *             estimate [B][n][2] (z), error [B][n][2] (e), ff [B][nf][2], fb [B][nb][2], the taps after the last symbol.
+ * The _dev form takes device pointers and a stream and is asynchronous; the other takes host pointers and returns synchronised.
+ * B = 0 returns CPX_OK without a launch.  cpx_last_kernel names the kernel (ad_lms_kernel for LMS and NLMS, ad_rls_kernel), nf, nb,
+ * the rows per wave and the grid cap (lms_cap / rls_cap, in workgroups).  No workspace is taken. */
+int cpx_adaptive_equalize(const cpx_modem *md, const double *y, int64_t B, int64_t n_y, int64_t n, int sps, const int32_t *training,
+                          int tr_batched, int64_t nt, int nf, int nb, int delay, int algorithm, const double *step, int step_batched,
+                          const double *forgetting, int fg_batched, const double *delta, int dl_batched, double eps, const double *ff0,
+                          int ff0_batched, const double *fb0, int fb0_batched, int32_t *indices, uint8_t *bits, double *estimate,
+                          double *error, double *ff, double *fb);
+int cpx_adaptive_equalize_dev(const cpx_modem *md, const double *d_y, int64_t B, int64_t n_y, int64_t n, int sps,
+                              const int32_t *d_training, int tr_batched, int64_t nt, int nf, int nb, int delay, int algorithm,
+                              const double *d_step, int step_batched, const double *d_forgetting, int fg_batched, const double *d_delta,
+                              int dl_batched, double eps, const double *d_ff0, int ff0_batched, const double *d_fb0, int fb0_batched,
+                              int32_t *d_indices, uint8_t *d_bits, double *d_estimate, double *d_error, double *d_ff, double *d_fb,
+                              void *stream);
+
 /* ---- multi-GPU: RCCL collectives of the sharded decode ------------------------------------
  * The path shards by codeword (contiguous blocks of B/G codewords per GPU, tables replicated) and has no exchange
  * step inside a decoder.  Two collectives exist around it:

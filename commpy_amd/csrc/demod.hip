@@ -643,8 +643,13 @@ __global__ __launch_bounds__(DEMOD_BLOCK, (NH <= 3 ? 4 : 3)) void link_front_ker
 // Not the parity mode: float32 arithmetic with the hardware exp2 / log2, in log-sum-exp form -- every exponent is taken relative to
 // the largest of its sum, so nothing underflows where float64 would not either and the result is FINITE wherever the exponents are
 // (the reference's -inf / NaN pattern of modulation.py:134-137 at extreme Es/N0 is deliberately not reproduced; it yields the LLR the
-// formula defines).  Contract (tests/test_fp32_fast_gpu.py): |LLR_fast - LLR_fp64| <= 2e-5 + 4e-6 |LLR_fp64| (measured: a quarter of
-// that at worst, PSK-2..16 / QAM-4..256, Es/N0 0..28 dB), identical hard decisions sign(LLR) wherever |LLR_fp64| > 1e-3.  Inputs and outputs stay float64 arrays (the API does not
+// formula defines).  Contract: every exponent t_a = |y - c_a|^2 / N0 is formed in float32, so the error grows with the LARGEST of them,
+// which is quadratic in |y| while the LLR is linear: |LLR_fast - LLR| <= 3.4e-5 + 35 * 2^-24 * max_a t_a (nats) against the exact
+// log-sum-exp, at every finite input (derived in tests/fp32_model.py, the constant measured; tests/test_fp32_edges_gpu.py).  For samples
+// within a few noise standard deviations of a constellation point (what a receiver sees: PSK-2..16 / QAM-4..256, Es/N0 0..28 dB) that
+// is within |LLR_fast - LLR_fp64| <= 2e-5 + 4e-6 |LLR_fp64| (tests/test_fp32_fast_gpu.py; measured: a quarter of that at worst), with
+// identical hard decisions sign(LLR) wherever |LLR_fp64| > 1e-3; far from the constellation the second form does NOT hold (thirty times
+// the constellation's size: measured 3 times the allowance for 256-QAM, 55 times for PSK-16).  Inputs and outputs stay float64 arrays (the API does not
 // change); the kernel is then bound by its 16 + 8 nb bytes per symbol, so the LLRs of a wave go through LDS and leave as full 512-byte
 // rows (a lane's own nb doubles are 8 nb bytes apart from its neighbour's).
 constexpr float LN2_F = 0.6931471805599453f;

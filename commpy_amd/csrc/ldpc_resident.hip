@@ -617,8 +617,12 @@ __device__ __forceinline__ void check_spa_f32(const ResParams &p, int c, int *fl
             if (j < deg) {
                 sx ^= __float_as_int(q[u]);
                 const float m = q[u] - ldsf(rb + 4 * j);
-                const float e = __expf(-fabsf(m));
-                const float t = __builtin_copysignf(__fdividef(1.0f - e, 1.0f + e), m);     // tanh(m / 2)
+                // tanh(m / 2).  e rounds to 1 for |m| < 3e-8 and 1 - e has lost half its bits at 2^-12, where m / 2 is tanh(m / 2) to
+                // float32 precision (m^2 / 12 < 2^-27): below that t = m / 2, never less than the smallest normal number, so that
+                // only a message that IS zero gives t = 0 (and, like the float64 row, inf * 0 = NaN on its own edge)
+                const float av = fabsf(m), e = __expf(-av);
+                const float ta = av < 0x1p-12f ? (av > 0.0f ? fmaxf(0.5f * av, 0x1p-126f) : 0.0f) : __fdividef(1.0f - e, 1.0f + e);
+                const float t = __builtin_copysignf(ta, m);
                 prod *= t;
                 stsf(rb + 4 * j, t);
             }

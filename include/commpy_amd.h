@@ -63,8 +63,11 @@ int cpx_last_kernel(char *name, int cap);
  * parity claims are made in.  "fp32-fast": kernels that have a float32 variant use it -- the fused codeword-per-lane Viterbi
  * kernel (float32 path metrics, correlation branch metric; measured mismatch rate in DESIGN.md 4.1) and the LDS-resident LDPC
  * kernels (float32 messages, hardware exp2 / log2 / reciprocal for sum-product; same decoded words and frame error rate on the
- * measured workloads) and soft demodulation (float32 log-sum-exp, |dLLR| <= 2e-5 + 4e-6 |LLR|, finite where the
- * reference's sums underflow) -- NOT bit-exact and NOT under the 1e-5 LLR criterion; every other kernel is unaffected.
+ * measured workloads) and soft demodulation (float32 log-sum-exp, |dLLR| <= 3.4e-5 + 35 * 2^-24 * max_a |y - c_a|^2 /
+ * noise_var at every finite input -- within 2e-5 + 4e-6 |LLR| for samples a few noise standard deviations from a constellation
+ * point, NOT far from the constellation --, finite where the reference's sums underflow) -- NOT bit-exact and NOT
+ * under the 1e-5 LLR criterion; every other kernel is unaffected.  Viterbi and min-sum are exact against a float32 model of the same
+ * operations, sum-product and the demodulator within bounds (tests/fp32_model.py).
  * cpx_last_kernel shows "f32" in the name when a variant ran. */
 int cpx_set_precision(const char *mode);
 int cpx_get_precision(void);   /* 0 fp64-parity, 1 fp32-fast */

@@ -5,7 +5,9 @@ The modules of veeresht/CommPy 0.8.0, re-implemented as hand-written HIP kernels
 hard/soft demodulation, MIMO detection, the fading channels (flat, static multipath and Doppler-fading multipath with time-varying
 taps) and links, OFDM with timing / frequency-offset synchronisation,
 pulse shaping / matched filtering / frequency offset of sampled waveforms, and equalisation of a multipath channel (MLSE / max-log MAP
-on the trellis, MMSE linear and decision-feedback, and adaptive LMS / NLMS / RLS equalisers trained on a known prefix) -- with the host-side descriptions either side of them (Trellis, interleavers, LDPC design files,
+on the trellis, MMSE linear and decision-feedback, and adaptive LMS / NLMS / RLS equalisers trained on a known prefix), and the
+single-carrier synchroniser in front of them (symbol-timing recovery with a Gardner or Mueller-Mueller detector and a decision-directed
+carrier PLL, one feedback loop per row) -- with the host-side descriptions either side of them (Trellis, interleavers, LDPC design files,
 constellations, encoders, filter taps, PN and Zadoff-Chu sequences).  No PyTorch, no Triton, no CPU fallback: the device entry
 points raise if the HIP library or the GPU is missing.
 
@@ -18,6 +20,7 @@ points raise if the HIP library or the GPU is missing.
     from commpy_amd.sync import schmidl_cox_preamble, sync_estimate_batch, frame_sync_batch
     from commpy_amd.channels import multipath_batch, fading_multipath_batch, fading_gains_batch, tap_frequency_response
     from commpy_amd.equalizers import mlse_equalize_batch, mmse_equalize_batch, adaptive_equalize_batch
+    from commpy_amd.recovery import timing_recover_batch, loop_gains
 """
 __version__ = "0.3.0"
 
@@ -57,4 +60,4 @@ class precision:
         return False
 
 
-__all__ = ["channelcoding", "modulation", "utilities", "parallel", "filters", "sequences", "impairments", "sync", "equalizers", "set_precision", "precision"]
+__all__ = ["channelcoding", "modulation", "utilities", "parallel", "filters", "sequences", "impairments", "sync", "equalizers", "recovery", "set_precision", "precision"]

@@ -247,6 +247,12 @@ SYMBOLS = {
     "cpx_adaptive_equalize_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int,
                                           c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_void_p, c_int, c_void_p, c_int,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpx_timing_recover": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                   c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpx_timing_recover_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                       c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cpx_comm_unique_id": (c_int, [c_void_p]),
     "cpx_comm_init_rank": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
     "cpx_comm_init_all": (c_int, [POINTER(c_int), c_int, POINTER(c_void_p)]),

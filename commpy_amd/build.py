@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "libcommpy_amd.so")
 SOURCES = ["runtime.hip", "viterbi.hip", "viterbi_cw.hip", "viterbi_generic.hip", "bcjr.hip", "bcjr_exact.hip", "ldpc.hip", "ldpc_resident.hip", "demod.hip", "linksim.hip", "encoders.hip",
-           "comm.hip", "mimo.hip", "mimo_linear.hip", "mimo_idd.hip", "mimo_channel.hip", "ofdm.hip", "fir.hip", "ofdm_chan.hip", "sync.hip", "fading.hip", "polar.hip", "bch.hip", "bch_chase.hip", "rs.hip", "tbcc.hip", "ldpc_layered.hip", "mlse.hip", "equalize.hip", "adaptive.hip"]
+           "comm.hip", "mimo.hip", "mimo_linear.hip", "mimo_idd.hip", "mimo_channel.hip", "ofdm.hip", "fir.hip", "ofdm_chan.hip", "sync.hip", "fading.hip", "polar.hip", "bch.hip", "bch_chase.hip", "rs.hip", "tbcc.hip", "ldpc_layered.hip", "mlse.hip", "equalize.hip", "adaptive.hip", "recovery.hip"]
 
 
 def _hipcc():
@@ -26,7 +26,7 @@ def _hipcc():
     return "hipcc"
 
 
-HEADERS = [os.path.join(CSRC, h) for h in ("cpx_internal.h", "cpx_math.h", "demod_dev.h", "cpx_rng.h", "ldpc_dev.h", "viterbi_cw_asm.h", "cpx_rotate.h", "cpx_wave.h", "cpx_gf.h", "bch_dev.h", "cpx_slice.h")] + [os.path.join(INCLUDE, "commpy_amd.h")]
+HEADERS = [os.path.join(CSRC, h) for h in ("cpx_internal.h", "cpx_math.h", "demod_dev.h", "cpx_rng.h", "ldpc_dev.h", "viterbi_cw_asm.h", "cpx_rotate.h", "cpx_wave.h", "cpx_gf.h", "bch_dev.h", "cpx_slice.h", "cpx_phasor.h")] + [os.path.join(INCLUDE, "commpy_amd.h")]
 OBJDIR = os.path.join(CSRC, "build")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden", "-Wall", "-Wno-unused-result",
          "-I", INCLUDE, "-I", CSRC]

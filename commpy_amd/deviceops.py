@@ -20,7 +20,8 @@ __all__ = ['DeviceBuf', 'conv_encode_gpu', 'modulate_gpu', 'bsc_gpu', 'bec_gpu',
            'triang_ldpc_systematic_encode_gpu', 'multipath_dev', 'ofdm_map_dev', 'ofdm_estimate_dev', 'ofdm_estimate_tv_dev', 'sync_estimate_dev', 'sync_align_dev',
            'fading_params_dev', 'fading_gains_dev', 'fading_convolve_dev', 'fading_channel_dev', 'polar_encode_dev', 'polar_decode_dev',
            'bch_encode_dev', 'bch_decode_dev', 'rs_encode_dev', 'rs_decode_dev', 'tailbiting_encode_dev', 'tailbiting_decode_dev',
-           'ldpc_layered_decode_dev', 'bch_chase_dev', 'tpc_decode_dev', 'mlse_equalize_dev', 'mmse_equalize_dev', 'adaptive_equalize_dev']
+           'ldpc_layered_decode_dev', 'bch_chase_dev', 'tpc_decode_dev', 'mlse_equalize_dev', 'mmse_equalize_dev', 'adaptive_equalize_dev',
+           'timing_recover_dev']
 
 
 class DeviceBuf:
@@ -755,4 +756,42 @@ def adaptive_equalize_dev(modem, d_y, B, n_y, d_training, tr_batched, nt, nf, nb
                                                          int(bool(step_batched)), opt(d_forgetting), int(bool(fg_batched)), opt(d_delta),
                                                          int(bool(dl_batched)), float(eps), opt(d_ff0), int(bool(ff0_batched)), opt(d_fb0),
                                                          int(bool(fb0_batched)), *map(p, ADAPT_WANT), stream))
+    return returned(out)
+
+
+# ---- symbol-timing and carrier recovery, device resident (csrc/recovery.hip) ---------------------------------------------------------
+
+def timing_recover_dev(d_y, B, n_y, sps, d_k1, k1_batched, d_k2, k2_batched, d_m0, m0_batched, d_mu0, mu0_batched, d_phase0,
+                       phase0_batched, modem=None, ted='gardner', interp='cubic', d_kc1=None, kc1_batched=False, d_kc2=None,
+                       kc2_batched=False, d_training=None, tr_batched=False, nt=0, n=None, want=('symbols',), stream=None):
+    """``cpx_timing_recover_dev``: ``d_y [B][n_y][2]`` float64 (re, im) at nominally ``sps`` samples per symbol; ``d_k1``, ``d_k2``,
+    ``d_mu0``, ``d_phase0`` (float64) and ``d_m0`` (int64): one value each or, with their ``_batched`` flag, ``[B]``; ``d_kc1`` and
+    ``d_kc2`` likewise, both given (the carrier loop) or both None; ``d_training`` ``[nt]`` int32 labels or, with ``tr_batched``,
+    ``[B][nt]`` (None with ``nt = 0``) -> new ``DeviceBuf``s queued on ``stream`` (None: the library's), the results of
+    ``recovery.timing_recover_batch`` that ``want`` names, in its order: 'symbols' ``[B][n][2]`` float64, 'indices' ``[B][n]`` int32,
+    'bits' ``[B][n m]`` uint8, 'position', 'error' and 'phase' ``[B][n]`` float64, 'count' ``[B]`` int32; a single result for one name.
+    The same rule and the same limits, checked on the host before any device call; the values of the gains and of the loop's start are
+    on the device, so one outside its range rejects its row."""
+    from commpy_amd.recovery import RECOVERY_WANT, check_recovery_sizes, recovery_shapes, whole_sps
+    want = _lib.wanted(want, RECOVERY_WANT)
+    B, n_y, nt, sps = whole(B, 'B', 0), whole(n_y, 'n_y', 0), whole(nt, 'nt', 0), whole_sps(sps)
+    n = n_y // max(sps, 1) if n is None else int(n)
+    if (d_kc1 is None) != (d_kc2 is None):
+        raise ValueError('the carrier loop takes both kc1 and kc2')
+    M, m, ted_code, interp_code = check_recovery_sizes(modem, n_y, n, nt, sps, ted, interp, d_kc1 is not None, nt > 0, want)
+    if d_k1 is None or d_k2 is None:
+        raise ValueError('k1 and k2 are required')
+    if d_m0 is None or d_mu0 is None or d_phase0 is None:
+        raise ValueError('m0, mu0 and phase0 are required')
+    if nt and d_training is None:
+        raise ValueError('training is required for nt = %d' % nt)
+    opt = lambda buf: None if buf is None else buf.ptr
+    out, p = device_outputs(want, recovery_shapes(B, n, m))
+    if B:
+        _lib.check(_lib.load().cpx_timing_recover_dev(None if modem is None else modem._device_handle(), d_y.ptr, B, n_y, n, sps, ted_code,
+                                                      interp_code, d_k1.ptr, int(bool(k1_batched)), d_k2.ptr, int(bool(k2_batched)),
+                                                      opt(d_kc1), int(bool(kc1_batched)), opt(d_kc2), int(bool(kc2_batched)),
+                                                      opt(d_training), int(bool(tr_batched)), nt, d_m0.ptr, int(bool(m0_batched)),
+                                                      d_mu0.ptr, int(bool(mu0_batched)), d_phase0.ptr, int(bool(phase0_batched)),
+                                                      *map(p, RECOVERY_WANT), stream))
     return returned(out)

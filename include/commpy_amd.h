@@ -1078,6 +1078,57 @@ int cpx_adaptive_equalize_dev(const cpx_modem *md, const double *d_y, int64_t B,
                               int32_t *d_indices, uint8_t *d_bits, double *d_estimate, double *d_error, double *d_ff, double *d_fb,
                               void *stream);
 
+/* ---- symbol-timing and carrier recovery of a single-carrier burst (csrc/recovery.hip) ---------------------------
+ * The interpolator / timing-error detector / loop filter / controller loop on rows of matched-filter output at nominally sps samples
+ * per symbol, with an optional decision-directed carrier PLL on the strobes; one row = one independent loop.  md may be NULL for the
+ * Gardner detector without carrier loop, training, indices and bits; c = the points of md (label = position).
+ * ted: 0 = Gardner (non-data-aided), 1 = Mueller-Mueller (decision-directed).  interp: 0 = linear, 1 = cubic (4-sample Lagrange, Farrow).
+ * The rule (float64, real and imaginary parts separate doubles, every product rounded before it is added, no fused multiply-add; a
+ * sample index outside [0, n_y) reads 0.0 and is used like any other).  State of a row: the position m (int64) and mu, from m0 and mu0;
+ * v = 0.0; the period w = (double)sps; phi = phase0 and f = 0.0; the previous strobe and reference.  For k = 0 .. n-1:
+ *   Interpolate.  z_k = I(m, mu), each part on its own.  Linear: x0 + mu (x1 - x0), x0 = y[m], x1 = y[m+1].  Cubic, with xm = y[m-1],
+ *                 x0 = y[m], x1 = y[m+1], x2 = y[m+2], S = 0.16666666666666666: v3 = ((x2 - xm) + 3.0 (x0 - x1)) S;
+ *                 v2 = ((x1 + xm) 0.5) - x0; v1 = ((6.0 x1 - x2) - (3.0 x0 + 2.0 xm)) S; I = ((v3 mu + v2) mu + v1) mu + x0.
+ *   Derotate.     With the carrier loop (c, s) = unit_phasor(phi) (csrc/cpx_phasor.h: a fixed float64 polynomial, no sincos) and
+ *                 z'_k = (zr c + zi s, zi c - zr s); without it z' = z.
+ *   Decide.       With md, a^_k = the first minimum over a ascending of e = z'_k - c[a], er er + ei ei, a later point winning only if
+ *                 strictly smaller; r_k = c[training[k]] for k < nt, else c[a^_k].
+ *   Timing error. e_0 = 0.0, no midpoint is read at k = 0.  Gardner: t = mu - 0.5 w, fl = floor(t), zm = I(m + fl, t - fl),
+ *                 e_k = (zr_{k-1} - zr_k) zmr + (zi_{k-1} - zi_k) zmi on the unrotated strobes.
+ *                 Mueller-Mueller: e_k = (rr_{k-1} z'r_k + ri_{k-1} z'i_k) - (rr_k z'r_{k-1} + ri_k z'i_{k-1}).
+ *   Carrier.      ep = z'i_k rr_k - z'r_k ri_k; f <- f + kc2 ep; phi <- phi + (f + kc1 ep); phi <- phi - rint(phi); the row is rejected
+ *                 unless |phi| <= 0.5 (a NaN fails).
+ *   Loop filter.  v <- v + k2 e_k; w = sps + (v + k1 e_k); the row is rejected unless 0.5 sps < w < 1.5 sps.
+ *   Controller.   t = mu + w, fl = floor(t), m <- m + fl, mu <- t - fl.
+ *   Rejection.    A row whose y (all n_y samples), k1, k2, kc1, kc2, mu0 or phase0 holds a NaN or +-inf or lies outside its range, whose
+ *                 m0 is outside [0, n_y), one of whose training labels is negative or >= M, or one of whose w or phi fails its test is
+ *                 rejected on its own: zero integers, NaN floats.
+ * Equal to tests/recovery_model.py bit for bit, whatever the batch size, the row's place, the stream and the outputs requested.
+ * Limits (CPX_EINVAL, naming the limit, checked before a device is looked for): ted and interp 0 or 1; 2 <= sps <= 8; 1 <= n <= 2^30;
+ * 1 <= n_y <= 2^33; k1, k2, m0, mu0, phase0 given; kc1 and kc2 both given (the carrier loop) or both NULL; md given for ted = 1, the
+ * carrier loop, nt > 0, indices and bits; 2 <= M <= 256; M a power of two when bits is asked for; phase only with the carrier loop;
+ * 0 <= nt <= n; and, where the values are host values, k1, k2, kc1, kc2 >= 0, 0 <= mu0 < 1, |phase0| <= 0.5, 0 <= m0 < n_y (a NaN passes
+ * and rejects its row; the _dev form leaves these to the kernel, which rejects the rows).
+ *   cpx_timing_recover  y [B][n_y][2] float64 (re, im); k1, k2, kc1, kc2, mu0, phase0 (float64) and m0 (int64): one value each or, with
+ *             their _batched flag, [B]; training [nt] int32 or, with tr_batched, [B][nt].  Outputs, each may be NULL (not all):
+ *             symbols [B][n][2] (z'), indices [B][n] int32, bits [B][n m] uint8 (MSB first), position [B][n] ((double)m + mu at the
+ *             strobe), error [B][n] (e_k), phase [B][n] (phi after the strobe's update, turns), count [B] int32 (the strobes all of
+ *             whose interpolator reads lay inside the row).
+ * The _dev form takes device pointers and a stream and is asynchronous; the other takes host pointers and returns synchronised.
+ * B = 0 returns CPX_OK without a launch.  cpx_last_kernel names tr_loop_kernel, the detector, the interpolator, carrier=0/1, sps, M and
+ * the grid cap (tr_cap, in workgroups).  No workspace is taken. */
+int cpx_timing_recover(const cpx_modem *md, const double *y, int64_t B, int64_t n_y, int64_t n, int sps, int ted, int interp,
+                       const double *k1, int k1_batched, const double *k2, int k2_batched, const double *kc1, int kc1_batched,
+                       const double *kc2, int kc2_batched, const int32_t *training, int tr_batched, int64_t nt, const int64_t *m0,
+                       int m0_batched, const double *mu0, int mu0_batched, const double *phase0, int phase0_batched, double *symbols,
+                       int32_t *indices, uint8_t *bits, double *position, double *error, double *phase, int32_t *count);
+int cpx_timing_recover_dev(const cpx_modem *md, const double *d_y, int64_t B, int64_t n_y, int64_t n, int sps, int ted, int interp,
+                           const double *d_k1, int k1_batched, const double *d_k2, int k2_batched, const double *d_kc1, int kc1_batched,
+                           const double *d_kc2, int kc2_batched, const int32_t *d_training, int tr_batched, int64_t nt, const int64_t *d_m0,
+                           int m0_batched, const double *d_mu0, int mu0_batched, const double *d_phase0, int phase0_batched,
+                           double *d_symbols, int32_t *d_indices, uint8_t *d_bits, double *d_position, double *d_error, double *d_phase,
+                           int32_t *d_count, void *stream);
+
 /* ---- multi-GPU: RCCL collectives of the sharded decode ------------------------------------
  * The path shards by codeword (contiguous blocks of B/G codewords per GPU, tables replicated) and has no exchange
  * step inside a decoder.  Two collectives exist around it:
